@@ -16,14 +16,28 @@ libMgcgGpu.so for the two scalar all-reduces and the halo exchange; torch.distri
 generator; no reference data set exists or is needed ("data": "synthetic").
 
 The timed loop multiplies by the PLAIN CSR arrays (12 B per nonzero: `value`, `ms_per_step` and `roofline` are all
-plain-CSR figures).  The library's opt-in lossless compact forms are timed separately and reported under
+plain-CSR figures).  The library's opt-in lossless compact forms are timed separately (--full) and reported under
 `lossless_forms`; they never enter `value` or `roofline`.
+
+A plain run sets up, warms up, times the --steps steps, writes --dump-outputs if asked and prints the line: the headline
+fields, `roofline` (timed inside those same steps), `placement_draw_rank0` and, N > 1, `per_rank`.  Everything below that
+takes work of its own -- the CPU baseline, the bare-export and streaming probes, the compact forms, MGCG, the single-rank
+replay and the N > 1 extras -- runs only with --full (--no-extras / --no-cpu-baseline trim that further).
+
+--dump-outputs DIR: after the timed steps (before any --full work), what the timed path leaves a caller, as float64 .npy:
+  x.npy                    -- the iterate after the last timed step; all of it up to DUMP_SAMPLE rows, above that a fixed
+                              sample of DUMP_SAMPLE entries, one per equal stratum of the rows at an offset drawn from a seeded
+                              generator (dump_sample_index), gathered over all ranks
+  residual_after_steps.npy -- the residual norm the last timed step returned (one entry)
+The inputs are synthetic (b = 1, x0 = 0), so the same arguments give the same inputs in every run.
 
 Output: ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
   roofline       -- dominant kernel = CSR SpMV fused with p.Ap (spmv_rowtile_kernel<EPI_DOT>): algorithmic bytes per
                     launch (12*nnz + 4*(N+1) + 16*N) divided by its average duration measured
                     with HIP events on the library's stream inside the timed region; peak = 8.0 TB/s HBM3E;
                     traffic = PMC bytes per launch (profiles/spmv_traffic.json, separate rocprofv3 --pmc passes).
+  With --full:
+  roofline_csr_spmv -- the bare CsrMV export (20 launches timed with HIP events) and what the box streams (Dot, Copy) (N=1, cg).
   cpu_baseline   -- the CPU oracle (single thread, the reference CPU path's behaviour) timed on a bounded
                     sample of the same workload (rank 0, N=1 only).
   mgcg           -- BASELINE config 3 (3-level V(1,1) Jacobi MGCG on the same matrix, plain CSR on every level):
@@ -59,6 +73,48 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_SAMPLE = 1 << 22    # --dump-outputs: entries of x written at most (32 MiB of float64)
+DUMP_SEED = 20240607
+
+
+def dump_sample_index(rows: int, k: int | None = None, seed: int = DUMP_SEED):
+    """The rows of x that --dump-outputs writes, ascending: every row up to k rows, else one row in each of k equal strata of
+    rows // k rows, at an offset drawn from a generator with a fixed seed (the same rows in every run with the same grid)."""
+    import numpy as np
+
+    k = DUMP_SAMPLE if k is None else k
+    if rows <= k:
+        return np.arange(rows, dtype=np.int64)
+    stride = rows // k
+    return np.arange(k, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, size=k, dtype=np.int64)
+
+
+def dump_outputs(out_dir: str, x_vec, offset: int, count: int, rows: int, residual: float, rank: int = 0, dist=None, chunk: int = 1 << 24):
+    """--dump-outputs: the sampled entries of x that fall into this rank's rows [offset, offset + count), read back chunk by chunk, gathered
+    over the ranks (every entry lives on one rank: a sum of zero-filled pieces is exact), written by rank 0 with the residual.  Collective."""
+    import numpy as np
+
+    idx = dump_sample_index(rows)
+    x = np.zeros(idx.size)
+    j, hi = (int(v) for v in np.searchsorted(idx, [offset, offset + count]))
+    buf = np.empty(min(chunk, count))
+    while j < hi:
+        c0 = int(idx[j]) - offset                          # chunk of this rank's vector starting at the next sampled row
+        n_ = min(buf.size, count - c0)
+        x_vec.CopyTo(buf, n_, 0, c0)
+        j1 = min(hi, int(np.searchsorted(idx, offset + c0 + n_)))
+        x[j:j1] = buf[idx[j:j1] - offset - c0]
+        j = j1
+    if dist is not None:
+        import torch
+
+        t = torch.from_numpy(x)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        x = t.numpy()
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "x.npy"), x)
+        np.save(os.path.join(out_dir, "residual_after_steps.npy"), np.array([residual], dtype=np.float64))
 
 
 def parse():
@@ -72,13 +128,17 @@ def parse():
     ap.add_argument("--mg-nu", type=int, default=1, help="--solver mgcg: pre/post Jacobi sweeps")
     ap.add_argument("--mg-nu-coarse", type=int, default=4, help="--solver mgcg: sweeps on the coarsest level")
     ap.add_argument("--mg-interpolation", type=int, default=0, choices=[0, 1], help="--solver mgcg: 0 piecewise-constant transfer (default), 1 cell-centred linear")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything the headline does not need: CPU baseline, probes, compact forms, MGCG, single-rank replay, N > 1 extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (x, residual) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline object")
     ap.add_argument("--cpu-iters", type=int, default=4, help="CG iterations of the CPU oracle sample")
     ap.add_argument("--no-compression", action="store_true", help="(default) plain CSR inside the loop")
     ap.add_argument("--compression", type=int, default=None, choices=[0, 1, 2],
                     help="MgcgSetMatrixCompression mode for the timed loop: 0 plain CSR (default, the BASELINE metric), "
                          "1 best lossless form, 2 per-nonzero codes only -- with 1 or 2 the line is NOT the BASELINE metric and says so")
-    ap.add_argument("--no-extras", action="store_true", help="skip the mgcg and lossless_forms extra objects")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the mgcg and lossless_forms extra objects (N > 1: the extras after the parity check)")
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N > 1: if RCCL does not form, run over the host-staged gloo transport instead of failing (never a scaling result)")
     ap.add_argument("--torch-first", action="store_true", help="import torch before the library even at N=1 (runtime-compat check)")
@@ -86,7 +146,10 @@ def parse():
     ap.add_argument("--spmv-rows", type=int, default=None)
     ap.add_argument("--spmv-flags", type=int, default=None)
     ap.add_argument("--spmv-grid", type=int, default=None)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def _cpu_share() -> int:
@@ -862,14 +925,15 @@ def main():
     launches = C.c_int(0)
     spmv_ms_total = L.MgcgProfileSpmvMs(cg.cusparse, C.byref(launches))
     L.MgcgProfileSpmv(cg.cusparse, 0)
+    if a.dump_outputs:                              # what the last timed step left, before any --full work touches the vectors
+        dump_outputs(a.dump_outputs, cg.vectorX, cg.part.offset, rows_local, N, res, rank, dist)
 
-
-    # What this box streams ("% of attainable" next to "% of spec"): read-only = Dot over two vectors,
+    # --full: what this box streams ("% of attainable" next to "% of spec"): read-only = Dot over two vectors,
     # copy = the library's Copy export (device-to-device), on the same 1 GiB vectors; and the plain CsrMV export (beta = 0,
     # no fused dot) on the same matrix.
     csr_ms = 0.0
     read_gbps = copy_gbps = 0.0
-    if world == 1 and a.solver == "cg":
+    if world == 1 and a.solver == "cg" and a.full:
         L.MgcgSetMatrixCompression(cg.cusparse, 0)
         ev0, ev1 = L.MgcgEventCreate(), L.MgcgEventCreate()
         ptrs = (cg.vectorAp.ToRawPtr(), cg.vectorElements.ToRawPtr(), cg.vectorRowOffsets.ToRawPtr(), cg.vectorColumnIndeces.ToRawPtr(), cg.vectorP.ToRawPtr())
@@ -894,9 +958,9 @@ def main():
         L.MgcgEventRecord(ev1)
         copy_gbps = 16 * rows_local / (L.MgcgEventElapsedMs(ev0, ev1) / 10 * 1e-3) / 1e9
 
-    # ---- secondary figures (N = 1 only, never part of value / roofline)
+    # ---- secondary figures (--full, N = 1 only, never part of value / roofline)
     lossless = None
-    if world == 1 and a.solver == "cg" and a.compression == 0 and not a.no_extras:
+    if world == 1 and a.solver == "cg" and a.compression == 0 and a.full and not a.no_extras:
         lossless = {"note": "opt-in lossless re-encodings of the same matrix (MgcgSetMatrixCompression); results bit-identical; "
                             "NOT the BASELINE metric: the CSR arrays are not streamed, so no CSR roofline fraction is quoted"}
         pmc_all = {}
@@ -955,10 +1019,10 @@ def main():
     if world > 1 and a.solver == "cg":
         ov = (C.c_longlong * 2)(0, 0)
         overlap = {"active": bool(L.MgcgLastOverlap(ov)), "interior_rows": [int(ov[0]), int(ov[1])], "local_rows": int(rows_local)}
-    # N > 1 (untimed): rank 0 replays the same iterations as ONE rank on its own GPU (the whole grid fits one card) and the line
+    # --full, N > 1 (untimed): rank 0 replays the same iterations as ONE rank on its own GPU (the whole grid fits one card) and the line
     # carries both residuals -- the partitioned run checks itself against the single-rank loop (north star: 1e-10 relative)
     parity = None
-    if world > 1 and a.compression == 0:
+    if world > 1 and a.compression == 0 and a.full:
         if rank == 0:
             single = None
             try:
@@ -1076,7 +1140,7 @@ def main():
         out["config"]["matrix_format_in_loop"] = fmt_text + ("" if fmt == "csr" else f" -- built once by MgcgSetMatrixCompression({a.compression})")
         if lossless is not None:
             out["lossless_forms"] = lossless
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             # the HIP loop on the SAME iterations of the SAME full-size system the oracle sample runs (x0 = 0, b = 1, plain CSR): a parity datum at
             # BASELINE size in every line (ConjugateGradientCpu.cs:45-98 is what the oracle restates)
             gpu_same = None
@@ -1117,9 +1181,9 @@ def main():
 
     if rank != 0:
         out = {}
-    # ---- N > 1, the driver's command (--solver cg): config 4, the communicator's prices and the halo schedules -- untimed extras behind a
+    # ---- --full, N > 1, the driver's command (--solver cg): config 4, the communicator's prices and the halo schedules -- untimed extras behind a
     # guard that never costs the line
-    if world > 1 and a.solver == "cg" and a.compression == 0 and not a.no_extras:
+    if world > 1 and a.solver == "cg" and a.compression == 0 and a.full and not a.no_extras:
         guard = _ExtrasGuard(rank, out)
         stage = guard.stage
 
@@ -1163,7 +1227,7 @@ def main():
                 print(json.dumps(dict(out, extras_aborted=broken, extras_failure="optional schedule" if optional else "error in a BASELINE configuration")), flush=True)
             os._exit(5 if (not optional and os.environ.get("MGCG_BENCH_STRICT") == "1") else 0)
     cg.Dispose()
-    if rank == 0 and world == 1 and a.solver == "cg" and a.compression == 0 and not a.no_extras:
+    if rank == 0 and world == 1 and a.solver == "cg" and a.compression == 0 and a.full and not a.no_extras:
         try:
             out["mgcg"] = mgcg_extra(L, n)
         except Exception as ex:     # noqa: BLE001 -- secondary figure

@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 export PYTHONPATH=$GRAFT_REPO_ROOT
 T="timeout -k 10"
-echo "== bench line (plain CSR headline + extras)";            $T 600 python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"; echo "rc=$?"
+echo "== bench line (plain CSR headline + extras)";            $T 600 python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"; echo "rc=$?"
 echo "== bench line, MGCG as the timed loop (CSR)";             $T 300 python bench.py --solver mgcg --steps 30 --warmup 3 --no-cpu-baseline --no-extras > "$OUT/bench_line_mgcg_csr.json" 2> "$OUT/bench_line_mgcg.err"; echo "rc=$?"
 echo "== rocprof stats + PMC of the CG loop (CSR)";             bash conjugategradient_amd/tools/profile_bench.sh "$OUT/prof_cg_csr" --steps 30 --warmup 3 > "$OUT/prof_cg_csr_summary.json" 2> "$OUT/prof_cg_csr.err"; echo "rc=$?"
 echo "== rocprof stats + PMC of the MGCG loop (CSR)";           bash conjugategradient_amd/tools/profile_bench.sh "$OUT/prof_mgcg_csr" --solver mgcg --steps 20 --warmup 2 > "$OUT/prof_mgcg_csr_summary.json" 2> "$OUT/prof_mgcg_csr.err"; echo "rc=$?"
@@ -20,5 +20,5 @@ echo "== the reference's own driver";                           $T 300 python te
 echo "== MGCG hierarchy next to CG (time to solution)";         $T 600 python conjugategradient_amd/tools/bench_mgcg.py > "$OUT/mgcg_vs_cg_512_csr.json" 2> "$OUT/mgcg_vs_cg.err"; echo "rc=$?"
 echo "== config 5";                                             $T 600 python tests/perf/cfg5_run.py --reps 20 > "$OUT/config5_random_spd_10M_line.json" 2> "$OUT/config5.err"; echo "rc=$?"
 echo "== N = 2 rehearsal of the driver's scaling command (two ranks share the one GPU over the host-staged transport)"
-$T 400 python bench.py --gpus 2 --grid 256 --steps 20 --warmup 3 --allow-fallback > "$OUT/bench_gpus2_grid256_one_gpu_box.json" 2> "$OUT/bench_gpus2_grid256.err"; echo "rc=$?"
+$T 400 python bench.py --full --gpus 2 --grid 256 --steps 20 --warmup 3 --allow-fallback > "$OUT/bench_gpus2_grid256_one_gpu_box.json" 2> "$OUT/bench_gpus2_grid256.err"; echo "rc=$?"
 ls -la "$OUT"

@@ -6,7 +6,7 @@ ROUNDS=${2:-4}
 : > "$OUT"
 for i in $(seq 1 "$ROUNDS"); do
   for k in ${KS:-0 3}; do
-    MGCG_PLACEMENT=$k python3 bench.py --no-extras --no-cpu-baseline --steps ${STEPS:-60} --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
+    MGCG_PLACEMENT=$k python3 bench.py --full --no-extras --no-cpu-baseline --steps ${STEPS:-60} --warmup 5 ${BENCH_ARGS:-} 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 p = d.get('placement_draw_rank0') or {}

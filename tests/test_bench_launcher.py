@@ -192,3 +192,47 @@ def test_cpu_baseline_leg_reports_the_oracle_in_both_summation_orders():
     assert cb["residual"] > 0 and abs(cb["residual"] - cb["residual_with_compensated_dots"]) <= 1e-12 * cb["residual"]
     assert O.lib().oracle_get_dot_mode() == 0
     assert "24^3" in cb["sample"] and cb["all_cores_variant"].get("value", 1) > 0
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: every row of x on a small grid; on a large one a fixed sample of DUMP_SAMPLE rows, one per stratum, ascending,
+    the same in every run (two builds of the project compare output for output), and within 64 MB of float64."""
+    import numpy as np
+
+    assert np.array_equal(bench.dump_sample_index(1000), np.arange(1000))
+    rows = 512**3
+    a, b = bench.dump_sample_index(rows), bench.dump_sample_index(rows)
+    assert np.array_equal(a, b) and a.size == bench.DUMP_SAMPLE and 8 * a.size <= 64 * 2**20
+    stride = rows // a.size
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < rows and np.array_equal(a // stride, np.arange(a.size))
+
+
+def test_dump_outputs_reads_back_in_chunks_and_pieces_sum_to_the_sample(tmp_path, monkeypatch):
+    """The read-back of x chunk by chunk (a stand-in for the device vector) and the rank pieces: each piece holds the sampled rows of its
+    own slice and zeros elsewhere, so the sum over ranks -- what the collective computes -- is the sample of the whole vector."""
+    import numpy as np
+
+    class Vec:
+        def __init__(self, a):
+            self.a = a
+
+        def CopyTo(self, array, count, arrayOffset=0, vectorOffset=0):
+            assert 0 <= vectorOffset and vectorOffset + count <= self.a.size and arrayOffset + count <= array.size
+            array[arrayOffset: arrayOffset + count] = self.a[vectorOffset: vectorOffset + count]
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    rows = 10_007
+    full = np.random.default_rng(1).standard_normal(rows)
+    idx = bench.dump_sample_index(rows)
+    assert idx.size == 1000
+    pieces = []
+    for k, (lo, hi) in enumerate(((0, 3_001), (3_001, 7_500), (7_500, rows))):
+        d = tmp_path / f"rank{k}"
+        bench.dump_outputs(str(d), Vec(full[lo:hi].copy()), lo, hi - lo, rows, 0.25, chunk=37)
+        pieces.append(np.load(d / "x.npy"))
+        assert np.load(d / "residual_after_steps.npy").tolist() == [0.25]
+    assert np.array_equal(sum(pieces), full[idx])
+    bench.dump_outputs(str(tmp_path / "one"), Vec(full), 0, rows, rows, 0.5, chunk=1 << 20)
+    assert np.array_equal(np.load(tmp_path / "one" / "x.npy"), full[idx])
+    bench.dump_outputs(str(tmp_path / "rank1_only"), Vec(full), 0, rows, rows, 0.5, rank=1)
+    assert not (tmp_path / "rank1_only").exists()                  # only rank 0 writes

@@ -1,10 +1,13 @@
-"""bench.py as a program on the GPU box: the N = 1 line's contract fields, and the self-launched N = 2 run over the host-staged
-transport (two processes share the one GPU) with its self-check against a single-rank replay of the same iterations."""
+"""bench.py as a program on the GPU box: the N = 1 line's contract fields, the plain (lean) line and its --dump-outputs, and the
+self-launched N = 2 run over the host-staged transport (two processes share the one GPU) with its self-check against a single-rank
+replay of the same iterations (--full)."""
+import ctypes as C
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +26,7 @@ def _run(*flags):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    rec = _run("--grid", "128", "--steps", "20", "--warmup", "5", "--no-extras", "--cpu-iters", "1")
+    rec = _run("--full", "--grid", "128", "--steps", "20", "--warmup", "5", "--no-extras", "--cpu-iters", "1")
     assert rec["n_gpus"] == 1 and rec["steps"] == 20 and rec["warmup"] == 5 and rec["unit"] == "iterations/s" and rec["dtype"] == "f64"
     assert rec["higher_is_better"] is True and rec["data"] == "synthetic" and rec["vs_baseline"] is None and "workload" in rec["config"]
     assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) <= 1e-6 * rec["value"]
@@ -40,9 +43,43 @@ def test_single_gpu_line_has_the_contract_fields():
     assert rf["traffic"] is None or "RECORDED" in rf["traffic_source"]
 
 
+def _dumped(d):
+    x, res = np.load(d / "x.npy"), np.load(d / "residual_after_steps.npy")
+    assert x.dtype == np.float64 and res.dtype == np.float64 and res.shape == (1,)
+    return x, res
+
+
+def _check_against_oracle(x, residual, n, iterations):
+    """x and the residual norm after `iterations` CG iterations from x0 = 0 on the 7-point n^3 system, b = 1, against the CPU oracle
+    (north star: 1e-10 relative; the loops differ only in the order of the dot products' sums)."""
+    from oracle import oracle as O
+
+    e, c, r = O.poisson_csr(n, n, n)
+    xr, rr = np.zeros(n**3), C.c_double(0)
+    O.lib().oracle_cg_steps(e, c, r, n**3, xr, np.ones(n**3), iterations, C.byref(rr), np.empty(3 * n**3))
+    assert np.abs(x - xr).max() <= 1e-10 * np.abs(xr).max()
+    assert abs(residual - rr.value) <= 1e-10 * rr.value, (residual, rr.value)
+
+
+def test_plain_line_is_lean_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """Without --full the line carries the headline and the in-loop roofline, and none of the objects that take work of their own;
+    --dump-outputs writes the iterate after the warm-up and the timed steps (all of x at this size) and the residual of the last step."""
+    n, steps, warmup = 24, 9, 3
+    rec = _run("--grid", str(n), "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "out"))
+    assert rec["steps"] == steps and rec["warmup"] == warmup and rec["unit"] == "iterations/s" and rec["dtype"] == "f64" and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 1e3 / rec["ms_per_step"]) <= 1e-6 * rec["value"] and rec["roofline"]["launches_timed"] == steps
+    for k in ("cpu_baseline", "roofline_csr_spmv", "lossless_forms", "mgcg"):
+        assert k not in rec, k
+    x, res = _dumped(tmp_path / "out")
+    assert sorted(os.listdir(tmp_path / "out")) == ["residual_after_steps.npy", "x.npy"]
+    assert x.shape == (n**3,) and res[0] == rec["residual_after_steps"]
+    _check_against_oracle(x, res[0], n, warmup + steps)
+
+
 @pytest.mark.parametrize("solver", ["cg", "mgcg"])
-def test_two_self_launched_ranks_check_themselves_against_one_rank(solver):
-    rec = _run("--gpus", "2", "--grid", "64", "--steps", "8", "--warmup", "2", "--allow-fallback", "--solver", solver)
+def test_two_self_launched_ranks_check_themselves_against_one_rank(solver, tmp_path):
+    rec = _run("--full", "--gpus", "2", "--grid", "64", "--steps", "8", "--warmup", "2", "--allow-fallback", "--solver", solver,
+               "--dump-outputs", str(tmp_path / "out"))
     assert rec["n_gpus"] == 2 and rec["scaling"] == "strong"
     if "rccl" not in rec["config"]["transport"].lower() or "fallback" in rec["config"]["transport"].lower():
         assert "not a scaling result" in rec["config"]["transport"]             # one GPU: the host-staged transport, and the line says so
@@ -53,8 +90,12 @@ def test_two_self_launched_ranks_check_themselves_against_one_rank(solver):
     assert len(pr["seconds_for_the_timed_steps"]) == 2 and len(pr["spmv_avg_launch_ms"]) == 2
     assert abs(max(pr["seconds_for_the_timed_steps"]) - rec["ms_per_step"] * rec["steps"] / 1e3) <= 1e-9       # the line reports the slowest rank
     assert par["single_rank_ms_per_step"] > 0 and par["speedup_vs_single_rank"] > 0
+    # --dump-outputs gathers x over the ranks: all 64^3 entries, and the residual the line reports
+    x, res = _dumped(tmp_path / "out")
+    assert x.shape == (64**3,) and res[0] == rec["residual_after_steps"]
     if solver == "cg":
         _check_multirank_extras(rec, 2)
+        _check_against_oracle(x, res[0], 64, 2 + 8)
 
 
 def _check_multirank_extras(rec, world):
@@ -95,7 +136,7 @@ def test_two_ranks_over_rccl_when_the_box_has_two_devices(solver):
 
     if _lib.lib().GetDeviceCount() < 2 or os.environ.get("MGCG_VIRTUAL_DEVICES"):
         pytest.skip("needs two physical devices")
-    rec = _run("--gpus", "2", "--grid", "128", "--steps", "10", "--warmup", "3", "--solver", solver)
+    rec = _run("--full", "--gpus", "2", "--grid", "128", "--steps", "10", "--warmup", "3", "--solver", solver)
     assert rec["n_gpus"] == 2 and rec["config"]["transport"] == "rccl"
     par = rec["parity_vs_single_rank"]
     assert par["within_1e-10"] is True, par
