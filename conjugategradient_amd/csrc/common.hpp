@@ -26,6 +26,8 @@ constexpr int kNumXcd = 8;
 constexpr int kNumCu = 256;
 constexpr int kMaxGrid = kNumCu * 8; // 8 resident 256-thread workgroups per CU (32 waves/CU)
 constexpr int kMaxPartials = kNumCu * 32; // single-wavefront workgroups: up to 32 per CU, one partial sum each
+constexpr int kXDeferMax = 8;         // longest group of the deferred x update (MGCG_X_DEFER): directions kept in the ring
+constexpr int kXDeferDefault = 8;
 constexpr int kMaxDevices = 64;
 constexpr int kPatMax = 256;         // row-pattern form: distinct rows-as-sequences a matrix may have ...
 constexpr int kPatEntries = 2048;    // ... and nPattern * longest row (the table lives in LDS: 12 bytes per entry)
@@ -63,6 +65,8 @@ struct Tuning {
                                              //                         sums in rank order, as the reference's CPU twin does (LongVector.cs:15-31, resultsDot.Sum()) -- traces and
                                              //                         iterates then EQUAL the oracle's; ~0.5 s per 1.3e8-entry dot, never on a timed path
     std::atomic<int> failCommInit{0};        // MGCG_FAIL_COMM_INIT     tests only: MgcgCommInitAll / MgcgCommInitRank report failure (what a host without a working RCCL does)
+    std::atomic<int> xDefer{kXDeferDefault}; // MGCG_X_DEFER            one-rank plain CG loop: x += alpha p applied once per group of this many iterations from a ring of
+                                             //                         p buffers (1: every iteration; at most kXDeferMax)
 };
 Tuning& tuning();
 void tuning_reload();
@@ -106,6 +110,10 @@ struct CgScalars {
     // (single rank, no preconditioner): that kernel's workgroups read these while its first workgroup rewrites the live fields
     double fRr, fRr0, fAlpha;
     int fIteration, fDone;
+    // Deferred x update (MGCG_X_DEFER > 1): the alphas of the group's earlier iterations, by position in the group, and the ring slot that
+    // holds p after the iteration that stopped the loop (0: the caller's buffer)
+    double alphaRing[kXDeferMax];
+    int pSlot, pad2;
 };
 
 static_assert(offsetof(CgScalars, rzNew) == offsetof(CgScalars, rrNew) + sizeof(double), "{rrNew, rzNew} are all-reduced as one pair");
@@ -130,9 +138,14 @@ struct Workspace {
     int* devInts = nullptr;          // device, 8 ints (small integer results: far band, longest row, sampled distance; a 64-bit checksum in [4..5])
     double* trace = nullptr;         // device residual trace
     int traceCap = 0;
+    // the library-owned slots 1 .. kXDeferMax-1 of the deferred x update's ring of p (slot 0 is the caller's p), ringSize entries each
+    double* ring[kXDeferMax] = {};
+    long long ringSize = 0;
     bool init();
     void destroy();
     bool ensure_trace(int cap);
+    bool ensure_ring(int slots, long long n);    // slots 1 .. slots-1 allocated with >= n entries (keeps what is there)
+    void free_ring();
 };
 
 } // namespace mgcg
@@ -398,6 +411,20 @@ void launch_update_xp(hipStream_t s, const CgScalars* sc, double* x, double* p, 
 struct FinalizeArgs;
 void launch_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
                             double* x, double* p, const double* z, long long n);
+
+// Deferred x update (one rank, no preconditioner): iteration k of a group reads p_k from slot[pos] and writes p_{k+1} to slot[pos + 1],
+// or, on the group's last iteration (flush), to slot[0] in place; the flush and the iteration that stops the loop also apply the group's
+// pending terms to x, oldest first (x = x + alpha_j p_j, j = slot 0 .. pos).  Same rounded operations in the same order as the x += alpha p
+// of every iteration: the same x, bit for bit.
+struct RingArgs {
+    double* slot[kXDeferMax];
+    int pos;        // position of this iteration in its group (= the slot of p_k)
+    int flush;      // 1: the group's last iteration
+};
+void launch_update_xp_ring(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
+                           double* x, const RingArgs& g, const double* z, long long n);
+// after a call that may have stopped inside a group: p back into slot 0 when sc->pSlot names another slot
+void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g, long long n);
 
 struct FinalizeArgs {
     CgScalars* sc;

@@ -597,6 +597,171 @@ void launch_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* 
     else hipLaunchKernelGGL((update_xp_final_kernel<false, false>), dim3(grid_for(n, 1)), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, p, z, n);
 }
 
+// The same with the deferred x update (RingArgs, common.hpp): the finalisation and stop decision of update_xp_final_kernel, then
+// p_{k+1} = z + beta p_k from slot[pos] into the next slot.  The group's last iteration (flush) and the iteration that stops the loop also
+// apply the NT = pos + 1 pending terms to x, oldest first; the other iterations do not touch x (24N bytes instead of 40N).  The slots may
+// alias (the flush writes slot 0 in place, pos = 0 reads and writes slot 0): every element is read before it is written, by the same lane.
+// FLUSH (the host knows which iterations close a group) compiles the unrolled form of the x terms, all loads in flight together (130 VGPRs
+// at NT = 8); the other iterations keep the register count of the p-only pass and apply the terms one slot after another when the stop
+// test fires in them (once per solve).
+template <bool V2, bool NTV, int NT, bool FLUSH>
+__global__ __launch_bounds__(kBlock) void update_xp_ring_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsInf,
+                                                                int nPartials, double* __restrict__ x, RingArgs g, const double* __restrict__ z, long long n)
+{
+    __shared__ double s_red[4];
+    __shared__ double s_red2[4];
+    __shared__ double s_beta;
+    __shared__ int s_stop;
+    CgScalars* sc = f.sc;
+    if (sc->fDone != 0) return;                                       // the loop had stopped before this iteration: nothing ran, nothing is pending
+    const double rrNew = reduce_partials_block(partials, nPartials, s_red, 0);
+    double inf = 0.0;
+    if (partialsInf != nullptr) inf = reduce_partials_block(partialsInf, nPartials, s_red2, 1);
+    const double alpha = sc->fAlpha;
+    if (threadIdx.x == 0) {
+        const int it = sc->fIteration;
+        const StopDecision d = decide_stop(f, rrNew, inf, sc->fRr0, it);
+        const double beta = rrNew / sc->fRr;
+        s_stop = d.stop ? 1 : 0; s_beta = beta;
+        if (blockIdx.x == 0) {                                        // publish (what finalize_kernel writes)
+            if (f.trace != nullptr && it < f.traceCap) f.trace[it] = d.shown;
+            sc->rrNew = rrNew; sc->residual = d.res; sc->nrmInf = inf; sc->pad = 0;
+            if (d.stop) {
+                sc->pSlot = NT - 1;                                   // p_k stays where it is (ring_copy_back_kernel)
+                sc->done = 1; sc->status = d.status;
+                f.mirror->residual = d.res; f.mirror->iteration = it; f.mirror->status = d.status;
+                __threadfence_system();
+                f.mirror->done = 1;
+            } else {
+                sc->alphaRing[NT - 1] = alpha;                        // (read by this group's later iterations only: no workgroup here reads it)
+                sc->beta = beta; sc->rr = rrNew; sc->iteration = it + 1;
+                f.mirror->residual = d.res; f.mirror->iteration = it + 1;
+            }
+        }
+    }
+    __syncthreads();
+    const double beta = s_beta;
+    const bool stop = s_stop != 0;
+    const double* pk = g.slot[NT - 1];
+    double* pn = g.slot[(FLUSH || NT == kXDeferMax) ? 0 : NT];
+    if (!FLUSH && stop) {                                             // stopped inside a group: x only, one term after another
+        for (int t = 0; t < NT; ++t) {
+            const double at = t < NT - 1 ? sc->alphaRing[t] : alpha;
+            const double* pt = g.slot[t];
+            grid_stride<false>(n, [&](long long) {}, [&](long long i) { double u = at * pt[i]; x[i] = x[i] + u; });
+        }
+        return;
+    }
+    if (FLUSH) {
+        double al[NT];
+#pragma unroll
+        for (int t = 0; t < NT - 1; ++t) al[t] = sc->alphaRing[t];
+        al[NT - 1] = alpha;
+        auto one = [&](long long i) {
+            double xv = x[i];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) { double u = al[t] * g.slot[t][i]; xv = xv + u; }
+            x[i] = xv;
+            if (!stop) { double u = beta * pk[i]; pn[i] = z[i] + u; }
+        };
+        if constexpr (V2) {
+            d2* x2 = (d2*)x; d2* pn2 = (d2*)pn; const d2* z2 = (const d2*)z;
+            auto fin = [&](d2& xv, const d2* pv) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) { double u0 = al[t] * pv[t].x; double u1 = al[t] * pv[t].y; xv.x = xv.x + u0; xv.y = xv.y + u1; }
+            };
+            chunk_pairs(n >> 1, [&](long long i, bool two) {
+                const long long j = two ? i + kBlock : i;
+                d2 pv0[NT], pv1[NT];
+                d2 xv0 = ldv<NTV>(x2 + i), xv1 = ldv<NTV>(x2 + j);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) { pv0[t] = ldv<NTV>((const d2*)g.slot[t] + i); pv1[t] = ldv<NTV>((const d2*)g.slot[t] + j); }
+                d2 zv0 = {}, zv1 = {};
+                if (!stop) { zv0 = ldv<NTV>(z2 + i); zv1 = ldv<NTV>(z2 + j); }
+                fin(xv0, pv0);
+                stv<NTV>(xv0, x2 + i);
+                if (!stop) { double u0 = beta * pv0[NT - 1].x; double u1 = beta * pv0[NT - 1].y; zv0.x = zv0.x + u0; zv0.y = zv0.y + u1; stv<NTV>(zv0, pn2 + i); }
+                if (two) {
+                    fin(xv1, pv1);
+                    stv<NTV>(xv1, x2 + j);
+                    if (!stop) { double u0 = beta * pv1[NT - 1].x; double u1 = beta * pv1[NT - 1].y; zv1.x = zv1.x + u0; zv1.y = zv1.y + u1; stv<NTV>(zv1, pn2 + j); }
+                }
+            });
+            if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
+        } else {
+            grid_stride<false>(n, [&](long long) {}, one);
+        }
+        return;
+    }
+    auto one = [&](long long i) { double u = beta * pk[i]; pn[i] = z[i] + u; };
+    if constexpr (V2) {
+        const d2* pk2 = (const d2*)pk; d2* pn2 = (d2*)pn; const d2* z2 = (const d2*)z;
+        chunk_pairs(n >> 1, [&](long long i, bool two) {
+            const long long j = two ? i + kBlock : i;
+            d2 pv0 = ldv<NTV>(pk2 + i), zv0 = ldv<NTV>(z2 + i), pv1 = ldv<NTV>(pk2 + j), zv1 = ldv<NTV>(z2 + j);
+            double u0 = beta * pv0.x; double u1 = beta * pv0.y; zv0.x = zv0.x + u0; zv0.y = zv0.y + u1;
+            stv<NTV>(zv0, pn2 + i);
+            if (two) { u0 = beta * pv1.x; u1 = beta * pv1.y; zv1.x = zv1.x + u0; zv1.y = zv1.y + u1; stv<NTV>(zv1, pn2 + j); }
+        });
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
+    } else {
+        grid_stride<false>(n, [&](long long) {}, one);
+    }
+}
+template <int NT, bool FLUSH>
+static void launch_xp_ring_nt2(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
+                               double* x, const RingArgs& g, const double* z, long long n, bool v2, bool nt)
+{
+    // the p-only pass (2 reads, 1 write: update_r's shape) takes update_r's two workgroups per CU -- 570-578 us against 597-598 for 2048
+    // workgroups at 512^3 (profiles/r6/ring_grid_ab.txt); the flush (B + 2 reads, 2 writes) keeps the x/p pass's 2048
+    int g2 = grid_for(n, 2);
+    if (!FLUSH) { DeviceState* d = device_state(); const int want = 2 * (d ? d->numCu : kNumCu); if (g2 > want) g2 = want; }
+    if (v2 && nt) hipLaunchKernelGGL((update_xp_ring_kernel<true, true, NT, FLUSH>), dim3(g2), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, g, z, n);
+    else if (v2) hipLaunchKernelGGL((update_xp_ring_kernel<true, false, NT, FLUSH>), dim3(g2), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, g, z, n);
+    else hipLaunchKernelGGL((update_xp_ring_kernel<false, false, NT, FLUSH>), dim3(grid_for(n, 1)), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, g, z, n);
+}
+template <int NT>
+static void launch_xp_ring_nt(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
+                              double* x, const RingArgs& g, const double* z, long long n, bool v2, bool nt)
+{
+    if (g.flush || NT == kXDeferMax) launch_xp_ring_nt2<NT, true>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt);
+    else launch_xp_ring_nt2<NT, false>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt);
+}
+void launch_update_xp_ring(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
+                           double* x, const RingArgs& g, const double* z, long long n)
+{
+    if (n <= 0) return;
+    bool v2 = al16(x) && al16(z);
+    for (int t = 0; t <= g.pos + 1 && t < kXDeferMax; ++t) v2 = v2 && al16(g.slot[t]);
+    const bool nt = vec_nt(n);
+    static_assert(kXDeferMax == 8, "one instantiation per position in the group");
+    switch (g.pos) {
+    case 0: launch_xp_ring_nt<1>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    case 1: launch_xp_ring_nt<2>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    case 2: launch_xp_ring_nt<3>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    case 3: launch_xp_ring_nt<4>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    case 4: launch_xp_ring_nt<5>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    case 5: launch_xp_ring_nt<6>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    case 6: launch_xp_ring_nt<7>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    default: launch_xp_ring_nt<8>(s, f, partials, partialsInf, nPartials, x, g, z, n, v2, nt); break;
+    }
+}
+
+// p back into slot 0 after a call that stopped inside a group (sc->pSlot: the slot that holds it; 0: nothing to do)
+__global__ __launch_bounds__(kBlock) void ring_copy_back_kernel(const CgScalars* __restrict__ sc, RingArgs g, long long n)
+{
+    const int from = sc->pSlot;
+    if (from <= 0 || from >= kXDeferMax) return;
+    const double* src = g.slot[from];
+    double* dst = g.slot[0];
+    grid_stride<false>(n, [&](long long) {}, [&](long long i) { dst[i] = src[i]; });
+}
+void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g, long long n)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(ring_copy_back_kernel, dim3(grid_for(n, 4)), dim3(kBlock), 0, s, sc, g, n);
+}
+
 // p = z + beta*p   (ConjugateGradientCpu.cs:94 with z = r; the preconditioned loop passes z = M^-1 r)
 template <bool V2>
 __global__ __launch_bounds__(kBlock) void update_p_kernel(const CgScalars* __restrict__ sc, double* __restrict__ p, const double* __restrict__ z, long long n)
@@ -626,7 +791,7 @@ __global__ __launch_bounds__(kBlock) void init_scalars_kernel(const double* __re
         if (!reduceFirst) rr = sc->rr;
         sc->rr = rr; sc->rr0 = rr; sc->pAp = 0; sc->rrNew = 0; sc->rzNew = 0; sc->residual = 0; sc->nrmInf = 0;
         sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = 0; sc->pad = 0;
-        sc->fRr = rr; sc->fRr0 = rr; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0;
+        sc->fRr = rr; sc->fRr0 = rr; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
         (void)rule;
         mirror->residual = 0; mirror->iteration = 0; mirror->status = 0; mirror->done = 0;
     }

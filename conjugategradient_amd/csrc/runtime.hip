@@ -38,6 +38,7 @@ const Knob kKnobs[] = {
     { "MGCG_DOT_ORDER", "dot_order", &Tuning::dotOrder, 0, false },
     { "MGCG_DEEP_HALO", "deep_halo", &Tuning::deepHalo, 1, false },
     { "MGCG_PLACEMENT", "placement", &Tuning::placement, 3, false },
+    { "MGCG_X_DEFER", "x_defer", &Tuning::xDefer, kXDeferDefault, false },
 };
 Tuning g_tuning;
 std::once_flag g_tuningOnce;
@@ -136,6 +137,7 @@ void Workspace::destroy()
     if (hostScalar) (void)hipHostFree(hostScalar);
     if (devInts) (void)hipFree(devInts);
     if (trace) (void)hipFree(trace);
+    free_ring();
     partials = nullptr; scalars = nullptr; mirror = nullptr; hostScalar = nullptr; devInts = nullptr; trace = nullptr; traceCap = 0;
 }
 bool Workspace::ensure_trace(int cap)
@@ -145,6 +147,27 @@ bool Workspace::ensure_trace(int cap)
     trace = nullptr; traceCap = 0;
     if (!MGCG_HIP(hipMalloc((void**)&trace, sizeof(double) * (size_t)cap))) return false;
     traceCap = cap;
+    return true;
+}
+
+void Workspace::free_ring()
+{
+    for (int i = 1; i < kXDeferMax; ++i) { if (ring[i]) (void)hipFree(ring[i]); ring[i] = nullptr; }
+    ringSize = 0;
+}
+bool Workspace::ensure_ring(int slots, long long n)
+{
+    if (ringSize < n) {
+        if (stream) (void)hipStreamSynchronize(stream);   // (a smaller ring may still be in use by enqueued work)
+        free_ring();
+        ringSize = n;
+    }
+    for (int i = 1; i < slots && i < kXDeferMax; ++i) {
+        if (ring[i]) continue;
+        size_t freeB = 0, totalB = 0;     // (leave the caller room: 2 GiB, as the placement draw does)
+        if (hipMemGetInfo(&freeB, &totalB) != hipSuccess || freeB < sizeof(double) * (size_t)ringSize + (2ULL << 30)) { (void)hipGetLastError(); return false; }
+        if (hipMalloc((void**)&ring[i], sizeof(double) * (size_t)ringSize) != hipSuccess) { (void)hipGetLastError(); ring[i] = nullptr; return false; }
+    }
     return true;
 }
 

@@ -9,6 +9,7 @@
 // later kernel exits at its first instruction, so x, r, p, Iteration and Residual are exactly those
 // of the iteration the reference would have stopped at.
 #include "common.hpp"
+#include <algorithm>
 #include <chrono>
 
 namespace mgcg {
@@ -519,6 +520,10 @@ struct CgRun {
     bool haloOnSide = false;               // tuning knob, resolved once per solve (every iteration of every rank takes the same path)
     Vector* pVec = nullptr;                // the handles behind p and Ap (the placement draw may move their data)
     Vector* ApVec = nullptr;
+    // deferred x update (MGCG_X_DEFER, cg_xdefer_setup): groups of xDefer iterations, the host's position in the current group
+    int xDefer = 1;
+    int groupPos = 0, groupLen = 1;
+    RingArgs ring{};
 };
 
 static thread_local long long t_lastOverlap[3] = { 0, 0, 0 };
@@ -554,7 +559,43 @@ __global__ void snapshot_kernel(const CgScalars* sc, HostMirror* m, volatile int
     m->residual = sc->residual;
 }
 
-__global__ void clear_done_kernel(CgScalars* sc) { sc->done = 0; sc->status = 0; }
+__global__ void clear_done_kernel(CgScalars* sc) { sc->done = 0; sc->status = 0; sc->pSlot = 0; }
+
+// ---------------------------------------------------------------- deferred x update (MGCG_X_DEFER)
+// Nothing in the loop reads x: it only has to be right when the call returns.  With B > 1 the one-rank plain loop keeps the directions of
+// a group of B iterations in a ring of B buffers (slot 0 the caller's p, slots 1 .. B-1 on the workspace) and the group's last iteration
+// applies x += alpha_j p_j for the whole group, oldest first -- the same rounded products and sums as one term per iteration, so x is the
+// same bit for bit, and r, p, Ap and every dot are untouched.  The update pass then moves 24N bytes on B-1 iterations of B and
+// (B + 4) 8N on the last one: 32N + 8N/B per iteration against 40N.
+// Groups: CgSteps(K) puts the short group (K mod B) first, so that its last iteration is a flush and writes p into the caller's buffer;
+// Solve groups from its first iteration, and the iteration that stops the loop flushes; if p then sits in a library slot it is copied back
+// once at the end of the call (ring_copy_back_kernel).  Several ranks and the preconditioned loop keep one term per iteration.
+static int cg_xdefer_slots(const CgRun& R)
+{
+    int B = tuning().xDefer.load(std::memory_order_relaxed);
+    B = B < 1 ? 1 : (B > kXDeferMax ? kXDeferMax : B);
+    const bool eligible = !R.multi && !R.mg && R.nLocal > 0 && R.offset == 0 && R.count == R.nLocal;
+    return eligible ? B : 1;
+}
+
+// steps: the call's iteration count when it is known (CgSteps), else 0
+static void cg_xdefer_setup(CgRun& R, long long steps)
+{
+    R.xDefer = 1; R.groupPos = 0; R.groupLen = 1;
+    const int B = cg_xdefer_slots(R);
+    if (B <= 1) return;
+    const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;
+    if (!R.ws->ensure_ring(B, R.nLocal)) {         // no room for the ring: one term per iteration, as with B = 1
+        if (report) fprintf(stderr, "[MgcgGpu] solve set-up: deferred x update off (the ring of %d more vectors of %lld entries could not be allocated)\n", B - 1, R.nLocal);
+        return;
+    }
+    R.ring = RingArgs{};
+    R.ring.slot[0] = R.p;
+    for (int i = 1; i < B; ++i) R.ring.slot[i] = R.ws->ring[i];
+    R.xDefer = B;
+    R.groupLen = (steps > 0 && steps % B != 0) ? (int)(steps % B) : B;
+    if (report) fprintf(stderr, "[MgcgGpu] solve set-up: deferred x update in groups of %d (first group %d)\n", B, R.groupLen);
+}
 
 // ---------------------------------------------------------------- placement draw for Ap and p
 // The same SpMV binary on the same matrix runs up to 17 % apart depending on WHERE the runtime placed its two vectors (identical HBM
@@ -639,11 +680,77 @@ static void placement_stage(CgRun& R, int stage, Vector* v)
 // the plain loop draws when its iteration cap leaves room for that many (the 512^3 system needs 1225), and CgSteps -- the fixed-length
 // form a caller uses to time the steady state -- always does (steps = 0 in R.maxIt).
 constexpr int kPlacementMinIterations = 1000;
+
+// The deferred x update's ring (cg_xdefer_setup): the SpMV gathers from its B - 1 library-owned slots in turn, and each of them moves it as
+// much as p's own placement does (in the loop at 512^3: 2.43 ms on the best of p's 4 candidates, 2.45-2.47 and 2.52 ms on ring slots drawn
+// as the best 7 of 10 -- profiles/r6).  So they are drawn the way p is, best of (1 + `placement`) per slot: (B - 1)(1 + placement)
+// allocations (at most 16) timed as the gathered vector, the B - 1 fastest kept in ascending time -- once per workspace, when the ring is
+// first needed at this size.  MgcgLastPlacement keeps reporting the two stages above; MGCG_VERBOSE=1 prints this one.
+static void placement_ring(CgRun& R)
+{
+    const int B = cg_xdefer_slots(R);
+    const int extra = tuning().placement.load(std::memory_order_relaxed);
+    Workspace* ws = R.ws;
+    if (B <= 1 || extra <= 0 || R.nLocal < kPlacementMinEntries || R.elementsCount < 8) return;
+    if (ws->ringSize >= R.nLocal) { bool some = false; for (int i = 1; i < kXDeferMax; ++i) some = some || ws->ring[i] != nullptr; if (some) return; }
+    hipStream_t s = ws->stream;
+    (void)hipStreamSynchronize(s);
+    ws->free_ring();
+    const size_t bytes = sizeof(double) * (size_t)R.nLocal;
+    size_t freeB = 0, totalB = 0;
+    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { (void)hipGetLastError(); return; }
+    double* cand[16];
+    int n = 0;
+    const int want = (B - 1) * (1 + extra) > 16 ? 16 : (B - 1) * (1 + extra);
+    for (int i = 0; i < want && freeB > (size_t)(i + 1) * bytes + (2ULL << 30); ++i) {
+        double* q = nullptr;
+        if (hipMalloc((void**)&q, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
+        cand[n++] = q;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool ok = n > 0 && MGCG_HIP(hipEventCreate(&e0)) && MGCG_HIP(hipEventCreate(&e1));
+    for (int i = 0; ok && i < n; ++i) ok = MGCG_HIP(hipMemcpyAsync(cand[i], R.p, bytes, hipMemcpyDeviceToDevice, s));
+    constexpr int kReps = 6;
+    double ms[16];
+    int order[16];
+    for (int i = 0; ok && i < n; ++i) {
+        SpmvArgs a{};
+        a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces;
+        a.x = cand[i]; a.y = R.Ap;
+        a.elementsCount = R.elementsCount; a.rowCount = (int)R.nLocal; a.columnCount = (int)R.count;
+        a.w = a.x; a.partials = ws->partials; a.doneFlag = nullptr;
+        (void)launch_spmv_auto(s, EPI_DOT, a, R.cfg, R.dcsr);                              // warm-up (Ap and the partial sums are rewritten by the solve)
+        ok = MGCG_HIP(hipEventRecord(e0, s));
+        for (int k = 0; k < kReps; ++k) (void)launch_spmv_auto(s, EPI_DOT, a, R.cfg, R.dcsr);
+        ok = ok && MGCG_HIP(hipEventRecord(e1, s)) && MGCG_HIP(hipEventSynchronize(e1));
+        float t = 0.0f;
+        ok = ok && MGCG_HIP(hipEventElapsedTime(&t, e0, e1));
+        ms[i] = (double)t / kReps;
+        order[i] = i;
+    }
+    (void)hipStreamSynchronize(s);
+    if (!ok) { (void)hipGetLastError(); for (int i = 0; i < n; ++i) ms[i] = (double)i; for (int i = 0; i < n; ++i) order[i] = i; }
+    std::stable_sort(order, order + n, [&](int a, int b) { return ms[a] < ms[b]; });
+    const int take = n < B - 1 ? n : B - 1;
+    ws->ringSize = R.nLocal;
+    for (int k = 0; k < take; ++k) ws->ring[1 + k] = cand[order[k]];
+    for (int k = take; k < n; ++k) (void)hipFree(cand[order[k]]);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (ok && tuning().verbose.load(std::memory_order_relaxed) >= 1) {
+        fprintf(stderr, "[MgcgGpu] placement draw for the ring of p (%d slots): SpMV", B - 1);
+        for (int i = 0; i < n; ++i) fprintf(stderr, " %.3f", ms[i]);
+        fprintf(stderr, " ms -> candidates");
+        for (int k = 0; k < take; ++k) fprintf(stderr, " %d", order[k]);
+        fprintf(stderr, "\n");
+    }
+}
 static void placement_draw(CgRun& R, bool fixedSteps)
 {
     if (R.mg != nullptr || (!fixedSteps && R.maxIt < kPlacementMinIterations)) { placement_report(0, nullptr); placement_report(1, nullptr); return; }
     placement_stage(R, 0, R.ApVec);                // the written vector first: it decides the most
     placement_stage(R, 1, R.pVec);
+    placement_ring(R);
 }
 
 static bool cg_enqueue_init(CgRun& R, bool fixedSteps = false)
@@ -696,10 +803,11 @@ static bool cg_enqueue_iteration(CgRun& R, bool withStopTest)
 {
     hipStream_t s = R.ws->stream;
     CgScalars* sc = R.ws->scalars;
-    double* pLoc = R.p + R.offset;
+    double* pIn = R.xDefer > 1 ? R.ring.slot[R.groupPos] : R.p;                      // the slot that holds p_k (deferred x update)
+    double* pLoc = pIn + R.offset;
     const int* done = &sc->done;
     SpmvArgs a{};
-    a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces; a.x = R.p; a.y = R.Ap;
+    a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces; a.x = pIn; a.y = R.Ap;
     a.elementsCount = R.elementsCount; a.rowCount = (int)R.nLocal; a.columnCount = (int)R.count;
     a.w = pLoc; a.partials = R.ws->partials; a.doneFlag = done;
     int n;
@@ -750,6 +858,13 @@ static bool cg_enqueue_iteration(CgRun& R, bool withStopTest)
     f.sc = sc; f.mirror = R.ws->mirror; f.trace = R.ws->trace; f.traceCap = R.ws->traceCap;
     f.tol = R.tol; f.minIt = R.minIt; f.maxIt = R.maxIt; f.rule = R.rule; f.preconditioned = R.mg ? 1 : 0;
     if (!withStopTest) { f.tol = -1.0; f.minIt = 0; f.maxIt = 0x7fffffff; f.rule = MGCG_RULE_NATIVE; }   // never converges
+    if (fold && R.xDefer > 1) {
+        RingArgs g = R.ring;
+        g.pos = R.groupPos; g.flush = R.groupPos + 1 == R.groupLen ? 1 : 0;
+        launch_update_xp_ring(s, f, rrPartials, pInf, n, R.x, g, R.r, R.nLocal);       // the same, x += a p once per group (cg_xdefer_setup)
+        if (g.flush) { R.groupPos = 0; R.groupLen = R.xDefer; } else ++R.groupPos;
+        return MGCG_HIP(hipGetLastError());
+    }
     if (fold) {
         launch_update_xp_final(s, f, rrPartials, pInf, n, R.x, pLoc, R.r, R.nLocal);     // residual, stop test, beta (:251-266) ; x += a p (:246) ; p = r + beta p (:265)
         return MGCG_HIP(hipGetLastError());
@@ -822,6 +937,7 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
     const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;
     const auto hostT0 = std::chrono::steady_clock::now();
     ok = ok && cg_enqueue_init(R);
+    if (ok) cg_xdefer_setup(R, 0);
     if (report) {
         const double enq = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT0).count();
         (void)hipStreamSynchronize(s);
@@ -847,6 +963,7 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
         }
         ++chunk;
     }
+    if (ok && R.xDefer > 1) launch_ring_copy_back(s, R.ws->scalars, R.ring, R.nLocal);   // p stopped inside a group: back into the caller's buffer
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
     if (report) fprintf(stderr, "[MgcgGpu] solve: %lld iterations enqueued, loop drained %.0f us after the call began\n", enqueued,
                         std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT0).count());
@@ -991,9 +1108,11 @@ double CgSteps(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
     R.haloOnSide = tuning().haloStream.load(std::memory_order_relaxed) != 0;
     if (ok && restart) ok = cg_enqueue_init(R, true);
     else if (ok) hipLaunchKernelGGL(clear_done_kernel, dim3(1), dim3(1), 0, R.ws->stream, R.ws->scalars);
+    if (ok) cg_xdefer_setup(R, steps);
     const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;      // MGCG_VERBOSE=2: is the host or the device the limit?
     const auto h0 = std::chrono::steady_clock::now();
     for (int k = 0; ok && k < steps; ++k) ok = cg_enqueue_iteration(R, false);
+    if (ok && R.xDefer > 1) launch_ring_copy_back(R.ws->stream, R.ws->scalars, R.ring, R.nLocal);   // (a non-finite residual stops the loop inside a group)
     if (ok) hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(1), 0, R.ws->stream, R.ws->scalars, R.ws->mirror, (volatile int*)&R.ws->hostScalar[2]);
     const auto h1 = std::chrono::steady_clock::now();
     ok = MGCG_HIP(hipStreamSynchronize(R.ws->stream)) && ok;

@@ -33,6 +33,7 @@ if [[ $PART == *d* ]]; then
 run MGCG_PLACEMENT=0
 run MGCG_AUTO_TILES=0
 run MGCG_TILE_SHIFT=19
+run MGCG_X_DEFER=1
 fi
 if [[ $PART == *e* ]]; then
 # every sum in the reference's order: one serial sum of 1.3e8 terms takes half a second, so the full-size SOLVES (hundreds of iterations at

@@ -199,6 +199,13 @@ int         MgcgAbiVersion(void);
  *     cannot form a communicator -- callers must then fall back or fail loudly).
  * (MGCG_COMPRESSION and the MGCG_SPMV_* variables are per-handle defaults of MgcgSetMatrixCompression / MgcgSetSpmv*, read by
  * CreateSparse.)  Knobs whose A/B was settled in rounds 2-4 have been removed with their settled value compiled in.
+ * Loop-shape knob (1), beside the list above:
+ *   x_defer (MGCG_X_DEFER, default 8, at most 8; 1 = one x update per iteration): the one-rank unpreconditioned loop keeps the
+ *     directions of a group of this many iterations in a ring (the caller's p and x_defer - 1 library-owned vectors of the same size,
+ *     held by the MgcgBlas handle) and applies x += alpha p for the whole group, oldest first, in the group's last iteration -- the same
+ *     rounded operations as one term per iteration, so x, r, p and Ap are the same bits after every call.  A solve that stops inside a
+ *     group applies its terms in the stopping iteration.  Several ranks and MGCG keep one term per iteration; if the ring cannot be
+ *     allocated (2 GiB of HBM are always left free) the loop takes x_defer = 1 by itself (MGCG_VERBOSE=2 says so).
  * MgcgSetTuning / MgcgGetTuning take the knob's name or its environment variable; they return 0, or -1 for an unknown
  * name (MgcgGetLastError).  MgcgReloadEnvironment reads all variables again.  Change knobs only while no solve is running. */
 int         MgcgSetTuning(const char* name, int value);
