@@ -133,6 +133,9 @@ SIGNATURES = {
 
 RULE_NATIVE, RULE_CSHARP, RULE_SIMPLE, RULE_HANDMADECL, RULE_VIENNACL = range(5)
 OK, MAXIT_EXCEEDED, NONFINITE, ERROR = 0, 1, 3, -1
+# MgcgSetMatrixCompression modes: off; the best lossless form (row patterns, per-nonzero codes, column tiles); per-nonzero codes only;
+# as the best form, with the propagation-blocking form (class 5) before the column tiles for matrices without locality
+COMPRESSION_OFF, COMPRESSION_BEST, COMPRESSION_CODES, COMPRESSION_PB = range(4)
 
 _LIB = None
 

@@ -31,6 +31,10 @@ constexpr int kXDeferDefault = 8;
 constexpr int kMaxDevices = 64;
 constexpr int kPatMax = 256;         // row-pattern form: distinct rows-as-sequences a matrix may have ...
 constexpr int kPatEntries = 2048;    // ... and nPattern * longest row (the table lives in LDS: 12 bytes per entry)
+constexpr int kPbTileShift = 14;     // propagation-blocking form (class 5, kernels_pb.hip): tiles of 2^14 columns = 128 KB of x in LDS ...
+constexpr int kPbTileWidth = 1 << kPbTileShift;
+constexpr int kPbMaxTiles = 1024;    // ... at most this many (16.7 M columns: pass 2 holds a block's piece table in LDS) ...
+constexpr int kPbRoundCap = 9088;    // ... and rounds of this many entries of a row block (71 KB of LDS in pass 2)
 
 // ---------------------------------------------------------------- errors
 void set_error(const char* fmt, ...);
@@ -89,7 +93,7 @@ bool select_device_only();       // hipSetDevice for the calling thread's device
 inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, kernel); }
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
-void preload_kernels_mg(); void preload_spectrum();
+void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -181,6 +185,18 @@ struct DcsrView {
     int tileWidth;                   // columns per tile (equal-width tiles, <= 2^tileShift)
     int nTiles;
     long long tileRows;              // rows of the analysed matrix
+    // propagation-blocking form (class 5, kernels_pb.hip explains the layout): pbVals != nullptr says the form exists
+    const double* pbVals;
+    const unsigned short* pbCols;
+    const unsigned short* pbPos;
+    double* pbProd;                  // the products of pass 1 (scratch of every product through this form)
+    const unsigned* pbPiece;
+    const int* pbTileStart;
+    const unsigned* pbPieceOff;
+    const int* pbRoundOff;
+    const unsigned short* pbRowBounds;
+    int pbTiles, pbBlocks;
+    long long pbColumns;             // length of x the form was built for
 };
 // ... and what the handle caches per analysed matrix (keyed by the CSR pointers and sizes).
 struct DcsrMatrix {
@@ -194,6 +210,9 @@ struct DcsrMatrix {
     double* tileVals = nullptr; int* tileCols = nullptr; int* tileRowIds = nullptr; int nTiles = 0; long long tileRows = 0;
     unsigned* tilePacked = nullptr; int2* tileHdr = nullptr; int tileShift = 0, tileWidth = 0;
     std::vector<int> tileStart, tileHdrBase;
+    double* pbVals = nullptr; unsigned short* pbCols = nullptr; unsigned short* pbPos = nullptr; double* pbProd = nullptr; unsigned* pbPiece = nullptr;
+    unsigned* pbPieceOff = nullptr; int* pbTileStart = nullptr; int* pbRoundOff = nullptr; unsigned short* pbRowBounds = nullptr;
+    int pbTiles = 0, pbBlocks = 0, pbMaxRounds = 0; long long pbColumns = 0;
     unsigned long long checksum = 0;  // of the CSR arrays the analysis was made from (forms chosen without the caller asking are re-verified per solve)
     int trustedUses = 0;              // per-op products served from this form since its checksum was last verified (dcsr_lookup_op: re-verified every 16th)
     bool automatic = false;           // built by the library's own choice (column tiles for a matrix without locality), not by MgcgSetMatrixCompression
@@ -206,6 +225,8 @@ struct DcsrMatrix {
         v.patternId = patternId; v.patCount = patCount; v.patDelta = patDelta; v.patValue = patValue; v.nPattern = nPattern; v.patWidth = patWidth;
         v.tileVals = tileVals; v.tileCols = tileCols; v.tileRowIds = tileRowIds; v.tileStartHost = tileStart.data(); v.nTiles = nTiles; v.tileRows = tileRows;
         v.tilePacked = tilePacked; v.tileHdr = tileHdr; v.tileHdrBaseHost = tileHdrBase.data(); v.tileShift = tileShift; v.tileWidth = tileWidth;
+        v.pbVals = pbVals; v.pbCols = pbCols; v.pbPos = pbPos; v.pbProd = pbProd; v.pbPiece = pbPiece; v.pbTileStart = pbTileStart; v.pbRoundOff = pbRoundOff;
+        v.pbPieceOff = pbPieceOff; v.pbRowBounds = pbRowBounds; v.pbTiles = pbTiles; v.pbBlocks = pbBlocks; v.pbColumns = pbColumns;
         return v;
     }
 };
@@ -226,7 +247,8 @@ struct MgcgSparse {
     int periodRows = 0;      // rows between strongly coupled windows (a grid plane); 0 = unknown
     int tileRows = 0, tilePlanes = 0;   // banded schedule tile (0 = default)
     int analysedMode = 0;               // the compression mode the cached analyses were built under
-    int compression = 0;                // opt-in: 0 off, 1 best lossless compact form (row patterns, else per-nonzero codes), 2 per-nonzero codes only
+    int compression = 0;                // opt-in: 0 off, 1 best lossless compact form (row patterns, else per-nonzero codes, else column tiles), 2 per-nonzero codes only,
+                                        // 3 as 1 with the propagation-blocking form before the column tiles
     std::vector<mgcg::DcsrMatrix*> analysed;
     // far-band distance found per matrix (the tile order of the row-tile kernel; any value gives the same results, so a stale
     // entry can only cost locality): keyed by the array pointers and the row count
@@ -346,6 +368,12 @@ bool pattern_build(hipStream_t s, const double* elements, const int* rowOffsets,
 bool tiled_build(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces,
                  long long rows, long long nnz, long long rowBase, long long columns, DcsrMatrix* out);
 int launch_spmv_tiled(hipStream_t s, int epilogue, const SpmvArgs& a, const DcsrView& m);
+bool exclusive_scan(hipStream_t s, int* data, long long n);      // in place, n ints whose total fits an int (kernels_tiled.hip)
+// Propagation-blocking form (compression mode 3): usable (out->pbVals != nullptr) for rows whose column tiles never step back, a sampled mean
+// distance from the diagonal of a tile or more, x of 2 .. kPbMaxTiles tiles, nnz < 2^31 and room on the device.
+bool pb_build(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces,
+              long long rows, long long nnz, long long columns, long long meanDistance, DcsrMatrix* out);
+int launch_spmv_pb(hipStream_t s, int epilogue, const SpmvArgs& a, const DcsrView& m);   // whole matrices only; every epilogue, beta != 0 included
 // Cached analysis of a matrix on a handle (nullptr: compression off, not applicable, or the build failed).
 const DcsrMatrix* dcsr_lookup(MgcgSparse* h, const double* elements, const int* rowOffsets, const int* columnIndeces,
                               long long rows, long long nnz, long long rowBase, long long columns = 0,    // columns: length of x (0: unknown, no column tiling)

@@ -218,6 +218,10 @@ void DcsrMatrix::release()
     if (tileHdr) (void)hipFree(tileHdr);
     tileVals = nullptr; tileCols = nullptr; tileRowIds = nullptr; nTiles = 0; tileRows = 0; tileStart.clear();
     tilePacked = nullptr; tileHdr = nullptr; tileShift = 0; tileWidth = 0; tileHdrBase.clear(); checksum = 0;
+    for (void* p : { (void*)pbVals, (void*)pbCols, (void*)pbPos, (void*)pbProd, (void*)pbPiece, (void*)pbTileStart, (void*)pbPieceOff, (void*)pbRoundOff, (void*)pbRowBounds })
+        if (p) (void)hipFree(p);
+    pbVals = nullptr; pbCols = nullptr; pbPos = nullptr; pbProd = nullptr; pbPiece = nullptr; pbTileStart = nullptr; pbRoundOff = nullptr; pbPieceOff = nullptr;
+    pbRowBounds = nullptr; pbTiles = pbBlocks = pbMaxRounds = 0; pbColumns = 0;
     colCode = valCode = nullptr; deltaDict = nullptr; valueDict = nullptr; nDelta = nValue = 0;
     patternId = nullptr; patCount = nullptr; patDelta = nullptr; patValue = nullptr; nPattern = patWidth = 0;
     usable = false;

@@ -330,7 +330,7 @@ int launch_spmv_tiled(hipStream_t s, int epilogue, const SpmvArgs& a, const Dcsr
 }
 
 // ---------------------------------------------------------------- build
-static bool exclusive_scan(hipStream_t s, int* data, long long n)
+bool exclusive_scan(hipStream_t s, int* data, long long n)
 {
     const long long perBlock = (long long)kScanBlock * kScanPer;
     const long long nBlocks = (n + perBlock - 1) / perBlock;

@@ -107,7 +107,7 @@ DeviceState* device_state()
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, pd) == hipSuccess) d->numCu = prop.multiProcessorCount;
         preload_kernels_spmv(); preload_kernels_rowtile(); preload_kernels_blas1(); preload_solver(); preload_ops();
-        preload_kernels_rows(); preload_kernels_mg(); preload_kernels_dcsr(); preload_kernels_tiled(); preload_comm(); preload_spectrum();
+        preload_kernels_rows(); preload_kernels_mg(); preload_kernels_dcsr(); preload_kernels_tiled(); preload_kernels_pb(); preload_comm(); preload_spectrum();
     }
     return d;
 }
@@ -307,13 +307,24 @@ const DcsrMatrix* dcsr_lookup(MgcgSparse* h, const double* elements, const int* 
     }
     // 1. one byte per row (few distinct rows-as-sequences), 2. one or two bytes per nonzero (few distinct offsets / values;
     //    the wide loads of that kernel need 16-byte aligned values and short average rows: one pass per 64-row block)
-    // 3. a column-tiled copy for matrices whose gathers have no locality (sorted rows, entries far from the diagonal)
-    if (h->compression == 1 && avg <= 32.0 && pattern_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, rowBase, m) && m->patternId != nullptr) {
+    // 3. for matrices whose gathers have no locality (sorted rows, entries far from the diagonal): mode 3 first the propagation-blocking
+    //    form (x from LDS, kernels_pb.hip), then -- modes 1 and 3 -- the column-tiled copy
+    const bool best = h->compression == 1 || h->compression == 3;
+    if (best && avg <= 32.0 && pattern_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, rowBase, m) && m->patternId != nullptr) {
         m->usable = true;
     } else if ((((uintptr_t)elements) & 15) == 0 && avg <= 7.75) {
         if (!dcsr_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, rowBase, m)) { std::lock_guard<std::mutex> lock(g_analysedMutex); m->release(); identify(); }
     }
-    if (!m->usable && h->compression == 1 && columns > 0) {
+    if (!m->usable && h->compression == 3 && columns > 0) {
+        long long meanDistance = 0;
+        (void)spmv_period(h, rowOffsets, columnIndeces, rows, rowBase, nullptr, &meanDistance);
+        if (!pb_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, columns, meanDistance, m)) { std::lock_guard<std::mutex> lock(g_analysedMutex); m->release(); identify(); }
+        else if (m->pbVals != nullptr) {
+            m->checksum = csr_checksum(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, (unsigned long long*)(h->ws.devInts + 4));
+            m->usable = true;
+        }
+    }
+    if (!m->usable && best && columns > 0) {
         if (tiled_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, rowBase, columns, m) && m->tileVals != nullptr) m->usable = true;
     }
     h->analysedMode = h->compression;                  // (also when the mode came from MGCG_COMPRESSION, not from the setter)
@@ -349,6 +360,7 @@ int launch_spmv_auto(hipStream_t s, int epilogue, const SpmvArgs& a, const SpmvC
 {
     if (dc != nullptr && dc->usable && a.elementsCount >= 8) {
         const DcsrView v = dc->view();
+        if (v.pbVals != nullptr) return launch_spmv_pb(s, epilogue, a, v);                 // (both passes; y is read once per row: beta != 0 too)
         if (v.tileVals == nullptr) return launch_spmv_rows(s, epilogue, a, &v, cfg.gridBlocks, cfg.periodRows);
         if (!(epilogue == EPI_AXPBY && a.beta != 0.0)) return launch_spmv_tiled(s, epilogue, a, v);   // (beta != 0 reads y: CSR kernels)
     }
@@ -377,7 +389,7 @@ int launch_spmv_range(hipStream_t s, int epilogue, const SpmvArgs& whole, const 
         DcsrView v = dc->view();
         v.rowBase += r0;
         if (v.patternId) v.patternId += r0;
-        if (v.tileVals != nullptr) {                                            // the tiled passes cover whole matrices only: CSR kernels for a row range
+        if (v.tileVals != nullptr || v.pbVals != nullptr) {                     // the tiled passes cover whole matrices only: CSR kernels for a row range
             if (c.kernel == 0) c.kernel = spmv_auto_kernel(whole.rowCount > 0 ? (double)whole.elementsCount / (double)whole.rowCount : 0.0);
             return launch_spmv(s, epilogue, a, c);
         }
@@ -514,7 +526,7 @@ MgcgSparse* CreateSparse(void)
     const char* g = getenv("MGCG_SPMV_GRID");         if (g) h->gridBlocks = atoi(g);
     const char* tr = getenv("MGCG_SPMV_TILE_ROWS");   if (tr) h->tileRows = atoi(tr);
     const char* tp = getenv("MGCG_SPMV_TILE_PLANES"); if (tp) h->tilePlanes = atoi(tp);
-    const char* cm = getenv("MGCG_COMPRESSION");      if (cm) { const int v = atoi(cm); const int mode = v < 0 ? 0 : (v > 2 ? 1 : v); h->compression = mode; if (mode != 0) h->analysedMode = mode; }   // as MgcgSetMatrixCompression
+    const char* cm = getenv("MGCG_COMPRESSION");      if (cm) { const int v = atoi(cm); const int mode = v < 0 ? 0 : (v > 3 ? 1 : v); h->compression = mode; if (mode != 0) h->analysedMode = mode; }   // as MgcgSetMatrixCompression
     const char* p = getenv("MGCG_SPMV_PERIOD");       if (p) { h->periodRows = atoi(p); if (h->periodRows > 0) h->flags |= 4; }
     return h;
 }
@@ -533,7 +545,7 @@ void MgcgAnalysisClear(MgcgSparse* h);
 void MgcgSetMatrixCompression(MgcgSparse* h, int enable)
 {
     if (!h) return;
-    const int mode = enable < 0 ? 0 : (enable > 2 ? 1 : enable);
+    const int mode = enable < 0 ? 0 : (enable > 3 ? 1 : enable);
     if (mode != 0 && h->analysedMode != 0 && mode != h->analysedMode && !h->analysed.empty()) MgcgAnalysisClear(h);   // another form was asked for: analyse again
     if (mode != 0) h->analysedMode = mode;
     h->compression = mode;
@@ -556,6 +568,7 @@ int MgcgAnalysisInfo(MgcgSparse* h, int index, int* distinctOffsets, int* distin
     if (rows) *rows = m->rows;
     if (nnz) *nnz = m->nnz;
     if (!m->usable) return 0;
+    if (m->pbVals != nullptr) { if (distinctOffsets) *distinctOffsets = m->pbTiles; if (distinctValues) *distinctValues = m->pbMaxRounds; return 5; }   // class 5: propagation blocking
     if (m->tileVals != nullptr) { if (distinctOffsets) *distinctOffsets = m->nTiles; if (distinctValues) *distinctValues = 0; return 4; }   // class 4: column tiles
     return pat ? 3 : (m->valCode ? 2 : 1);   // 3 = one byte per row, 2 = offset + value code per nonzero, 1 = offset code per nonzero, 0 = plain CSR
 }

@@ -2,7 +2,7 @@
 // problem in compile-time constants of each Main; here they are flags).  Builds a 5/7-point Poisson system in HBM,
 // runs CG or MGCG on one device or on R devices of this process and prints one JSON line.
 //   mgcg_solve [--nx N] [--ny N] [--nz N] [--mgcg] [--levels L] [--nu K] [--nu-coarse K] [--omega W] [--linear-transfer] [--tol T] [--rel-tol T]
-//              [--min-it I] [--max-it I] [--rule native|csharp|simple|viennacl|handmadecl] [--compression 0|1|2] [--b V] [--x0 V] [--ranks R]
+//              [--min-it I] [--max-it I] [--rule native|csharp|simple|viennacl|handmadecl] [--compression 0|1|2|3] [--b V] [--x0 V] [--ranks R]
 //              [--write-x FILE]     (the solution as raw little-endian doubles, for element-by-element comparison: MgcgMain.cs:129-162 compares so)
 // --ranks R > 1: the grid is split into R equal z-slabs, one per device of this process and one host thread per device (the shape of the
 // reference's ConjugateGradientParallelGpu), communicators from MgcgCommInitAll, SolveParallel / MgSetupParallel + SolveMgParallel per rank.

@@ -261,11 +261,20 @@ void   MgcgSetSpmvTile(MgcgSparse* cusparse, int tileRows, int tilePlanes);
  *       class 4  a column-tiled copy (16 bytes per nonzero MORE, not fewer) for sorted rows whose entries are spread over
  *                an x far larger than the L2: the gathers of a pass stay inside one 4 MiB window of x,
  *       class 0  otherwise (plain CSR kernels);
- *   enable = 2: per-nonzero codes only (classes 2 / 1 / 0);   enable = 0: off.
+ *   enable = 3: the same choice as 1, but for a matrix without locality the propagation-blocking form comes before the column tiles
+ *   (order 3, 2 / 1, 5, 4, 0) --
+ *       class 5  x gathered from LDS in tiles of 16384 columns (pass 1 stores every product, pass 2 sums each block of 1024 rows in
+ *                rounds of 9088 entries in stored order and applies the epilogue, beta != 0 included); about 20 bytes per nonzero MORE
+ *                (10 B of entries, 8 B of products, 2 B of positions) plus 12 B per (row block, tile) and 2 KB per (block, round).
+ *                Taken only for rows whose column tiles never step back (sorted rows suffice), a sampled mean distance from the
+ *                diagonal of at least one tile, 2 .. 1024 tiles (x of at most 16.7 M columns), nnz < 2^31 and at most half of
+ *                the free device memory; otherwise mode 3 falls through to class 4 and class 0 as mode 1 does (MGCG_VERBOSE=1
+ *                prints why).  Whole products only: row ranges and multigrid levels use the other forms;
+ *   enable = 2: per-nonzero codes only (classes 2 / 1 / 0);   enable = 0: off;   enable >= 4 means 1.
  * The cache is keyed by the array pointers and sizes: a caller that rewrites a matrix in place must call
  * MgcgAnalysisClear.  MgcgAnalysisInfo(index) reports a cached analysis: returns the class (-1 past the end);
  * distinctOffsets / distinctValues receive, for class 3, the number of distinct rows and the longest row; for class 4
- * the number of column tiles and 0. */
+ * the number of column tiles and 0; for class 5 the number of column tiles and the most rounds any row block takes. */
 void   MgcgSetMatrixCompression(MgcgSparse* cusparse, int enable);
 void   MgcgAnalysisClear(MgcgSparse* cusparse);
 int    MgcgAnalysisInfo(MgcgSparse* cusparse, int index, int* distinctOffsets, int* distinctValues, long long* rows, long long* nnz);
