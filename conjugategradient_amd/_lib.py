@@ -97,6 +97,8 @@ SIGNATURES = {
     "MgcgMinMaxColumn": (_i, [_vp, _i, _pi, _pi]),
     "MgcgFill": (None, [_vp, _d]),
     "SolveEx": (_i, [_vp] * 11 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
+    "SolveBlockEx": (_i, [_vp] * 11 + [_i, _i, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "CsrMVBlock": (None, [_vp] * 7 + [_i, _i, _i]),
     "MgSetup": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _i, _d]),
     "MgSetupParallel": (_vp, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _d]),
     "MgDestroy": (None, [_vp]),
@@ -133,6 +135,7 @@ SIGNATURES = {
 
 RULE_NATIVE, RULE_CSHARP, RULE_SIMPLE, RULE_HANDMADECL, RULE_VIENNACL = range(5)
 OK, MAXIT_EXCEEDED, NONFINITE, ERROR = 0, 1, 3, -1
+BLOCK_MAX_K = 8      # right-hand sides of one SolveBlockEx / CsrMVBlock call
 # MgcgSetMatrixCompression modes: off; the best lossless form (row patterns, per-nonzero codes, column tiles); per-nonzero codes only;
 # as the best form, with the propagation-blocking form (class 5) before the column tiles for matrices without locality
 COMPRESSION_OFF, COMPRESSION_BEST, COMPRESSION_CODES, COMPRESSION_PB = range(4)

@@ -28,6 +28,7 @@ constexpr int kMaxGrid = kNumCu * 8; // 8 resident 256-thread workgroups per CU 
 constexpr int kMaxPartials = kNumCu * 32; // single-wavefront workgroups: up to 32 per CU, one partial sum each
 constexpr int kXDeferMax = 8;         // longest group of the deferred x update (MGCG_X_DEFER): directions kept in the ring
 constexpr int kXDeferDefault = 8;
+constexpr int kBlockMaxK = 8;         // right-hand sides of one block CG call (SolveBlockEx / CsrMVBlock)
 constexpr int kMaxDevices = 64;
 constexpr int kPatMax = 256;         // row-pattern form: distinct rows-as-sequences a matrix may have ...
 constexpr int kPatEntries = 2048;    // ... and nPattern * longest row (the table lives in LDS: 12 bytes per entry)
@@ -93,7 +94,7 @@ bool select_device_only();       // hipSetDevice for the calling thread's device
 inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, kernel); }
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
-void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb();
+void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -132,6 +133,7 @@ struct HostMirror {
 };
 
 // ---------------------------------------------------------------- handles
+struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct Workspace {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -145,11 +147,16 @@ struct Workspace {
     // the library-owned slots 1 .. kXDeferMax-1 of the deferred x update's ring of p (slot 0 is the caller's p), ringSize entries each
     double* ring[kXDeferMax] = {};
     long long ringSize = 0;
+    // block CG (kernels_block.hip), allocated at its first call and kept: 3 regions of kBlockMaxK * kMaxPartials partial sums, one
+    // region per column of kMaxPartials doubles, and the per-column scalars
+    double* blockPartials = nullptr;
+    BlockScalars* blockScalars = nullptr;
     bool init();
     void destroy();
     bool ensure_trace(int cap);
     bool ensure_ring(int slots, long long n);    // slots 1 .. slots-1 allocated with >= n entries (keeps what is there)
     void free_ring();
+    bool ensure_block();                         // blockPartials / blockScalars (kernels_block.hip)
 };
 
 } // namespace mgcg
@@ -461,6 +468,28 @@ struct FinalizeArgs {
     double tol; int minIt; int maxIt; int rule;
     int preconditioned;     // 1: beta = rzNew/rr(rz) computed by finalize_precond instead; 2: by this kernel from the all-reduced sc->rzNew
 };
+// The stop decision of one iteration (the five rules of SURVEY.md 3.5): residual to show, stop or not, status.  Shared by the
+// single-vector loop (kernels_blas1.hip) and the block loop (kernels_block.hip); it reads f.rule, f.tol, f.minIt and f.maxIt only.
+struct StopDecision { double res, shown; bool stop; int status; };
+__device__ __forceinline__ StopDecision decide_stop(const FinalizeArgs& f, double rrNew, double inf, double rr0, int it)
+{
+    StopDecision d;
+    d.res = sqrt(rrNew);
+    if (f.rule == MGCG_RULE_HANDMADECL) d.res = inf;
+    d.shown = d.res;
+    bool converged;
+    switch (f.rule) {
+    case MGCG_RULE_NATIVE:   converged = (f.minIt <= it) && (d.res < f.tol); break;
+    case MGCG_RULE_SIMPLE:   converged = (f.minIt < it) && (d.res < f.tol); break;
+    case MGCG_RULE_VIENNACL: d.shown = sqrt(rrNew / rr0); converged = (f.minIt < it) && (rrNew / rr0 < f.tol * f.tol); break;
+    default:                 converged = (it >= f.minIt) && (it <= f.maxIt) && (d.res < f.tol); break;  // ConjugateGradient.cs:56-79
+    }
+    d.status = MGCG_OK;
+    d.stop = converged;
+    if (!d.stop && it >= f.minIt && it > f.maxIt) { d.stop = true; d.status = MGCG_MAXIT_EXCEEDED; }
+    if (!d.stop && !(d.res == d.res && fabs(d.res) <= 1.79e308)) { d.stop = true; d.status = MGCG_NONFINITE; }
+    return d;
+}
 // Single-workgroup kernels that turn partial sums into the loop's scalars.
 void launch_reduce_to(hipStream_t s, const double* partials, int n, double* dst, const int* done);          // dst = sum
 void launch_reduce2_to(hipStream_t s, const double* pA, int nA, double* dstA, const double* pB, int nB, double* dstB, const int* done);   // two sums, one launch

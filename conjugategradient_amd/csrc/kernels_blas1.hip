@@ -496,28 +496,6 @@ void launch_update_xp(hipStream_t s, const CgScalars* sc, double* x, double* p, 
     else hipLaunchKernelGGL((update_xp_kernel<false, false>), dim3(grid_for(n, 1)), dim3(kBlock), 0, s, sc, x, p, z, n);
 }
 
-// The stop decision of one iteration (the five rules of SURVEY.md 3.5): residual to show, stop or not, status.
-struct StopDecision { double res, shown; bool stop; int status; };
-__device__ __forceinline__ StopDecision decide_stop(const FinalizeArgs& f, double rrNew, double inf, double rr0, int it)
-{
-    StopDecision d;
-    d.res = sqrt(rrNew);
-    if (f.rule == MGCG_RULE_HANDMADECL) d.res = inf;
-    d.shown = d.res;
-    bool converged;
-    switch (f.rule) {
-    case MGCG_RULE_NATIVE:   converged = (f.minIt <= it) && (d.res < f.tol); break;
-    case MGCG_RULE_SIMPLE:   converged = (f.minIt < it) && (d.res < f.tol); break;
-    case MGCG_RULE_VIENNACL: d.shown = sqrt(rrNew / rr0); converged = (f.minIt < it) && (rrNew / rr0 < f.tol * f.tol); break;
-    default:                 converged = (it >= f.minIt) && (it <= f.maxIt) && (d.res < f.tol); break;  // ConjugateGradient.cs:56-79
-    }
-    d.status = MGCG_OK;
-    d.stop = converged;
-    if (!d.stop && it >= f.minIt && it > f.maxIt) { d.stop = true; d.status = MGCG_MAXIT_EXCEEDED; }
-    if (!d.stop && !(d.res == d.res && fabs(d.res) <= 1.79e308)) { d.stop = true; d.status = MGCG_NONFINITE; }
-    return d;
-}
-
 // The x/p update with the iteration's finalisation folded in (single rank, no preconditioner: z = r).  Every workgroup reduces the
 // r.r (and max|r|) partial sums of update_r in the order finalize_kernel uses and takes the same decision from the values update_r
 // froze (fRr, fRr0, fAlpha, fIteration, fDone); workgroup 0 alone rewrites the live scalars, the host mirror and the trace, which

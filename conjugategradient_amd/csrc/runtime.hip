@@ -107,7 +107,7 @@ DeviceState* device_state()
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, pd) == hipSuccess) d->numCu = prop.multiProcessorCount;
         preload_kernels_spmv(); preload_kernels_rowtile(); preload_kernels_blas1(); preload_solver(); preload_ops();
-        preload_kernels_rows(); preload_kernels_mg(); preload_kernels_dcsr(); preload_kernels_tiled(); preload_kernels_pb(); preload_comm(); preload_spectrum();
+        preload_kernels_rows(); preload_kernels_mg(); preload_kernels_dcsr(); preload_kernels_tiled(); preload_kernels_pb(); preload_kernels_block(); preload_comm(); preload_spectrum();
     }
     return d;
 }
@@ -138,6 +138,9 @@ void Workspace::destroy()
     if (devInts) (void)hipFree(devInts);
     if (trace) (void)hipFree(trace);
     free_ring();
+    if (blockPartials) (void)hipFree(blockPartials);
+    if (blockScalars) (void)hipFree((void*)blockScalars);
+    blockPartials = nullptr; blockScalars = nullptr;
     partials = nullptr; scalars = nullptr; mirror = nullptr; hostScalar = nullptr; devInts = nullptr; trace = nullptr; traceCap = 0;
 }
 bool Workspace::ensure_trace(int cap)

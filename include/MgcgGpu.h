@@ -319,6 +319,29 @@ int SolveEx(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
             int* iteration, double* residual,
             double* residualTrace, int traceCapacity);
 
+/* ---- block CG: k right-hand sides per matrix pass (one rank, no preconditioner, plain CSR) ---- */
+/* k (1..8) independent CG solves on one matrix, each iteration reading the matrix once for all k.  Column j of x, b and r lies at
+ * [j*count, (j+1)*count) of its vector (k*count entries each); Ap and p are k*count entries of work space whose layout is internal
+ * (row-interleaved).  Per column: the stop rule `rule` of SolveEx, its own iteration / residual / status (iteration[], residual[],
+ * status[]: k entries each, may be NULL); a column that has stopped is not changed by later iterations.  residualTrace (may be
+ * NULL): column j's trace at j*traceCapacity.  Every column is exactly the classical CG of SolveEx on that column (the k recurrences
+ * share the matrix pass only); under dot_order = 1 its trace, iterate, residual and iteration equal SolveEx's / the oracle's bit for
+ * bit.  The matrix is always read as plain CSR, whatever the handle's compression mode; placement draw and x_defer do not apply.
+ * Returns MGCG_ERROR on a library error (k outside 1..8, a null handle, a vector that is too small; MgcgGetLastError), else the
+ * worst column status (MGCG_NONFINITE > MGCG_MAXIT_EXCEEDED > MGCG_OK). */
+int SolveBlockEx(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                 int elementsCount, int count, int k,
+                 double allowableResidual, int minIteration, int maxIteration, int rule,
+                 int iteration[], double residual[], int status[], double residualTrace[], int traceCapacity);
+/* y = A x for k (1..8) columns of a square count x count CSR matrix on raw device pointers, column j of x and y at [j*count, (j+1)*count),
+ * the matrix read once.  Every row adds its rounded products in stored order: column j equals the stored-order product of column j alone
+ * (CsrMV with alpha 1, beta 0 under dot_order = 1, or by its lane = row kernels), bit for bit.  Plain CSR, whatever the handle's
+ * compression mode.  Stream-ordered; errors: MgcgGetLastError. */
+void CsrMVBlock(MgcgSparse* cusparse, MgcgMatDescr* matDescr, double* y, const double* elements, const int* rowOffsets,
+                const int* columnIndeces, const double* x, int elementsCount, int count, int k);
+
 /* ---- multigrid preconditioner (defined by this build; the reference's "Mgcg" never implemented it) ---- */
 typedef struct MgcgMg MgcgMg;
 /* Geometric cell-centred hierarchy on an nx*ny*nz lexicographic grid for the CSR matrix in the
