@@ -433,8 +433,6 @@ int  launch_copy_dot(hipStream_t s, double* p, const double* r, long long n, dou
 // alpha = sc->rr / sc->pAp ; x += alpha p ; r -= alpha Ap ; partial r.r (and max|r| in partials2 when wantInf)
 int  launch_update_xr(hipStream_t s, const CgScalars* sc, double* x, double* r, const double* p, const double* Ap,
                       long long n, double* partials, double* partialsInf);
-// p = z + beta p with beta = sc->beta ; skipped when sc->done
-void launch_update_p(hipStream_t s, const CgScalars* sc, double* p, const double* z, long long n);
 // the loop's own split: r -= alpha Ap (+ r.r), then x += alpha p and p = z + beta p in one pass over p
 // pApPartials != nullptr: p.Ap is still in nPAp per-workgroup partial sums; every workgroup adds them up itself (same fixed
 // order everywhere) instead of a separate reduction launch.  partials (output) must not overlap pApPartials.
@@ -495,7 +493,7 @@ void launch_reduce_to(hipStream_t s, const double* partials, int n, double* dst,
 void launch_reduce2_to(hipStream_t s, const double* pA, int nA, double* dstA, const double* pB, int nB, double* dstB, const int* done);   // two sums, one launch
 void launch_finalize(hipStream_t s, const double* partials, const double* partialsInf, int n, bool reduceFirst, const FinalizeArgs& f);
 void launch_finalize_precond(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc);  // rzNew -> beta, rr
-void launch_init_scalars(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror, int rule);
+void launch_init_scalars(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror);
 
 // ---------------------------------------------------------------- multigrid kernels
 // dinvUniform: dinv[i] == dinvScalar for every i (the array is then not read)

@@ -64,6 +64,21 @@ template <bool NTV, typename T> __device__ __forceinline__ T ldv(const T* p) { i
 template <bool NTV, typename T> __device__ __forceinline__ void stv(const T& v, T* p) { if constexpr (NTV) __builtin_nontemporal_store(v, p); else *p = v; }
 static bool vec_nt(long long n) { return n > 3000000; }
 
+// Run-time flags to template arguments: go(std::bool_constant<flag>...).  The kernels' launches name every form they instantiate here.
+template <typename Go> static void with_flags(Go go) { go(); }
+template <typename Go, typename... Rest> static void with_flags(Go go, bool flag, Rest... rest)
+{
+    if (flag) with_flags([&](auto... c) { go(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { go(std::false_type{}, c...); }, rest...);
+}
+// The three forms of the loop's x/p passes, go(V2, NTV): 16-byte accesses with the streaming hint, without it, or one element at a time.
+template <typename Go> static void with_v2_nt(bool v2, bool nt, Go go)
+{
+    if (v2 && nt) go(std::true_type{}, std::true_type{});
+    else if (v2) go(std::true_type{}, std::false_type{});
+    else go(std::false_type{}, std::false_type{});
+}
+
 template <bool V2, typename F2, typename F1>
 __device__ __forceinline__ void grid_stride(long long n, F2 f2, F1 f1)
 {
@@ -314,6 +329,18 @@ int launch_copy_dot(hipStream_t s, double* p, const double* r, long long n, doub
     return grid;
 }
 
+// The element step of update_xr_kernel and update_r_kernel (one element, or the two halves of a 16-byte pair in turn), in two parts so
+// that the callers can store r in between: r + (-alpha)*Ap with the product rounded first, then the new r's share of r.r and, with INF,
+// of max|r|.
+__device__ __forceinline__ double r_step(double malpha, double ap, double r) { double u = malpha * ap; return r + u; }
+template <bool INF, typename... T>
+__device__ __forceinline__ void r_sums(double& acc, double& mx, T... rv)
+{
+    const double q[] = { rv * rv... };
+    for (double v : q) acc += v;
+    if (INF) { const double a[] = { fabs(rv)... }; for (double v : a) mx = v > mx ? v : mx; }
+}
+
 // alpha = rr / pAp ; x = x + alpha*p ; r = r + (-alpha)*Ap ; partial r.r [, partial max|r|]
 // (ConjugateGradientCpu.cs:71-74 in one pass over x, p, r, Ap)
 template <bool V2, bool INF>
@@ -331,15 +358,13 @@ __global__ __launch_bounds__(kBlock) void update_xr_kernel(const CgScalars* __re
         [&](long long i) {
             d2 pv = *(const d2*)(p + i); d2 xv = *(d2*)(x + i); d2 av = *(const d2*)(Ap + i); d2 rv = *(d2*)(r + i);
             double t0 = alpha * pv.x; double t1 = alpha * pv.y; xv.x = xv.x + t0; xv.y = xv.y + t1; *(d2*)(x + i) = xv;
-            double u0 = malpha * av.x; double u1 = malpha * av.y; rv.x = rv.x + u0; rv.y = rv.y + u1; *(d2*)(r + i) = rv;
-            double q0 = rv.x * rv.x; double q1 = rv.y * rv.y; acc += q0; acc += q1;
-            if (INF) { double a0 = fabs(rv.x); double a1 = fabs(rv.y); mx = a0 > mx ? a0 : mx; mx = a1 > mx ? a1 : mx; }
+            rv.x = r_step(malpha, av.x, rv.x); rv.y = r_step(malpha, av.y, rv.y); *(d2*)(r + i) = rv;
+            r_sums<INF>(acc, mx, rv.x, rv.y);
         },
         [&](long long i) {
             double t = alpha * p[i]; x[i] = x[i] + t;
-            double u = malpha * Ap[i]; double rv = r[i] + u; r[i] = rv;
-            double q = rv * rv; acc += q;
-            if (INF) { double a0 = fabs(rv); mx = a0 > mx ? a0 : mx; }
+            double rv = r_step(malpha, Ap[i], r[i]); r[i] = rv;
+            r_sums<INF>(acc, mx, rv);
         });
     const double t = block_sum(acc, s_red);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
@@ -354,10 +379,9 @@ int launch_update_xr(hipStream_t s, const CgScalars* sc, double* x, double* r, c
     const bool v2 = al16(x) && al16(r) && al16(p) && al16(Ap);
     const int grid = grid_for(n, v2 ? 4 : 2);
     const bool inf = partialsInf != nullptr;
-#define GO(V, I) hipLaunchKernelGGL((update_xr_kernel<V, I>), dim3(grid), dim3(kBlock), 0, s, sc, x, r, p, Ap, n, partials, partialsInf)
-    if (v2) { if (inf) GO(true, true); else GO(true, false); }
-    else { if (inf) GO(false, true); else GO(false, false); }
-#undef GO
+    with_flags([&](auto V2, auto INF) {
+        hipLaunchKernelGGL((update_xr_kernel<V2.value, INF.value>), dim3(grid), dim3(kBlock), 0, s, sc, x, r, p, Ap, n, partials, partialsInf);
+    }, v2, inf);
     if (dot_reference_order()) {
         launch_dot_serial(s, r, r, n, partials, nullptr);
         if (inf) hipLaunchKernelGGL(reduce_inplace_kernel, dim3(1), dim3(kBlock), 0, s, partialsInf, grid, 1, (const int*)nullptr);   // max of the partial maxima (order-free)
@@ -396,17 +420,12 @@ __global__ __launch_bounds__(kBlock) void update_r_kernel(CgScalars* __restrict_
     }
     const double malpha = -alpha;
     double acc = 0.0, mx = 0.0;
-    auto one = [&](long long i) {
-        double u = malpha * Ap[i]; double rv = r[i] + u; r[i] = rv;
-        double q = rv * rv; acc += q;
-        if (INF) { double a0 = fabs(rv); mx = a0 > mx ? a0 : mx; }
-    };
+    auto one = [&](long long i) { double rv = r_step(malpha, Ap[i], r[i]); r[i] = rv; r_sums<INF>(acc, mx, rv); };
     if constexpr (V2) {
         d2* r2 = (d2*)r; const d2* a2 = (const d2*)Ap;
         auto fin = [&](d2& rv, const d2& av) {
-            double u0 = malpha * av.x; double u1 = malpha * av.y; rv.x = rv.x + u0; rv.y = rv.y + u1;
-            double q0 = rv.x * rv.x; double q1 = rv.y * rv.y; acc += q0; acc += q1;
-            if (INF) { double a0 = fabs(rv.x); double a1 = fabs(rv.y); mx = a0 > mx ? a0 : mx; mx = a1 > mx ? a1 : mx; }
+            rv.x = r_step(malpha, av.x, rv.x); rv.y = r_step(malpha, av.y, rv.y);
+            r_sums<INF>(acc, mx, rv.x, rv.y);
         };
         chunk_pairs(n >> 1, [&](long long i, bool two) {
             const long long j = two ? i + kBlock : i;
@@ -438,11 +457,9 @@ int launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, l
     if (grid > want) grid = want;
     const bool inf = partialsInf != nullptr;
     const bool nt = vec_nt(n);
-#define GO(V, I) do { if (nt) hipLaunchKernelGGL((update_r_kernel<V, I, true>), dim3(grid), dim3(kBlock), 0, s, sc, r, Ap, n, partials, partialsInf, pApPartials, nPAp, freeze ? 1 : 0); \
-                      else hipLaunchKernelGGL((update_r_kernel<V, I, false>), dim3(grid), dim3(kBlock), 0, s, sc, r, Ap, n, partials, partialsInf, pApPartials, nPAp, freeze ? 1 : 0); } while (0)
-    if (v2) { if (inf) GO(true, true); else GO(true, false); }
-    else { if (inf) GO(false, true); else GO(false, false); }
-#undef GO
+    with_flags([&](auto V2, auto INF, auto NTV) {
+        hipLaunchKernelGGL((update_r_kernel<V2.value, INF.value, NTV.value>), dim3(grid), dim3(kBlock), 0, s, sc, r, Ap, n, partials, partialsInf, pApPartials, nPAp, freeze ? 1 : 0);
+    }, v2, inf, nt);
     if (dot_reference_order()) {
         launch_dot_serial(s, r, r, n, partials, &sc->done);
         if (inf) hipLaunchKernelGGL(reduce_inplace_kernel, dim3(1), dim3(kBlock), 0, s, partialsInf, grid, 1, (const int*)&sc->done);
@@ -451,15 +468,12 @@ int launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, l
     return grid;
 }
 
-// x = x + alpha*p (whenever the iteration ran: sc->pad is the finalisation kernel's "x pending" mark) and, unless the
-// stop test fired, p = z + beta*p.
+// The element pass of update_xp_kernel and update_xp_final_kernel: x = x + alpha*p and, unless this iteration stopped the loop (stop: x
+// only), p = z + beta*p.  Every product is rounded, then added; p is read once for both.
 template <bool V2, bool NTV>
-__global__ __launch_bounds__(kBlock) void update_xp_kernel(const CgScalars* __restrict__ sc, double* __restrict__ x, double* __restrict__ p,
-                                                           const double* __restrict__ z, long long n)
+__device__ __forceinline__ void xp_pass(double alpha, double beta, bool stop, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ z, long long n)
 {
-    if (sc->pad == 0) return;                   // this iteration did not run (the loop had already stopped)
-    const double alpha = sc->alpha, beta = sc->beta;
-    if (sc->done != 0) {                        // the iteration that stopped the loop: x only
+    if (stop) {
         grid_stride<V2>(n,
             [&](long long i) { d2 pv = *(const d2*)(p + i); d2 xv = *(d2*)(x + i); double t0 = alpha * pv.x; double t1 = alpha * pv.y; xv.x = xv.x + t0; xv.y = xv.y + t1; *(d2*)(x + i) = xv; },
             [&](long long i) { double t = alpha * p[i]; x[i] = x[i] + t; });
@@ -486,93 +500,101 @@ __global__ __launch_bounds__(kBlock) void update_xp_kernel(const CgScalars* __re
         grid_stride<false>(n, [&](long long) {}, one);
     }
 }
+
+// x = x + alpha*p (whenever the iteration ran: sc->pad is the finalisation kernel's "x pending" mark) and, unless the
+// stop test fired, p = z + beta*p.
+template <bool V2, bool NTV>
+__global__ __launch_bounds__(kBlock) void update_xp_kernel(const CgScalars* __restrict__ sc, double* __restrict__ x, double* __restrict__ p,
+                                                           const double* __restrict__ z, long long n)
+{
+    if (sc->pad == 0) return;                   // this iteration did not run (the loop had already stopped)
+    const double alpha = sc->alpha, beta = sc->beta;
+    xp_pass<V2, NTV>(alpha, beta, sc->done != 0, x, p, z, n);   // (done: this is the iteration that stopped the loop)
+}
 void launch_update_xp(hipStream_t s, const CgScalars* sc, double* x, double* p, const double* z, long long n)
 {
     if (n <= 0) return;
     const bool v2 = al16(x) && al16(p) && al16(z);
-    const bool nt = vec_nt(n);
-    if (v2 && nt) hipLaunchKernelGGL((update_xp_kernel<true, true>), dim3(grid_for(n, 2)), dim3(kBlock), 0, s, sc, x, p, z, n);
-    else if (v2) hipLaunchKernelGGL((update_xp_kernel<true, false>), dim3(grid_for(n, 2)), dim3(kBlock), 0, s, sc, x, p, z, n);
-    else hipLaunchKernelGGL((update_xp_kernel<false, false>), dim3(grid_for(n, 1)), dim3(kBlock), 0, s, sc, x, p, z, n);
+    with_v2_nt(v2, vec_nt(n), [&](auto V2, auto NTV) {
+        hipLaunchKernelGGL((update_xp_kernel<V2.value, NTV.value>), dim3(grid_for(n, V2.value ? 2 : 1)), dim3(kBlock), 0, s, sc, x, p, z, n);
+    });
 }
 
-// The x/p update with the iteration's finalisation folded in (single rank, no preconditioner: z = r).  Every workgroup reduces the
-// r.r (and max|r|) partial sums of update_r in the order finalize_kernel uses and takes the same decision from the values update_r
-// froze (fRr, fRr0, fAlpha, fIteration, fDone); workgroup 0 alone rewrites the live scalars, the host mirror and the trace, which
-// nothing in this kernel reads.  The arithmetic of x and p is update_xp_kernel's.
-template <bool V2, bool NTV>
-__global__ __launch_bounds__(kBlock) void update_xp_final_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsInf,
-                                                                 int nPartials, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ z, long long n)
+// What a finished iteration publishes, by one thread: the trace entry, the live scalars, the host mirror (its `done` last, behind a
+// system-wide fence).  pad: 1 when this iteration's x += alpha p is still to be done by update_xp_kernel.  RING_NT > 0 (deferred x update):
+// the iteration that stops the loop also records the slot that holds p.  `next` hands beta and r.r (or r.z) over to the next iteration:
+// the callers differ in where they take them from.
+template <int RING_NT, typename Next>
+__device__ __forceinline__ void publish_iteration(const FinalizeArgs& f, const StopDecision& d, int it, double rrNew, double inf, int pad, Next next)
+{
+    CgScalars* sc = f.sc;
+    if (f.trace != nullptr && it < f.traceCap) f.trace[it] = d.shown;
+    sc->rrNew = rrNew; sc->residual = d.res; sc->nrmInf = inf; sc->pad = pad;
+    if (d.stop) {
+        if constexpr (RING_NT > 0) sc->pSlot = RING_NT - 1;           // p_k stays where it is (ring_copy_back_kernel)
+        sc->done = 1; sc->status = d.status;
+        f.mirror->residual = d.res; f.mirror->iteration = it; f.mirror->status = d.status;
+        __threadfence_system();
+        f.mirror->done = 1;
+    } else {
+        next();
+        sc->iteration = it + 1;
+        f.mirror->residual = d.res; f.mirror->iteration = it + 1;
+    }
+}
+
+// The finalisation that the x/p updates below fold in.  Every workgroup reduces the r.r (and max|r|) partial sums of update_r in the order
+// finalize_kernel uses and takes the same decision from the values update_r froze (fRr, fRr0, fAlpha, fIteration); workgroup 0 alone
+// rewrites the live scalars, the host mirror and the trace, which nothing in these kernels reads.  beta and the decision reach the other
+// lanes through LDS.  ALLREDUCED: the kernel also serves several ranks, where nPartials == 0 says that r.r has been reduced and
+// all-reduced into sc->rrNew before the launch (workgroup 0 writes the same bits back).  RING_NT > 0: the deferred x update's two stores.
+struct FrozenStep { double alpha, beta; bool stop; };
+template <bool ALLREDUCED, int RING_NT>
+__device__ __forceinline__ FrozenStep finalize_frozen(const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials)
 {
     __shared__ double s_red[4];
     __shared__ double s_red2[4];
     __shared__ double s_beta;
     __shared__ int s_stop;
     CgScalars* sc = f.sc;
-    if (sc->fDone != 0) return;                                       // the loop had stopped before this iteration: nothing ran, nothing is pending
-    // nPartials == 0: several ranks -- r.r has been reduced and all-reduced into sc->rrNew before this launch (workgroup 0 writes the
-    // same bits back below)
-    const double rrNew = nPartials > 0 ? reduce_partials_block(partials, nPartials, s_red, 0) : sc->rrNew;
+    const double rrNew = (!ALLREDUCED || nPartials > 0) ? reduce_partials_block(partials, nPartials, s_red, 0) : sc->rrNew;
     double inf = 0.0;
-    if (partialsInf != nullptr && nPartials > 0) inf = reduce_partials_block(partialsInf, nPartials, s_red2, 1);
+    if (partialsInf != nullptr && (!ALLREDUCED || nPartials > 0)) inf = reduce_partials_block(partialsInf, nPartials, s_red2, 1);
     const double alpha = sc->fAlpha;
     if (threadIdx.x == 0) {
         const int it = sc->fIteration;
         const StopDecision d = decide_stop(f, rrNew, inf, sc->fRr0, it);
         const double beta = rrNew / sc->fRr;
         s_stop = d.stop ? 1 : 0; s_beta = beta;
-        if (blockIdx.x == 0) {                                        // publish (what finalize_kernel writes)
-            if (f.trace != nullptr && it < f.traceCap) f.trace[it] = d.shown;
-            sc->rrNew = rrNew; sc->residual = d.res; sc->nrmInf = inf; sc->pad = 0;
-            if (d.stop) {
-                sc->done = 1; sc->status = d.status;
-                f.mirror->residual = d.res; f.mirror->iteration = it; f.mirror->status = d.status;
-                __threadfence_system();
-                f.mirror->done = 1;
-            } else {
-                sc->beta = beta; sc->rr = rrNew; sc->iteration = it + 1;
-                f.mirror->residual = d.res; f.mirror->iteration = it + 1;
-            }
-        }
+        if (blockIdx.x == 0)
+            publish_iteration<RING_NT>(f, d, it, rrNew, inf, 0, [&] {
+                if constexpr (RING_NT > 0) sc->alphaRing[RING_NT - 1] = alpha;   // (read by this group's later iterations only: no workgroup here reads it)
+                sc->beta = beta; sc->rr = rrNew;
+            });
     }
     __syncthreads();
-    const double beta = s_beta;
-    if (s_stop) {                                                     // the iteration that stops the loop: x only
-        grid_stride<V2>(n,
-            [&](long long i) { d2 pv = *(const d2*)(p + i); d2 xv = *(d2*)(x + i); double t0 = alpha * pv.x; double t1 = alpha * pv.y; xv.x = xv.x + t0; xv.y = xv.y + t1; *(d2*)(x + i) = xv; },
-            [&](long long i) { double t = alpha * p[i]; x[i] = x[i] + t; });
-        return;
-    }
-    auto one = [&](long long i) { const double pv = p[i]; double t = alpha * pv; x[i] = x[i] + t; double u = beta * pv; p[i] = z[i] + u; };
-    if constexpr (V2) {
-        d2* x2 = (d2*)x; d2* p2 = (d2*)p; const d2* z2 = (const d2*)z;
-        auto fin = [&](d2& xv, d2& pv, const d2& zv) {
-            double t0 = alpha * pv.x; double t1 = alpha * pv.y; xv.x = xv.x + t0; xv.y = xv.y + t1;
-            double u0 = beta * pv.x; double u1 = beta * pv.y; pv.x = zv.x + u0; pv.y = zv.y + u1;
-        };
-        chunk_pairs(n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            d2 pv0 = ldv<NTV>(p2 + i), xv0 = ldv<NTV>(x2 + i), zv0 = ldv<NTV>(z2 + i);
-            d2 pv1 = ldv<NTV>(p2 + j), xv1 = ldv<NTV>(x2 + j), zv1 = ldv<NTV>(z2 + j);
-            fin(xv0, pv0, zv0);
-            stv<NTV>(xv0, x2 + i); stv<NTV>(pv0, p2 + i);
-            if (two) { fin(xv1, pv1, zv1); stv<NTV>(xv1, x2 + j); stv<NTV>(pv1, p2 + j); }
-        });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
-    } else {
-        grid_stride<false>(n, [&](long long) {}, one);
-    }
+    return { alpha, s_beta, s_stop != 0 };
+}
+
+// The x/p update with the iteration's finalisation folded in (no preconditioner: z = r; one rank, or several behind their all-reduce
+// of r.r).  Needs update_r launched with freeze = true.  The arithmetic of x and p is update_xp_kernel's.
+template <bool V2, bool NTV>
+__global__ __launch_bounds__(kBlock) void update_xp_final_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsInf,
+                                                                 int nPartials, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ z, long long n)
+{
+    CgScalars* sc = f.sc;
+    if (sc->fDone != 0) return;                                       // the loop had stopped before this iteration: nothing ran, nothing is pending
+    const FrozenStep k = finalize_frozen<true, 0>(f, partials, partialsInf, nPartials);
+    xp_pass<V2, NTV>(k.alpha, k.beta, k.stop, x, p, z, n);
 }
 void launch_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
                             double* x, double* p, const double* z, long long n)
 {
     if (n <= 0) return;
     const bool v2 = al16(x) && al16(p) && al16(z);
-    const bool nt = vec_nt(n);
-    const int g2 = grid_for(n, 2);
-    if (v2 && nt) hipLaunchKernelGGL((update_xp_final_kernel<true, true>), dim3(g2), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, p, z, n);
-    else if (v2) hipLaunchKernelGGL((update_xp_final_kernel<true, false>), dim3(g2), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, p, z, n);
-    else hipLaunchKernelGGL((update_xp_final_kernel<false, false>), dim3(grid_for(n, 1)), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, p, z, n);
+    with_v2_nt(v2, vec_nt(n), [&](auto V2, auto NTV) {
+        hipLaunchKernelGGL((update_xp_final_kernel<V2.value, NTV.value>), dim3(grid_for(n, V2.value ? 2 : 1)), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, p, z, n);
+    });
 }
 
 // The same with the deferred x update (RingArgs, common.hpp): the finalisation and stop decision of update_xp_final_kernel, then
@@ -586,40 +608,11 @@ template <bool V2, bool NTV, int NT, bool FLUSH>
 __global__ __launch_bounds__(kBlock) void update_xp_ring_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsInf,
                                                                 int nPartials, double* __restrict__ x, RingArgs g, const double* __restrict__ z, long long n)
 {
-    __shared__ double s_red[4];
-    __shared__ double s_red2[4];
-    __shared__ double s_beta;
-    __shared__ int s_stop;
     CgScalars* sc = f.sc;
     if (sc->fDone != 0) return;                                       // the loop had stopped before this iteration: nothing ran, nothing is pending
-    const double rrNew = reduce_partials_block(partials, nPartials, s_red, 0);
-    double inf = 0.0;
-    if (partialsInf != nullptr) inf = reduce_partials_block(partialsInf, nPartials, s_red2, 1);
-    const double alpha = sc->fAlpha;
-    if (threadIdx.x == 0) {
-        const int it = sc->fIteration;
-        const StopDecision d = decide_stop(f, rrNew, inf, sc->fRr0, it);
-        const double beta = rrNew / sc->fRr;
-        s_stop = d.stop ? 1 : 0; s_beta = beta;
-        if (blockIdx.x == 0) {                                        // publish (what finalize_kernel writes)
-            if (f.trace != nullptr && it < f.traceCap) f.trace[it] = d.shown;
-            sc->rrNew = rrNew; sc->residual = d.res; sc->nrmInf = inf; sc->pad = 0;
-            if (d.stop) {
-                sc->pSlot = NT - 1;                                   // p_k stays where it is (ring_copy_back_kernel)
-                sc->done = 1; sc->status = d.status;
-                f.mirror->residual = d.res; f.mirror->iteration = it; f.mirror->status = d.status;
-                __threadfence_system();
-                f.mirror->done = 1;
-            } else {
-                sc->alphaRing[NT - 1] = alpha;                        // (read by this group's later iterations only: no workgroup here reads it)
-                sc->beta = beta; sc->rr = rrNew; sc->iteration = it + 1;
-                f.mirror->residual = d.res; f.mirror->iteration = it + 1;
-            }
-        }
-    }
-    __syncthreads();
-    const double beta = s_beta;
-    const bool stop = s_stop != 0;
+    const FrozenStep k = finalize_frozen<false, NT>(f, partials, partialsInf, nPartials);
+    const double alpha = k.alpha, beta = k.beta;
+    const bool stop = k.stop;
     const double* pk = g.slot[NT - 1];
     double* pn = g.slot[(FLUSH || NT == kXDeferMax) ? 0 : NT];
     if (!FLUSH && stop) {                                             // stopped inside a group: x only, one term after another
@@ -694,9 +687,9 @@ static void launch_xp_ring_nt2(hipStream_t s, const FinalizeArgs& f, const doubl
     // workgroups at 512^3 (profiles/r6/ring_grid_ab.txt); the flush (B + 2 reads, 2 writes) keeps the x/p pass's 2048
     int g2 = grid_for(n, 2);
     if (!FLUSH) { DeviceState* d = device_state(); const int want = 2 * (d ? d->numCu : kNumCu); if (g2 > want) g2 = want; }
-    if (v2 && nt) hipLaunchKernelGGL((update_xp_ring_kernel<true, true, NT, FLUSH>), dim3(g2), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, g, z, n);
-    else if (v2) hipLaunchKernelGGL((update_xp_ring_kernel<true, false, NT, FLUSH>), dim3(g2), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, g, z, n);
-    else hipLaunchKernelGGL((update_xp_ring_kernel<false, false, NT, FLUSH>), dim3(grid_for(n, 1)), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, g, z, n);
+    with_v2_nt(v2, nt, [&](auto V2, auto NTV) {
+        hipLaunchKernelGGL((update_xp_ring_kernel<V2.value, NTV.value, NT, FLUSH>), dim3(V2.value ? g2 : grid_for(n, 1)), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, g, z, n);
+    });
 }
 template <int NT>
 static void launch_xp_ring_nt(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
@@ -740,27 +733,9 @@ void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g
     hipLaunchKernelGGL(ring_copy_back_kernel, dim3(grid_for(n, 4)), dim3(kBlock), 0, s, sc, g, n);
 }
 
-// p = z + beta*p   (ConjugateGradientCpu.cs:94 with z = r; the preconditioned loop passes z = M^-1 r)
-template <bool V2>
-__global__ __launch_bounds__(kBlock) void update_p_kernel(const CgScalars* __restrict__ sc, double* __restrict__ p, const double* __restrict__ z, long long n)
-{
-    if (sc->done != 0) return;
-    const double beta = sc->beta;
-    grid_stride<V2>(n,
-        [&](long long i) { d2 zv = *(const d2*)(z + i); d2 pv = *(d2*)(p + i); double t0 = beta * pv.x; double t1 = beta * pv.y; pv.x = zv.x + t0; pv.y = zv.y + t1; *(d2*)(p + i) = pv; },
-        [&](long long i) { double t = beta * p[i]; p[i] = z[i] + t; });
-}
-void launch_update_p(hipStream_t s, const CgScalars* sc, double* p, const double* z, long long n)
-{
-    if (n <= 0) return;
-    const bool v2 = al16(p) && al16(z);
-    if (v2) hipLaunchKernelGGL(update_p_kernel<true>, dim3(grid_for(n, 2)), dim3(kBlock), 0, s, sc, p, z, n);
-    else hipLaunchKernelGGL(update_p_kernel<false>, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, sc, p, z, n);
-}
-
 // ------------------------------------------------------------------ scalar bookkeeping (one workgroup)
 __global__ __launch_bounds__(kBlock) void init_scalars_kernel(const double* __restrict__ partials, int n, int reduceFirst,
-                                                              CgScalars* sc, HostMirror* mirror, int rule)
+                                                              CgScalars* sc, HostMirror* mirror)
 {
     __shared__ double s_red[4];
     double rr = 0.0;
@@ -770,13 +745,12 @@ __global__ __launch_bounds__(kBlock) void init_scalars_kernel(const double* __re
         sc->rr = rr; sc->rr0 = rr; sc->pAp = 0; sc->rrNew = 0; sc->rzNew = 0; sc->residual = 0; sc->nrmInf = 0;
         sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = 0; sc->pad = 0;
         sc->fRr = rr; sc->fRr0 = rr; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
-        (void)rule;
         mirror->residual = 0; mirror->iteration = 0; mirror->status = 0; mirror->done = 0;
     }
 }
-void launch_init_scalars(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror, int rule)
+void launch_init_scalars(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror)
 {
-    hipLaunchKernelGGL(init_scalars_kernel, dim3(1), dim3(kBlock), 0, s, partials, n, reduceFirst ? 1 : 0, sc, mirror, rule);
+    hipLaunchKernelGGL(init_scalars_kernel, dim3(1), dim3(kBlock), 0, s, partials, n, reduceFirst ? 1 : 0, sc, mirror);
 }
 
 // Residual, stop test, beta and the rr hand-over.
@@ -796,23 +770,10 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(const double* __restri
     if (!reduceFirst) { rrNew = sc->rrNew; inf = sc->nrmInf; }
     const int it = sc->iteration;
     const StopDecision d = decide_stop(f, rrNew, inf, sc->rr0, it);
-    const double res = d.res, shown = d.shown;
-    const bool stop = d.stop;
-    const int status = d.status;
-    if (f.trace != nullptr && it < f.traceCap) f.trace[it] = shown;
-    sc->rrNew = rrNew; sc->residual = res; sc->nrmInf = inf;
-    sc->pad = 1;                                 // this iteration's x += alpha p is still to be done (update_xp)
-    if (stop) {
-        sc->done = 1; sc->status = status;
-        f.mirror->residual = res; f.mirror->iteration = it; f.mirror->status = status;
-        __threadfence_system();
-        f.mirror->done = 1;
-    } else {
+    publish_iteration<0>(f, d, it, rrNew, inf, 1, [&] {                                                         // pad = 1: x += alpha p is left to update_xp
         if (!f.preconditioned) { sc->beta = rrNew / sc->rr; sc->rr = rrNew; }
         else if (f.preconditioned == 2) { const double rz = sc->rzNew; sc->beta = rz / sc->rr; sc->rr = rz; }   // (all-reduced r.z already in place)
-        sc->iteration = it + 1;
-        f.mirror->residual = res; f.mirror->iteration = it + 1;
-    }
+    });
 }
 void launch_finalize(hipStream_t s, const double* partials, const double* partialsInf, int n, bool reduceFirst, const FinalizeArgs& f)
 {

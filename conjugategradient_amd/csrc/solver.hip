@@ -618,38 +618,38 @@ static void placement_report(int stage, const Vector* v)
     for (int i = 0; v && i < v->drawCount && i < 16; ++i) t_placementMs[stage][i] = v->drawMs[i];
 }
 
-// one stage: candidates for vector v (stage 0: the SpMV's output Ap, whose contents do not matter at this point; stage 1: its input p)
-static void placement_stage(CgRun& R, int stage, Vector* v)
+// The loop's SpMV (fused with p.Ap) on this run's matrix: x gathered, y written.
+static SpmvArgs cg_spmv_args(const CgRun& R, const double* x, double* y)
 {
-    placement_report(stage, v);                    // MgcgLastPlacement speaks of THIS solve's vectors: the record of their one draw, or nothing
-    const int extra = tuning().placement.load(std::memory_order_relaxed);
-    double*& mine = stage == 0 ? R.Ap : R.p;
-    if (!v || v->placed || v->rawExported || extra <= 0 || v->size < kPlacementMinEntries || v->data != mine || R.nLocal < 4096 || R.elementsCount < 8) return;
-    v->placed = true;                              // one draw per vector, whatever comes of it
-    hipStream_t s = R.ws->stream;
-    const size_t bytes = sizeof(double) * (size_t)v->size;
+    SpmvArgs a{};
+    a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces; a.x = x; a.y = y;
+    a.elementsCount = R.elementsCount; a.rowCount = (int)R.nLocal; a.columnCount = (int)R.count;
+    return a;
+}
+
+// The two halves of a draw.  Candidates: up to `want` more buffers of `bytes` bytes appended to cand[n...], as long as 2 GiB stay free.
+static int placement_alloc(double** cand, int n, int want, size_t bytes)
+{
     size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { (void)hipGetLastError(); return; }
-    double* cand[16];
-    int n = 1;
-    cand[0] = v->data;
-    const int want = extra > 15 ? 15 : extra;
+    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { (void)hipGetLastError(); return -1; }
     for (int i = 0; i < want && freeB > (size_t)(i + 1) * bytes + (2ULL << 30); ++i) {
         double* q = nullptr;
         if (hipMalloc((void**)&q, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
         cand[n++] = q;
     }
+    return n;
+}
+// Timing: the contents of src copied into cand[from..n), then the loop's SpMV on every candidate as the gathered vector (asX) or the written
+// one -- one warm-up and kReps timed launches each; ms[i] per launch.  false: some call failed and ms means nothing.
+static bool placement_time(CgRun& R, double* const* cand, int from, int n, const double* src, size_t bytes, bool asX, double* ms)
+{
+    hipStream_t s = R.ws->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = n > 1 && MGCG_HIP(hipEventCreate(&e0)) && MGCG_HIP(hipEventCreate(&e1));
-    for (int i = 1; ok && i < n; ++i) ok = MGCG_HIP(hipMemcpyAsync(cand[i], v->data, bytes, hipMemcpyDeviceToDevice, s));   // the same contents everywhere
-    int best = 0;
+    bool ok = n > from && MGCG_HIP(hipEventCreate(&e0)) && MGCG_HIP(hipEventCreate(&e1));
+    for (int i = from; ok && i < n; ++i) ok = MGCG_HIP(hipMemcpyAsync(cand[i], src, bytes, hipMemcpyDeviceToDevice, s));   // the same contents everywhere
     constexpr int kReps = 6;
-    double ms[16];
     for (int i = 0; ok && i < n; ++i) {
-        SpmvArgs a{};
-        a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces;
-        a.x = stage == 1 ? cand[i] : R.p; a.y = stage == 0 ? cand[i] : R.Ap;
-        a.elementsCount = R.elementsCount; a.rowCount = (int)R.nLocal; a.columnCount = (int)R.count;
+        SpmvArgs a = cg_spmv_args(R, asX ? cand[i] : R.p, asX ? R.Ap : cand[i]);
         a.w = a.x + R.offset; a.partials = R.ws->partials; a.doneFlag = nullptr;
         (void)launch_spmv_auto(s, EPI_DOT, a, R.cfg, R.dcsr);                              // warm-up (Ap and the partial sums are rewritten by the solve)
         ok = MGCG_HIP(hipEventRecord(e0, s));
@@ -658,14 +658,34 @@ static void placement_stage(CgRun& R, int stage, Vector* v)
         float t = 0.0f;
         ok = ok && MGCG_HIP(hipEventElapsedTime(&t, e0, e1));
         ms[i] = (double)t / kReps;
-        if (ok && ms[i] < ms[best]) best = i;
     }
     (void)hipStreamSynchronize(s);
-    if (!ok) { best = 0; (void)hipGetLastError(); }
-    for (int i = 0; i < n; ++i) if (i != best) { analysis_note_write(cand[i], bytes); if (i == 0) vector_registry_remove(cand[0]); (void)hipFree(cand[i]); }   // (freed addresses may be handed out again)
-    if (best != 0) { v->data = cand[best]; mine = v->data; vector_registry_add(v->data, bytes); }
+    if (!ok) (void)hipGetLastError();
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
+    return ok;
+}
+
+// one stage: candidates for vector v (stage 0: the SpMV's output Ap, whose contents do not matter at this point; stage 1: its input p);
+// the fastest stays, in place of v's own buffer if it is another
+static void placement_stage(CgRun& R, int stage, Vector* v)
+{
+    placement_report(stage, v);                    // MgcgLastPlacement speaks of THIS solve's vectors: the record of their one draw, or nothing
+    const int extra = tuning().placement.load(std::memory_order_relaxed);
+    double*& mine = stage == 0 ? R.Ap : R.p;
+    if (!v || v->placed || v->rawExported || extra <= 0 || v->size < kPlacementMinEntries || v->data != mine || R.nLocal < 4096 || R.elementsCount < 8) return;
+    v->placed = true;                              // one draw per vector, whatever comes of it
+    const size_t bytes = sizeof(double) * (size_t)v->size;
+    double* cand[16];
+    cand[0] = v->data;
+    const int n = placement_alloc(cand, 1, extra > 15 ? 15 : extra, bytes);
+    if (n < 0) return;
+    double ms[16];
+    const bool ok = placement_time(R, cand, 1, n, v->data, bytes, stage == 1, ms);
+    int best = 0;
+    for (int i = 1; ok && i < n; ++i) if (ms[i] < ms[best]) best = i;
+    for (int i = 0; i < n; ++i) if (i != best) { analysis_note_write(cand[i], bytes); if (i == 0) vector_registry_remove(cand[0]); (void)hipFree(cand[i]); }   // (freed addresses may be handed out again)
+    if (best != 0) { v->data = cand[best]; mine = v->data; vector_registry_add(v->data, bytes); }
     if (ok) { v->drawCount = n; v->drawChosen = best; for (int i = 0; i < n; ++i) v->drawMs[i] = (float)ms[i]; placement_report(stage, v); }
     if (ok && tuning().verbose.load(std::memory_order_relaxed) >= 1) {
         fprintf(stderr, "[MgcgGpu] placement draw for %s (%lld entries): SpMV", stage == 0 ? "Ap" : "p", v->size);
@@ -693,50 +713,21 @@ static void placement_ring(CgRun& R)
     Workspace* ws = R.ws;
     if (B <= 1 || extra <= 0 || R.nLocal < kPlacementMinEntries || R.elementsCount < 8) return;
     if (ws->ringSize >= R.nLocal) { bool some = false; for (int i = 1; i < kXDeferMax; ++i) some = some || ws->ring[i] != nullptr; if (some) return; }
-    hipStream_t s = ws->stream;
-    (void)hipStreamSynchronize(s);
+    (void)hipStreamSynchronize(ws->stream);
     ws->free_ring();
     const size_t bytes = sizeof(double) * (size_t)R.nLocal;
-    size_t freeB = 0, totalB = 0;
-    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) { (void)hipGetLastError(); return; }
     double* cand[16];
-    int n = 0;
-    const int want = (B - 1) * (1 + extra) > 16 ? 16 : (B - 1) * (1 + extra);
-    for (int i = 0; i < want && freeB > (size_t)(i + 1) * bytes + (2ULL << 30); ++i) {
-        double* q = nullptr;
-        if (hipMalloc((void**)&q, bytes) != hipSuccess) { (void)hipGetLastError(); break; }
-        cand[n++] = q;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = n > 0 && MGCG_HIP(hipEventCreate(&e0)) && MGCG_HIP(hipEventCreate(&e1));
-    for (int i = 0; ok && i < n; ++i) ok = MGCG_HIP(hipMemcpyAsync(cand[i], R.p, bytes, hipMemcpyDeviceToDevice, s));
-    constexpr int kReps = 6;
+    const int n = placement_alloc(cand, 0, (B - 1) * (1 + extra) > 16 ? 16 : (B - 1) * (1 + extra), bytes);
+    if (n < 0) return;
     double ms[16];
     int order[16];
-    for (int i = 0; ok && i < n; ++i) {
-        SpmvArgs a{};
-        a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces;
-        a.x = cand[i]; a.y = R.Ap;
-        a.elementsCount = R.elementsCount; a.rowCount = (int)R.nLocal; a.columnCount = (int)R.count;
-        a.w = a.x; a.partials = ws->partials; a.doneFlag = nullptr;
-        (void)launch_spmv_auto(s, EPI_DOT, a, R.cfg, R.dcsr);                              // warm-up (Ap and the partial sums are rewritten by the solve)
-        ok = MGCG_HIP(hipEventRecord(e0, s));
-        for (int k = 0; k < kReps; ++k) (void)launch_spmv_auto(s, EPI_DOT, a, R.cfg, R.dcsr);
-        ok = ok && MGCG_HIP(hipEventRecord(e1, s)) && MGCG_HIP(hipEventSynchronize(e1));
-        float t = 0.0f;
-        ok = ok && MGCG_HIP(hipEventElapsedTime(&t, e0, e1));
-        ms[i] = (double)t / kReps;
-        order[i] = i;
-    }
-    (void)hipStreamSynchronize(s);
-    if (!ok) { (void)hipGetLastError(); for (int i = 0; i < n; ++i) ms[i] = (double)i; for (int i = 0; i < n; ++i) order[i] = i; }
+    const bool ok = placement_time(R, cand, 0, n, R.p, bytes, true, ms);
+    for (int i = 0; i < n; ++i) { order[i] = i; if (!ok) ms[i] = (double)i; }
     std::stable_sort(order, order + n, [&](int a, int b) { return ms[a] < ms[b]; });
     const int take = n < B - 1 ? n : B - 1;
     ws->ringSize = R.nLocal;
     for (int k = 0; k < take; ++k) ws->ring[1 + k] = cand[order[k]];
     for (int k = take; k < n; ++k) (void)hipFree(cand[order[k]]);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     if (ok && tuning().verbose.load(std::memory_order_relaxed) >= 1) {
         fprintf(stderr, "[MgcgGpu] placement draw for the ring of p (%d slots): SpMV", B - 1);
         for (int i = 0; i < n; ++i) fprintf(stderr, " %.3f", ms[i]);
@@ -776,9 +767,8 @@ static bool cg_enqueue_init(CgRun& R, bool fixedSteps = false)
     if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, R.nLocal);             // SimpleConjugateGradient.cu:53
     launch_copy(s, pLoc, R.x, R.nLocal);                                             // p_loc = x  (Mgcg.cu:80)
     if (!halo_exchange(R.comm, R.halo, R.p, s)) return false;                        // SyncP  (ConjugateGradientParallelGpu.cs:427)
-    SpmvArgs a{};
-    a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces; a.x = R.p; a.y = R.r;
-    a.elementsCount = R.elementsCount; a.rowCount = (int)R.nLocal; a.columnCount = (int)R.count; a.b = R.b;
+    SpmvArgs a = cg_spmv_args(R, R.p, R.r);
+    a.b = R.b;
     launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);                             // r = b - A x   (Mgcg.cu:225-226)
     int n;
     if (R.mg) {
@@ -792,24 +782,21 @@ static bool cg_enqueue_init(CgRun& R, bool fixedSteps = false)
     if (R.multi) {
         launch_reduce_to(s, R.ws->partials, n, &sc->rr, nullptr);
         if (!comm_allreduce_sum(R.comm, &sc->rr, 1, s)) return false;                // resultsDot.Sum()  (:463)
-        launch_init_scalars(s, R.ws->partials, n, false, sc, R.ws->mirror, R.rule);
+        launch_init_scalars(s, R.ws->partials, n, false, sc, R.ws->mirror);
     } else {
-        launch_init_scalars(s, R.ws->partials, n, true, sc, R.ws->mirror, R.rule);
+        launch_init_scalars(s, R.ws->partials, n, true, sc, R.ws->mirror);
     }
     return MGCG_HIP(hipGetLastError());
 }
 
-static bool cg_enqueue_iteration(CgRun& R, bool withStopTest)
+// The product step of one iteration: SyncP, Ap = A p with the partial sums of p.Ap in ws->partials[0 .. *nPAp).  pIn: the vector that
+// holds p_k (the caller's p, or a slot of the deferred x update's ring).
+static bool cg_enqueue_product(CgRun& R, double* pIn, int* nPAp)
 {
     hipStream_t s = R.ws->stream;
-    CgScalars* sc = R.ws->scalars;
-    double* pIn = R.xDefer > 1 ? R.ring.slot[R.groupPos] : R.p;                      // the slot that holds p_k (deferred x update)
-    double* pLoc = pIn + R.offset;
-    const int* done = &sc->done;
-    SpmvArgs a{};
-    a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces; a.x = pIn; a.y = R.Ap;
-    a.elementsCount = R.elementsCount; a.rowCount = (int)R.nLocal; a.columnCount = (int)R.count;
-    a.w = pLoc; a.partials = R.ws->partials; a.doneFlag = done;
+    const int* done = &R.ws->scalars->done;
+    SpmvArgs a = cg_spmv_args(R, pIn, R.Ap);
+    a.w = pIn + R.offset; a.partials = R.ws->partials; a.doneFlag = done;
     int n;
     if (R.overlap) {
         // interior rows on the side stream while SyncP (:469) travels on the main stream, then the boundary rows
@@ -836,81 +823,116 @@ static bool cg_enqueue_iteration(CgRun& R, bool withStopTest)
         n = launch_spmv_auto(s, EPI_DOT, a, R.cfg, R.dcsr);                          // Ap = A p ; p.Ap   (Mgcg.cu:244-245)
         prof_mark(R, false);
     }
-    const bool refDots = dot_reference_order();                                      // validation mode: p.Ap once more, in the reference's order
-    if (refDots) { launch_dot_serial(s, pLoc, R.Ap, R.nLocal, R.ws->partials, done); n = 1; }
+    if (dot_reference_order()) { launch_dot_serial(s, a.w, R.Ap, R.nLocal, R.ws->partials, done); n = 1; }   // validation mode: p.Ap once more, in the reference's order
+    *nPAp = n;
+    return true;
+}
+
+// What follows the product in one iteration.  Every variant starts with update_r (alpha, r -= alpha Ap, partial r.r); they differ in who
+// takes the stop decision and where x and p are updated.  Launches per iteration after the product, all-reduces in brackets:
+enum class CgUpdate {
+    FusedOneRank,       // update_r, update_xp_final (or update_xp_ring: deferred x update)                                          2
+    FusedRanks,         // reduce, [p.Ap], update_r, reduce, [r.r], update_xp_final                                                 4
+    PrecondOneRank,     // update_r, finalize, V-cycle (+ dot), finalize_precond, update_xp                                         4 + V-cycle
+    PrecondRanks,       // reduce, [p.Ap], update_r, V-cycle (+ dot), reduce2, [r.r, r.z], finalize, update_xp                      5 + V-cycle
+    Unfused             // a rank without rows: as the plain variants, with finalize in place of the x/p update                         2 or 4
+};
+static CgUpdate cg_update_variant(const CgRun& R)
+{
+    if (R.mg) return R.multi ? CgUpdate::PrecondRanks : CgUpdate::PrecondOneRank;
+    // a rank without rows: launch_update_xp_final returns before it launches (n <= 0), so only launch_finalize can finalise its iteration
+    if (R.nLocal <= 0) return CgUpdate::Unfused;
+    return R.multi ? CgUpdate::FusedRanks : CgUpdate::FusedOneRank;
+}
+
+static FinalizeArgs cg_finalize_args(const CgRun& R, bool withStopTest, int preconditioned)
+{
+    FinalizeArgs f{};
+    f.sc = R.ws->scalars; f.mirror = R.ws->mirror; f.trace = R.ws->trace; f.traceCap = R.ws->traceCap;
+    f.tol = R.tol; f.minIt = R.minIt; f.maxIt = R.maxIt; f.rule = R.rule; f.preconditioned = preconditioned;
+    if (!withStopTest) { f.tol = -1.0; f.minIt = 0; f.maxIt = 0x7fffffff; f.rule = MGCG_RULE_NATIVE; }   // never converges
+    return f;
+}
+
+// The update step.  pLoc: this rank's rows of p_k; nPAp: the product step's count of p.Ap partial sums.
+static bool cg_enqueue_update(CgRun& R, double* pLoc, int nPAp, bool withStopTest)
+{
+    hipStream_t s = R.ws->stream;
+    CgScalars* sc = R.ws->scalars;
+    const int* done = &sc->done;
+    const CgUpdate variant = cg_update_variant(R);
+    const bool fused = variant == CgUpdate::FusedOneRank || variant == CgUpdate::FusedRanks;   // update_r freezes the scalars for update_xp_final / _ring
+    const bool refDots = dot_reference_order();
     double* pInf = R.wantInf ? R.ws->partials + kMaxPartials : nullptr;
-    double* rrPartials = R.ws->partials;
-    // one rank, no preconditioner: the x/p update finalises the iteration itself (one launch fewer)
-    const bool fold = !R.multi && !R.mg && R.nLocal > 0;
-    const bool foldRanks = R.multi && !R.mg && R.nLocal > 0;                    // several ranks: the same fold behind the all-reduce of r.r
+    double* rrPartials;
+    int n;
     if (R.multi) {
-        launch_reduce_to(s, R.ws->partials, n, &sc->pAp, done);
+        launch_reduce_to(s, R.ws->partials, nPAp, &sc->pAp, done);
         if (!comm_allreduce_sum(R.comm, &sc->pAp, 1, s)) return false;               // (:499)
-        if (R.mg) rrPartials = R.ws->partials + 2 * kMaxPartials;                    // (they must outlive the V-cycle, whose r.z partial sums take the first region)
-        n = launch_update_r(s, sc, R.r, R.Ap, R.nLocal, rrPartials, pInf, nullptr, 0, foldRanks);   // r -= a Ap ; r.r  (:247-248); x += a p rides with the p update below
+        rrPartials = R.mg ? R.ws->partials + 2 * kMaxPartials : R.ws->partials;      // (with the V-cycle they must outlive it: its r.z partial sums take the first region)
+        n = launch_update_r(s, sc, R.r, R.Ap, R.nLocal, rrPartials, pInf, nullptr, 0, fused);   // r -= a Ap ; r.r  (:247-248); x += a p rides with the p update below
     } else {
         // one rank: the workgroups of the r update add the p.Ap partial sums themselves (one launch fewer per iteration);
         // their own r.r partial sums go to the third region of the buffer
         rrPartials = R.ws->partials + 2 * kMaxPartials;
-        n = launch_update_r(s, sc, R.r, R.Ap, R.nLocal, rrPartials, pInf, R.ws->partials, n, fold);
+        n = launch_update_r(s, sc, R.r, R.Ap, R.nLocal, rrPartials, pInf, R.ws->partials, nPAp, fused);
     }
-    FinalizeArgs f{};
-    f.sc = sc; f.mirror = R.ws->mirror; f.trace = R.ws->trace; f.traceCap = R.ws->traceCap;
-    f.tol = R.tol; f.minIt = R.minIt; f.maxIt = R.maxIt; f.rule = R.rule; f.preconditioned = R.mg ? 1 : 0;
-    if (!withStopTest) { f.tol = -1.0; f.minIt = 0; f.maxIt = 0x7fffffff; f.rule = MGCG_RULE_NATIVE; }   // never converges
-    if (fold && R.xDefer > 1) {
-        RingArgs g = R.ring;
-        g.pos = R.groupPos; g.flush = R.groupPos + 1 == R.groupLen ? 1 : 0;
-        launch_update_xp_ring(s, f, rrPartials, pInf, n, R.x, g, R.r, R.nLocal);       // the same, x += a p once per group (cg_xdefer_setup)
-        if (g.flush) { R.groupPos = 0; R.groupLen = R.xDefer; } else ++R.groupPos;
-        return MGCG_HIP(hipGetLastError());
+    if (R.multi && !R.mg) {                                                          // plain loop of several ranks: r.r all-reduced into sc->rrNew
+        launch_reduce_to(s, rrPartials, n, &sc->rrNew, done);
+        if (!comm_allreduce_sum(R.comm, &sc->rrNew, 1, s)) return false;             // (:525)
     }
-    if (fold) {
-        launch_update_xp_final(s, f, rrPartials, pInf, n, R.x, pLoc, R.r, R.nLocal);     // residual, stop test, beta (:251-266) ; x += a p (:246) ; p = r + beta p (:265)
-        return MGCG_HIP(hipGetLastError());
+    const FinalizeArgs f = cg_finalize_args(R, withStopTest, variant == CgUpdate::PrecondRanks ? 2 : (R.mg ? 1 : 0));
+    switch (variant) {
+    case CgUpdate::FusedOneRank:
+        // the x/p update finalises the iteration itself: residual, stop test, beta (:251-266) ; x += a p (:246) ; p = r + beta p (:265)
+        if (R.xDefer > 1) {
+            RingArgs g = R.ring;
+            g.pos = R.groupPos; g.flush = R.groupPos + 1 == R.groupLen ? 1 : 0;
+            launch_update_xp_ring(s, f, rrPartials, pInf, n, R.x, g, R.r, R.nLocal);     // the same, x += a p once per group (cg_xdefer_setup)
+            if (g.flush) { R.groupPos = 0; R.groupLen = R.xDefer; } else ++R.groupPos;
+        } else {
+            launch_update_xp_final(s, f, rrPartials, pInf, n, R.x, pLoc, R.r, R.nLocal);
+        }
+        break;
+    case CgUpdate::FusedRanks:
+        launch_update_xp_final(s, f, nullptr, nullptr, 0, R.x, pLoc, R.r, R.nLocal);     // the same fold behind the all-reduce of r.r
+        break;
+    case CgUpdate::Unfused:
+        launch_finalize(s, rrPartials, pInf, n, !R.multi, f);                        // residual, stop test, beta  (:251-266); one rank: it adds r.r up first
+        launch_update_xp(s, sc, R.x, pLoc, R.r, R.nLocal);                           // x += a p (:246) ; p = r + beta p   (:265) -- returns at once without rows
+        break;
+    case CgUpdate::PrecondOneRank: {
+        launch_finalize(s, rrPartials, pInf, n, true, f);                            // residual, stop test  (:251-266)
+        int nz = 0;
+        if (!mg_apply(R.mg, R.r, R.z, done, refDots ? nullptr : R.ws->partials, &nz)) return false;   // z = M^-1 r (+ r.z on the last sweep)
+        n = nz > 0 ? nz : launch_dot_partials(s, R.r, R.z, R.nLocal, R.ws->partials);
+        launch_finalize_precond(s, R.ws->partials, n, true, sc);                     // beta = rzNew / rz
+        launch_update_xp(s, sc, R.x, pLoc, R.z, R.nLocal);                           // x += a p (:246) ; p = z + beta p
+        break;
     }
-    if (R.multi && R.mg) {
-        // Preconditioned, several ranks: r.r (stop test) and r.z (beta) travel in ONE all-reduce of two doubles behind the
-        // V-cycle ("[r.z, r.r] batched"); the stop decision of an iteration is taken one V-cycle later,
-        // which costs one wasted V-cycle at the very end and saves a collective per iteration.
+    case CgUpdate::PrecondRanks: {
+        // r.r (stop test) and r.z (beta) travel in ONE all-reduce of two doubles behind the V-cycle ("[r.z, r.r]
+        // batched"); the stop decision of an iteration is taken one V-cycle later, which costs one wasted V-cycle at the very end and
+        // saves a collective per iteration.
         const int nrr = n;
         int nz = 0;
         if (!mg_apply(R.mg, R.r, R.z, done, refDots ? nullptr : R.ws->partials, &nz)) return false;      // z = M^-1 r (+ partial sums of r.z on the last sweep)
         n = nz > 0 ? nz : launch_dot_partials(s, R.r, R.z, R.nLocal, R.ws->partials);
         launch_reduce2_to(s, rrPartials, nrr, &sc->rrNew, R.ws->partials, n, &sc->rzNew, done);   // local r.r and r.z, one launch
         if (!comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;             // {rrNew, rzNew} are adjacent in CgScalars  (:525 and the PCG's r.z)
-        f.preconditioned = 2;                                                        // finalize also does beta = rzNew / rz, rz = rzNew
-        launch_finalize(s, rrPartials, pInf, n, false, f);
+        launch_finalize(s, rrPartials, pInf, n, false, f);                           // (preconditioned = 2: also beta = rzNew / rz, rz = rzNew)
         launch_update_xp(s, sc, R.x, pLoc, R.z, R.nLocal);                           // x += a p (:246) ; p = z + beta p
-        return MGCG_HIP(hipGetLastError());
+        break;
     }
-    if (R.multi) {
-        launch_reduce_to(s, rrPartials, n, &sc->rrNew, done);
-        if (!comm_allreduce_sum(R.comm, &sc->rrNew, 1, s)) return false;             // (:525)
-        if (foldRanks) {
-            launch_update_xp_final(s, f, nullptr, nullptr, 0, R.x, pLoc, R.r, R.nLocal);     // stop test, beta, x += a p, p = r + beta p in one launch
-            return MGCG_HIP(hipGetLastError());
-        }
-        launch_finalize(s, rrPartials, pInf, n, false, f);
-    } else {
-        launch_finalize(s, rrPartials, pInf, n, true, f);                            // residual, stop test, beta  (:251-266)
-    }
-    if (R.mg) {
-        int nz = 0;
-        if (!mg_apply(R.mg, R.r, R.z, done, (!R.multi && !refDots) ? R.ws->partials : nullptr, &nz)) return false;   // z = M^-1 r (+ r.z on the last sweep)
-        n = nz > 0 ? nz : launch_dot_partials(s, R.r, R.z, R.nLocal, R.ws->partials);
-        if (R.multi) {
-            launch_reduce_to(s, R.ws->partials, n, &sc->rzNew, done);
-            if (!comm_allreduce_sum(R.comm, &sc->rzNew, 1, s)) return false;
-            launch_finalize_precond(s, R.ws->partials, n, false, sc);
-        } else {
-            launch_finalize_precond(s, R.ws->partials, n, true, sc);                 // beta = rzNew / rz
-        }
-        launch_update_xp(s, sc, R.x, pLoc, R.z, R.nLocal);                           // x += a p (:246) ; p = z + beta p
-    } else {
-        launch_update_xp(s, sc, R.x, pLoc, R.r, R.nLocal);                           // x += a p (:246) ; p = r + beta p   (:265)
     }
     return MGCG_HIP(hipGetLastError());
+}
+
+static bool cg_enqueue_iteration(CgRun& R, bool withStopTest)
+{
+    double* pIn = R.xDefer > 1 ? R.ring.slot[R.groupPos] : R.p;                      // the slot that holds p_k (deferred x update)
+    int nPAp = 0;
+    return cg_enqueue_product(R, pIn, &nPAp) && cg_enqueue_update(R, pIn + R.offset, nPAp, withStopTest);
 }
 
 static int cg_solve(CgRun& R, int* iteration, double* residual, double* residualTrace, int traceCapacity)
