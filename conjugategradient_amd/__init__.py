@@ -4,6 +4,7 @@
 ``solver``    LinerEquations / ConjugateGradient / ...SingleGpu / ...ParallelGpu (reference class surface)
 ``parallel``  one-process-per-GPU driver (RCCL inside the library; torch.distributed bootstrap)
 ``multigrid`` the V-cycle preconditioner the reference named but never wrote
+``jacobi``    Jacobi-preconditioned CG for general CSR matrices (the call the ViennaCL front-end left commented out)
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "jacobi", "problems"]

@@ -111,6 +111,9 @@ SIGNATURES = {
     "MgApply": (None, [_vp, _vp, _vp]),
     "SolveMg": (_i, [_vp] * 13 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "SolveMgParallel": (_i, [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
+    "MgcgJacobiSetup": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "SolveJacobi": (_i, [_vp] * 12 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
+    "SolveJacobiParallel": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "MgcgCommGetUniqueId": (_i, [_vp]),
     "MgcgRcclAvailable": (_i, []),
     "MgcgCommInitRank": (_vp, [_vp, _i, _i]),

@@ -421,7 +421,8 @@ void launch_xpay(hipStream_t s, double* y, const double* x, long long n, double 
 void launch_copy(hipStream_t s, double* y, const double* x, long long n);
 void launch_fill(hipStream_t s, double* y, double v, long long n);
 // knob dot_order: every dot product in the reference's order (one serial sum; the launch_* functions below then return 1 partial)
-void launch_dot_serial(hipStream_t s, const double* x, const double* y, long long n, double* out, const int* done);   // out[0] = ((x0 y0 + x1 y1) + x2 y2) + ...
+void launch_dot_serial(hipStream_t s, const double* x, const double* y, long long n, double* out, const int* done,   // out[0] = ((x0 y0 + x1 y1) + x2 y2) + ...
+                       const double* w = nullptr);   // w (this kernel only; the Jacobi loop's r.z): the terms become x_i * (w_i * y_i), inner product rounded first
 // partials[0..grid) = per-workgroup partial of sum x_i*y_i ; returns grid
 int  launch_dot_partials(hipStream_t s, const double* x, const double* y, long long n, double* partials);
 int  launch_nrminf_partials(hipStream_t s, const double* x, long long n, double* partials);
@@ -458,6 +459,17 @@ void launch_update_xp_ring(hipStream_t s, const FinalizeArgs& f, const double* p
                            double* x, const RingArgs& g, const double* z, long long n);
 // after a call that may have stopped inside a group: p back into slot 0 when sc->pSlot names another slot
 void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g, long long n);
+
+// Jacobi-preconditioned loop (kernels_blas1.hip): z = dinv * r is formed inside the passes, never stored.  partials / partialsZ: the
+// per-workgroup partial sums of r.r and r.z (one each under dot_order = 1).
+void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,
+                         double* dinv, int* bad /* device {0, INT_MAX}: {some row failed, the first such row} */);
+int  launch_jacobi_start(hipStream_t s, double* p, const double* r, const double* dinv, long long n, double* partials, double* partialsZ);   // p = dinv r
+int  launch_jacobi_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, const double* dinv, long long n, double* partials, double* partialsZ,
+                            double* partialsInf, const double* pApPartials, int nPAp, bool freeze);
+void launch_jacobi_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsZ, const double* partialsInf, int nPartials,
+                                   double* x, double* p, const double* r, const double* dinv, long long n);
+void launch_jacobi_init_scalars(hipStream_t s, const double* partials, const double* partialsZ, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror);
 
 struct FinalizeArgs {
     CgScalars* sc;

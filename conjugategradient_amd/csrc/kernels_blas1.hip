@@ -194,8 +194,9 @@ __global__ __launch_bounds__(kBlock) void dot_kernel(const double* __restrict__ 
 // adds the current batch in index order -- one dependent fp64 add per element, ~0.5 s per 1.3e8 entries.  A test instrument, never
 // on a timed path.  (Padding a batch with +0.0 changes nothing: a running sum that started at +0.0 is never -0.0.)
 constexpr int kSerialBatch = 2048;
+// w (optional, the Jacobi-preconditioned loop's r.z without a stored z): the terms are x_i * (w_i * y_i), the inner product rounded first.
 __global__ __launch_bounds__(kBlock) void dot_serial_kernel(const double* __restrict__ x, const double* __restrict__ y, long long n,
-                                                            double* __restrict__ out, const int* done)
+                                                            double* __restrict__ out, const int* done, const double* __restrict__ w)
 {
     __shared__ double s_prod[2][kSerialBatch];
     if (done != nullptr && *done != 0) return;
@@ -206,7 +207,10 @@ __global__ __launch_bounds__(kBlock) void dot_serial_kernel(const double* __rest
         for (int k = tid - kWave; k < kSerialBatch; k += kBlock - kWave) {
             const long long i = base + k;
             double t = 0.0;
-            if (i < n) t = x[i] * y[i];
+            if (i < n) {
+                if (w != nullptr) { double z = w[i] * y[i]; t = x[i] * z; }
+                else t = x[i] * y[i];
+            }
             s_prod[buf][k] = t;
         }
     };
@@ -225,9 +229,9 @@ __global__ __launch_bounds__(kBlock) void dot_serial_kernel(const double* __rest
     if (tid == 0) out[0] = acc;
 }
 bool dot_reference_order() { return tuning().dotOrder.load(std::memory_order_relaxed) != 0; }
-void launch_dot_serial(hipStream_t s, const double* x, const double* y, long long n, double* out, const int* done)
+void launch_dot_serial(hipStream_t s, const double* x, const double* y, long long n, double* out, const int* done, const double* w)
 {
-    hipLaunchKernelGGL(dot_serial_kernel, dim3(1), dim3(kBlock), 0, s, x, y, n < 0 ? 0 : n, out, done);
+    hipLaunchKernelGGL(dot_serial_kernel, dim3(1), dim3(kBlock), 0, s, x, y, n < 0 ? 0 : n, out, done, w);
 }
 
 int launch_dot_partials(hipStream_t s, const double* x, const double* y, long long n, double* partials)
@@ -548,9 +552,12 @@ __device__ __forceinline__ void publish_iteration(const FinalizeArgs& f, const S
 // rewrites the live scalars, the host mirror and the trace, which nothing in these kernels reads.  beta and the decision reach the other
 // lanes through LDS.  ALLREDUCED: the kernel also serves several ranks, where nPartials == 0 says that r.r has been reduced and
 // all-reduced into sc->rrNew before the launch (workgroup 0 writes the same bits back).  RING_NT > 0: the deferred x update's two stores.
+// PRECOND (the Jacobi-preconditioned loop): the r.z partial sums (partialsZ, or the all-reduced sc->rzNew) are reduced as well; the stop
+// test keeps the true r.r against the true r0.r0 in fRr0, while beta = rzNew / rz and the hand-over take r.z (rz lives in sc->rr / fRr).
 struct FrozenStep { double alpha, beta; bool stop; };
-template <bool ALLREDUCED, int RING_NT>
-__device__ __forceinline__ FrozenStep finalize_frozen(const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials)
+template <bool ALLREDUCED, int RING_NT, bool PRECOND = false>
+__device__ __forceinline__ FrozenStep finalize_frozen(const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
+                                                      const double* partialsZ = nullptr)
 {
     __shared__ double s_red[4];
     __shared__ double s_red2[4];
@@ -560,16 +567,23 @@ __device__ __forceinline__ FrozenStep finalize_frozen(const FinalizeArgs& f, con
     const double rrNew = (!ALLREDUCED || nPartials > 0) ? reduce_partials_block(partials, nPartials, s_red, 0) : sc->rrNew;
     double inf = 0.0;
     if (partialsInf != nullptr && (!ALLREDUCED || nPartials > 0)) inf = reduce_partials_block(partialsInf, nPartials, s_red2, 1);
+    double rzNew = 0.0;
+    if constexpr (PRECOND) {
+        __shared__ double s_red3[4];
+        rzNew = (!ALLREDUCED || nPartials > 0) ? reduce_partials_block(partialsZ, nPartials, s_red3, 0) : sc->rzNew;
+    }
     const double alpha = sc->fAlpha;
     if (threadIdx.x == 0) {
         const int it = sc->fIteration;
         const StopDecision d = decide_stop(f, rrNew, inf, sc->fRr0, it);
-        const double beta = rrNew / sc->fRr;
+        const double handOver = PRECOND ? rzNew : rrNew;
+        const double beta = handOver / sc->fRr;
         s_stop = d.stop ? 1 : 0; s_beta = beta;
         if (blockIdx.x == 0)
             publish_iteration<RING_NT>(f, d, it, rrNew, inf, 0, [&] {
                 if constexpr (RING_NT > 0) sc->alphaRing[RING_NT - 1] = alpha;   // (read by this group's later iterations only: no workgroup here reads it)
-                sc->beta = beta; sc->rr = rrNew;
+                if constexpr (PRECOND) sc->rzNew = rzNew;
+                sc->beta = beta; sc->rr = handOver;
             });
     }
     __syncthreads();
@@ -734,6 +748,15 @@ void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g
 }
 
 // ------------------------------------------------------------------ scalar bookkeeping (one workgroup)
+// The scalars in front of iteration 0.  rr: what alpha and beta divide (r.r, or r.z of a preconditioned loop); rr0: what the relative
+// stop rule divides by (the true r0.r0).
+__device__ __forceinline__ void reset_scalars(CgScalars* sc, HostMirror* mirror, double rr, double rr0)
+{
+    sc->rr = rr; sc->rr0 = rr0; sc->pAp = 0; sc->rrNew = 0; sc->rzNew = 0; sc->residual = 0; sc->nrmInf = 0;
+    sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = 0; sc->pad = 0;
+    sc->fRr = rr; sc->fRr0 = rr0; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
+    mirror->residual = 0; mirror->iteration = 0; mirror->status = 0; mirror->done = 0;
+}
 __global__ __launch_bounds__(kBlock) void init_scalars_kernel(const double* __restrict__ partials, int n, int reduceFirst,
                                                               CgScalars* sc, HostMirror* mirror)
 {
@@ -742,10 +765,7 @@ __global__ __launch_bounds__(kBlock) void init_scalars_kernel(const double* __re
     if (reduceFirst) rr = reduce_partials_block(partials, n, s_red, 0);
     if (threadIdx.x == 0) {
         if (!reduceFirst) rr = sc->rr;
-        sc->rr = rr; sc->rr0 = rr; sc->pAp = 0; sc->rrNew = 0; sc->rzNew = 0; sc->residual = 0; sc->nrmInf = 0;
-        sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = 0; sc->pad = 0;
-        sc->fRr = rr; sc->fRr0 = rr; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
-        mirror->residual = 0; mirror->iteration = 0; mirror->status = 0; mirror->done = 0;
+        reset_scalars(sc, mirror, rr, rr);
     }
 }
 void launch_init_scalars(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror)
@@ -796,6 +816,220 @@ __global__ __launch_bounds__(kBlock) void finalize_precond_kernel(const double* 
 void launch_finalize_precond(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc)
 {
     hipLaunchKernelGGL(finalize_precond_kernel, dim3(1), dim3(kBlock), 0, s, partials, n, reduceFirst ? 1 : 0, sc);
+}
+
+// ------------------------------------------------------------------ Jacobi-preconditioned loop (SolveJacobi / SolveJacobiParallel)
+// z = D^-1 r is element-wise, so the preconditioned iteration keeps the plain loop's two launches after the product and stores no z:
+// both passes form z_i = dinv_i * r_i themselves -- one rounded product, the same bits in both (never contracted with the add that
+// follows: product into a named double, then the add).  The r update moves 32 bytes per row (Ap, r, dinv in; r out), the x/p update 48
+// (p, x, r, dinv in; x, p out): 80 against the plain loop's 64.  Partial sums, the done / frozen-scalars protocol and the streaming hints
+// are those of update_r_kernel and update_xp_final_kernel.
+
+// dinv_i = 1 / a_ii, a_ii = the first stored entry of local row i in column rowBase + i (rows need not be sorted).  A row without that
+// entry, or with one that is not finite and > 0 (or so small that its reciprocal is not finite), raises bad[0] and lowers bad[1] to its index (pre-set to {0, INT_MAX} by the caller).
+__global__ __launch_bounds__(kBlock) void jacobi_setup_kernel(const double* __restrict__ elements, const int* __restrict__ rowOffsets, const int* __restrict__ columnIndeces,
+                                                              long long nnz, long long n, long long rowBase, double* __restrict__ dinv, int* bad)
+{
+    grid_stride<false>(n, [&](long long) {}, [&](long long i) {
+        long long k = rowOffsets[i], end = rowOffsets[i + 1];
+        if (k < 0) k = 0;
+        if (end > nnz) end = nnz;                                      // (offsets that run past the arrays: the row counts as what is stored)
+        double d = 0.0;
+        for (; k < end; ++k) if (columnIndeces[k] == rowBase + i) { d = elements[k]; break; }
+        const double inv = 1.0 / d;
+        if (d > 0.0 && isfinite(d) && isfinite(inv)) dinv[i] = inv;    // (no entry: d = 0; a subnormal diagonal, whose reciprocal overflows, fails as well)
+        else { bad[0] = 1; atomicMin(&bad[1], (int)i); }
+    });
+}
+void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,
+                         double* dinv, int* bad)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(jacobi_setup_kernel, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, elements, rowOffsets, columnIndeces, nnz, n, rowBase, dinv, bad);
+}
+
+// The element step of the start pass and of the r update: the new r's share of r.z, z = dinv * r rounded first.
+__device__ __forceinline__ double rz_term(double dinv, double r, double& acc) { double z = dinv * r; double t = r * z; acc += t; return z; }
+
+// p = z = dinv * r ; partial r.r and r.z   (the start of the loop: copy_dot_kernel's place)
+template <bool V2>
+__global__ __launch_bounds__(kBlock) void jacobi_start_kernel(double* __restrict__ p, const double* __restrict__ r, const double* __restrict__ dinv, long long n,
+                                                              double* __restrict__ partials, double* __restrict__ partialsZ)
+{
+    __shared__ double s_red[4];
+    __shared__ double s_red2[4];
+    double acc = 0.0, accZ = 0.0, mx = 0.0;
+    grid_stride<V2>(n,
+        [&](long long i) {
+            d2 rv = *(const d2*)(r + i); d2 dv = *(const d2*)(dinv + i); d2 zv;
+            r_sums<false>(acc, mx, rv.x, rv.y);
+            zv.x = rz_term(dv.x, rv.x, accZ); zv.y = rz_term(dv.y, rv.y, accZ);
+            *(d2*)(p + i) = zv;
+        },
+        [&](long long i) { double rv = r[i]; r_sums<false>(acc, mx, rv); p[i] = rz_term(dinv[i], rv, accZ); });
+    const double t = block_sum(acc, s_red);
+    const double tz = block_sum(accZ, s_red2);
+    if (threadIdx.x == 0) { partials[blockIdx.x] = t; partialsZ[blockIdx.x] = tz; }
+}
+int launch_jacobi_start(hipStream_t s, double* p, const double* r, const double* dinv, long long n, double* partials, double* partialsZ)
+{
+    const bool v2 = al16(p) && al16(r) && al16(dinv);
+    const int grid = grid_for(n, v2 ? 4 : 2);
+    if (v2) hipLaunchKernelGGL(jacobi_start_kernel<true>, dim3(grid), dim3(kBlock), 0, s, p, r, dinv, n, partials, partialsZ);
+    else hipLaunchKernelGGL(jacobi_start_kernel<false>, dim3(grid), dim3(kBlock), 0, s, p, r, dinv, n, partials, partialsZ);
+    if (dot_reference_order()) {
+        launch_dot_serial(s, r, r, n, partials, nullptr);
+        launch_dot_serial(s, r, r, n, partialsZ, nullptr, dinv);
+        return 1;
+    }
+    return grid;
+}
+
+// update_r_kernel with two sums (its head and element step, plus dinv and the second sum): alpha = rz / pAp ; r = r + (-alpha)*Ap ; partial r.r, r.z [, max|r|] of the rounded r
+template <bool V2, bool INF, bool NTV>
+__global__ __launch_bounds__(kBlock) void jacobi_update_r_kernel(CgScalars* __restrict__ sc, double* __restrict__ r, const double* __restrict__ Ap,
+                                                                 const double* __restrict__ dinv, long long n,
+                                                                 double* __restrict__ partials, double* __restrict__ partialsZ, double* __restrict__ partialsInf,
+                                                                 const double* __restrict__ pApPartials, int nPAp, int freeze)
+{
+    __shared__ double s_red[4];
+    __shared__ double s_red2[4];
+    __shared__ double s_red3[4];
+    __shared__ double s_pAp;
+    if (sc->done != 0) { if (freeze && blockIdx.x == 0 && threadIdx.x == 0) sc->fDone = 1; return; }
+    double pAp;
+    if (pApPartials != nullptr) {                                     // single-rank loop: no separate reduction launch
+        const double t = reduce_partials_block(pApPartials, nPAp, s_red, 0);
+        if (threadIdx.x == 0) s_pAp = t;
+        __syncthreads();
+        pAp = s_pAp;
+        if (blockIdx.x == 0 && threadIdx.x == 0) sc->pAp = pAp;
+    } else {
+        pAp = sc->pAp;
+    }
+    const double alpha = sc->rr / pAp;                              // (sc->rr holds r.z)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        sc->alpha = alpha;                                            // for update_xp of this iteration
+        if (freeze) { sc->fRr = sc->rr; sc->fRr0 = sc->rr0; sc->fAlpha = alpha; sc->fIteration = sc->iteration; sc->fDone = 0; }
+    }
+    const double malpha = -alpha;
+    double acc = 0.0, accZ = 0.0, mx = 0.0;
+    auto one = [&](long long i) { double rv = r_step(malpha, Ap[i], r[i]); r[i] = rv; r_sums<INF>(acc, mx, rv); (void)rz_term(dinv[i], rv, accZ); };
+    if constexpr (V2) {
+        d2* r2 = (d2*)r; const d2* a2 = (const d2*)Ap; const d2* d2p = (const d2*)dinv;
+        auto fin = [&](d2& rv, const d2& av, const d2& dv) {
+            rv.x = r_step(malpha, av.x, rv.x); rv.y = r_step(malpha, av.y, rv.y);
+            r_sums<INF>(acc, mx, rv.x, rv.y);
+            (void)rz_term(dv.x, rv.x, accZ); (void)rz_term(dv.y, rv.y, accZ);
+        };
+        chunk_pairs(n >> 1, [&](long long i, bool two) {
+            const long long j = two ? i + kBlock : i;
+            // Ap is not read again; r and dinv come back in the x/p update, after that pass's own 48 bytes per row
+            d2 av0 = ldv<NTV>(a2 + i), rv0 = ldv<NTV>(r2 + i), dv0 = ldv<NTV>(d2p + i), av1 = ldv<NTV>(a2 + j), rv1 = ldv<NTV>(r2 + j), dv1 = ldv<NTV>(d2p + j);
+            fin(rv0, av0, dv0); stv<NTV>(rv0, r2 + i);
+            if (two) { fin(rv1, av1, dv1); stv<NTV>(rv1, r2 + j); }
+        });
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
+    } else {
+        grid_stride<false>(n, [&](long long) {}, one);
+    }
+    const double t = block_sum(acc, s_red);
+    const double tz = block_sum(accZ, s_red3);
+    if (threadIdx.x == 0) { partials[blockIdx.x] = t; partialsZ[blockIdx.x] = tz; }
+    if (INF) {
+        const double m = block_max(mx, s_red2);
+        if (threadIdx.x == 0) partialsInf[blockIdx.x] = m;
+    }
+}
+int launch_jacobi_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, const double* dinv, long long n, double* partials, double* partialsZ,
+                           double* partialsInf, const double* pApPartials, int nPAp, bool freeze)
+{
+    const bool v2 = al16(r) && al16(Ap) && al16(dinv);
+    int grid = grid_for(n, v2 ? 4 : 2);
+    DeviceState* d = device_state();                               // a 3-reads-1-write stream: update_r's two workgroups per CU
+    const int want = 2 * (d ? d->numCu : kNumCu);
+    if (grid > want) grid = want;
+    const bool inf = partialsInf != nullptr;
+    with_flags([&](auto V2, auto INF, auto NTV) {
+        hipLaunchKernelGGL((jacobi_update_r_kernel<V2.value, INF.value, NTV.value>), dim3(grid), dim3(kBlock), 0, s, sc, r, Ap, dinv, n, partials, partialsZ, partialsInf,
+                           pApPartials, nPAp, freeze ? 1 : 0);
+    }, v2, inf, vec_nt(n));
+    if (dot_reference_order()) {
+        launch_dot_serial(s, r, r, n, partials, &sc->done);
+        launch_dot_serial(s, r, r, n, partialsZ, &sc->done, dinv);
+        if (inf) hipLaunchKernelGGL(reduce_inplace_kernel, dim3(1), dim3(kBlock), 0, s, partialsInf, grid, 1, (const int*)&sc->done);
+        return 1;
+    }
+    return grid;
+}
+
+// xp_pass with z_i = dinv_i * r_i formed here: x = x + alpha*p and, unless this iteration stopped the loop, p = z + beta*p
+template <bool V2, bool NTV>
+__device__ __forceinline__ void jacobi_xp_pass(double alpha, double beta, bool stop, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ r,
+                                               const double* __restrict__ dinv, long long n)
+{
+    if (stop) { xp_pass<V2, NTV>(alpha, beta, true, x, p, r, n); return; }              // x only
+    auto one = [&](long long i) { const double pv = p[i]; double t = alpha * pv; x[i] = x[i] + t; double z = dinv[i] * r[i]; double u = beta * pv; p[i] = z + u; };
+    if constexpr (V2) {
+        d2* x2 = (d2*)x; d2* p2 = (d2*)p; const d2* r2 = (const d2*)r; const d2* d2p = (const d2*)dinv;
+        auto fin = [&](d2& xv, d2& pv, const d2& rv, const d2& dv) {
+            double t0 = alpha * pv.x; double t1 = alpha * pv.y; xv.x = xv.x + t0; xv.y = xv.y + t1;
+            double z0 = dv.x * rv.x; double z1 = dv.y * rv.y;
+            double u0 = beta * pv.x; double u1 = beta * pv.y; pv.x = z0 + u0; pv.y = z1 + u1;
+        };
+        chunk_pairs(n >> 1, [&](long long i, bool two) {
+            const long long j = two ? i + kBlock : i;
+            d2 pv0 = ldv<NTV>(p2 + i), xv0 = ldv<NTV>(x2 + i), rv0 = ldv<NTV>(r2 + i), dv0 = ldv<NTV>(d2p + i);
+            d2 pv1 = ldv<NTV>(p2 + j), xv1 = ldv<NTV>(x2 + j), rv1 = ldv<NTV>(r2 + j), dv1 = ldv<NTV>(d2p + j);
+            fin(xv0, pv0, rv0, dv0);
+            stv<NTV>(xv0, x2 + i); stv<NTV>(pv0, p2 + i);
+            if (two) { fin(xv1, pv1, rv1, dv1); stv<NTV>(xv1, x2 + j); stv<NTV>(pv1, p2 + j); }
+        });
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
+    } else {
+        grid_stride<false>(n, [&](long long) {}, one);
+    }
+}
+
+// update_xp_final_kernel for this loop: the finalisation (residual and stop decision from r.r, beta = rzNew / rz), then the pass above.
+// Needs jacobi_update_r launched with freeze = true.  nPartials == 0 (several ranks): {rrNew, rzNew} are all-reduced already.
+template <bool V2, bool NTV>
+__global__ __launch_bounds__(kBlock) void jacobi_update_xp_final_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsZ,
+                                                                        const double* __restrict__ partialsInf, int nPartials, double* __restrict__ x,
+                                                                        double* __restrict__ p, const double* __restrict__ r, const double* __restrict__ dinv, long long n)
+{
+    CgScalars* sc = f.sc;
+    if (sc->fDone != 0) return;
+    const FrozenStep k = finalize_frozen<true, 0, true>(f, partials, partialsInf, nPartials, partialsZ);
+    jacobi_xp_pass<V2, NTV>(k.alpha, k.beta, k.stop, x, p, r, dinv, n);
+}
+void launch_jacobi_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsZ, const double* partialsInf, int nPartials,
+                                   double* x, double* p, const double* r, const double* dinv, long long n)
+{
+    if (n <= 0) return;
+    const bool v2 = al16(x) && al16(p) && al16(r) && al16(dinv);
+    with_v2_nt(v2, vec_nt(n), [&](auto V2, auto NTV) {
+        hipLaunchKernelGGL((jacobi_update_xp_final_kernel<V2.value, NTV.value>), dim3(grid_for(n, V2.value ? 2 : 1)), dim3(kBlock), 0, s, f, partials, partialsZ, partialsInf,
+                           nPartials, x, p, r, dinv, n);
+    });
+}
+
+// init_scalars_kernel for this loop: rz = r0.z0 goes where alpha and beta look for it, the true r0.r0 where the relative rule does
+__global__ __launch_bounds__(kBlock) void jacobi_init_scalars_kernel(const double* __restrict__ partials, const double* __restrict__ partialsZ, int n, int reduceFirst,
+                                                                     CgScalars* sc, HostMirror* mirror)
+{
+    __shared__ double s_red[4];
+    __shared__ double s_red2[4];
+    double rr = 0.0, rz = 0.0;
+    if (reduceFirst) { rr = reduce_partials_block(partials, n, s_red, 0); rz = reduce_partials_block(partialsZ, n, s_red2, 0); }
+    if (threadIdx.x == 0) {
+        if (!reduceFirst) { rr = sc->rrNew; rz = sc->rzNew; }          // (all-reduced as one pair)
+        reset_scalars(sc, mirror, rz, rr);
+    }
+}
+void launch_jacobi_init_scalars(hipStream_t s, const double* partials, const double* partialsZ, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror)
+{
+    hipLaunchKernelGGL(jacobi_init_scalars_kernel, dim3(1), dim3(kBlock), 0, s, partials, partialsZ, n, reduceFirst ? 1 : 0, sc, mirror);
 }
 
 void preload_kernels_blas1() { preload_code_object(reinterpret_cast<const void*>(&fill_kernel)); }

@@ -503,6 +503,7 @@ struct CgRun {
     MgcgComm* comm = nullptr;
     HaloPlan* halo = nullptr;
     MgcgMg* mg = nullptr;
+    const double* dinv = nullptr;          // Jacobi-preconditioned loop (SolveJacobi*): D^-1 of the local rows; z = dinv * r is formed inside the vector passes
     const double* elements = nullptr; const int* rowOffsets = nullptr; const int* columnIndeces = nullptr;
     int elementsCount = 0;
     double *x = nullptr, *b = nullptr, *Ap = nullptr, *p = nullptr, *r = nullptr, *z = nullptr;  // p is FULL length (count), the rest local
@@ -569,12 +570,12 @@ __global__ void clear_done_kernel(CgScalars* sc) { sc->done = 0; sc->status = 0;
 // (B + 4) 8N on the last one: 32N + 8N/B per iteration against 40N.
 // Groups: CgSteps(K) puts the short group (K mod B) first, so that its last iteration is a flush and writes p into the caller's buffer;
 // Solve groups from its first iteration, and the iteration that stops the loop flushes; if p then sits in a library slot it is copied back
-// once at the end of the call (ring_copy_back_kernel).  Several ranks and the preconditioned loop keep one term per iteration.
+// once at the end of the call (ring_copy_back_kernel).  Several ranks and the preconditioned loops keep one term per iteration.
 static int cg_xdefer_slots(const CgRun& R)
 {
     int B = tuning().xDefer.load(std::memory_order_relaxed);
     B = B < 1 ? 1 : (B > kXDeferMax ? kXDeferMax : B);
-    const bool eligible = !R.multi && !R.mg && R.nLocal > 0 && R.offset == 0 && R.count == R.nLocal;
+    const bool eligible = !R.multi && !R.mg && !R.dinv && R.nLocal > 0 && R.offset == 0 && R.count == R.nLocal;
     return eligible ? B : 1;
 }
 
@@ -738,7 +739,7 @@ static void placement_ring(CgRun& R)
 }
 static void placement_draw(CgRun& R, bool fixedSteps)
 {
-    if (R.mg != nullptr || (!fixedSteps && R.maxIt < kPlacementMinIterations)) { placement_report(0, nullptr); placement_report(1, nullptr); return; }
+    if (R.mg != nullptr || R.dinv != nullptr || (!fixedSteps && R.maxIt < kPlacementMinIterations)) { placement_report(0, nullptr); placement_report(1, nullptr); return; }
     placement_stage(R, 0, R.ApVec);                // the written vector first: it decides the most
     placement_stage(R, 1, R.pVec);
     placement_ring(R);
@@ -771,6 +772,18 @@ static bool cg_enqueue_init(CgRun& R, bool fixedSteps = false)
     a.b = R.b;
     launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);                             // r = b - A x   (Mgcg.cu:225-226)
     int n;
+    if (R.dinv) {
+        // p = z = D^-1 r with r.z and r.r in the same pass: rz is what alpha and beta divide, the true r0.r0 what the relative rule divides by
+        double* rrPartials = R.ws->partials + 2 * kMaxPartials;
+        double* rzPartials = rrPartials + kMaxPartials / 2;
+        n = launch_jacobi_start(s, pLoc, R.r, R.dinv, R.nLocal, rrPartials, rzPartials);
+        if (R.multi) {
+            launch_reduce2_to(s, rrPartials, n, &sc->rrNew, rzPartials, n, &sc->rzNew, nullptr);
+            if (!comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;
+        }
+        launch_jacobi_init_scalars(s, rrPartials, rzPartials, n, !R.multi, sc, R.ws->mirror);
+        return MGCG_HIP(hipGetLastError());
+    }
     if (R.mg) {
         int nz = 0;
         if (!mg_apply(R.mg, R.r, R.z, nullptr, dot_reference_order() ? nullptr : R.ws->partials, &nz)) return false;   // z = M^-1 r (+ r.z)
@@ -835,11 +848,14 @@ enum class CgUpdate {
     FusedRanks,         // reduce, [p.Ap], update_r, reduce, [r.r], update_xp_final                                                 4
     PrecondOneRank,     // update_r, finalize, V-cycle (+ dot), finalize_precond, update_xp                                         4 + V-cycle
     PrecondRanks,       // reduce, [p.Ap], update_r, V-cycle (+ dot), reduce2, [r.r, r.z], finalize, update_xp                      5 + V-cycle
-    Unfused             // a rank without rows: as the plain variants, with finalize in place of the x/p update                         2 or 4
+    Unfused,            // a rank without rows: as the plain variants, with finalize in place of the x/p update                         2 or 4
+    JacobiOneRank,      // jacobi_update_r, jacobi_update_xp_final: FusedOneRank with z = D^-1 r formed inside both passes                2
+    JacobiRanks         // reduce, [p.Ap], jacobi_update_r, reduce2, [r.r, r.z], jacobi_update_xp_final                                   4
 };
 static CgUpdate cg_update_variant(const CgRun& R)
 {
     if (R.mg) return R.multi ? CgUpdate::PrecondRanks : CgUpdate::PrecondOneRank;
+    if (R.dinv && R.nLocal > 0) return R.multi ? CgUpdate::JacobiRanks : CgUpdate::JacobiOneRank;
     // a rank without rows: launch_update_xp_final returns before it launches (n <= 0), so only launch_finalize can finalise its iteration
     if (R.nLocal <= 0) return CgUpdate::Unfused;
     return R.multi ? CgUpdate::FusedRanks : CgUpdate::FusedOneRank;
@@ -861,12 +877,27 @@ static bool cg_enqueue_update(CgRun& R, double* pLoc, int nPAp, bool withStopTes
     CgScalars* sc = R.ws->scalars;
     const int* done = &sc->done;
     const CgUpdate variant = cg_update_variant(R);
-    const bool fused = variant == CgUpdate::FusedOneRank || variant == CgUpdate::FusedRanks;   // update_r freezes the scalars for update_xp_final / _ring
+    const bool fused = variant == CgUpdate::FusedOneRank || variant == CgUpdate::FusedRanks ||   // update_r freezes the scalars for update_xp_final / _ring
+                       variant == CgUpdate::JacobiOneRank || variant == CgUpdate::JacobiRanks;
     const bool refDots = dot_reference_order();
     double* pInf = R.wantInf ? R.ws->partials + kMaxPartials : nullptr;
     double* rrPartials;
+    double* rzPartials = nullptr;
     int n;
-    if (R.multi) {
+    if (R.dinv) {
+        // the r update leaves both partial-sum sets in the third region of the buffer (its grid is a few hundred workgroups)
+        rrPartials = R.ws->partials + 2 * kMaxPartials;
+        rzPartials = rrPartials + kMaxPartials / 2;
+        if (R.multi) {
+            launch_reduce_to(s, R.ws->partials, nPAp, &sc->pAp, done);
+            if (!comm_allreduce_sum(R.comm, &sc->pAp, 1, s)) return false;
+        }
+        n = launch_jacobi_update_r(s, sc, R.r, R.Ap, R.dinv, R.nLocal, rrPartials, rzPartials, pInf, R.multi ? nullptr : R.ws->partials, R.multi ? 0 : nPAp, fused);
+        if (R.multi || variant == CgUpdate::Unfused) {                               // r.r and r.z: one launch, one all-reduce of the adjacent pair
+            launch_reduce2_to(s, rrPartials, n, &sc->rrNew, rzPartials, n, &sc->rzNew, done);
+            if (R.multi && !comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;
+        }
+    } else if (R.multi) {
         launch_reduce_to(s, R.ws->partials, nPAp, &sc->pAp, done);
         if (!comm_allreduce_sum(R.comm, &sc->pAp, 1, s)) return false;               // (:499)
         rrPartials = R.mg ? R.ws->partials + 2 * kMaxPartials : R.ws->partials;      // (with the V-cycle they must outlive it: its r.z partial sums take the first region)
@@ -877,11 +908,11 @@ static bool cg_enqueue_update(CgRun& R, double* pLoc, int nPAp, bool withStopTes
         rrPartials = R.ws->partials + 2 * kMaxPartials;
         n = launch_update_r(s, sc, R.r, R.Ap, R.nLocal, rrPartials, pInf, R.ws->partials, nPAp, fused);
     }
-    if (R.multi && !R.mg) {                                                          // plain loop of several ranks: r.r all-reduced into sc->rrNew
+    if (R.multi && !R.mg && !R.dinv) {                                               // plain loop of several ranks: r.r all-reduced into sc->rrNew
         launch_reduce_to(s, rrPartials, n, &sc->rrNew, done);
         if (!comm_allreduce_sum(R.comm, &sc->rrNew, 1, s)) return false;             // (:525)
     }
-    const FinalizeArgs f = cg_finalize_args(R, withStopTest, variant == CgUpdate::PrecondRanks ? 2 : (R.mg ? 1 : 0));
+    const FinalizeArgs f = cg_finalize_args(R, withStopTest, (variant == CgUpdate::PrecondRanks || R.dinv) ? 2 : (R.mg ? 1 : 0));
     switch (variant) {
     case CgUpdate::FusedOneRank:
         // the x/p update finalises the iteration itself: residual, stop test, beta (:251-266) ; x += a p (:246) ; p = r + beta p (:265)
@@ -897,7 +928,14 @@ static bool cg_enqueue_update(CgRun& R, double* pLoc, int nPAp, bool withStopTes
     case CgUpdate::FusedRanks:
         launch_update_xp_final(s, f, nullptr, nullptr, 0, R.x, pLoc, R.r, R.nLocal);     // the same fold behind the all-reduce of r.r
         break;
+    case CgUpdate::JacobiOneRank:
+        launch_jacobi_update_xp_final(s, f, rrPartials, rzPartials, pInf, n, R.x, pLoc, R.r, R.dinv, R.nLocal);   // residual, stop test, beta = rzNew / rz ; x += a p ; p = D^-1 r + beta p
+        break;
+    case CgUpdate::JacobiRanks:
+        launch_jacobi_update_xp_final(s, f, nullptr, nullptr, nullptr, 0, R.x, pLoc, R.r, R.dinv, R.nLocal);      // the same behind the all-reduce of {r.r, r.z}
+        break;
     case CgUpdate::Unfused:
+        if (R.dinv) { launch_finalize(s, rrPartials, pInf, n, false, f); break; }    // (preconditioned = 2: {rrNew, rzNew} are in place)
         launch_finalize(s, rrPartials, pInf, n, !R.multi, f);                        // residual, stop test, beta  (:251-266); one rank: it adds r.r up first
         launch_update_xp(s, sc, R.x, pLoc, R.r, R.nLocal);                           // x += a p (:246) ; p = r + beta p   (:265) -- returns at once without rows
         break;
@@ -1600,6 +1638,106 @@ int SolveMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, Mgcg
     return SolveMgParallel(nullptr, cublas, cusparse, matDescr, mg, elementsVector, rowOffsetsVector, columnIndecesVector,
                            xVector, bVector, ApVector, pVector, rVector, zVector, count, count, 0, elementsCount, 0, count - 1,
                            allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
+}
+
+// ---------------------------------------------------------------- Jacobi-preconditioned CG for general CSR matrices
+// The loop of SolveEx / SolveParallel with z = D^-1 r: alpha = r.z / p.Ap, beta = r.z_new / r.z, p = z + beta p, the stop rules on the
+// true residual.  z is element-wise, so it is formed inside the two vector passes (kernels_blas1.hip) and the iteration keeps the plain
+// loop's launch count.  The product goes through launch_spmv_auto: compression modes and the automatic column tiles apply unchanged.
+// The deferred x update (x_defer) and the placement draw do not apply, as for the V-cycle loop.
+int MgcgJacobiSetup(MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    int elementsCount, int countForDevice, int offsetForDevice, Vector* dinvVector)
+{
+    if (!cusparse || !elementsVector || !rowOffsetsVector || !columnIndecesVector || !dinvVector) { set_error("MgcgJacobiSetup: null handle"); return -1; }
+    if (elementsCount < 0 || countForDevice < 0 || offsetForDevice < 0) { set_error("MgcgJacobiSetup: bad sizes"); return -1; }
+    if (elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount || rowOffsetsVector->size < (long long)countForDevice + 1) {
+        set_error("MgcgJacobiSetup: a device vector is smaller than the matrix"); return -1;
+    }
+    if (dinvVector->size < countForDevice) { set_error("MgcgJacobiSetup: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice); return -1; }
+    if (!device_state()) return -1;
+    if (countForDevice == 0) return 0;
+    hipStream_t s = cusparse->ws.stream;
+    int* bad = cusparse->ws.devInts + 6;
+    int h2[2] = { 0, 0x7fffffff };
+    analysis_note_write(dinvVector->data, sizeof(double) * (size_t)countForDevice);
+    bool ok = MGCG_HIP(hipMemcpyAsync(bad, h2, sizeof(h2), hipMemcpyHostToDevice, s));
+    if (ok) launch_jacobi_setup(s, elementsVector->data, rowOffsetsVector->data, columnIndecesVector->data, elementsCount, countForDevice, offsetForDevice, dinvVector->data, bad);
+    ok = ok && MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(h2, bad, sizeof(h2), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));   // the one read-back
+    if (!ok) return -1;
+    if (h2[0] == 0) return 0;
+    // the failure path: look at the first such row to say what is wrong with it.  These copies go through the null stream, not s: that is
+    // correct because s was synchronised just above and the call has enqueued nothing on it since
+    const long long row = h2[1];
+    int ro[2] = { 0, 0 };
+    const char* what = "has no stored diagonal entry";
+    double diag = 0.0;
+    if (MGCG_HIP(hipMemcpy(ro, rowOffsetsVector->data + row, sizeof(ro), hipMemcpyDeviceToHost))) {
+        long long k0 = ro[0] < 0 ? 0 : ro[0], k1 = ro[1] > elementsCount ? elementsCount : ro[1];
+        if (k1 <= k0) what = "is empty: it has no stored diagonal entry";
+        else {
+            std::vector<int> cols((size_t)(k1 - k0));
+            if (MGCG_HIP(hipMemcpy(cols.data(), columnIndecesVector->data + k0, sizeof(int) * cols.size(), hipMemcpyDeviceToHost))) {
+                for (size_t k = 0; k < cols.size(); ++k) {
+                    if (cols[k] != offsetForDevice + row) continue;
+                    if (MGCG_HIP(hipMemcpy(&diag, elementsVector->data + k0 + (long long)k, sizeof(double), hipMemcpyDeviceToHost))) what = nullptr;
+                    break;
+                }
+            }
+        }
+    }
+    if (what) set_error("MgcgJacobiSetup: row %lld (local row %lld) %s", (long long)offsetForDevice + row, row, what);
+    else set_error("MgcgJacobiSetup: row %lld (local row %lld) has the diagonal %g, which is not finite and > 0 with a finite reciprocal", (long long)offsetForDevice + row, row, diag);
+    return -1;
+}
+
+int SolveJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                        Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector,
+                        int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                        double allowableResidual, int minIteration, int maxIteration, int rule,
+                        int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    // A rank whose diagonal set-up failed calls with a null dinvVector: like every other unusable argument it travels in the halo plan's
+    // one all-reduce (see SolveParallel), and every rank leaves with MGCG_ERROR.
+    bool pre = true;
+    if (!cublas || !cusparse || !dinvVector) { set_error("SolveJacobi: null handle"); pre = false; }
+    if (pre && !device_state()) return MGCG_ERROR;
+    if (!pre && MgcgCommSize(comm) <= 1) return MGCG_ERROR;
+    pre = pre && check_vectors("SolveJacobi", elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                               elementsCountForDevice, countForDevice, count);
+    if (pre && dinvVector->size < countForDevice) { set_error("SolveJacobi: the dinv vector is smaller than the problem"); pre = false; }
+    if (pre && (offsetForDevice < 0 || (long long)offsetForDevice + countForDevice > count)) { set_error("SolveJacobi: bad partition"); pre = false; }
+    if (!pre) {       // leave together with the peers (see SolveParallel)
+        if (MgcgCommSize(comm) > 1 && device_state()) (void)halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, nullptr, 0, true, false);
+        return MGCG_ERROR;
+    }
+    CgRun R;
+    R.ws = &cublas->ws; R.cfg = cfg_of(cusparse); R.prof = &cusparse->prof; R.cusparse = cusparse; R.dinv = dinvVector->data; R.comm = comm; R.nranks = MgcgCommSize(comm); R.multi = comm_multi(comm);
+    R.elements = elementsVector->data; R.rowOffsets = rowOffsetsVector->data; R.columnIndeces = columnIndecesVector->data; R.elementsCount = elementsCountForDevice;
+    R.x = xVector->data; R.b = bVector->data; R.Ap = ApVector->data; R.p = pVector->data; R.r = rVector->data; R.pVec = pVector; R.ApVec = ApVector;
+    R.count = count; R.nLocal = countForDevice; R.offset = offsetForDevice;
+    R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+    if (R.multi) {
+        R.halo = halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, R.columnIndeces, R.elementsCount, true);
+        if (!R.halo) return MGCG_ERROR;
+        if (!cg_plan_overlap(R)) { halo_plan_destroy(R.halo); return MGCG_ERROR; }
+    }
+    const int st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
+    if (R.halo) halo_plan_destroy(R.halo);
+    return st;
+}
+
+int SolveJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector,
+                int elementsCount, int count,
+                double allowableResidual, int minIteration, int maxIteration, int rule,
+                int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    return SolveJacobiParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
+                               xVector, bVector, ApVector, pVector, rVector, dinvVector, count, count, 0, elementsCount, 0, count - 1,
+                               allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
 }
 
 } // extern "C"

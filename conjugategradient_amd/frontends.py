@@ -5,7 +5,8 @@
 * ``ConjugateGradientCLGpu`` -- Mgcg/HandmadeCL/MgcgCL/ConjugateGradientSingleGpu.cs: the max-norm residual
   (``ReductionMaxAbsolute``, Mgcg.cl:110-159; ConjugateGradientSingleGpu.cs:268) with the C# IsConverged rule.
 
-Both are thin: the arithmetic is ``SolveEx`` with MGCG_RULE_VIENNACL / MGCG_RULE_HANDMADECL.
+Both are thin: the arithmetic is ``SolveEx`` with MGCG_RULE_VIENNACL / MGCG_RULE_HANDMADECL (``ComputerGpu.SolvePreconditioned``:
+``SolveJacobi``, the Jacobi-preconditioned loop the reference's ViennaCL front-end left commented out).
 """
 from __future__ import annotations
 
@@ -29,6 +30,7 @@ class ComputerGpu:
         check("ComputerGpu")
         self.vx, self.vb, self.vAp, self.vp, self.vr = (VectorDouble(n) for _ in range(5))
         self.vE = self.vC = self.vRO = None
+        self.vdinv = None                  # 1 / diag(A) of the matrix last written (SolvePreconditioned sets it up once per Write)
         self.nnz = 0
         self.iteration = 0
 
@@ -38,6 +40,9 @@ class ComputerGpu:
         ro = np.ascontiguousarray(np.asarray(rowOffsets, dtype=np.uint32).astype(np.int32))
         ci = np.ascontiguousarray(np.asarray(columnIndeces, dtype=np.uint32).astype(np.int32))
         self.nnz = int(ro[self.count])
+        if self.vdinv is not None:
+            self.vdinv.Dispose()
+            self.vdinv = None
         self.vE, self.vC, self.vRO = VectorDouble(max(self.nnz, 1)), VectorInt(max(self.nnz, 1)), VectorInt(self.count + 1)
         self.vE.CopyFrom(e, self.nnz)
         self.vC.CopyFrom(ci, self.nnz)
@@ -58,6 +63,34 @@ class ComputerGpu:
             lib().MgcgClearLastError()
             raise MgcgError(msg or f"SolveEx failed with status {st}")
 
+    def SolvePreconditioned(self, residual: float, minIteration: int, maxIteration: int):
+        """The call the reference left commented out behind its hand-written loop -- ``solve(A, b, cg_tag, jacobi_precond)``
+        (ComputerGpu.cpp) -- under the same relative stop rule: the diagonal is extracted and checked (MgcgError names a row without
+        a positive stored diagonal, before any iteration), then SolveJacobi runs with MGCG_RULE_VIENNACL."""
+        from .jacobi import jacobi_setup
+
+        if self.vE is None:
+            raise MgcgError("ComputerGpu.SolvePreconditioned: Write() first")
+        if self.vdinv is None:
+            dinv = VectorDouble(self.count)
+            try:
+                jacobi_setup(self.cusparse, self.vE, self.vRO, self.vC, self.nnz, self.count, 0, dinv)
+            except MgcgError:
+                dinv.Dispose()
+                raise
+            self.vdinv = dinv
+        it, res = C.c_int(0), C.c_double(0.0)
+        st = lib().SolveJacobi(self.cublas, self.cusparse, self.matDescr, self.vE.Ptr, self.vRO.Ptr, self.vC.Ptr,
+                               self.vx.Ptr, self.vb.Ptr, self.vAp.Ptr, self.vp.Ptr, self.vr.Ptr, self.vdinv.Ptr, self.nnz, self.count,
+                               float(residual), int(minIteration), int(maxIteration), _lib.RULE_VIENNACL,
+                               C.byref(it), C.byref(res), None, 0)
+        self.iteration = it.value + 1
+        self.relative_residual = res.value
+        if st != _lib.OK:
+            msg = _lib.last_error()
+            lib().MgcgClearLastError()
+            raise MgcgError(msg or f"SolveJacobi failed with status {st}")
+
     def Read(self, x: np.ndarray):
         self.vx.CopyTo(x, self.count)
 
@@ -66,7 +99,7 @@ class ComputerGpu:
 
     def Dispose(self):
         if getattr(self, "cublas", None):
-            for v in (self.vx, self.vb, self.vAp, self.vp, self.vr, self.vE, self.vC, self.vRO):
+            for v in (self.vx, self.vb, self.vAp, self.vp, self.vr, self.vE, self.vC, self.vRO, self.vdinv):
                 if v is not None:
                     v.Dispose()
             lib().DestroyBlas(self.cublas)

@@ -7,7 +7,8 @@ Two drivers share the partition / halo arithmetic in this file:
   the loop, the two scalar all-reduces (RCCL ``ncclAllReduce`` over xGMI, replacing
   ``resultsDot.Sum()`` :463,499,525) and the halo exchange of p (grouped ``ncclSend/ncclRecv``,
   replacing ``SyncP`` :384-419) all run inside libMgcgGpu.so on the rank's stream.
-  ``torch.distributed`` only carries the 128-byte RCCL unique id to the ranks.
+  ``torch.distributed`` only carries the 128-byte RCCL unique id to the ranks.  ``SetupJacobi()`` / ``SolveJacobi()`` run the same
+  loop with the diagonal preconditioner (``SolveJacobiParallel``) over whichever transport the communicator has.
 * ``PhasedRankSolver`` -- the reference's host-driven phase structure (Solve0..3 around host-side
   sums) with ``torch.distributed`` collectives (gloo or nccl) between the phases.  The phase
   arithmetic is a ``backend`` object: ``HipPhases`` (the C ABI exports) in production; the CPU-only
@@ -198,7 +199,7 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
     def Dispose(self):
         if getattr(self, "cublas", None):
             for v in (self.vectorElements, self.vectorColumnIndeces, self.vectorRowOffsets, self.vectorX, self.vectorB,
-                      self.vectorAp, self.vectorP, self.vectorR):
+                      self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None)):
                 if v is not None:
                     v.Dispose()
             if self._own_comm and self.comm:
@@ -283,6 +284,47 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if st != _lib.OK:
             check("SolveParallel")
             raise MgcgError(f"SolveParallel failed with status {st}")
+
+    def SetupJacobi(self):
+        """dinv = 1 / diag(A) for this rank's rows (call after Initialize / InitializePoisson; no collective: the diagonal needs no halo).
+        A failure is raised here AND remembered: SolveJacobi then still enters the native call, with no dinv vector, so that the peers
+        are not left waiting in the solve's first collective -- every rank gets MGCG_ERROR."""
+        from .jacobi import jacobi_setup
+
+        p = self.part
+        if getattr(self, "vectorDinv", None) is None or self.vectorDinv.size < p.count:
+            self.vectorDinv = VectorDouble(p.count)
+        self.jacobiError = None
+        try:
+            jacobi_setup(self.cusparse, self.vectorElements, self.vectorRowOffsets, self.vectorColumnIndeces, p.elementCount, p.count, p.offset, self.vectorDinv)
+        except MgcgError as e:
+            self.jacobiError = e
+            raise
+
+    def SolveJacobi(self, trace: bool = False):
+        """Solve() with the Jacobi preconditioner (SolveJacobiParallel); SetupJacobi() first."""
+        self._ensure_comm()
+        p = self.part
+        usable = getattr(self, "vectorDinv", None) is not None and getattr(self, "jacobiError", None) is None
+        iteration, residual = C.c_int(0), C.c_double(0.0)
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        st = lib().SolveJacobiParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
+                                       self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                       self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                       self.vectorDinv.Ptr if usable else None,
+                                       self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
+                                       self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
+                                       C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"Jacobi-preconditioned CG did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveJacobiParallel")
+            raise MgcgError(f"SolveJacobiParallel failed with status {st}")
 
     @staticmethod
     def LastOverlap():

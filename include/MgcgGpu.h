@@ -460,6 +460,39 @@ int SolveMgParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, Mgcg
                     double allowableResidual, int minIteration, int maxIteration, int rule,
                     int* iteration, double* residual, double* residualTrace, int traceCapacity);
 
+/* ---- Jacobi-preconditioned CG for general CSR matrices (any SPD matrix with a positive diagonal; one rank or several) ---- */
+/* dinv[i] = 1 / a_ii for the local rows [offsetForDevice, +countForDevice): a_ii is the first stored entry of local row i whose column is
+ * offsetForDevice + i, wherever it sits in the row (rows need not be sorted).  A row without a stored diagonal -- an empty row included --
+ * or with a diagonal that is not finite and > 0 makes the call fail: it returns -1, MgcgGetLastError names the first such row, and
+ * dinvVector must not be handed to a solve.  The check runs on the device and is read back once; the call is ordered with the handle's
+ * other work.  Returns 0 on success. */
+int MgcgJacobiSetup(MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    int elementsCount, int countForDevice, int offsetForDevice, Vector* dinvVector);
+/* SolveEx with the preconditioner M = diag(A): z = dinv * r, alpha = r.z / p.Ap, beta = r.z_new / r.z, p = z + beta p.  The five stop
+ * rules, the trace, *iteration, *residual and the status codes are SolveEx's and test the TRUE residual: sqrt(r.r), max|r| under
+ * MGCG_RULE_HANDMADECL, r.r against the true r0.r0 under MGCG_RULE_VIENNACL.  dinvVector: what MgcgJacobiSetup wrote (count entries).
+ * No z vector exists: both vector passes of an iteration form z_i = dinv_i * r_i themselves (one rounded product, never fused with the
+ * add that follows), so an iteration is the product plus two launches, as SolveEx's, at 80 bytes per row of vector traffic against 64.
+ * Rounding contract: r = r + (-alpha) Ap with the product rounded first; the terms of r.r and r.z are r_i * r_i and r_i * z_i of the
+ * rounded r; p = z + beta p with both products rounded first.  Under dot_order = 1 every dot of the loop is a serial left-to-right sum.
+ * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer) and the
+ * placement draw do not apply. */
+int SolveJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector,
+                int elementsCount, int count,
+                double allowableResidual, int minIteration, int maxIteration, int rule,
+                int* iteration, double* residual, double* residualTrace, int traceCapacity);
+/* SolveParallel with the same preconditioner; dinvVector holds the local rows (the diagonal needs no halo).  r.r and r.z travel in one
+ * all-reduce of two doubles.  A rank whose MgcgJacobiSetup failed passes dinvVector = NULL: every rank then returns MGCG_ERROR and
+ * nobody waits in a collective.  MGCG_RULE_HANDMADECL is single-rank only, as in SolveParallel. */
+int SolveJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                        Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector,
+                        int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                        double allowableResidual, int minIteration, int maxIteration, int rule,
+                        int* iteration, double* residual, double* residualTrace, int traceCapacity);
+
 /* Fixed number of CG iterations with no stop test and no host synchronisation inside (bench.py's
  * "steps"): runs `steps` more iterations of the recurrence held in x,r,p (call with restart != 0 first
  * to compute r = b - A x, p = r, rr).  comm may be NULL.  Returns the residual after the last step. */
