@@ -429,22 +429,25 @@ int  launch_nrminf_partials(hipStream_t s, const double* x, long long n, double*
 // out[0] = sum(partials[0..n)) in a fixed order (mode 0) or max (mode 1)
 void launch_reduce(hipStream_t s, const double* partials, int n, double* out, int mode);
 
-// p = r ; partial r.r      (CG init)
-int  launch_copy_dot(hipStream_t s, double* p, const double* r, long long n, double* partials, const int* done);
+// The Jacobi-preconditioned loop (SolveJacobi*) runs the plain loop's start, r update and folded x/p update with dinv != nullptr: z = dinv * r
+// is formed inside the passes, never stored, and partialsZ receives the per-workgroup partial sums of r.z next to those of r.r in partials
+// (one each under dot_order = 1).  Both are null for the plain loop.
+// p = r ; partial r.r      (CG init; with dinv: p = dinv r ; partial r.r and r.z)
+int  launch_copy_dot(hipStream_t s, double* p, const double* r, const double* dinv, long long n, double* partials, double* partialsZ, const int* done);
 // alpha = sc->rr / sc->pAp ; x += alpha p ; r -= alpha Ap ; partial r.r (and max|r| in partials2 when wantInf)
 int  launch_update_xr(hipStream_t s, const CgScalars* sc, double* x, double* r, const double* p, const double* Ap,
                       long long n, double* partials, double* partialsInf);
 // the loop's own split: r -= alpha Ap (+ r.r), then x += alpha p and p = z + beta p in one pass over p
 // pApPartials != nullptr: p.Ap is still in nPAp per-workgroup partial sums; every workgroup adds them up itself (same fixed
 // order everywhere) instead of a separate reduction launch.  partials (output) must not overlap pApPartials.
-int  launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, long long n, double* partials, double* partialsInf,
-                     const double* pApPartials = nullptr, int nPAp = 0, bool freeze = false);
+int  launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, const double* dinv, long long n, double* partials, double* partialsZ,
+                     double* partialsInf, const double* pApPartials, int nPAp, bool freeze);
 void launch_update_xp(hipStream_t s, const CgScalars* sc, double* x, double* p, const double* z, long long n);
 // x/p update that first does what finalize_kernel does (every workgroup reduces the r.r partial sums itself and takes the same stop
 // decision; workgroup 0 publishes it): one launch fewer per iteration.  Needs update_r launched with freeze = true.
 struct FinalizeArgs;
-void launch_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
-                            double* x, double* p, const double* z, long long n);
+void launch_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsZ, const double* partialsInf, int nPartials,
+                            double* x, double* p, const double* r, const double* dinv, long long n);
 
 // Deferred x update (one rank, no preconditioner): iteration k of a group reads p_k from slot[pos] and writes p_{k+1} to slot[pos + 1],
 // or, on the group's last iteration (flush), to slot[0] in place; the flush and the iteration that stops the loop also apply the group's
@@ -460,16 +463,9 @@ void launch_update_xp_ring(hipStream_t s, const FinalizeArgs& f, const double* p
 // after a call that may have stopped inside a group: p back into slot 0 when sc->pSlot names another slot
 void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g, long long n);
 
-// Jacobi-preconditioned loop (kernels_blas1.hip): z = dinv * r is formed inside the passes, never stored.  partials / partialsZ: the
-// per-workgroup partial sums of r.r and r.z (one each under dot_order = 1).
+// dinv_i = 1 / a_ii for the Jacobi-preconditioned loop
 void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,
                          double* dinv, int* bad /* device {0, INT_MAX}: {some row failed, the first such row} */);
-int  launch_jacobi_start(hipStream_t s, double* p, const double* r, const double* dinv, long long n, double* partials, double* partialsZ);   // p = dinv r
-int  launch_jacobi_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, const double* dinv, long long n, double* partials, double* partialsZ,
-                            double* partialsInf, const double* pApPartials, int nPAp, bool freeze);
-void launch_jacobi_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsZ, const double* partialsInf, int nPartials,
-                                   double* x, double* p, const double* r, const double* dinv, long long n);
-void launch_jacobi_init_scalars(hipStream_t s, const double* partials, const double* partialsZ, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror);
 
 struct FinalizeArgs {
     CgScalars* sc;
@@ -505,7 +501,7 @@ void launch_reduce_to(hipStream_t s, const double* partials, int n, double* dst,
 void launch_reduce2_to(hipStream_t s, const double* pA, int nA, double* dstA, const double* pB, int nB, double* dstB, const int* done);   // two sums, one launch
 void launch_finalize(hipStream_t s, const double* partials, const double* partialsInf, int n, bool reduceFirst, const FinalizeArgs& f);
 void launch_finalize_precond(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc);  // rzNew -> beta, rr
-void launch_init_scalars(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror);
+void launch_init_scalars(hipStream_t s, const double* partials, const double* partialsZ, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror);   // partialsZ: null, or r.z (Jacobi)
 
 // ---------------------------------------------------------------- multigrid kernels
 // dinvUniform: dinv[i] == dinvScalar for every i (the array is then not read)

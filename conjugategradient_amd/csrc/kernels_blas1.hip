@@ -310,26 +310,44 @@ void launch_reduce2_to(hipStream_t s, const double* pA, int nA, double* dstA, co
 }
 
 // ------------------------------------------------------------------ fused CG pieces
-// p = r ; partial r.r
-template <bool V2>
-__global__ __launch_bounds__(kBlock) void copy_dot_kernel(double* __restrict__ p, const double* __restrict__ r, long long n, double* __restrict__ partials, const int* done)
+// The Jacobi-preconditioned loop's share of r.z for one element, z = dinv * r rounded first (never contracted with the add that follows:
+// product into a named double, then the add).  The r update and the x/p update both form z this way, so they see the same bits.
+__device__ __forceinline__ double rz_term(double dinv, double r, double& acc) { double z = dinv * r; double t = r * z; acc += t; return z; }
+
+// p = r ; partial r.r      DINV (the Jacobi-preconditioned loop's start): p = z = dinv * r ; partial r.r and r.z
+template <bool V2, bool DINV>
+__global__ __launch_bounds__(kBlock) void copy_dot_kernel(double* __restrict__ p, const double* __restrict__ r, const double* __restrict__ dinv, long long n,
+                                                          double* __restrict__ partials, double* __restrict__ partialsZ, const int* done)
 {
     __shared__ double s_red[4];
     if (done != nullptr && *done != 0) return;
-    double acc = 0.0;
+    double acc = 0.0, accZ = 0.0;
     grid_stride<V2>(n,
-        [&](long long i) { d2 rv = *(const d2*)(r + i); *(d2*)(p + i) = rv; double t0 = rv.x * rv.x; double t1 = rv.y * rv.y; acc += t0; acc += t1; },
-        [&](long long i) { double rv = r[i]; p[i] = rv; double t = rv * rv; acc += t; });
+        [&](long long i) {
+            d2 rv = *(const d2*)(r + i), zv = rv;
+            if constexpr (DINV) { d2 dv = *(const d2*)(dinv + i); zv.x = rz_term(dv.x, rv.x, accZ); zv.y = rz_term(dv.y, rv.y, accZ); }
+            *(d2*)(p + i) = zv; double t0 = rv.x * rv.x; double t1 = rv.y * rv.y; acc += t0; acc += t1; },
+        [&](long long i) { double rv = r[i], zv = rv; if constexpr (DINV) zv = rz_term(dinv[i], rv, accZ); p[i] = zv; double t = rv * rv; acc += t; });
     const double t = block_sum(acc, s_red);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
+    if constexpr (DINV) {
+        __shared__ double s_red2[4];
+        const double tz = block_sum(accZ, s_red2);
+        if (threadIdx.x == 0) partialsZ[blockIdx.x] = tz;
+    }
 }
-int launch_copy_dot(hipStream_t s, double* p, const double* r, long long n, double* partials, const int* done)
+int launch_copy_dot(hipStream_t s, double* p, const double* r, const double* dinv, long long n, double* partials, double* partialsZ, const int* done)
 {
-    const bool v2 = al16(p) && al16(r);
+    const bool v2 = al16(p) && al16(r) && al16(dinv);
     const int grid = grid_for(n, v2 ? 4 : 2);
-    if (v2) hipLaunchKernelGGL(copy_dot_kernel<true>, dim3(grid), dim3(kBlock), 0, s, p, r, n, partials, done);
-    else hipLaunchKernelGGL(copy_dot_kernel<false>, dim3(grid), dim3(kBlock), 0, s, p, r, n, partials, done);
-    if (dot_reference_order()) { launch_dot_serial(s, r, r, n, partials, done); return 1; }      // the one sum in the reference's order replaces the partial sums
+    with_flags([&](auto V2, auto DINV) {
+        hipLaunchKernelGGL((copy_dot_kernel<V2.value, DINV.value>), dim3(grid), dim3(kBlock), 0, s, p, r, dinv, n, partials, partialsZ, done);
+    }, v2, dinv != nullptr);
+    if (dot_reference_order()) {                                      // the sums in the reference's order replace the partial sums
+        launch_dot_serial(s, r, r, n, partials, done);
+        if (dinv != nullptr) launch_dot_serial(s, r, r, n, partialsZ, done, dinv);
+        return 1;
+    }
     return grid;
 }
 
@@ -398,9 +416,12 @@ int launch_update_xr(hipStream_t s, const CgScalars* sc, double* x, double* r, c
 // reference's phase functions: r first (its norm decides the stop test), then x and p together, so that p is read
 // once for both x += alpha p and p = z + beta p  (64N bytes per iteration instead of 72N).
 // alpha = rr / pAp ; r = r + (-alpha)*Ap ; partial r.r [, partial max|r|]
-template <bool V2, bool INF, bool NTV>
-__global__ __launch_bounds__(kBlock) void update_r_kernel(CgScalars* __restrict__ sc, double* __restrict__ r, const double* __restrict__ Ap, long long n,
-                                                          double* __restrict__ partials, double* __restrict__ partialsInf,
+// DINV (the Jacobi-preconditioned loop, sc->rr holds r.z): one more load per element and the partial r.z of the rounded r with
+// z = dinv * r (rz_term); dinv and partialsZ are null otherwise.  32 bytes per row (Ap, r, dinv in; r out) against 24.
+template <bool V2, bool INF, bool NTV, bool DINV>
+__global__ __launch_bounds__(kBlock) void update_r_kernel(CgScalars* __restrict__ sc, double* __restrict__ r, const double* __restrict__ Ap,
+                                                          const double* __restrict__ dinv, long long n,
+                                                          double* __restrict__ partials, double* __restrict__ partialsZ, double* __restrict__ partialsInf,
                                                           const double* __restrict__ pApPartials, int nPAp, int freeze)
 {
     __shared__ double s_red[4];
@@ -423,20 +444,28 @@ __global__ __launch_bounds__(kBlock) void update_r_kernel(CgScalars* __restrict_
         if (freeze) { sc->fRr = sc->rr; sc->fRr0 = sc->rr0; sc->fAlpha = alpha; sc->fIteration = sc->iteration; sc->fDone = 0; }
     }
     const double malpha = -alpha;
-    double acc = 0.0, mx = 0.0;
-    auto one = [&](long long i) { double rv = r_step(malpha, Ap[i], r[i]); r[i] = rv; r_sums<INF>(acc, mx, rv); };
+    double acc = 0.0, accZ = 0.0, mx = 0.0;
+    auto one = [&](long long i) {
+        double rv = r_step(malpha, Ap[i], r[i]); r[i] = rv; r_sums<INF>(acc, mx, rv);
+        if constexpr (DINV) (void)rz_term(dinv[i], rv, accZ);
+    };
     if constexpr (V2) {
-        d2* r2 = (d2*)r; const d2* a2 = (const d2*)Ap;
-        auto fin = [&](d2& rv, const d2& av) {
+        d2* r2 = (d2*)r; const d2* a2 = (const d2*)Ap; const d2* d2p = (const d2*)dinv;
+        auto fin = [&](d2& rv, const d2& av, const d2& dv) {
             rv.x = r_step(malpha, av.x, rv.x); rv.y = r_step(malpha, av.y, rv.y);
             r_sums<INF>(acc, mx, rv.x, rv.y);
+            if constexpr (DINV) { (void)rz_term(dv.x, rv.x, accZ); (void)rz_term(dv.y, rv.y, accZ); }
         };
         chunk_pairs(n >> 1, [&](long long i, bool two) {
             const long long j = two ? i + kBlock : i;
             // streaming hints as in update_xp (measured there: 5.2 -> 6.3 TB/s): Ap is not read again, r not before 2 GB of other traffic
-            d2 av0 = ldv<NTV>(a2 + i), rv0 = ldv<NTV>(r2 + i), av1 = ldv<NTV>(a2 + j), rv1 = ldv<NTV>(r2 + j);
-            fin(rv0, av0); stv<NTV>(rv0, r2 + i);
-            if (two) { fin(rv1, av1); stv<NTV>(rv1, r2 + j); }
+            // (DINV: r and dinv come back in the x/p update, after that pass's own 48 bytes per row)
+            d2 av0 = ldv<NTV>(a2 + i), rv0 = ldv<NTV>(r2 + i), dv0 = {}, av1, rv1, dv1 = {};
+            if constexpr (DINV) dv0 = ldv<NTV>(d2p + i);
+            av1 = ldv<NTV>(a2 + j); rv1 = ldv<NTV>(r2 + j);
+            if constexpr (DINV) dv1 = ldv<NTV>(d2p + j);
+            fin(rv0, av0, dv0); stv<NTV>(rv0, r2 + i);
+            if (two) { fin(rv1, av1, dv1); stv<NTV>(rv1, r2 + j); }
         });
         if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
     } else {
@@ -444,15 +473,20 @@ __global__ __launch_bounds__(kBlock) void update_r_kernel(CgScalars* __restrict_
     }
     const double t = block_sum(acc, s_red);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
+    if constexpr (DINV) {
+        __shared__ double s_red3[4];
+        const double tz = block_sum(accZ, s_red3);
+        if (threadIdx.x == 0) partialsZ[blockIdx.x] = tz;
+    }
     if (INF) {
         const double m = block_max(mx, s_red2);
         if (threadIdx.x == 0) partialsInf[blockIdx.x] = m;
     }
 }
-int launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, long long n, double* partials, double* partialsInf,
-                    const double* pApPartials, int nPAp, bool freeze)
+int launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, const double* dinv, long long n, double* partials, double* partialsZ,
+                    double* partialsInf, const double* pApPartials, int nPAp, bool freeze)
 {
-    const bool v2 = al16(r) && al16(Ap);
+    const bool v2 = al16(r) && al16(Ap) && al16(dinv);
     int grid = grid_for(n, v2 ? 4 : 2);
     // two workgroups per CU measured best for this 2-reads-1-write pass (0.565 ms against 0.59-0.61 for 768 / 1024 / 2048 and 0.72 for 256
     // workgroups at 512^3; the 3-reads-2-writes x/p pass keeps 2048)
@@ -460,12 +494,13 @@ int launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, l
     const int want = 2 * (d ? d->numCu : kNumCu);
     if (grid > want) grid = want;
     const bool inf = partialsInf != nullptr;
-    const bool nt = vec_nt(n);
-    with_flags([&](auto V2, auto INF, auto NTV) {
-        hipLaunchKernelGGL((update_r_kernel<V2.value, INF.value, NTV.value>), dim3(grid), dim3(kBlock), 0, s, sc, r, Ap, n, partials, partialsInf, pApPartials, nPAp, freeze ? 1 : 0);
-    }, v2, inf, nt);
+    with_flags([&](auto V2, auto INF, auto NTV, auto DINV) {
+        hipLaunchKernelGGL((update_r_kernel<V2.value, INF.value, NTV.value, DINV.value>), dim3(grid), dim3(kBlock), 0, s, sc, r, Ap, dinv, n, partials, partialsZ, partialsInf,
+                           pApPartials, nPAp, freeze ? 1 : 0);
+    }, v2, inf, vec_nt(n), dinv != nullptr);
     if (dot_reference_order()) {
         launch_dot_serial(s, r, r, n, partials, &sc->done);
+        if (dinv != nullptr) launch_dot_serial(s, r, r, n, partialsZ, &sc->done, dinv);
         if (inf) hipLaunchKernelGGL(reduce_inplace_kernel, dim3(1), dim3(kBlock), 0, s, partialsInf, grid, 1, (const int*)&sc->done);
         return 1;
     }
@@ -473,9 +508,11 @@ int launch_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, l
 }
 
 // The element pass of update_xp_kernel and update_xp_final_kernel: x = x + alpha*p and, unless this iteration stopped the loop (stop: x
-// only), p = z + beta*p.  Every product is rounded, then added; p is read once for both.
-template <bool V2, bool NTV>
-__device__ __forceinline__ void xp_pass(double alpha, double beta, bool stop, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ z, long long n)
+// only), p = z + beta*p.  Every product is rounded, then added; p is read once for both.  DINV (the Jacobi-preconditioned loop): the
+// caller passes r for z and z_i = dinv_i * r_i is formed here, the bits update_r summed (48 bytes per row against 40); dinv is null otherwise.
+template <bool V2, bool NTV, bool DINV>
+__device__ __forceinline__ void xp_pass(double alpha, double beta, bool stop, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ z,
+                                        const double* __restrict__ dinv, long long n)
 {
     if (stop) {
         grid_stride<V2>(n,
@@ -483,21 +520,30 @@ __device__ __forceinline__ void xp_pass(double alpha, double beta, bool stop, do
             [&](long long i) { double t = alpha * p[i]; x[i] = x[i] + t; });
         return;
     }
-    auto one = [&](long long i) { const double pv = p[i]; double t = alpha * pv; x[i] = x[i] + t; double u = beta * pv; p[i] = z[i] + u; };
+    auto one = [&](long long i) {
+        const double pv = p[i]; double t = alpha * pv; x[i] = x[i] + t;
+        double zv = z[i];
+        if constexpr (DINV) zv = dinv[i] * zv;
+        double u = beta * pv; p[i] = zv + u;
+    };
     if constexpr (V2) {
         // streaming hints on both sides: none of x, p, z is touched again before ~2 GB of other traffic
-        d2* x2 = (d2*)x; d2* p2 = (d2*)p; const d2* z2 = (const d2*)z;
-        auto fin = [&](d2& xv, d2& pv, const d2& zv) {
+        d2* x2 = (d2*)x; d2* p2 = (d2*)p; const d2* z2 = (const d2*)z; const d2* d2p = (const d2*)dinv;
+        auto fin = [&](d2& xv, d2& pv, const d2& zv, const d2& dv) {
             double t0 = alpha * pv.x; double t1 = alpha * pv.y; xv.x = xv.x + t0; xv.y = xv.y + t1;
-            double u0 = beta * pv.x; double u1 = beta * pv.y; pv.x = zv.x + u0; pv.y = zv.y + u1;
+            double z0 = zv.x, z1 = zv.y;
+            if constexpr (DINV) { z0 = dv.x * zv.x; z1 = dv.y * zv.y; }
+            double u0 = beta * pv.x; double u1 = beta * pv.y; pv.x = z0 + u0; pv.y = z1 + u1;
         };
         chunk_pairs(n >> 1, [&](long long i, bool two) {
             const long long j = two ? i + kBlock : i;
-            d2 pv0 = ldv<NTV>(p2 + i), xv0 = ldv<NTV>(x2 + i), zv0 = ldv<NTV>(z2 + i);
+            d2 pv0 = ldv<NTV>(p2 + i), xv0 = ldv<NTV>(x2 + i), zv0 = ldv<NTV>(z2 + i), dv0 = {}, dv1 = {};
+            if constexpr (DINV) dv0 = ldv<NTV>(d2p + i);
             d2 pv1 = ldv<NTV>(p2 + j), xv1 = ldv<NTV>(x2 + j), zv1 = ldv<NTV>(z2 + j);
-            fin(xv0, pv0, zv0);
+            if constexpr (DINV) dv1 = ldv<NTV>(d2p + j);
+            fin(xv0, pv0, zv0, dv0);
             stv<NTV>(xv0, x2 + i); stv<NTV>(pv0, p2 + i);
-            if (two) { fin(xv1, pv1, zv1); stv<NTV>(xv1, x2 + j); stv<NTV>(pv1, p2 + j); }
+            if (two) { fin(xv1, pv1, zv1, dv1); stv<NTV>(xv1, x2 + j); stv<NTV>(pv1, p2 + j); }
         });
         if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
     } else {
@@ -513,7 +559,7 @@ __global__ __launch_bounds__(kBlock) void update_xp_kernel(const CgScalars* __re
 {
     if (sc->pad == 0) return;                   // this iteration did not run (the loop had already stopped)
     const double alpha = sc->alpha, beta = sc->beta;
-    xp_pass<V2, NTV>(alpha, beta, sc->done != 0, x, p, z, n);   // (done: this is the iteration that stopped the loop)
+    xp_pass<V2, NTV, false>(alpha, beta, sc->done != 0, x, p, z, nullptr, n);   // (done: this is the iteration that stopped the loop)
 }
 void launch_update_xp(hipStream_t s, const CgScalars* sc, double* x, double* p, const double* z, long long n)
 {
@@ -590,24 +636,29 @@ __device__ __forceinline__ FrozenStep finalize_frozen(const FinalizeArgs& f, con
     return { alpha, s_beta, s_stop != 0 };
 }
 
-// The x/p update with the iteration's finalisation folded in (no preconditioner: z = r; one rank, or several behind their all-reduce
-// of r.r).  Needs update_r launched with freeze = true.  The arithmetic of x and p is update_xp_kernel's.
-template <bool V2, bool NTV>
-__global__ __launch_bounds__(kBlock) void update_xp_final_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsInf,
-                                                                 int nPartials, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ z, long long n)
+// The x/p update with the iteration's finalisation folded in (one rank, or several behind their all-reduce of r.r).  Needs update_r
+// launched with freeze = true.  The arithmetic of x and p is update_xp_kernel's.  No preconditioner: z = r.  DINV (the Jacobi-preconditioned
+// loop): the finalisation takes beta from r.z (partialsZ, or with nPartials == 0 the all-reduced pair {rrNew, rzNew}) and z = dinv * r.
+template <bool V2, bool NTV, bool DINV>
+__global__ __launch_bounds__(kBlock) void update_xp_final_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsZ,
+                                                                 const double* __restrict__ partialsInf, int nPartials, double* __restrict__ x,
+                                                                 double* __restrict__ p, const double* __restrict__ r, const double* __restrict__ dinv, long long n)
 {
     CgScalars* sc = f.sc;
     if (sc->fDone != 0) return;                                       // the loop had stopped before this iteration: nothing ran, nothing is pending
-    const FrozenStep k = finalize_frozen<true, 0>(f, partials, partialsInf, nPartials);
-    xp_pass<V2, NTV>(k.alpha, k.beta, k.stop, x, p, z, n);
+    const FrozenStep k = finalize_frozen<true, 0, DINV>(f, partials, partialsInf, nPartials, partialsZ);
+    xp_pass<V2, NTV, DINV>(k.alpha, k.beta, k.stop, x, p, r, dinv, n);
 }
-void launch_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsInf, int nPartials,
-                            double* x, double* p, const double* z, long long n)
+void launch_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsZ, const double* partialsInf, int nPartials,
+                            double* x, double* p, const double* r, const double* dinv, long long n)
 {
     if (n <= 0) return;
-    const bool v2 = al16(x) && al16(p) && al16(z);
+    const bool v2 = al16(x) && al16(p) && al16(r) && al16(dinv);
     with_v2_nt(v2, vec_nt(n), [&](auto V2, auto NTV) {
-        hipLaunchKernelGGL((update_xp_final_kernel<V2.value, NTV.value>), dim3(grid_for(n, V2.value ? 2 : 1)), dim3(kBlock), 0, s, f, partials, partialsInf, nPartials, x, p, z, n);
+        with_flags([&](auto DINV) {
+            hipLaunchKernelGGL((update_xp_final_kernel<V2.value, NTV.value, DINV.value>), dim3(grid_for(n, V2.value ? 2 : 1)), dim3(kBlock), 0, s, f, partials, partialsZ,
+                               partialsInf, nPartials, x, p, r, dinv, n);
+        }, dinv != nullptr);
     });
 }
 
@@ -757,20 +808,26 @@ __device__ __forceinline__ void reset_scalars(CgScalars* sc, HostMirror* mirror,
     sc->fRr = rr; sc->fRr0 = rr0; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
     mirror->residual = 0; mirror->iteration = 0; mirror->status = 0; mirror->done = 0;
 }
-__global__ __launch_bounds__(kBlock) void init_scalars_kernel(const double* __restrict__ partials, int n, int reduceFirst,
+// partialsZ (the Jacobi-preconditioned loop, else null): rz = r0.z0 goes where alpha and beta look for it, the true r0.r0 where the relative
+// rule does.  !reduceFirst (several ranks): the sums are all-reduced already, r.r in sc->rr, or with partialsZ the pair in {sc->rrNew, sc->rzNew}.
+__global__ __launch_bounds__(kBlock) void init_scalars_kernel(const double* __restrict__ partials, const double* __restrict__ partialsZ, int n, int reduceFirst,
                                                               CgScalars* sc, HostMirror* mirror)
 {
     __shared__ double s_red[4];
-    double rr = 0.0;
-    if (reduceFirst) rr = reduce_partials_block(partials, n, s_red, 0);
+    const bool precond = partialsZ != nullptr;
+    double rr = 0.0, rz = 0.0;
+    if (reduceFirst) {
+        rr = reduce_partials_block(partials, n, s_red, 0);
+        if (precond) { __syncthreads(); rz = reduce_partials_block(partialsZ, n, s_red, 0); }   // (s_red again: every wave has read the first sum)
+    }
     if (threadIdx.x == 0) {
-        if (!reduceFirst) rr = sc->rr;
-        reset_scalars(sc, mirror, rr, rr);
+        if (!reduceFirst) { rr = precond ? sc->rrNew : sc->rr; rz = sc->rzNew; }
+        reset_scalars(sc, mirror, precond ? rz : rr, rr);
     }
 }
-void launch_init_scalars(hipStream_t s, const double* partials, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror)
+void launch_init_scalars(hipStream_t s, const double* partials, const double* partialsZ, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror)
 {
-    hipLaunchKernelGGL(init_scalars_kernel, dim3(1), dim3(kBlock), 0, s, partials, n, reduceFirst ? 1 : 0, sc, mirror);
+    hipLaunchKernelGGL(init_scalars_kernel, dim3(1), dim3(kBlock), 0, s, partials, partialsZ, n, reduceFirst ? 1 : 0, sc, mirror);
 }
 
 // Residual, stop test, beta and the rr hand-over.
@@ -820,10 +877,8 @@ void launch_finalize_precond(hipStream_t s, const double* partials, int n, bool 
 
 // ------------------------------------------------------------------ Jacobi-preconditioned loop (SolveJacobi / SolveJacobiParallel)
 // z = D^-1 r is element-wise, so the preconditioned iteration keeps the plain loop's two launches after the product and stores no z:
-// both passes form z_i = dinv_i * r_i themselves -- one rounded product, the same bits in both (never contracted with the add that
-// follows: product into a named double, then the add).  The r update moves 32 bytes per row (Ap, r, dinv in; r out), the x/p update 48
-// (p, x, r, dinv in; x, p out): 80 against the plain loop's 64.  Partial sums, the done / frozen-scalars protocol and the streaming hints
-// are those of update_r_kernel and update_xp_final_kernel.
+// the DINV forms of copy_dot_kernel, update_r_kernel and update_xp_final_kernel above form z_i = dinv_i * r_i themselves (rz_term).  The r
+// update moves 32 bytes per row, the x/p update 48: 80 against the plain loop's 64.  What is left here is the set-up.
 
 // dinv_i = 1 / a_ii, a_ii = the first stored entry of local row i in column rowBase + i (rows need not be sorted).  A row without that
 // entry, or with one that is not finite and > 0 (or so small that its reciprocal is not finite), raises bad[0] and lowers bad[1] to its index (pre-set to {0, INT_MAX} by the caller).
@@ -846,190 +901,6 @@ void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOf
 {
     if (n <= 0) return;
     hipLaunchKernelGGL(jacobi_setup_kernel, dim3(grid_for(n, 1)), dim3(kBlock), 0, s, elements, rowOffsets, columnIndeces, nnz, n, rowBase, dinv, bad);
-}
-
-// The element step of the start pass and of the r update: the new r's share of r.z, z = dinv * r rounded first.
-__device__ __forceinline__ double rz_term(double dinv, double r, double& acc) { double z = dinv * r; double t = r * z; acc += t; return z; }
-
-// p = z = dinv * r ; partial r.r and r.z   (the start of the loop: copy_dot_kernel's place)
-template <bool V2>
-__global__ __launch_bounds__(kBlock) void jacobi_start_kernel(double* __restrict__ p, const double* __restrict__ r, const double* __restrict__ dinv, long long n,
-                                                              double* __restrict__ partials, double* __restrict__ partialsZ)
-{
-    __shared__ double s_red[4];
-    __shared__ double s_red2[4];
-    double acc = 0.0, accZ = 0.0, mx = 0.0;
-    grid_stride<V2>(n,
-        [&](long long i) {
-            d2 rv = *(const d2*)(r + i); d2 dv = *(const d2*)(dinv + i); d2 zv;
-            r_sums<false>(acc, mx, rv.x, rv.y);
-            zv.x = rz_term(dv.x, rv.x, accZ); zv.y = rz_term(dv.y, rv.y, accZ);
-            *(d2*)(p + i) = zv;
-        },
-        [&](long long i) { double rv = r[i]; r_sums<false>(acc, mx, rv); p[i] = rz_term(dinv[i], rv, accZ); });
-    const double t = block_sum(acc, s_red);
-    const double tz = block_sum(accZ, s_red2);
-    if (threadIdx.x == 0) { partials[blockIdx.x] = t; partialsZ[blockIdx.x] = tz; }
-}
-int launch_jacobi_start(hipStream_t s, double* p, const double* r, const double* dinv, long long n, double* partials, double* partialsZ)
-{
-    const bool v2 = al16(p) && al16(r) && al16(dinv);
-    const int grid = grid_for(n, v2 ? 4 : 2);
-    if (v2) hipLaunchKernelGGL(jacobi_start_kernel<true>, dim3(grid), dim3(kBlock), 0, s, p, r, dinv, n, partials, partialsZ);
-    else hipLaunchKernelGGL(jacobi_start_kernel<false>, dim3(grid), dim3(kBlock), 0, s, p, r, dinv, n, partials, partialsZ);
-    if (dot_reference_order()) {
-        launch_dot_serial(s, r, r, n, partials, nullptr);
-        launch_dot_serial(s, r, r, n, partialsZ, nullptr, dinv);
-        return 1;
-    }
-    return grid;
-}
-
-// update_r_kernel with two sums (its head and element step, plus dinv and the second sum): alpha = rz / pAp ; r = r + (-alpha)*Ap ; partial r.r, r.z [, max|r|] of the rounded r
-template <bool V2, bool INF, bool NTV>
-__global__ __launch_bounds__(kBlock) void jacobi_update_r_kernel(CgScalars* __restrict__ sc, double* __restrict__ r, const double* __restrict__ Ap,
-                                                                 const double* __restrict__ dinv, long long n,
-                                                                 double* __restrict__ partials, double* __restrict__ partialsZ, double* __restrict__ partialsInf,
-                                                                 const double* __restrict__ pApPartials, int nPAp, int freeze)
-{
-    __shared__ double s_red[4];
-    __shared__ double s_red2[4];
-    __shared__ double s_red3[4];
-    __shared__ double s_pAp;
-    if (sc->done != 0) { if (freeze && blockIdx.x == 0 && threadIdx.x == 0) sc->fDone = 1; return; }
-    double pAp;
-    if (pApPartials != nullptr) {                                     // single-rank loop: no separate reduction launch
-        const double t = reduce_partials_block(pApPartials, nPAp, s_red, 0);
-        if (threadIdx.x == 0) s_pAp = t;
-        __syncthreads();
-        pAp = s_pAp;
-        if (blockIdx.x == 0 && threadIdx.x == 0) sc->pAp = pAp;
-    } else {
-        pAp = sc->pAp;
-    }
-    const double alpha = sc->rr / pAp;                              // (sc->rr holds r.z)
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        sc->alpha = alpha;                                            // for update_xp of this iteration
-        if (freeze) { sc->fRr = sc->rr; sc->fRr0 = sc->rr0; sc->fAlpha = alpha; sc->fIteration = sc->iteration; sc->fDone = 0; }
-    }
-    const double malpha = -alpha;
-    double acc = 0.0, accZ = 0.0, mx = 0.0;
-    auto one = [&](long long i) { double rv = r_step(malpha, Ap[i], r[i]); r[i] = rv; r_sums<INF>(acc, mx, rv); (void)rz_term(dinv[i], rv, accZ); };
-    if constexpr (V2) {
-        d2* r2 = (d2*)r; const d2* a2 = (const d2*)Ap; const d2* d2p = (const d2*)dinv;
-        auto fin = [&](d2& rv, const d2& av, const d2& dv) {
-            rv.x = r_step(malpha, av.x, rv.x); rv.y = r_step(malpha, av.y, rv.y);
-            r_sums<INF>(acc, mx, rv.x, rv.y);
-            (void)rz_term(dv.x, rv.x, accZ); (void)rz_term(dv.y, rv.y, accZ);
-        };
-        chunk_pairs(n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            // Ap is not read again; r and dinv come back in the x/p update, after that pass's own 48 bytes per row
-            d2 av0 = ldv<NTV>(a2 + i), rv0 = ldv<NTV>(r2 + i), dv0 = ldv<NTV>(d2p + i), av1 = ldv<NTV>(a2 + j), rv1 = ldv<NTV>(r2 + j), dv1 = ldv<NTV>(d2p + j);
-            fin(rv0, av0, dv0); stv<NTV>(rv0, r2 + i);
-            if (two) { fin(rv1, av1, dv1); stv<NTV>(rv1, r2 + j); }
-        });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
-    } else {
-        grid_stride<false>(n, [&](long long) {}, one);
-    }
-    const double t = block_sum(acc, s_red);
-    const double tz = block_sum(accZ, s_red3);
-    if (threadIdx.x == 0) { partials[blockIdx.x] = t; partialsZ[blockIdx.x] = tz; }
-    if (INF) {
-        const double m = block_max(mx, s_red2);
-        if (threadIdx.x == 0) partialsInf[blockIdx.x] = m;
-    }
-}
-int launch_jacobi_update_r(hipStream_t s, CgScalars* sc, double* r, const double* Ap, const double* dinv, long long n, double* partials, double* partialsZ,
-                           double* partialsInf, const double* pApPartials, int nPAp, bool freeze)
-{
-    const bool v2 = al16(r) && al16(Ap) && al16(dinv);
-    int grid = grid_for(n, v2 ? 4 : 2);
-    DeviceState* d = device_state();                               // a 3-reads-1-write stream: update_r's two workgroups per CU
-    const int want = 2 * (d ? d->numCu : kNumCu);
-    if (grid > want) grid = want;
-    const bool inf = partialsInf != nullptr;
-    with_flags([&](auto V2, auto INF, auto NTV) {
-        hipLaunchKernelGGL((jacobi_update_r_kernel<V2.value, INF.value, NTV.value>), dim3(grid), dim3(kBlock), 0, s, sc, r, Ap, dinv, n, partials, partialsZ, partialsInf,
-                           pApPartials, nPAp, freeze ? 1 : 0);
-    }, v2, inf, vec_nt(n));
-    if (dot_reference_order()) {
-        launch_dot_serial(s, r, r, n, partials, &sc->done);
-        launch_dot_serial(s, r, r, n, partialsZ, &sc->done, dinv);
-        if (inf) hipLaunchKernelGGL(reduce_inplace_kernel, dim3(1), dim3(kBlock), 0, s, partialsInf, grid, 1, (const int*)&sc->done);
-        return 1;
-    }
-    return grid;
-}
-
-// xp_pass with z_i = dinv_i * r_i formed here: x = x + alpha*p and, unless this iteration stopped the loop, p = z + beta*p
-template <bool V2, bool NTV>
-__device__ __forceinline__ void jacobi_xp_pass(double alpha, double beta, bool stop, double* __restrict__ x, double* __restrict__ p, const double* __restrict__ r,
-                                               const double* __restrict__ dinv, long long n)
-{
-    if (stop) { xp_pass<V2, NTV>(alpha, beta, true, x, p, r, n); return; }              // x only
-    auto one = [&](long long i) { const double pv = p[i]; double t = alpha * pv; x[i] = x[i] + t; double z = dinv[i] * r[i]; double u = beta * pv; p[i] = z + u; };
-    if constexpr (V2) {
-        d2* x2 = (d2*)x; d2* p2 = (d2*)p; const d2* r2 = (const d2*)r; const d2* d2p = (const d2*)dinv;
-        auto fin = [&](d2& xv, d2& pv, const d2& rv, const d2& dv) {
-            double t0 = alpha * pv.x; double t1 = alpha * pv.y; xv.x = xv.x + t0; xv.y = xv.y + t1;
-            double z0 = dv.x * rv.x; double z1 = dv.y * rv.y;
-            double u0 = beta * pv.x; double u1 = beta * pv.y; pv.x = z0 + u0; pv.y = z1 + u1;
-        };
-        chunk_pairs(n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            d2 pv0 = ldv<NTV>(p2 + i), xv0 = ldv<NTV>(x2 + i), rv0 = ldv<NTV>(r2 + i), dv0 = ldv<NTV>(d2p + i);
-            d2 pv1 = ldv<NTV>(p2 + j), xv1 = ldv<NTV>(x2 + j), rv1 = ldv<NTV>(r2 + j), dv1 = ldv<NTV>(d2p + j);
-            fin(xv0, pv0, rv0, dv0);
-            stv<NTV>(xv0, x2 + i); stv<NTV>(pv0, p2 + i);
-            if (two) { fin(xv1, pv1, rv1, dv1); stv<NTV>(xv1, x2 + j); stv<NTV>(pv1, p2 + j); }
-        });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(n - 1);
-    } else {
-        grid_stride<false>(n, [&](long long) {}, one);
-    }
-}
-
-// update_xp_final_kernel for this loop: the finalisation (residual and stop decision from r.r, beta = rzNew / rz), then the pass above.
-// Needs jacobi_update_r launched with freeze = true.  nPartials == 0 (several ranks): {rrNew, rzNew} are all-reduced already.
-template <bool V2, bool NTV>
-__global__ __launch_bounds__(kBlock) void jacobi_update_xp_final_kernel(FinalizeArgs f, const double* __restrict__ partials, const double* __restrict__ partialsZ,
-                                                                        const double* __restrict__ partialsInf, int nPartials, double* __restrict__ x,
-                                                                        double* __restrict__ p, const double* __restrict__ r, const double* __restrict__ dinv, long long n)
-{
-    CgScalars* sc = f.sc;
-    if (sc->fDone != 0) return;
-    const FrozenStep k = finalize_frozen<true, 0, true>(f, partials, partialsInf, nPartials, partialsZ);
-    jacobi_xp_pass<V2, NTV>(k.alpha, k.beta, k.stop, x, p, r, dinv, n);
-}
-void launch_jacobi_update_xp_final(hipStream_t s, const FinalizeArgs& f, const double* partials, const double* partialsZ, const double* partialsInf, int nPartials,
-                                   double* x, double* p, const double* r, const double* dinv, long long n)
-{
-    if (n <= 0) return;
-    const bool v2 = al16(x) && al16(p) && al16(r) && al16(dinv);
-    with_v2_nt(v2, vec_nt(n), [&](auto V2, auto NTV) {
-        hipLaunchKernelGGL((jacobi_update_xp_final_kernel<V2.value, NTV.value>), dim3(grid_for(n, V2.value ? 2 : 1)), dim3(kBlock), 0, s, f, partials, partialsZ, partialsInf,
-                           nPartials, x, p, r, dinv, n);
-    });
-}
-
-// init_scalars_kernel for this loop: rz = r0.z0 goes where alpha and beta look for it, the true r0.r0 where the relative rule does
-__global__ __launch_bounds__(kBlock) void jacobi_init_scalars_kernel(const double* __restrict__ partials, const double* __restrict__ partialsZ, int n, int reduceFirst,
-                                                                     CgScalars* sc, HostMirror* mirror)
-{
-    __shared__ double s_red[4];
-    __shared__ double s_red2[4];
-    double rr = 0.0, rz = 0.0;
-    if (reduceFirst) { rr = reduce_partials_block(partials, n, s_red, 0); rz = reduce_partials_block(partialsZ, n, s_red2, 0); }
-    if (threadIdx.x == 0) {
-        if (!reduceFirst) { rr = sc->rrNew; rz = sc->rzNew; }          // (all-reduced as one pair)
-        reset_scalars(sc, mirror, rz, rr);
-    }
-}
-void launch_jacobi_init_scalars(hipStream_t s, const double* partials, const double* partialsZ, int n, bool reduceFirst, CgScalars* sc, HostMirror* mirror)
-{
-    hipLaunchKernelGGL(jacobi_init_scalars_kernel, dim3(1), dim3(kBlock), 0, s, partials, partialsZ, n, reduceFirst ? 1 : 0, sc, mirror);
 }
 
 void preload_kernels_blas1() { preload_code_object(reinterpret_cast<const void*>(&fill_kernel)); }

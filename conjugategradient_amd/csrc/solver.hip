@@ -515,6 +515,7 @@ struct CgRun {
     SpmvProfile* prof = nullptr;
     const DcsrMatrix* dcsr = nullptr;      // compressed form of the matrix if the handle has one
     MgcgSparse* cusparse = nullptr;
+    double usShape = 0, usForm = 0;        // what cg_matrix_setup took (MGCG_VERBOSE=2)
     // rows [interior0, interior1) reference local columns only: they are multiplied (side stream) while the halo of p is in flight
     bool overlap = false;
     long long interior0 = 0, interior1 = 0;
@@ -745,24 +746,31 @@ static void placement_draw(CgRun& R, bool fixedSteps)
     placement_ring(R);
 }
 
+// What the loop's SpMV needs to know about this call's matrix: its shape, its compressed form if the handle has one, and the kernel flags
+// that follow.  Once per call.
+static void cg_matrix_setup(CgRun& R)
+{
+    long long meanDistance = 0;
+    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
+    const auto t0 = std::chrono::steady_clock::now();
+    if (R.elementsCount >= 8) R.cfg.periodRows = spmv_period(R.cusparse, R.rowOffsets, R.columnIndeces, R.nLocal, R.offset, &R.cfg.maxRow, &meanDistance);
+    R.usShape = since(t0);
+    const auto t1 = std::chrono::steady_clock::now();
+    R.dcsr = dcsr_lookup(R.cusparse, R.elements, R.rowOffsets, R.columnIndeces, R.nLocal, R.elementsCount, R.offset, R.count, R.mg ? -1 : meanDistance);
+    R.usForm = since(t1);
+    if (meanDistance >= (1LL << 19) && R.count >= (8LL << 19)) R.cfg.flags |= 16;      // gathers without locality: the stream form among the CSR kernels
+    if (!R.mg) R.cfg.flags |= 8;                 // plain CG loop: the row-tile kernel may read the matrix with the non-temporal hint (kernels_rowtile.hip)
+}
+
 static bool cg_enqueue_init(CgRun& R, bool fixedSteps = false)
 {
     hipStream_t s = R.ws->stream;
-    long long meanDistance = 0;
     // MGCG_VERBOSE=2: what a solve pays before its first iteration is enqueued (the reference's driver times a cold Solve(): MgcgMain.cs:121-126)
-    const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
-    if (R.cusparse && R.elementsCount >= 8) R.cfg.periodRows = spmv_period(R.cusparse, R.rowOffsets, R.columnIndeces, R.nLocal, R.offset, &R.cfg.maxRow, &meanDistance);
-    const double usShape = since(t0);
-    const auto t1 = std::chrono::steady_clock::now();
-    if (R.cusparse) R.dcsr = dcsr_lookup(R.cusparse, R.elements, R.rowOffsets, R.columnIndeces, R.nLocal, R.elementsCount, R.offset, R.count, R.mg ? -1 : meanDistance);
-    const double usForm = since(t1);
-    if (meanDistance >= (1LL << 19) && R.count >= (8LL << 19)) R.cfg.flags |= 16;      // gathers without locality: the stream form among the CSR kernels
-    if (!R.mg) R.cfg.flags |= 8;                 // plain CG loop: the row-tile kernel may read the matrix with the non-temporal hint (kernels_rowtile.hip)
     const auto t2 = std::chrono::steady_clock::now();
     placement_draw(R, fixedSteps);               // (before p is touched: may move p's data once per vector)
-    if (report) fprintf(stderr, "[MgcgGpu] solve set-up: matrix shape %.0f us, matrix form %.0f us, placement draw %.0f us\n", usShape, usForm, since(t2));
+    if (tuning().verbose.load(std::memory_order_relaxed) >= 2)
+        fprintf(stderr, "[MgcgGpu] solve set-up: matrix shape %.0f us, matrix form %.0f us, placement draw %.0f us\n", R.usShape, R.usForm,
+                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t2).count());
     CgScalars* sc = R.ws->scalars;
     double* pLoc = R.p + R.offset;
     if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, R.nLocal);             // SimpleConjugateGradient.cu:53
@@ -771,34 +779,25 @@ static bool cg_enqueue_init(CgRun& R, bool fixedSteps = false)
     SpmvArgs a = cg_spmv_args(R, R.p, R.r);
     a.b = R.b;
     launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);                             // r = b - A x   (Mgcg.cu:225-226)
+    // The partial sums of what alpha and beta divide: r.r, or r.z with the V-cycle.  The Jacobi loop keeps r.z next to the true r.r, which
+    // its relative stop rule divides by (the start pass runs at most kMaxGrid <= kMaxPartials / 2 workgroups).
+    double* partials = R.ws->partials;
+    double* partialsZ = R.dinv ? partials + kMaxPartials / 2 : nullptr;
     int n;
-    if (R.dinv) {
-        // p = z = D^-1 r with r.z and r.r in the same pass: rz is what alpha and beta divide, the true r0.r0 what the relative rule divides by
-        double* rrPartials = R.ws->partials + 2 * kMaxPartials;
-        double* rzPartials = rrPartials + kMaxPartials / 2;
-        n = launch_jacobi_start(s, pLoc, R.r, R.dinv, R.nLocal, rrPartials, rzPartials);
-        if (R.multi) {
-            launch_reduce2_to(s, rrPartials, n, &sc->rrNew, rzPartials, n, &sc->rzNew, nullptr);
-            if (!comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;
-        }
-        launch_jacobi_init_scalars(s, rrPartials, rzPartials, n, !R.multi, sc, R.ws->mirror);
-        return MGCG_HIP(hipGetLastError());
-    }
     if (R.mg) {
         int nz = 0;
-        if (!mg_apply(R.mg, R.r, R.z, nullptr, dot_reference_order() ? nullptr : R.ws->partials, &nz)) return false;   // z = M^-1 r (+ r.z)
+        if (!mg_apply(R.mg, R.r, R.z, nullptr, dot_reference_order() ? nullptr : partials, &nz)) return false;   // z = M^-1 r (+ r.z)
         launch_copy(s, pLoc, R.z, R.nLocal);                                         // p = z
-        n = nz > 0 ? nz : launch_dot_partials(s, R.r, R.z, R.nLocal, R.ws->partials);   // rz = r.z
+        n = nz > 0 ? nz : launch_dot_partials(s, R.r, R.z, R.nLocal, partials);      // rz = r.z
     } else {
-        n = launch_copy_dot(s, pLoc, R.r, R.nLocal, R.ws->partials, nullptr);        // p = r ; rr = r.r  (Mgcg.cu:227-228)
+        n = launch_copy_dot(s, pLoc, R.r, R.dinv, R.nLocal, partials, partialsZ, nullptr);   // p = r ; rr = r.r  (Mgcg.cu:227-228), or p = z = D^-1 r ; r.r and r.z
     }
-    if (R.multi) {
-        launch_reduce_to(s, R.ws->partials, n, &sc->rr, nullptr);
-        if (!comm_allreduce_sum(R.comm, &sc->rr, 1, s)) return false;                // resultsDot.Sum()  (:463)
-        launch_init_scalars(s, R.ws->partials, n, false, sc, R.ws->mirror);
-    } else {
-        launch_init_scalars(s, R.ws->partials, n, true, sc, R.ws->mirror);
+    if (R.multi) {                                                                   // resultsDot.Sum()  (:463); the Jacobi loop's pair {rrNew, rzNew} in one all-reduce
+        if (R.dinv) launch_reduce2_to(s, partials, n, &sc->rrNew, partialsZ, n, &sc->rzNew, nullptr);
+        else launch_reduce_to(s, partials, n, &sc->rr, nullptr);
+        if (!comm_allreduce_sum(R.comm, R.dinv ? &sc->rrNew : &sc->rr, R.dinv ? 2 : 1, s)) return false;
     }
+    launch_init_scalars(s, partials, partialsZ, n, !R.multi, sc, R.ws->mirror);
     return MGCG_HIP(hipGetLastError());
 }
 
@@ -842,20 +841,19 @@ static bool cg_enqueue_product(CgRun& R, double* pIn, int* nPAp)
 }
 
 // What follows the product in one iteration.  Every variant starts with update_r (alpha, r -= alpha Ap, partial r.r); they differ in who
-// takes the stop decision and where x and p are updated.  Launches per iteration after the product, all-reduces in brackets:
+// takes the stop decision and where x and p are updated.  The Jacobi loop (R.dinv) takes the Fused and Unfused rows: update_r and
+// update_xp_final form z = D^-1 r themselves, and r.z travels with r.r (reduce2, [r.r, r.z] in place of reduce, [r.r]).
+// Launches per iteration after the product, all-reduces in brackets:
 enum class CgUpdate {
     FusedOneRank,       // update_r, update_xp_final (or update_xp_ring: deferred x update)                                          2
     FusedRanks,         // reduce, [p.Ap], update_r, reduce, [r.r], update_xp_final                                                 4
     PrecondOneRank,     // update_r, finalize, V-cycle (+ dot), finalize_precond, update_xp                                         4 + V-cycle
     PrecondRanks,       // reduce, [p.Ap], update_r, V-cycle (+ dot), reduce2, [r.r, r.z], finalize, update_xp                      5 + V-cycle
-    Unfused,            // a rank without rows: as the plain variants, with finalize in place of the x/p update                         2 or 4
-    JacobiOneRank,      // jacobi_update_r, jacobi_update_xp_final: FusedOneRank with z = D^-1 r formed inside both passes                2
-    JacobiRanks         // reduce, [p.Ap], jacobi_update_r, reduce2, [r.r, r.z], jacobi_update_xp_final                                   4
+    Unfused             // a rank without rows: as the Fused variants, with finalize in place of the x/p update (Jacobi: reduce2 in front)   2 to 4
 };
 static CgUpdate cg_update_variant(const CgRun& R)
 {
     if (R.mg) return R.multi ? CgUpdate::PrecondRanks : CgUpdate::PrecondOneRank;
-    if (R.dinv && R.nLocal > 0) return R.multi ? CgUpdate::JacobiRanks : CgUpdate::JacobiOneRank;
     // a rank without rows: launch_update_xp_final returns before it launches (n <= 0), so only launch_finalize can finalise its iteration
     if (R.nLocal <= 0) return CgUpdate::Unfused;
     return R.multi ? CgUpdate::FusedRanks : CgUpdate::FusedOneRank;
@@ -877,38 +875,24 @@ static bool cg_enqueue_update(CgRun& R, double* pLoc, int nPAp, bool withStopTes
     CgScalars* sc = R.ws->scalars;
     const int* done = &sc->done;
     const CgUpdate variant = cg_update_variant(R);
-    const bool fused = variant == CgUpdate::FusedOneRank || variant == CgUpdate::FusedRanks ||   // update_r freezes the scalars for update_xp_final / _ring
-                       variant == CgUpdate::JacobiOneRank || variant == CgUpdate::JacobiRanks;
+    const bool fused = variant == CgUpdate::FusedOneRank || variant == CgUpdate::FusedRanks;   // update_r freezes the scalars for update_xp_final / _ring
     const bool refDots = dot_reference_order();
     double* pInf = R.wantInf ? R.ws->partials + kMaxPartials : nullptr;
-    double* rrPartials;
-    double* rzPartials = nullptr;
-    int n;
-    if (R.dinv) {
-        // the r update leaves both partial-sum sets in the third region of the buffer (its grid is a few hundred workgroups)
-        rrPartials = R.ws->partials + 2 * kMaxPartials;
-        rzPartials = rrPartials + kMaxPartials / 2;
-        if (R.multi) {
-            launch_reduce_to(s, R.ws->partials, nPAp, &sc->pAp, done);
-            if (!comm_allreduce_sum(R.comm, &sc->pAp, 1, s)) return false;
-        }
-        n = launch_jacobi_update_r(s, sc, R.r, R.Ap, R.dinv, R.nLocal, rrPartials, rzPartials, pInf, R.multi ? nullptr : R.ws->partials, R.multi ? 0 : nPAp, fused);
-        if (R.multi || variant == CgUpdate::Unfused) {                               // r.r and r.z: one launch, one all-reduce of the adjacent pair
-            launch_reduce2_to(s, rrPartials, n, &sc->rrNew, rzPartials, n, &sc->rzNew, done);
-            if (R.multi && !comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;
-        }
-    } else if (R.multi) {
+    // the r update leaves its partial sums of r.r and, in the Jacobi loop, of r.z in the third region of the buffer (its grid is a few hundred
+    // workgroups; with the V-cycle they must outlive it: its r.z partial sums take the first region)
+    double* rrPartials = R.ws->partials + 2 * kMaxPartials;
+    double* rzPartials = R.dinv ? rrPartials + kMaxPartials / 2 : nullptr;
+    if (R.multi) {
         launch_reduce_to(s, R.ws->partials, nPAp, &sc->pAp, done);
         if (!comm_allreduce_sum(R.comm, &sc->pAp, 1, s)) return false;               // (:499)
-        rrPartials = R.mg ? R.ws->partials + 2 * kMaxPartials : R.ws->partials;      // (with the V-cycle they must outlive it: its r.z partial sums take the first region)
-        n = launch_update_r(s, sc, R.r, R.Ap, R.nLocal, rrPartials, pInf, nullptr, 0, fused);   // r -= a Ap ; r.r  (:247-248); x += a p rides with the p update below
-    } else {
-        // one rank: the workgroups of the r update add the p.Ap partial sums themselves (one launch fewer per iteration);
-        // their own r.r partial sums go to the third region of the buffer
-        rrPartials = R.ws->partials + 2 * kMaxPartials;
-        n = launch_update_r(s, sc, R.r, R.Ap, R.nLocal, rrPartials, pInf, R.ws->partials, nPAp, fused);
     }
-    if (R.multi && !R.mg && !R.dinv) {                                               // plain loop of several ranks: r.r all-reduced into sc->rrNew
+    // r -= a Ap ; r.r  (:247-248); x += a p rides with the p update below.  One rank: the workgroups of the r update add the p.Ap partial sums
+    // themselves (one launch fewer per iteration)
+    int n = launch_update_r(s, sc, R.r, R.Ap, R.dinv, R.nLocal, rrPartials, rzPartials, pInf, R.multi ? nullptr : R.ws->partials, R.multi ? 0 : nPAp, fused);
+    if (R.dinv && (R.multi || variant == CgUpdate::Unfused)) {                       // Jacobi loop: r.r and r.z in one launch, one all-reduce of the adjacent pair
+        launch_reduce2_to(s, rrPartials, n, &sc->rrNew, rzPartials, n, &sc->rzNew, done);
+        if (R.multi && !comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;
+    } else if (R.multi && !R.mg) {                                                   // plain loop of several ranks: r.r all-reduced into sc->rrNew
         launch_reduce_to(s, rrPartials, n, &sc->rrNew, done);
         if (!comm_allreduce_sum(R.comm, &sc->rrNew, 1, s)) return false;             // (:525)
     }
@@ -916,27 +900,22 @@ static bool cg_enqueue_update(CgRun& R, double* pLoc, int nPAp, bool withStopTes
     switch (variant) {
     case CgUpdate::FusedOneRank:
         // the x/p update finalises the iteration itself: residual, stop test, beta (:251-266) ; x += a p (:246) ; p = r + beta p (:265)
+        // (Jacobi: beta = rzNew / rz ; p = D^-1 r + beta p)
         if (R.xDefer > 1) {
             RingArgs g = R.ring;
             g.pos = R.groupPos; g.flush = R.groupPos + 1 == R.groupLen ? 1 : 0;
             launch_update_xp_ring(s, f, rrPartials, pInf, n, R.x, g, R.r, R.nLocal);     // the same, x += a p once per group (cg_xdefer_setup)
             if (g.flush) { R.groupPos = 0; R.groupLen = R.xDefer; } else ++R.groupPos;
         } else {
-            launch_update_xp_final(s, f, rrPartials, pInf, n, R.x, pLoc, R.r, R.nLocal);
+            launch_update_xp_final(s, f, rrPartials, rzPartials, pInf, n, R.x, pLoc, R.r, R.dinv, R.nLocal);
         }
         break;
     case CgUpdate::FusedRanks:
-        launch_update_xp_final(s, f, nullptr, nullptr, 0, R.x, pLoc, R.r, R.nLocal);     // the same fold behind the all-reduce of r.r
-        break;
-    case CgUpdate::JacobiOneRank:
-        launch_jacobi_update_xp_final(s, f, rrPartials, rzPartials, pInf, n, R.x, pLoc, R.r, R.dinv, R.nLocal);   // residual, stop test, beta = rzNew / rz ; x += a p ; p = D^-1 r + beta p
-        break;
-    case CgUpdate::JacobiRanks:
-        launch_jacobi_update_xp_final(s, f, nullptr, nullptr, nullptr, 0, R.x, pLoc, R.r, R.dinv, R.nLocal);      // the same behind the all-reduce of {r.r, r.z}
+        launch_update_xp_final(s, f, nullptr, nullptr, nullptr, 0, R.x, pLoc, R.r, R.dinv, R.nLocal);   // the same fold behind the all-reduce of r.r (Jacobi: of {r.r, r.z})
         break;
     case CgUpdate::Unfused:
-        if (R.dinv) { launch_finalize(s, rrPartials, pInf, n, false, f); break; }    // (preconditioned = 2: {rrNew, rzNew} are in place)
-        launch_finalize(s, rrPartials, pInf, n, !R.multi, f);                        // residual, stop test, beta  (:251-266); one rank: it adds r.r up first
+        // residual, stop test, beta  (:251-266); one rank of the plain loop: it adds r.r up first (Jacobi, preconditioned = 2: {rrNew, rzNew} are in place)
+        launch_finalize(s, rrPartials, pInf, n, !R.multi && !R.dinv, f);
         launch_update_xp(s, sc, R.x, pLoc, R.r, R.nLocal);                           // x += a p (:246) ; p = r + beta p   (:265) -- returns at once without rows
         break;
     case CgUpdate::PrecondOneRank: {
@@ -996,6 +975,7 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
     for (int i = 0; i < 4; ++i) slots[i] = 0;
     const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;
     const auto hostT0 = std::chrono::steady_clock::now();
+    if (ok) cg_matrix_setup(R);
     ok = ok && cg_enqueue_init(R);
     if (ok) cg_xdefer_setup(R, 0);
     if (report) {
@@ -1044,14 +1024,65 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
     return ok ? status : MGCG_ERROR;
 }
 
-static bool check_vectors(const char* who, Vector* e, VectorInt* ro, VectorInt* ci, Vector* x, Vector* b, Vector* Ap, Vector* p, Vector* r,
-                          long long elementsCount, long long nLocal, long long count)
+// The arguments that every entry point of the loop takes: the handles, the matrix and the vectors of this rank, the partition.
+struct CgCall {
+    const char* who;                       // the caller's name in its messages
+    MgcgComm* comm; MgcgBlas* cublas; MgcgSparse* cusparse;
+    Vector* elements; VectorInt* rowOffsets; VectorInt* columnIndeces;
+    Vector *x, *b, *Ap, *p, *r;
+    int count, nLocal, offset, elementsCount, minJ, maxJ;
+};
+
+// One call of the loop: the checks of the arguments, the run's description, the halo plan of p with its overlap schedule, body(R), and the
+// plan's release.  handles: the caller's verdict on the handles that only it takes; checks(): its own checks of the arguments, behind the
+// common ones.  false: the body did not run (set_error says why).
+// A rank whose own arguments are unusable must not simply return: its peers would block in the solve's first collective.  The verdict
+// travels in the halo plan's one all-reduce (halo_plan_create, localOk) and every rank leaves.
+template <typename Checks, typename Body>
+static bool cg_call(const CgCall& c, bool handles, Checks checks, Body body)
 {
-    if (!e || !ro || !ci || !x || !b || !Ap || !p || !r) { set_error("%s: null vector handle", who); return false; }
-    if (elementsCount < 0 || nLocal < 0 || count < nLocal) { set_error("%s: bad sizes", who); return false; }
-    if (e->size < elementsCount || ci->size < elementsCount || ro->size < nLocal + 1 || x->size < nLocal || b->size < nLocal ||
-        Ap->size < nLocal || r->size < nLocal || p->size < count) { set_error("%s: a device vector is smaller than the problem", who); return false; }
+    bool pre = handles && c.cublas && c.cusparse;
+    if (!pre) set_error("%s: null handle", c.who);
+    Vector *e = c.elements, *x = c.x, *b = c.b, *Ap = c.Ap, *p = c.p, *r = c.r;
+    VectorInt *ro = c.rowOffsets, *ci = c.columnIndeces;
+    if (pre && (!e || !ro || !ci || !x || !b || !Ap || !p || !r)) { set_error("%s: null vector handle", c.who); pre = false; }
+    if (pre && (c.elementsCount < 0 || c.nLocal < 0 || c.count < c.nLocal)) { set_error("%s: bad sizes", c.who); pre = false; }
+    if (pre && (e->size < c.elementsCount || ci->size < c.elementsCount || ro->size < (long long)c.nLocal + 1 || x->size < c.nLocal || b->size < c.nLocal ||
+                Ap->size < c.nLocal || r->size < c.nLocal || p->size < c.count)) { set_error("%s: a device vector is smaller than the problem", c.who); pre = false; }
+    pre = pre && checks();
+    if (pre && (c.offset < 0 || (long long)c.offset + c.nLocal > c.count)) { set_error("%s: bad partition", c.who); pre = false; }
+    if (!pre) {
+        if (MgcgCommSize(c.comm) > 1 && device_state()) (void)halo_plan_create(c.comm, c.count, c.offset, c.nLocal, c.minJ, c.maxJ, nullptr, 0, true, false);
+        return false;
+    }
+    CgRun R;
+    R.ws = &c.cublas->ws; R.cfg = cfg_of(c.cusparse); R.prof = &c.cusparse->prof; R.cusparse = c.cusparse;
+    R.comm = c.comm; R.nranks = MgcgCommSize(c.comm); R.multi = comm_multi(c.comm);
+    R.elements = e->data; R.rowOffsets = ro->data; R.columnIndeces = ci->data; R.elementsCount = c.elementsCount;
+    R.x = x->data; R.b = b->data; R.Ap = Ap->data; R.p = p->data; R.r = r->data; R.pVec = p; R.ApVec = Ap;
+    R.count = c.count; R.nLocal = c.nLocal; R.offset = c.offset;
+    if (R.multi) {
+        R.halo = halo_plan_create(c.comm, c.count, c.offset, c.nLocal, c.minJ, c.maxJ, R.columnIndeces, R.elementsCount, true);
+        if (!R.halo) return false;
+        if (!cg_plan_overlap(R)) { halo_plan_destroy(R.halo); return false; }
+    }
+    body(R);
+    if (R.halo) halo_plan_destroy(R.halo);
     return true;
+}
+static bool no_more_checks() { return true; }
+
+// SolveEx and SolveParallel
+static int solve_plain(const CgCall& c, double allowableResidual, int minIteration, int maxIteration, int rule,
+                       int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    if (!device_state()) return MGCG_ERROR;
+    int st = MGCG_ERROR;
+    cg_call(c, true, no_more_checks, [&](CgRun& R) {
+        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
+    });
+    return st;
 }
 
 void preload_solver() { preload_code_object(reinterpret_cast<const void*>(&snapshot_kernel)); }
@@ -1070,16 +1101,9 @@ int SolveEx(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
             int* iteration, double* residual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    if (!device_state()) return MGCG_ERROR;
-    if (!cublas || !cusparse) { set_error("SolveEx: null handle"); return MGCG_ERROR; }
-    if (!check_vectors("SolveEx", elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count, count)) return MGCG_ERROR;
-    CgRun R;
-    R.ws = &cublas->ws; R.cfg = cfg_of(cusparse); R.prof = &cusparse->prof; R.cusparse = cusparse;
-    R.elements = elementsVector->data; R.rowOffsets = rowOffsetsVector->data; R.columnIndeces = columnIndecesVector->data; R.elementsCount = elementsCount;
-    R.x = xVector->data; R.b = bVector->data; R.Ap = ApVector->data; R.p = pVector->data; R.r = rVector->data; R.pVec = pVector; R.ApVec = ApVector;
-    R.count = count; R.nLocal = count; R.offset = 0;
-    R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
-    return cg_solve(R, iteration, residual, residualTrace, traceCapacity);
+    const CgCall c = { "SolveEx", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, count, 0, elementsCount, 0, count - 1 };
+    return solve_plain(c, allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
 }
 
 void Solve(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -1107,32 +1131,9 @@ int SolveParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMa
                   int* iteration, double* residual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    if (!device_state()) return MGCG_ERROR;
-    // A rank whose own arguments are unusable must not simply return: its peers would block in the solve's first collective.  The verdict
-    // travels in the halo plan's one all-reduce (halo_plan_create, localOk) and every rank leaves with MGCG_ERROR.
-    bool pre = true;
-    if (!cublas || !cusparse) { set_error("SolveParallel: null handle"); pre = false; }
-    pre = pre && check_vectors("SolveParallel", elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                               elementsCountForDevice, countForDevice, count);
-    if (pre && (offsetForDevice < 0 || (long long)offsetForDevice + countForDevice > count)) { set_error("SolveParallel: bad partition"); pre = false; }
-    if (!pre) {
-        if (MgcgCommSize(comm) > 1) (void)halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, nullptr, 0, true, false);
-        return MGCG_ERROR;
-    }
-    CgRun R;
-    R.ws = &cublas->ws; R.cfg = cfg_of(cusparse); R.prof = &cusparse->prof; R.cusparse = cusparse; R.comm = comm; R.nranks = MgcgCommSize(comm); R.multi = comm_multi(comm);
-    R.elements = elementsVector->data; R.rowOffsets = rowOffsetsVector->data; R.columnIndeces = columnIndecesVector->data; R.elementsCount = elementsCountForDevice;
-    R.x = xVector->data; R.b = bVector->data; R.Ap = ApVector->data; R.p = pVector->data; R.r = rVector->data; R.pVec = pVector; R.ApVec = ApVector;
-    R.count = count; R.nLocal = countForDevice; R.offset = offsetForDevice;
-    R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
-    if (R.multi) {
-        R.halo = halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, R.columnIndeces, R.elementsCount, true);
-        if (!R.halo) return MGCG_ERROR;
-        if (!cg_plan_overlap(R)) { halo_plan_destroy(R.halo); return MGCG_ERROR; }
-    }
-    const int st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
-    if (R.halo) halo_plan_destroy(R.halo);
-    return st;
+    const CgCall c = { "SolveParallel", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    return solve_plain(c, allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
 }
 
 double CgSteps(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
@@ -1142,47 +1143,35 @@ double CgSteps(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
                int minJ, int maxJ, int steps, int restart)
 {
     if (!device_state()) return NAN;
-    bool pre = true;
-    if (!cublas || !cusparse) { set_error("CgSteps: null handle"); pre = false; }
-    pre = pre && check_vectors("CgSteps", elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                               elementsCountForDevice, countForDevice, count);
-    if (pre && (offsetForDevice < 0 || (long long)offsetForDevice + countForDevice > count)) { set_error("CgSteps: bad partition"); pre = false; }
-    if (!pre) {       // leave together with the peers (see SolveParallel)
-        if (MgcgCommSize(comm) > 1) (void)halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, nullptr, 0, true, false);
-        return NAN;
-    }
-    CgRun R;
-    R.ws = &cublas->ws; R.cfg = cfg_of(cusparse); R.prof = &cusparse->prof; R.cusparse = cusparse; R.comm = comm; R.nranks = MgcgCommSize(comm); R.multi = comm_multi(comm);
-    R.elements = elementsVector->data; R.rowOffsets = rowOffsetsVector->data; R.columnIndeces = columnIndecesVector->data; R.elementsCount = elementsCountForDevice;
-    R.x = xVector->data; R.b = bVector->data; R.Ap = ApVector->data; R.p = pVector->data; R.r = rVector->data; R.pVec = pVector; R.ApVec = ApVector;
-    R.count = count; R.nLocal = countForDevice; R.offset = offsetForDevice; R.rule = MGCG_RULE_NATIVE;
-    double* savedTrace = R.ws->trace; const int savedCap = R.ws->traceCap;
-    R.ws->trace = nullptr; R.ws->traceCap = 0;
-    bool ok = true;
-    if (R.multi) { R.halo = halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, R.columnIndeces, R.elementsCount, true); ok = R.halo != nullptr && cg_plan_overlap(R); }
-    long long meanDistance = 0;
-    if (R.elementsCount >= 8) R.cfg.periodRows = spmv_period(cusparse, R.rowOffsets, R.columnIndeces, R.nLocal, R.offset, &R.cfg.maxRow, &meanDistance);
-    R.dcsr = dcsr_lookup(cusparse, R.elements, R.rowOffsets, R.columnIndeces, R.nLocal, R.elementsCount, R.offset, R.count, meanDistance);
-    if (meanDistance >= (1LL << 19) && R.count >= (8LL << 19)) R.cfg.flags |= 16;
-    R.cfg.flags |= 8;
-    R.haloOnSide = tuning().haloStream.load(std::memory_order_relaxed) != 0;
-    if (ok && restart) ok = cg_enqueue_init(R, true);
-    else if (ok) hipLaunchKernelGGL(clear_done_kernel, dim3(1), dim3(1), 0, R.ws->stream, R.ws->scalars);
-    if (ok) cg_xdefer_setup(R, steps);
-    const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;      // MGCG_VERBOSE=2: is the host or the device the limit?
-    const auto h0 = std::chrono::steady_clock::now();
-    for (int k = 0; ok && k < steps; ++k) ok = cg_enqueue_iteration(R, false);
-    if (ok && R.xDefer > 1) launch_ring_copy_back(R.ws->stream, R.ws->scalars, R.ring, R.nLocal);   // (a non-finite residual stops the loop inside a group)
-    if (ok) hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(1), 0, R.ws->stream, R.ws->scalars, R.ws->mirror, (volatile int*)&R.ws->hostScalar[2]);
-    const auto h1 = std::chrono::steady_clock::now();
-    ok = MGCG_HIP(hipStreamSynchronize(R.ws->stream)) && ok;
-    if (report && steps > 0) {
-        const double enq = std::chrono::duration<double, std::micro>(h1 - h0).count() / steps, all = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count() / steps;
-        fprintf(stderr, "[MgcgGpu] CgSteps: host enqueue %.1f us per iteration, enqueue + drain %.1f us per iteration (%d steps)\n", enq, all, steps);
-    }
-    if (R.halo) halo_plan_destroy(R.halo);
-    R.ws->trace = savedTrace; R.ws->traceCap = savedCap;
-    return ok ? (double)R.ws->mirror->residual : NAN;
+    const CgCall c = { "CgSteps", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    bool ok = false;
+    double res = NAN;
+    cg_call(c, true, no_more_checks, [&](CgRun& R) {
+        hipStream_t s = R.ws->stream;
+        R.rule = MGCG_RULE_NATIVE;
+        double* savedTrace = R.ws->trace; const int savedCap = R.ws->traceCap;
+        R.ws->trace = nullptr; R.ws->traceCap = 0;
+        cg_matrix_setup(R);
+        R.haloOnSide = tuning().haloStream.load(std::memory_order_relaxed) != 0;
+        if (restart) ok = cg_enqueue_init(R, true);
+        else { hipLaunchKernelGGL(clear_done_kernel, dim3(1), dim3(1), 0, s, R.ws->scalars); ok = true; }
+        if (ok) cg_xdefer_setup(R, steps);
+        const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;      // MGCG_VERBOSE=2: is the host or the device the limit?
+        const auto h0 = std::chrono::steady_clock::now();
+        for (int k = 0; ok && k < steps; ++k) ok = cg_enqueue_iteration(R, false);
+        if (ok && R.xDefer > 1) launch_ring_copy_back(s, R.ws->scalars, R.ring, R.nLocal);   // (a non-finite residual stops the loop inside a group)
+        if (ok) hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(1), 0, s, R.ws->scalars, R.ws->mirror, (volatile int*)&R.ws->hostScalar[2]);
+        const auto h1 = std::chrono::steady_clock::now();
+        ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+        if (report && steps > 0) {
+            const double enq = std::chrono::duration<double, std::micro>(h1 - h0).count() / steps, all = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count() / steps;
+            fprintf(stderr, "[MgcgGpu] CgSteps: host enqueue %.1f us per iteration, enqueue + drain %.1f us per iteration (%d steps)\n", enq, all, steps);
+        }
+        R.ws->trace = savedTrace; R.ws->traceCap = savedCap;
+        res = (double)R.ws->mirror->residual;
+    });
+    return ok ? res : NAN;
 }
 
 int MgcgLastHalo(long long volume[2])
@@ -1591,40 +1580,30 @@ int SolveMgParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, Mgcg
 {
     (void)matDescr;
     if (!device_state()) return MGCG_ERROR;
-    bool pre = true;
-    if (!cublas || !cusparse || !mg || !zVector) { set_error("SolveMg: null handle"); pre = false; }
-    pre = pre && check_vectors("SolveMg", elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                               elementsCountForDevice, countForDevice, count);
-    if (pre && (zVector->size < countForDevice || mg->lv[0].n != countForDevice || mg->lv[0].nGlobal != count || mg->lv[0].offset != offsetForDevice)) {
-        set_error("SolveMg: z vector or hierarchy does not match the problem"); pre = false;
-    }
-    if (pre && (mg->nranks != MgcgCommSize(comm) || mg->multi != comm_multi(comm))) { set_error("SolveMg: the hierarchy was built for %d rank(s)%s", mg->nranks, mg->multi ? " on the several-ranks path" : ""); pre = false; }
-    if (pre && (rule == MGCG_RULE_HANDMADECL || rule == MGCG_RULE_VIENNACL)) { set_error("SolveMg supports the 2-norm absolute rules only"); pre = false; }
-    if (!pre) {       // leave together with the peers (see SolveParallel)
-        if (MgcgCommSize(comm) > 1) (void)halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, nullptr, 0, true, false);
-        return MGCG_ERROR;
-    }
-    CgRun R;
-    R.ws = &cublas->ws; R.cfg = cfg_of(cusparse); R.prof = &cusparse->prof; R.cusparse = cusparse; R.mg = mg; R.comm = comm; R.nranks = MgcgCommSize(comm); R.multi = comm_multi(comm);
-    R.elements = elementsVector->data; R.rowOffsets = rowOffsetsVector->data; R.columnIndeces = columnIndecesVector->data; R.elementsCount = elementsCountForDevice;
-    R.x = xVector->data; R.b = bVector->data; R.Ap = ApVector->data; R.p = pVector->data; R.r = rVector->data; R.z = zVector->data; R.pVec = pVector; R.ApVec = ApVector;
-    R.count = count; R.nLocal = countForDevice; R.offset = offsetForDevice;
-    R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
-    if (R.multi) {
-        R.halo = halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, R.columnIndeces, R.elementsCount, true);
-        if (!R.halo) return MGCG_ERROR;
-        if (!cg_plan_overlap(R)) { halo_plan_destroy(R.halo); return MGCG_ERROR; }
-    }
-    // deep-halo cycle: the loop keeps r in the hierarchy's extended buffer (room for the halo planes the cycle's one exchange brings) and the
-    // caller's vector receives it when the solve is over
-    const bool rExtended = R.multi && mg->deep && mg->rExt != nullptr;
-    if (rExtended) R.r = mg->rExt + (long long)mg->lv[0].nx * mg->lv[0].ny;
-    int st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
-    if (rExtended && countForDevice > 0) {
-        analysis_note_write(rVector->data, sizeof(double) * (size_t)countForDevice);
-        if (!MGCG_HIP(hipMemcpyAsync(rVector->data, R.r, sizeof(double) * (size_t)countForDevice, hipMemcpyDeviceToDevice, R.ws->stream)) || !MGCG_HIP(hipStreamSynchronize(R.ws->stream))) st = MGCG_ERROR;
-    }
-    if (R.halo) halo_plan_destroy(R.halo);
+    const CgCall c = { "SolveMg", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    auto checks = [&] {
+        if (zVector->size < countForDevice || mg->lv[0].n != countForDevice || mg->lv[0].nGlobal != count || mg->lv[0].offset != offsetForDevice) {
+            set_error("SolveMg: z vector or hierarchy does not match the problem"); return false;
+        }
+        if (mg->nranks != MgcgCommSize(comm) || mg->multi != comm_multi(comm)) { set_error("SolveMg: the hierarchy was built for %d rank(s)%s", mg->nranks, mg->multi ? " on the several-ranks path" : ""); return false; }
+        if (rule == MGCG_RULE_HANDMADECL || rule == MGCG_RULE_VIENNACL) { set_error("SolveMg supports the 2-norm absolute rules only"); return false; }
+        return true;
+    };
+    int st = MGCG_ERROR;
+    cg_call(c, mg && zVector, checks, [&](CgRun& R) {
+        R.mg = mg; R.z = zVector->data;
+        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        // deep-halo cycle: the loop keeps r in the hierarchy's extended buffer (room for the halo planes the cycle's one exchange brings) and the
+        // caller's vector receives it when the solve is over
+        const bool rExtended = R.multi && mg->deep && mg->rExt != nullptr;
+        if (rExtended) R.r = mg->rExt + (long long)mg->lv[0].nx * mg->lv[0].ny;
+        st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
+        if (rExtended && countForDevice > 0) {
+            analysis_note_write(rVector->data, sizeof(double) * (size_t)countForDevice);
+            if (!MGCG_HIP(hipMemcpyAsync(rVector->data, R.r, sizeof(double) * (size_t)countForDevice, hipMemcpyDeviceToDevice, R.ws->stream)) || !MGCG_HIP(hipStreamSynchronize(R.ws->stream))) st = MGCG_ERROR;
+        }
+    });
     return st;
 }
 
@@ -1699,32 +1678,23 @@ int SolveJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, 
 {
     (void)matDescr;
     // A rank whose diagonal set-up failed calls with a null dinvVector: like every other unusable argument it travels in the halo plan's
-    // one all-reduce (see SolveParallel), and every rank leaves with MGCG_ERROR.
-    bool pre = true;
-    if (!cublas || !cusparse || !dinvVector) { set_error("SolveJacobi: null handle"); pre = false; }
-    if (pre && !device_state()) return MGCG_ERROR;
-    if (!pre && MgcgCommSize(comm) <= 1) return MGCG_ERROR;
-    pre = pre && check_vectors("SolveJacobi", elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                               elementsCountForDevice, countForDevice, count);
-    if (pre && dinvVector->size < countForDevice) { set_error("SolveJacobi: the dinv vector is smaller than the problem"); pre = false; }
-    if (pre && (offsetForDevice < 0 || (long long)offsetForDevice + countForDevice > count)) { set_error("SolveJacobi: bad partition"); pre = false; }
-    if (!pre) {       // leave together with the peers (see SolveParallel)
-        if (MgcgCommSize(comm) > 1 && device_state()) (void)halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, nullptr, 0, true, false);
-        return MGCG_ERROR;
-    }
-    CgRun R;
-    R.ws = &cublas->ws; R.cfg = cfg_of(cusparse); R.prof = &cusparse->prof; R.cusparse = cusparse; R.dinv = dinvVector->data; R.comm = comm; R.nranks = MgcgCommSize(comm); R.multi = comm_multi(comm);
-    R.elements = elementsVector->data; R.rowOffsets = rowOffsetsVector->data; R.columnIndeces = columnIndecesVector->data; R.elementsCount = elementsCountForDevice;
-    R.x = xVector->data; R.b = bVector->data; R.Ap = ApVector->data; R.p = pVector->data; R.r = rVector->data; R.pVec = pVector; R.ApVec = ApVector;
-    R.count = count; R.nLocal = countForDevice; R.offset = offsetForDevice;
-    R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
-    if (R.multi) {
-        R.halo = halo_plan_create(comm, count, offsetForDevice, countForDevice, minJ, maxJ, R.columnIndeces, R.elementsCount, true);
-        if (!R.halo) return MGCG_ERROR;
-        if (!cg_plan_overlap(R)) { halo_plan_destroy(R.halo); return MGCG_ERROR; }
-    }
-    const int st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
-    if (R.halo) halo_plan_destroy(R.halo);
+    // one all-reduce (cg_call), and every rank leaves with MGCG_ERROR.  Null handles are reported before the device is asked for.
+    if (!cublas || !cusparse || !dinvVector) {
+        set_error("SolveJacobi: null handle");
+        if (MgcgCommSize(comm) <= 1) return MGCG_ERROR;
+    } else if (!device_state()) return MGCG_ERROR;
+    const CgCall c = { "SolveJacobi", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    auto checks = [&] {
+        if (dinvVector->size < countForDevice) { set_error("SolveJacobi: the dinv vector is smaller than the problem"); return false; }
+        return true;
+    };
+    int st = MGCG_ERROR;
+    cg_call(c, dinvVector != nullptr, checks, [&](CgRun& R) {
+        R.dinv = dinvVector->data;
+        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
+    });
     return st;
 }
 

@@ -5,8 +5,9 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python conjugategradient_amd/tools/launch_sequence.py run
     python conjugategradient_amd/tools/launch_sequence.py table OUT > counts.json
 
-``run``: 64^3 SolveEx with x_defer 8 and 1, CgSteps(20), a 64^3 MGCG solve, two loopback ranks plain and MGCG, four loopback ranks
-of which three hold no rows.  The placement draw is off (its timing loops launch SpMVs by the free memory of the moment).
+``run``: 64^3 SolveEx with x_defer 8 and 1, CgSteps(20), a 64^3 MGCG solve and a 64^3 Jacobi-preconditioned solve, two loopback ranks
+plain, MGCG and Jacobi, four loopback ranks of which three hold no rows, plain and Jacobi.  The placement draw is off (its timing loops
+launch SpMVs by the free memory of the moment).
 ``table``: per-kernel call counts of the run's *kernel_stats.csv, as one JSON object sorted by name."""
 import csv
 import glob
@@ -50,6 +51,7 @@ def ranks_in_threads(world, make_rank):
 
 def run():
     from conjugategradient_amd import _lib, problems
+    from conjugategradient_amd.jacobi import ConjugateGradientJacobiGpu
     from conjugategradient_amd.multigrid import ConjugateGradientMgGpu
     from conjugategradient_amd.parallel import ConjugateGradientMgRankGpu, ConjugateGradientRankGpu
     from conjugategradient_amd.solver import ConjugateGradientSingleGpu
@@ -75,6 +77,11 @@ def run():
     mg.Solve()
     done.append(("MGCG", mg.Iteration))
     mg.Dispose()
+    jc = ConjugateGradientJacobiGpu(s.Count, 7, 0, 5000, 1e-8, rule=_lib.RULE_NATIVE).load(s)      # one rank, z = D^-1 r inside the vector passes
+    jc.Initialize()
+    jc.Solve()
+    done.append(("Jacobi", jc.Iteration))
+    jc.Dispose()
 
     t = problems.poisson(32, 32, 16)
     its = {}
@@ -94,10 +101,20 @@ def run():
         its["mgcg", rank] = cg.Iteration
         cg.Dispose()
 
+    def jacobi(rank, comm):                                     # several ranks, Jacobi
+        cg = ConjugateGradientRankGpu(t.Count, 7, 0, 500, 1e-8, rank=rank, world=2, comm=comm, device=rank).load(t)
+        cg.Initialize()
+        cg.SetupJacobi()
+        cg.SolveJacobi()
+        its["jacobi", rank] = cg.Iteration
+        cg.Dispose()
+
     ranks_in_threads(2, plain)
     ranks_in_threads(2, precond)
+    ranks_in_threads(2, jacobi)
     done.append(("two ranks plain", its["plain", 0]))
     done.append(("two ranks MGCG", its["mgcg", 0]))
+    done.append(("two ranks Jacobi", its["jacobi", 0]))
 
     e = problems.mgcg_main(3, 160)                              # 3 rows over 4 ranks: three ranks without rows
     assert problems.partition_offsets(e.Count, 4) == [0, 0, 0, 0, 3]
@@ -109,8 +126,18 @@ def run():
         its["empty", rank] = cg.Iteration
         cg.Dispose()
 
+    def empty_jacobi(rank, comm):
+        cg = ConjugateGradientRankGpu(e.Count, 3, 0, 50, 1e-8, rank=rank, world=4, comm=comm, device=rank).load(e)
+        cg.Initialize()
+        cg.SetupJacobi()
+        cg.SolveJacobi()
+        its["empty jacobi", rank] = cg.Iteration
+        cg.Dispose()
+
     ranks_in_threads(4, empty)
+    ranks_in_threads(4, empty_jacobi)
     done.append(("four ranks, three empty", its["empty", 3]))
+    done.append(("four ranks, three empty, Jacobi", its["empty jacobi", 3]))
     print(json.dumps({"iterations": dict(done)}))
 
 

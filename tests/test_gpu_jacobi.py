@@ -58,8 +58,9 @@ def stop_decision(rule, tol, min_it, max_it, it, rr_new, inf, rr0):
     return res, shown, stop, status
 
 
-def jacobi_pcg_oracle(s, rule=_lib.RULE_CSHARP, tol=1e-8, min_it=0, max_it=MAX_IT, parts=None, dot=None, spmv=None, set_added=None):
-    """dot / spmv / set_added: the primitives (default: the CPU oracle's; tests/test_jacobi_host.py plugs numpy's in to test this loop)."""
+def jacobi_pcg_oracle(s, rule=_lib.RULE_CSHARP, tol=1e-8, min_it=0, max_it=MAX_IT, parts=None, dot=None, spmv=None, set_added=None, diag=None):
+    """dot / spmv / set_added: the primitives (default: the CPU oracle's; tests/test_jacobi_host.py plugs numpy's in to test this loop).
+    diag: the matrix diagonal if the caller knows it (default: diagonal_of(s), a Python loop over the rows)."""
     dot = dot or O.dot
     spmv = spmv or (lambda v: O.spmv(s.Elements, s.ColumnIndeces, s.RowOffsets, v))
     set_added = set_added or O.set_added
@@ -71,7 +72,7 @@ def jacobi_pcg_oracle(s, rule=_lib.RULE_CSHARP, tol=1e-8, min_it=0, max_it=MAX_I
             total += dot(a[lo:hi], b[lo:hi]) if hi > lo else 0.0
         return total
 
-    dinv = 1.0 / diagonal_of(s)
+    dinv = 1.0 / (diagonal_of(s) if diag is None else diag)
     x = np.zeros(s.Count) if rule == _lib.RULE_SIMPLE else np.array(s.x, dtype=np.float64)
     r = set_added(np.asarray(s.b, dtype=np.float64), spmv(x), -1.0)
     z = dinv * r
@@ -137,6 +138,17 @@ def ragged(n=1337, seed=7):
     return problems.LinearSystem(e, c, r, np.zeros(n), b, "ragged")
 
 
+def tridiagonal(n):
+    """Symmetric tridiagonal, -1 off the diagonal, the diagonal 2.5 + (i mod 7) (strictly dominant), b = cos(0.3 i).  Returns (system, diagonal)."""
+    i = np.arange(n)
+    cols = np.stack([i - 1, i, i + 1], axis=1)
+    diag = 2.5 + (i % 7)
+    vals = np.stack([-np.ones(n), diag, -np.ones(n)], axis=1)
+    keep = (cols >= 0) & (cols < n)
+    ro = np.concatenate([[0], np.cumsum(keep.sum(axis=1))]).astype(np.int32)
+    return problems.LinearSystem(vals[keep], cols[keep].astype(np.int32), ro, np.zeros(n), np.cos(0.3 * i), "tridiagonal"), diag
+
+
 SYSTEMS = {
     "viennacl4000": lambda: problems.viennacl_main(4000),      # diagonal first, columns unsorted
     "mgcgmain3000": lambda: problems.mgcg_main(3000),
@@ -195,6 +207,26 @@ def test_solve_jacobi_equals_the_oracle_bit_for_bit(oracle, dot_order, which, ru
     assert ref["status"] == _lib.OK and ref["iteration"] >= 1, ref["iteration"]
     got = solve(ConjugateGradientJacobiGpu, s, rule, tol)
     print(which, rule, "iterations", got["iteration"], ref["iteration"], "residual", got["residual"], ref["residual"])
+    assert_equal_runs(got, ref)
+
+
+STREAMING_ROWS = 3_000_001      # the smallest row count at which the vector passes take their streaming-hint forms (n > 3 000 000); odd: the tail element runs
+
+
+@pytest.fixture(scope="module")
+def streaming_system():
+    return tridiagonal(STREAMING_ROWS)
+
+
+@pytest.mark.parametrize("rule", [_lib.RULE_CSHARP, _lib.RULE_HANDMADECL])
+def test_streaming_hint_forms_equal_the_oracle_bit_for_bit(oracle, dot_order, streaming_system, rule):
+    """The r update and the x/p update above 3 M rows (non-temporal loads and stores; under RULE_HANDMADECL also the max-norm form of the r
+    update): six forced iterations, tolerance 0, so that both sides stop at the iteration cap."""
+    s, diag = streaming_system
+    ref = jacobi_pcg_oracle(s, rule, 0.0, min_it=0, max_it=6, diag=diag)
+    assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 7, (ref["status"], ref["iteration"])
+    got = solve(ConjugateGradientJacobiGpu, s, rule, 0.0, min_it=0, max_it=6)
+    print(rule, "iterations", got["iteration"], ref["iteration"], "residual", got["residual"], ref["residual"])
     assert_equal_runs(got, ref)
 
 
