@@ -113,6 +113,7 @@ SIGNATURES = {
     "SolveMgParallel": (_i, [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "MgcgJacobiSetup": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "SolveJacobi": (_i, [_vp] * 12 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
+    "SolveShifted": (_i, [_vp] * 12 + [_i, _i, _i, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "SolveJacobiParallel": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "MgcgCommGetUniqueId": (_i, [_vp]),
     "MgcgRcclAvailable": (_i, []),
@@ -139,6 +140,7 @@ SIGNATURES = {
 RULE_NATIVE, RULE_CSHARP, RULE_SIMPLE, RULE_HANDMADECL, RULE_VIENNACL = range(5)
 OK, MAXIT_EXCEEDED, NONFINITE, ERROR = 0, 1, 3, -1
 BLOCK_MAX_K = 8      # right-hand sides of one SolveBlockEx / CsrMVBlock call
+SHIFT_MAX_K = 8      # shifts of one SolveShifted call
 # MgcgSetMatrixCompression modes: off; the best lossless form (row patterns, per-nonzero codes, column tiles); per-nonzero codes only;
 # as the best form, with the propagation-blocking form (class 5) before the column tiles for matrices without locality
 COMPRESSION_OFF, COMPRESSION_BEST, COMPRESSION_CODES, COMPRESSION_PB = range(4)

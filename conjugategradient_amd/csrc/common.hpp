@@ -29,6 +29,7 @@ constexpr int kMaxPartials = kNumCu * 32; // single-wavefront workgroups: up to 
 constexpr int kXDeferMax = 8;         // longest group of the deferred x update (MGCG_X_DEFER): directions kept in the ring
 constexpr int kXDeferDefault = 8;
 constexpr int kBlockMaxK = 8;         // right-hand sides of one block CG call (SolveBlockEx / CsrMVBlock)
+constexpr int kShiftMaxK = 8;         // shifts of one multi-shift CG call (SolveShifted)
 constexpr int kMaxDevices = 64;
 constexpr int kPatMax = 256;         // row-pattern form: distinct rows-as-sequences a matrix may have ...
 constexpr int kPatEntries = 2048;    // ... and nPattern * longest row (the table lives in LDS: 12 bytes per entry)
@@ -94,7 +95,7 @@ bool select_device_only();       // hipSetDevice for the calling thread's device
 inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, kernel); }
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
-void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block();
+void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -132,6 +133,21 @@ struct HostMirror {
     volatile int pad;
 };
 
+// Per-column scalars of the multi-shift loop (SolveShifted, kernels_shift.hip).  The state of the recurrences is kept twice: iteration k
+// reads st[k & 1] in every workgroup of its fused pass while that pass's first workgroup writes st[(k + 1) & 1], so no workgroup can see
+// a half-written state and no scalar launch of its own is needed.
+struct ShiftState {
+    double zeta[kShiftMaxK], zetaPrev[kShiftMaxK];   // zeta_k, zeta_{k-1} per column
+    double alphaPrev, betaPrev;                      // alpha_{k-1}, beta_{k-1} of the base recurrence
+    int live[kShiftMaxK];                            // 1: the column has not stopped
+};
+struct ShiftScalars {
+    double sigma[kShiftMaxK];
+    ShiftState st[2];
+    double residual[kShiftMaxK];                     // what the caller gets back, written in the column's stopping iteration
+    int iteration[kShiftMaxK], status[kShiftMaxK];
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct Workspace {
@@ -151,12 +167,14 @@ struct Workspace {
     // region per column of kMaxPartials doubles, and the per-column scalars
     double* blockPartials = nullptr;
     BlockScalars* blockScalars = nullptr;
+    ShiftScalars* shiftScalars = nullptr;        // multi-shift CG (kernels_shift.hip), allocated at its first call and kept
     bool init();
     void destroy();
     bool ensure_trace(int cap);
     bool ensure_ring(int slots, long long n);    // slots 1 .. slots-1 allocated with >= n entries (keeps what is there)
     void free_ring();
     bool ensure_block();                         // blockPartials / blockScalars (kernels_block.hip)
+    bool ensure_shift();                         // shiftScalars (kernels_shift.hip)
 };
 
 } // namespace mgcg
@@ -462,6 +480,13 @@ void launch_update_xp_ring(hipStream_t s, const FinalizeArgs& f, const double* p
                            double* x, const RingArgs& g, const double* z, long long n);
 // after a call that may have stopped inside a group: p back into slot 0 when sc->pSlot names another slot
 void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g, long long n);
+
+// Multi-shift CG (SolveShifted): the fused pass behind update_r (launched with freeze = true) of one base iteration.  It finalises the
+// iteration as update_xp_final does, forms every live column's zeta, alpha_j, beta_j and stop decision, and in one pass over r and p does
+// p = r + beta p and, per column, x_j += alpha_j p_j and p_j = zeta_j r + beta_j p_j.  x and ps hold k columns of n entries, column j at j * n.
+// f.trace: k traces of f.traceCap entries.
+void launch_update_shifted(hipStream_t s, int k, const FinalizeArgs& f, ShiftScalars* sh, const double* partials, const double* partialsInf, int nPartials,
+                           double* x, double* p, const double* r, double* ps, long long n);
 
 // dinv_i = 1 / a_ii for the Jacobi-preconditioned loop
 void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,

@@ -10,100 +10,9 @@
 // bit-identical to it.  Reductions: per-lane partial -> __shfl_down over the 64-lane wavefront ->
 // LDS across the 4 waves -> one partial per workgroup -> a single-workgroup second stage that adds
 // the partials in a fixed order.  No atomics: results are run-to-run reproducible.
-#include "common.hpp"
+#include "vec_passes.hpp"
 
 namespace mgcg {
-
-typedef double d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ double wave_sum_b(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max_b(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { double o = __shfl_down(v, off, 64); v = o > v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ double block_sum(double v, double* s_red)
-{
-    v = wave_sum_b(v);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-}
-__device__ __forceinline__ double block_max(double v, double* s_red)
-{
-    v = wave_max_b(v);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double a = s_red[0] > s_red[1] ? s_red[0] : s_red[1];
-    double b = s_red[2] > s_red[3] ? s_red[2] : s_red[3];
-    return a > b ? a : b;
-}
-
-static inline int grid_for(long long n, int perThread)
-{
-    const int cap = kMaxGrid;
-    long long blocks = (n + (long long)kBlock * perThread - 1) / ((long long)kBlock * perThread);
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// Element-wise grid-stride driver.  V2: f2(i) handles elements i, i+1 with 16-byte accesses and the
-// odd tail goes to f1 on one thread; otherwise f1(i) per element.
-// Streaming hint of the CG vector passes (non-temporal loads and stores).  Measured per size, alternating inside one process
-// (profiles/r2/vec_nt_ab.log; the A/B script is in the history): with the hint the CG iteration is 2-11 % faster from 4 M rows up (11 % at the 16.8 M rows
-// of one rank's slab of an 8-GPU run, 2 % at 134 M) and 2.5 % slower at 2 M rows and below, where every vector stays in the caches anyway.
-template <bool NTV, typename T> __device__ __forceinline__ T ldv(const T* p) { if constexpr (NTV) return __builtin_nontemporal_load(p); else return *p; }
-template <bool NTV, typename T> __device__ __forceinline__ void stv(const T& v, T* p) { if constexpr (NTV) __builtin_nontemporal_store(v, p); else *p = v; }
-static bool vec_nt(long long n) { return n > 3000000; }
-
-// Run-time flags to template arguments: go(std::bool_constant<flag>...).  The kernels' launches name every form they instantiate here.
-template <typename Go> static void with_flags(Go go) { go(); }
-template <typename Go, typename... Rest> static void with_flags(Go go, bool flag, Rest... rest)
-{
-    if (flag) with_flags([&](auto... c) { go(std::true_type{}, c...); }, rest...);
-    else with_flags([&](auto... c) { go(std::false_type{}, c...); }, rest...);
-}
-// The three forms of the loop's x/p passes, go(V2, NTV): 16-byte accesses with the streaming hint, without it, or one element at a time.
-template <typename Go> static void with_v2_nt(bool v2, bool nt, Go go)
-{
-    if (v2 && nt) go(std::true_type{}, std::true_type{});
-    else if (v2) go(std::true_type{}, std::false_type{});
-    else go(std::false_type{}, std::false_type{});
-}
-
-template <bool V2, typename F2, typename F1>
-__device__ __forceinline__ void grid_stride(long long n, F2 f2, F1 f1)
-{
-    const long long stride = (long long)gridDim.x * kBlock;
-    if constexpr (V2) {
-        const long long n2 = n >> 1;
-        for (long long i2 = (long long)blockIdx.x * kBlock + threadIdx.x; i2 < n2; i2 += stride) f2(i2 * 2);
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) f1(n - 1);
-    } else {
-        for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) f1(i);
-    }
-}
-
-// Contiguous-chunk driver for the loop's own vector updates: workgroup b walks its own run of element pairs, two
-// 16-byte accesses per array in flight per lane.  Measured 8-15 % faster than the grid-stride form on the 1 GiB vectors
-// of the 512^3 system (profiles/r1/vec_probe_update_kernels.log); same arithmetic per element.
-template <typename F2>
-__device__ __forceinline__ void chunk_pairs(long long n2, F2 f2x2)
-{
-    const long long per = ((n2 + gridDim.x - 1) / gridDim.x + (kBlock - 1)) & ~(long long)(kBlock - 1);
-    long long i = per * blockIdx.x + threadIdx.x;
-    long long end = per * (blockIdx.x + 1);
-    end = end < n2 ? end : n2;
-    for (; i < end; i += 2 * kBlock) f2x2(i, i + kBlock < end);    // pairs i and i + kBlock
-}
 
 // ------------------------------------------------------------------ axpy: y = y + alpha*x
 template <bool V2>
@@ -261,15 +170,6 @@ int launch_nrminf_partials(hipStream_t s, const double* x, long long n, double* 
 }
 
 // ------------------------------------------------------------------ second stage (one workgroup)
-// Fixed-order sum (or max) of n partials; result valid in thread 0.
-__device__ __forceinline__ double reduce_partials_block(const double* __restrict__ partials, int n, double* s_red, int mode)
-{
-    double acc = 0.0;
-    if (mode == 0) { for (int i = threadIdx.x; i < n; i += kBlock) acc += partials[i]; return block_sum(acc, s_red); }
-    for (int i = threadIdx.x; i < n; i += kBlock) { double a = partials[i]; acc = a > acc ? a : acc; }
-    return block_max(acc, s_red);
-}
-
 __global__ __launch_bounds__(kBlock) void reduce_kernel(const double* __restrict__ partials, int n, double* __restrict__ out, int mode, const int* done)
 {
     __shared__ double s_red[4];
@@ -570,28 +470,6 @@ void launch_update_xp(hipStream_t s, const CgScalars* sc, double* x, double* p, 
     });
 }
 
-// What a finished iteration publishes, by one thread: the trace entry, the live scalars, the host mirror (its `done` last, behind a
-// system-wide fence).  pad: 1 when this iteration's x += alpha p is still to be done by update_xp_kernel.  RING_NT > 0 (deferred x update):
-// the iteration that stops the loop also records the slot that holds p.  `next` hands beta and r.r (or r.z) over to the next iteration:
-// the callers differ in where they take them from.
-template <int RING_NT, typename Next>
-__device__ __forceinline__ void publish_iteration(const FinalizeArgs& f, const StopDecision& d, int it, double rrNew, double inf, int pad, Next next)
-{
-    CgScalars* sc = f.sc;
-    if (f.trace != nullptr && it < f.traceCap) f.trace[it] = d.shown;
-    sc->rrNew = rrNew; sc->residual = d.res; sc->nrmInf = inf; sc->pad = pad;
-    if (d.stop) {
-        if constexpr (RING_NT > 0) sc->pSlot = RING_NT - 1;           // p_k stays where it is (ring_copy_back_kernel)
-        sc->done = 1; sc->status = d.status;
-        f.mirror->residual = d.res; f.mirror->iteration = it; f.mirror->status = d.status;
-        __threadfence_system();
-        f.mirror->done = 1;
-    } else {
-        next();
-        sc->iteration = it + 1;
-        f.mirror->residual = d.res; f.mirror->iteration = it + 1;
-    }
-}
 
 // The finalisation that the x/p updates below fold in.  Every workgroup reduces the r.r (and max|r|) partial sums of update_r in the order
 // finalize_kernel uses and takes the same decision from the values update_r froze (fRr, fRr0, fAlpha, fIteration); workgroup 0 alone

@@ -952,6 +952,45 @@ static bool cg_enqueue_iteration(CgRun& R, bool withStopTest)
     return cg_enqueue_product(R, pIn, &nPAp) && cg_enqueue_update(R, pIn + R.offset, nPAp, withStopTest);
 }
 
+// The host's side of a device-resident loop.  It enqueues checkEvery iterations, a snapshot of the device's stop flag and an event, and then
+// looks at the snapshot of the chunk BEFORE the one just enqueued, so that the device never waits for the host.  A loop whose flag has not
+// risen a little beyond max(minIt, maxIt) iterations is an error (who names the loop in the message).  The stream is not drained here.
+template <typename Enqueue>
+static bool cg_drive(CgRun& R, const char* who, Enqueue enqueueIteration, long long* enqueuedOut = nullptr)
+{
+    hipStream_t s = R.ws->stream;
+    int checkEvery = 4;
+    { const int v = tuning().checkEvery.load(std::memory_order_relaxed); if (v >= 1) checkEvery = v; }
+    const long long hostCap = (long long)(R.maxIt > R.minIt ? R.maxIt : R.minIt) + 4;
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    volatile int* slots = (volatile int*)&R.ws->hostScalar[2];   // two ints per double: slots[0..3]
+    bool ok = MGCG_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming)) && MGCG_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+    for (int i = 0; i < 4; ++i) slots[i] = 0;
+    long long enqueued = 0;
+    int chunk = 0;
+    bool finished = false;
+    while (ok && !finished) {
+        for (int k = 0; ok && k < checkEvery; ++k) ok = enqueueIteration();
+        enqueued += checkEvery;
+        hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(1), 0, s, R.ws->scalars, R.ws->mirror, &slots[chunk & 1]);
+        ok = ok && MGCG_HIP(hipEventRecord(ev[chunk & 1], s));
+        if (chunk > 0) {                                  // look at the chunk BEFORE the one just enqueued
+            ok = ok && MGCG_HIP(hipEventSynchronize(ev[(chunk - 1) & 1]));
+            if (ok && slots[(chunk - 1) & 1] != 0) finished = true;
+        }
+        if (!finished && enqueued > hostCap + 2LL * checkEvery) {
+            ok = ok && MGCG_HIP(hipStreamSynchronize(s));
+            if (ok && slots[chunk & 1] != 0) finished = true;
+            else { set_error("%s: the device never raised its stop flag after %lld iterations", who, enqueued); ok = false; }
+        }
+        ++chunk;
+    }
+    if (ev[0]) (void)hipEventDestroy(ev[0]);
+    if (ev[1]) (void)hipEventDestroy(ev[1]);
+    if (enqueuedOut) *enqueuedOut = enqueued;
+    return ok;
+}
+
 static int cg_solve(CgRun& R, int* iteration, double* residual, double* residualTrace, int traceCapacity)
 {
     hipStream_t s = R.ws->stream;
@@ -966,17 +1005,10 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
 
     R.haloOnSide = tuning().haloStream.load(std::memory_order_relaxed) != 0;
     int status = MGCG_ERROR;
-    int checkEvery = 4;
-    { const int v = tuning().checkEvery.load(std::memory_order_relaxed); if (v >= 1) checkEvery = v; }
-    const long long hostCap = (long long)(R.maxIt > R.minIt ? R.maxIt : R.minIt) + 4;
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    volatile int* slots = (volatile int*)&R.ws->hostScalar[2];   // two ints per double: slots[0..3]
-    bool ok = MGCG_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming)) && MGCG_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-    for (int i = 0; i < 4; ++i) slots[i] = 0;
     const bool report = tuning().verbose.load(std::memory_order_relaxed) >= 2;
     const auto hostT0 = std::chrono::steady_clock::now();
-    if (ok) cg_matrix_setup(R);
-    ok = ok && cg_enqueue_init(R);
+    cg_matrix_setup(R);
+    bool ok = cg_enqueue_init(R);
     if (ok) cg_xdefer_setup(R, 0);
     if (report) {
         const double enq = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT0).count();
@@ -985,24 +1017,7 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - hostT0).count());
     }
     long long enqueued = 0;
-    int chunk = 0;
-    bool finished = false;
-    while (ok && !finished) {
-        for (int k = 0; ok && k < checkEvery; ++k) ok = cg_enqueue_iteration(R, true);
-        enqueued += checkEvery;
-        hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(1), 0, s, R.ws->scalars, m, &slots[chunk & 1]);
-        ok = ok && MGCG_HIP(hipEventRecord(ev[chunk & 1], s));
-        if (chunk > 0) {                                  // look at the chunk BEFORE the one just enqueued
-            ok = ok && MGCG_HIP(hipEventSynchronize(ev[(chunk - 1) & 1]));
-            if (ok && slots[(chunk - 1) & 1] != 0) finished = true;
-        }
-        if (!finished && enqueued > hostCap + 2LL * checkEvery) {
-            ok = ok && MGCG_HIP(hipStreamSynchronize(s));
-            if (ok && slots[chunk & 1] != 0) finished = true;
-            else { set_error("CG: the device never raised its stop flag after %lld iterations", enqueued); ok = false; }
-        }
-        ++chunk;
-    }
+    ok = ok && cg_drive(R, "CG", [&] { return cg_enqueue_iteration(R, true); }, &enqueued);
     if (ok && R.xDefer > 1) launch_ring_copy_back(s, R.ws->scalars, R.ring, R.nLocal);   // p stopped inside a group: back into the caller's buffer
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
     if (report) fprintf(stderr, "[MgcgGpu] solve: %lld iterations enqueued, loop drained %.0f us after the call began\n", enqueued,
@@ -1018,10 +1033,65 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
         if (status == MGCG_MAXIT_EXCEEDED) set_error("CG did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
         if (status == MGCG_NONFINITE) set_error("CG stopped: residual is not finite at iteration %d", m->iteration);
     }
-    if (ev[0]) (void)hipEventDestroy(ev[0]);
-    if (ev[1]) (void)hipEventDestroy(ev[1]);
     R.ws->trace = savedTrace; R.ws->traceCap = savedCap;
     return ok ? status : MGCG_ERROR;
+}
+
+// ---------------------------------------------------------------- multi-shift CG (SolveShifted)
+// One CG recurrence on A serves the k systems (A + sigma_j I) x_j = b (kernels_shift.hip has the method).  An iteration is the plain loop's
+// product and r update followed by the one fused pass launch_update_shifted: three launches, as SolveEx's.  x_j starts from 0, so r = b
+// exactly and no product is needed in front of the loop.  ps: the k directions p_j, column j at j * count.
+static int cg_solve_shifted(CgRun& R, double* ps, int k, const double* shifts, int iteration[], double residual[], int status[],
+                            double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    R.wantInf = (R.rule == MGCG_RULE_HANDMADECL);
+    if (!ws->ensure_shift()) return MGCG_ERROR;
+    const int devTraceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
+    if (devTraceCap && !ws->ensure_trace(k * devTraceCap)) return MGCG_ERROR;
+    cg_matrix_setup(R);
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    f.trace = devTraceCap ? ws->trace : nullptr; f.traceCap = devTraceCap;
+
+    ShiftScalars h{};
+    for (int j = 0; j < k; ++j) { h.sigma[j] = shifts[j]; h.st[0].zeta[j] = 1.0; h.st[0].zetaPrev[j] = 1.0; h.st[0].live[j] = 1; }
+    h.st[0].alphaPrev = 1.0; h.st[0].betaPrev = 0.0;
+    bool ok = MGCG_HIP(hipMemcpyAsync(ws->shiftScalars, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    launch_fill(s, R.x, 0.0, (long long)k * n);                                       // x_j = 0
+    launch_copy(s, R.r, R.b, n);                                                       // r = b - A 0
+    const int nRR = launch_copy_dot(s, R.p, R.r, nullptr, n, ws->partials, nullptr, nullptr);   // p = r ; r.r
+    for (int j = 0; j < k; ++j) launch_copy(s, ps + j * n, R.b, n);                    // p_j = b
+    launch_init_scalars(s, ws->partials, nullptr, nRR, true, ws->scalars, ws->mirror);
+    ok = ok && MGCG_HIP(hipGetLastError());
+
+    double* pInf = R.wantInf ? ws->partials + kMaxPartials : nullptr;
+    double* rrPartials = ws->partials + 2 * kMaxPartials;                              // (the plain loop's regions: cg_enqueue_update)
+    ok = ok && cg_drive(R, "SolveShifted", [&] {
+        int nPAp = 0;
+        if (!cg_enqueue_product(R, R.p, &nPAp)) return false;                          // Ap = A p ; p.Ap
+        const int nP = launch_update_r(s, ws->scalars, R.r, R.Ap, nullptr, n, rrPartials, nullptr, pInf, ws->partials, nPAp, true);   // alpha ; r -= alpha Ap ; r.r
+        launch_update_shifted(s, k, f, ws->shiftScalars, rrPartials, pInf, nP, R.x, R.p, R.r, ps, n);
+        return MGCG_HIP(hipGetLastError());
+    });
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    int worst = MGCG_OK;
+    ok = ok && MGCG_HIP(hipMemcpy(&h, ws->shiftScalars, sizeof(h), hipMemcpyDeviceToHost));
+    for (int j = 0; ok && j < k; ++j) {
+        if (iteration) iteration[j] = h.iteration[j];
+        if (residual) residual[j] = h.residual[j];
+        if (status) status[j] = h.status[j];
+        if (h.status[j] == MGCG_NONFINITE) worst = MGCG_NONFINITE;
+        else if (h.status[j] == MGCG_MAXIT_EXCEEDED && worst == MGCG_OK) worst = MGCG_MAXIT_EXCEEDED;
+        if (devTraceCap) {
+            int nTrace = h.iteration[j] + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
+            ok = MGCG_HIP(hipMemcpy(residualTrace + (size_t)j * traceCapacity, ws->trace + (size_t)j * devTraceCap, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
+        }
+    }
+    if (ok && worst == MGCG_NONFINITE) set_error("SolveShifted: a column broke down (p.Ap <= 0 or a scalar that is not finite)");
+    else if (ok && worst == MGCG_MAXIT_EXCEEDED) set_error("SolveShifted: a column did not converge within maxIteration %d", R.maxIt);
+    return ok ? worst : MGCG_ERROR;
 }
 
 // The arguments that every entry point of the loop takes: the handles, the matrix and the vectors of this rank, the partition.
@@ -1120,6 +1190,41 @@ void Solve(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
     (void)st;
     if (iteration) *iteration = it + 1;     // the reference returns its post-incremented loop counter (Mgcg.cu:234)
     if (residual) *residual = res;
+}
+
+int SolveShifted(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* shiftedPVector,
+                 int elementsCount, int count, int k, const double shifts[],
+                 double allowableResidual, int minIteration, int maxIteration, int rule,
+                 int iteration[], double residual[], int status[], double residualTrace[], int traceCapacity)
+{
+    (void)matDescr;
+    // what needs no device is refused before one is asked for; nothing is enqueued for a call that fails here or in cg_call's checks
+    if (!cublas || !cusparse || !shiftedPVector) { set_error("SolveShifted: null handle"); return MGCG_ERROR; }
+    if (k < 1 || k > kShiftMaxK) { set_error("SolveShifted: k = %d shifts, must be 1 .. %d", k, kShiftMaxK); return MGCG_ERROR; }
+    if (!shifts) { set_error("SolveShifted: shifts is NULL"); return MGCG_ERROR; }
+    for (int j = 0; j < k; ++j)
+        if (!(shifts[j] >= 0.0 && shifts[j] <= 1.79e308)) { set_error("SolveShifted: shift %d is %g, must be finite and >= 0", j, shifts[j]); return MGCG_ERROR; }
+    if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) { set_error("SolveShifted: unknown stop rule %d", rule); return MGCG_ERROR; }
+    if (count < 1) { set_error("SolveShifted: bad sizes"); return MGCG_ERROR; }
+    if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) { set_error("SolveShifted: trace capacity too large"); return MGCG_ERROR; }
+    if (!device_state()) return MGCG_ERROR;
+    const CgCall c = { "SolveShifted", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, count, 0, elementsCount, 0, count - 1 };
+    const long long kn = (long long)k * count;
+    auto checks = [&] {
+        if (xVector->size < kn || shiftedPVector->size < kn) { set_error("SolveShifted: a device vector is smaller than the problem (x and the direction work space need k * count entries)"); return false; }
+        return true;
+    };
+    int st = MGCG_ERROR;
+    cg_call(c, true, checks, [&](CgRun& R) {
+        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        analysis_note_write(R.x, sizeof(double) * (size_t)kn);
+        analysis_note_write(shiftedPVector->data, sizeof(double) * (size_t)kn);
+        st = cg_solve_shifted(R, shiftedPVector->data, k, shifts, iteration, residual, status, residualTrace, traceCapacity);
+    });
+    return st;
 }
 
 int SolveParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,

@@ -493,6 +493,46 @@ int SolveJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, 
                         double allowableResidual, int minIteration, int maxIteration, int rule,
                         int* iteration, double* residual, double* residualTrace, int traceCapacity);
 
+/* ---- Multi-shift CG: (A + shifts[j] I) x_j = b for k = 1 .. 8 shifts >= 0 from ONE CG recurrence on A (one rank, no preconditioner) ---- */
+/* Krylov spaces are shift-invariant: the residual of every shifted system is collinear with the base residual, r_j = zeta_j r, so an
+ * iteration is SolveEx's product and r update plus ONE fused vector pass for all columns -- three launches, one matrix pass, whatever k
+ * is -- where a caller would otherwise build k shifted matrices and run k solves.  The base iterate is not stored: list the shift 0 for it.
+ *   xVector         k * count entries, column j at [j * count, (j + 1) * count); OVERWRITTEN: every x_j starts from 0
+ *   bVector         count entries; ApVector, pVector, rVector: count entries of work space each
+ *   shiftedPVector  k * count entries of work space (the directions p_j; its layout is internal)
+ *   shifts          HOST array of k entries, finite and >= 0; they may repeat and need not be sorted
+ *   iteration / residual / status   k entries each, any of them may be NULL; residualTrace: column j at [j * traceCapacity, ...), may be NULL
+ * Base recurrence (SolveEx's): alpha_k = r.r / p.Ap ; r = r + (-alpha_k) Ap ; beta_k = r.r_new / r.r ; p = r + beta_k p.  Per column,
+ * with zeta_{-1} = zeta_0 = 1, alpha_{-1} = 1, beta_{-1} = 0 and p_j = b at the start:
+ *   zeta_new = zeta_k zeta_{k-1} alpha_{k-1} / ( alpha_{k-1} zeta_{k-1} (1 + sigma_j alpha_k) + alpha_k beta_{k-1} (zeta_{k-1} - zeta_k) )
+ *   alpha_j  = alpha_k (zeta_new / zeta_k) ;  beta_j = beta_k (zeta_new / zeta_k)^2
+ *   x_j = x_j + alpha_j p_j (the old p_j) ;  p_j = zeta_new r_new + beta_j p_j
+ * Rounding contract: every product is rounded into a double of its own before the add that follows it and nothing is fused into an FMA;
+ * the scalar expressions are evaluated in exactly this order --
+ *   num = (zeta_k * zeta_{k-1}) * alpha_{k-1}
+ *   den = (alpha_{k-1} * zeta_{k-1}) * (1 + sigma_j * alpha_k)  +  (alpha_k * beta_{k-1}) * (zeta_{k-1} - zeta_k)
+ *   zeta_new = num / den ; ratio = zeta_new / zeta_k ; alpha_j = alpha_k * ratio ; beta_j = beta_k * (ratio * ratio)
+ * -- and x_j = x_j + (alpha_j * p_j), p_j = (zeta_new * r) + (beta_j * p_j).  For sigma_j = 0 this gives zeta = 1.0, alpha_j = alpha_k and
+ * beta_j = beta_k exactly: a shift-0 column is SolveEx's x (from x = 0) bit for bit, and so are its trace, iteration and residual under
+ * dot_order = 1, where the loop's two dots are the serial sums; the per-column residuals need no sums of their own.
+ * Stop rules: the five of SolveEx per column, on the column's residual zeta_new r_new: they see (zeta_new * zeta_new) * (r.r) where SolveEx
+ * sees r.r, |zeta_new| * max|r| under MGCG_RULE_HANDMADECL, and the common r0.r0 = b.b under MGCG_RULE_VIENNACL.  A column that stops gets
+ * its last x update in that iteration and is frozen: nothing touches its x or p_j again, its trace gets no further entry, and the pass
+ * no longer streams it.  The loop runs until no column is live.
+ * Returns the worst column status (MGCG_NONFINITE > MGCG_MAXIT_EXCEEDED > MGCG_OK).  A breakdown -- p.Ap <= 0 or not finite (the matrix
+ * is not positive definite, or b = 0), a zeta_new, alpha_j or beta_j that is not finite (a zeta that
+ * underflowed to 0 shows as such one iteration later) -- ends the affected columns with MGCG_NONFINITE in that iteration, before its x
+ * update; their x keeps the last good iterate.  MGCG_ERROR with a message, and nothing enqueued, for k outside 1 .. 8, shifts == NULL, a shift that is negative or
+ * not finite, a null handle or a vector that is too small.
+ * The product is SolveEx's: compression modes and the automatic column tiles apply.  Out of scope: several ranks, preconditioners (they
+ * break the shift invariance), a non-zero initial guess, the deferred x update (x_defer) and the placement draw. */
+int SolveShifted(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* shiftedPVector,
+                 int elementsCount, int count, int k, const double shifts[],
+                 double allowableResidual, int minIteration, int maxIteration, int rule,
+                 int iteration[], double residual[], int status[], double residualTrace[], int traceCapacity);
+
 /* Fixed number of CG iterations with no stop test and no host synchronisation inside (bench.py's
  * "steps"): runs `steps` more iterations of the recurrence held in x,r,p (call with restart != 0 first
  * to compute r = b - A x, p = r, rr).  comm may be NULL.  Returns the residual after the last step. */
