@@ -6,6 +6,7 @@
 ``multigrid`` the V-cycle preconditioner the reference named but never wrote
 ``jacobi``    Jacobi-preconditioned CG for general CSR matrices (the call the ViennaCL front-end left commented out)
 ``shifted``   multi-shift CG: (A + s_j I) x_j = b for up to 8 shifts from one CG recurrence on A
+``blockkrylov`` shared-subspace block CG: up to 8 right-hand sides in one block Krylov space (fewer iterations than ``block``)
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "jacobi", "shifted", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "jacobi", "shifted", "blockkrylov", "problems"]

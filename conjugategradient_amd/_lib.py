@@ -98,6 +98,7 @@ SIGNATURES = {
     "MgcgFill": (None, [_vp, _d]),
     "SolveEx": (_i, [_vp] * 11 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "SolveBlockEx": (_i, [_vp] * 11 + [_i, _i, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "SolveBlockKrylov": (_i, [_vp] * 11 + [_i, _i, _i, _d, _i, _i, _i, _pi, _vp, _vp, _vp, _i]),
     "CsrMVBlock": (None, [_vp] * 7 + [_i, _i, _i]),
     "MgSetup": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _i, _d]),
     "MgSetupParallel": (_vp, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _d]),

@@ -96,6 +96,7 @@ inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (voi
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
+void preload_kernels_bkrylov();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -150,6 +151,7 @@ struct ShiftScalars {
 
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
+struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
 struct Workspace {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -168,6 +170,10 @@ struct Workspace {
     double* blockPartials = nullptr;
     BlockScalars* blockScalars = nullptr;
     ShiftScalars* shiftScalars = nullptr;        // multi-shift CG (kernels_shift.hip), allocated at its first call and kept
+    // shared-subspace block CG (kernels_bkrylov.hip), allocated at its first call and kept: 36 regions of kMaxPartials partial sums, one per
+    // entry of the upper triangle of an 8 x 8 Gram matrix, and the loop's small matrices
+    double* gramPartials = nullptr;
+    BkScalars* bkScalars = nullptr;
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -175,6 +181,7 @@ struct Workspace {
     void free_ring();
     bool ensure_block();                         // blockPartials / blockScalars (kernels_block.hip)
     bool ensure_shift();                         // shiftScalars (kernels_shift.hip)
+    bool ensure_bkrylov();                       // gramPartials / bkScalars (kernels_bkrylov.hip)
 };
 
 } // namespace mgcg
@@ -487,6 +494,25 @@ void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g
 // f.trace: k traces of f.traceCap entries.
 void launch_update_shifted(hipStream_t s, int k, const FinalizeArgs& f, ShiftScalars* sh, const double* partials, const double* partialsInf, int nPartials,
                            double* x, double* p, const double* r, double* ps, long long n);
+
+// Shared-subspace block CG (SolveBlockKrylov; kernels_bkrylov.hip has the method).  X and B column-major, column j at j * n; S, Q and T the
+// row-interleaved work blocks.  The loop's stop flag is ws->scalars->done: bk_enqueue_start expects it cleared, and every kernel of the loop
+// returns at once when it is up.  bk_enqueue_start: R = B - A X, its Cholesky factor, Q, S.  bk_enqueue_iteration: the five launches of
+// one iteration (seven under dot_order = 1); f carries the stop rule and k traces of f.traceCap entries.
+struct BkRun {
+    Workspace* ws;
+    const double* elements; const int* rowOffsets; const int* columnIndeces;
+    long long n; int k;
+    double* X; const double* B; double *S, *Q, *T;
+};
+struct BkResult { int iteration; int failWhich, failPivot; double residual[kBlockMaxK]; int status[kBlockMaxK]; };   // failWhich: 0 none, 1 R0^T R0, 2 S^T A S, 3 W^T W
+bool bk_enqueue_start(const BkRun& R);
+bool bk_enqueue_iteration(const BkRun& R, const FinalizeArgs& f);
+bool bk_read_results(Workspace* ws, int k, BkResult* out);
+// T = A S for k interleaved columns with the per-wavefront partial sums of the upper triangle of S^T T, entry e at gramPartials + e * kMaxPartials
+// (kernels_block.hip: spmv_block_kernel's gather with the Gram epilogue); returns the number of partial sums per entry
+int launch_spmv_block_gram(hipStream_t s, int k, const double* elements, const int* rowOffsets, const int* columnIndeces,
+                           const double* S, double* T, long long rows, double* gramPartials, const int* done);
 
 // dinv_i = 1 / a_ii for the Jacobi-preconditioned loop
 void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,

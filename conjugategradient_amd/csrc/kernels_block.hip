@@ -110,7 +110,8 @@ constexpr int kBNG = 8;
 
 enum { BEPI_AP = 0,          // x interleaved; y interleaved = A x; partial[j] += x_j[row] * y_j[row]   (Ap = A p ; p.Ap)
        BEPI_RESIDUAL = 1,    // x, y, b column-major; y_j = b_j - A x_j
-       BEPI_PLAIN = 2 };     // x, y column-major; y_j = A x_j
+       BEPI_PLAIN = 2,       // x, y column-major; y_j = A x_j
+       BEPI_GRAM = 3 };      // x interleaved; y interleaved = A x; partial[(a, b)] += x_a[row] * y_b[row], a <= b   (T = A S ; S^T T, kernels_bkrylov.hip)
 
 struct BlockSpmvArgs {
     const double* elements; const int* rowOffsets; const int* columnIndeces;
@@ -120,13 +121,14 @@ struct BlockSpmvArgs {
     long long ld;            // column stride of the column-major operands
     int rows;
     double* partials;        // BEPI_AP: column j's partial sums at partials + j * kMaxPartials, one per wavefront
+                             // BEPI_GRAM: the same per entry (a, b), a <= b, of the upper triangle in row-major order (gram_index)
     const int* done;
 };
 
 template <int K, int EPI>
 __device__ __forceinline__ void gather(const BlockSpmvArgs& a, int col, double (&v)[K])
 {
-    if constexpr (EPI == BEPI_AP) load_row<K>(a.x + (long long)col * K, v);
+    if constexpr (EPI == BEPI_AP || EPI == BEPI_GRAM) load_row<K>(a.x + (long long)col * K, v);
     else {
 #pragma unroll
         for (int j = 0; j < K; ++j) v[j] = a.x[j * a.ld + col];
@@ -143,9 +145,10 @@ __global__ __launch_bounds__(64 * kBTW) void spmv_block_kernel(BlockSpmvArgs a)
     int* s_col = s_colAll + wv * kBTCap;
     double* s_val = s_valAll + wv * kBTCap;
     const int nTiles = (a.rows + kBTRows - 1) / kBTRows;
-    double dot[K];
+    constexpr int nDot = EPI == BEPI_GRAM ? K * (K + 1) / 2 : K;
+    double dot[nDot];
 #pragma unroll
-    for (int j = 0; j < K; ++j) dot[j] = 0.0;
+    for (int j = 0; j < nDot; ++j) dot[j] = 0.0;
     for (int tile = blockIdx.x; tile < nTiles; tile += gridDim.x) {       // workgroup-uniform trip count: the barriers below are safe
         const int r0 = tile * kBTRows + wv * 64;
         const int row = r0 + lane;
@@ -205,6 +208,16 @@ __global__ __launch_bounds__(64 * kBTW) void spmv_block_kernel(BlockSpmvArgs a)
 #pragma unroll
                 for (int j = 0; j < K; ++j) { const double t = w[j] * acc[j]; dot[j] += t; }
                 store_row<K, NT>(a.y + (long long)row * K, acc);
+            } else if constexpr (EPI == BEPI_GRAM) {
+                double w[K];
+                load_row<K>(a.x + (long long)row * K, w);
+                int e = 0;
+#pragma unroll
+                for (int i = 0; i < K; ++i) {
+#pragma unroll
+                    for (int j = i; j < K; ++j) { const double t = w[i] * acc[j]; dot[e] += t; ++e; }
+                }
+                store_row<K, NT>(a.y + (long long)row * K, acc);
             } else if constexpr (EPI == BEPI_RESIDUAL) {
 #pragma unroll
                 for (int j = 0; j < K; ++j) a.y[j * a.ld + row] = a.b[j * a.ld + row] - acc[j];
@@ -215,9 +228,9 @@ __global__ __launch_bounds__(64 * kBTW) void spmv_block_kernel(BlockSpmvArgs a)
         }
         __syncthreads();                                                   // the next trip overwrites the staged span
     }
-    if constexpr (EPI == BEPI_AP) {
+    if constexpr (EPI == BEPI_AP || EPI == BEPI_GRAM) {
 #pragma unroll
-        for (int j = 0; j < K; ++j) {
+        for (int j = 0; j < nDot; ++j) {
             const double t = wave_sum(dot[j]);
             if (lane == 0) a.partials[(long long)j * kMaxPartials + blockIdx.x * kBTW + wv] = t;
         }
@@ -240,6 +253,40 @@ static int launch_spmv_block(hipStream_t s, int epi, const BlockSpmvArgs& a, boo
     else { if (nt) GO(BEPI_PLAIN, true); else GO(BEPI_PLAIN, false); }
 #undef GO
     return nWG * kBTW;
+}
+
+// T = A S with the partial sums of the upper triangle of S^T T (shared-subspace block CG, kernels_bkrylov.hip); returns their count per entry
+template <int K>
+static int spmv_block_gram(hipStream_t s, const BlockSpmvArgs& a, bool nt)
+{
+    const int nTiles = (a.rows + kBTRows - 1) / kBTRows;
+    DeviceState* d = device_state();
+    int nWG = 2 * (d ? d->numCu : kNumCu);
+    if (nWG > nTiles) nWG = nTiles;
+    if (nWG * kBTW > kMaxPartials) nWG = kMaxPartials / kBTW;
+    if (nt) hipLaunchKernelGGL((spmv_block_kernel<K, BEPI_GRAM, true>), dim3(nWG), dim3(64 * kBTW), 0, s, a);
+    else hipLaunchKernelGGL((spmv_block_kernel<K, BEPI_GRAM, false>), dim3(nWG), dim3(64 * kBTW), 0, s, a);
+    return nWG * kBTW;
+}
+
+int launch_spmv_block_gram(hipStream_t s, int k, const double* elements, const int* rowOffsets, const int* columnIndeces,
+                           const double* S, double* T, long long rows, double* gramPartials, const int* done)
+{
+    if (rows <= 0) return 0;
+    BlockSpmvArgs a{};
+    a.elements = elements; a.rowOffsets = rowOffsets; a.columnIndeces = columnIndeces;
+    a.x = S; a.y = T; a.ld = rows; a.rows = (int)rows; a.partials = gramPartials; a.done = done;
+    const bool nt = rows >= 8000000;                   // (block_solve's rule)
+    switch (k) {
+    case 1: return spmv_block_gram<1>(s, a, nt);
+    case 2: return spmv_block_gram<2>(s, a, nt);
+    case 3: return spmv_block_gram<3>(s, a, nt);
+    case 4: return spmv_block_gram<4>(s, a, nt);
+    case 5: return spmv_block_gram<5>(s, a, nt);
+    case 6: return spmv_block_gram<6>(s, a, nt);
+    case 7: return spmv_block_gram<7>(s, a, nt);
+    default: return spmv_block_gram<8>(s, a, nt);
+    }
 }
 
 // ------------------------------------------------------------------ vector passes

@@ -1094,6 +1094,50 @@ static int cg_solve_shifted(CgRun& R, double* ps, int k, const double* shifts, i
     return ok ? worst : MGCG_ERROR;
 }
 
+// ---------------------------------------------------------------- shared-subspace block CG (SolveBlockKrylov)
+// k right-hand sides in one block Krylov space (kernels_bkrylov.hip has the method and the kernels).  The matrix is read as plain CSR by the
+// block product, so no matrix set-up, no placement draw and no deferred x update; the host's side is cg_drive.  R.p, R.r and R.Ap hold S, Q, T.
+static int cg_solve_bkrylov(CgRun& R, int k, int* iteration, double residual[], int status[], double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    if (!ws->ensure_bkrylov()) return MGCG_ERROR;
+    const int devTraceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
+    if (devTraceCap && !ws->ensure_trace(k * devTraceCap)) return MGCG_ERROR;
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    f.trace = devTraceCap ? ws->trace : nullptr; f.traceCap = devTraceCap;
+    const BkRun B = { ws, R.elements, R.rowOffsets, R.columnIndeces, n, k, R.x, R.b, R.p, R.r, R.Ap };
+    hipLaunchKernelGGL(clear_done_kernel, dim3(1), dim3(1), 0, s, ws->scalars);
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, (long long)k * n);       // SimpleConjugateGradient.cu:53, per column (as SolveBlockEx)
+    bool ok = bk_enqueue_start(B);
+    ok = ok && cg_drive(R, "SolveBlockKrylov", [&] { return bk_enqueue_iteration(B, f); });
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    BkResult h{};
+    ok = ok && bk_read_results(ws, k, &h);
+    if (!ok) return MGCG_ERROR;
+    int worst = MGCG_OK;
+    if (iteration) *iteration = h.iteration;
+    for (int j = 0; j < k; ++j) {
+        if (residual) residual[j] = h.residual[j];
+        if (status) status[j] = h.status[j];
+        if (h.status[j] == MGCG_NONFINITE) worst = MGCG_NONFINITE;
+        else if (h.status[j] == MGCG_MAXIT_EXCEEDED && worst == MGCG_OK) worst = MGCG_MAXIT_EXCEEDED;
+        if (devTraceCap && h.failWhich != 1) {
+            int nTrace = h.iteration + (h.failWhich ? 0 : 1); if (nTrace > devTraceCap) nTrace = devTraceCap;
+            if (nTrace > 0) ok = MGCG_HIP(hipMemcpy(residualTrace + (size_t)j * traceCapacity, ws->trace + (size_t)j * devTraceCap, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost)) && ok;
+        }
+    }
+    if (h.failWhich) {
+        static const char* const names[] = { "", "the first factorisation, of R0^T R0 (dependent or zero initial residual columns)", "the factorisation of S^T A S (is the matrix positive definite?)",
+                                             "the factorisation of W^T W" };
+        set_error("SolveBlockKrylov: breakdown in %s: pivot %d is not finite and > 0 (iteration %d); x keeps the last completed iterate -- fall back to SolveBlockEx",
+                  names[h.failWhich], h.failPivot, h.iteration);
+    } else if (worst == MGCG_NONFINITE) set_error("SolveBlockKrylov: the residual of a column is not finite");
+    else if (worst == MGCG_MAXIT_EXCEEDED) set_error("SolveBlockKrylov: a column did not converge within maxIteration %d", R.maxIt);
+    return ok ? worst : MGCG_ERROR;
+}
+
 // The arguments that every entry point of the loop takes: the handles, the matrix and the vectors of this rank, the partition.
 struct CgCall {
     const char* who;                       // the caller's name in its messages
@@ -1223,6 +1267,43 @@ int SolveShifted(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
         analysis_note_write(R.x, sizeof(double) * (size_t)kn);
         analysis_note_write(shiftedPVector->data, sizeof(double) * (size_t)kn);
         st = cg_solve_shifted(R, shiftedPVector->data, k, shifts, iteration, residual, status, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveBlockKrylov(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                     Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                     Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                     int elementsCount, int count, int k,
+                     double allowableResidual, int minIteration, int maxIteration, int rule,
+                     int* iteration, double residual[], int status[], double residualTrace[], int traceCapacity)
+{
+    (void)matDescr;
+    // what needs no device is refused before one is asked for; nothing is enqueued for a call that fails here or in cg_call's checks
+    if (!cublas || !cusparse) { set_error("SolveBlockKrylov: null handle"); return MGCG_ERROR; }
+    if (k < 1 || k > kBlockMaxK) { set_error("SolveBlockKrylov: k = %d right-hand sides, must be 1 .. %d", k, kBlockMaxK); return MGCG_ERROR; }
+    if (rule == MGCG_RULE_HANDMADECL) {
+        set_error("SolveBlockKrylov: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: it needs max|r| and the residual block is never formed");
+        return MGCG_ERROR;
+    }
+    if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) { set_error("SolveBlockKrylov: unknown stop rule %d", rule); return MGCG_ERROR; }
+    if (count < 1) { set_error("SolveBlockKrylov: bad sizes"); return MGCG_ERROR; }
+    if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) { set_error("SolveBlockKrylov: trace capacity too large"); return MGCG_ERROR; }
+    if (!device_state()) return MGCG_ERROR;
+    const CgCall c = { "SolveBlockKrylov", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, count, 0, elementsCount, 0, count - 1 };
+    const long long kn = (long long)k * count;
+    auto checks = [&] {
+        if (xVector->size < kn || bVector->size < kn || ApVector->size < kn || pVector->size < kn || rVector->size < kn) {
+            set_error("SolveBlockKrylov: a device vector is smaller than the problem (x, b, Ap, p, r need k * count entries)"); return false;
+        }
+        return true;
+    };
+    int st = MGCG_ERROR;
+    cg_call(c, true, checks, [&](CgRun& R) {
+        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        for (double* v : { R.x, R.r, R.p, R.Ap }) analysis_note_write(v, sizeof(double) * (size_t)kn);
+        st = cg_solve_bkrylov(R, k, iteration, residual, status, residualTrace, traceCapacity);
     });
     return st;
 }

@@ -533,6 +533,50 @@ int SolveShifted(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                  double allowableResidual, int minIteration, int maxIteration, int rule,
                  int iteration[], double residual[], int status[], double residualTrace[], int traceCapacity);
 
+/* ---- Shared-subspace block CG: k = 1 .. 8 right-hand sides in ONE block Krylov space (one rank, no preconditioner, plain CSR) ---- */
+/* O'Leary's block CG in Dubrulle's breakdown-free form (BCGrQ).  SolveBlockEx runs k independent recurrences that share the matrix pass;
+ * here every column minimises over the union of the k Krylov spaces, so all columns converge in fewer iterations, for two more block
+ * reads/writes per iteration.  Arguments as SolveBlockEx: column j of x and b at [j*count, (j+1)*count), k*count entries each; Ap, p, r:
+ * k*count entries of work space whose layout is internal (row-interleaved T = A S, the search block S, the orthonormal residual block Q).
+ * The initial guess in x is honoured (MGCG_RULE_SIMPLE starts from 0, as everywhere).  *iteration: the one common counter (may be NULL);
+ * residual[] / status[]: k entries each, may be NULL; residualTrace (may be NULL): column j's trace at j*traceCapacity.
+ * Method, with k x k matrices C, alpha, M, zeta (row-major) --
+ *   start:  R = B - A X ;  R^T R = U^T U (Cholesky, U upper triangular) ;  Q = R U^-1 ;  C = U ;  S = Q ;  rr0_j = sum_i C[i][j]^2
+ *   1. T = A S ;  G = S^T T                               2. G = Ug^T Ug ;  alpha = G^-1 ;  M = alpha C
+ *   3. X = X + S M ;  W = Q - T alpha ;  H = W^T W        4. H = zeta^T zeta ;  C = zeta C ;  rr_j = sum_i C[i][j]^2 ;  the stop decision
+ *   5. Q = W zeta^-1 ;  S = Q + S zeta^T
+ * Q stays orthonormal and the columns' sizes travel in C: || r_j || = || C[:, j] ||, no sums of their own.
+ * Rounding contract: every product is rounded into a double of its own before the add or subtraction that follows it, nothing is fused into
+ * an FMA, sqrt and / are the correctly rounded ones.  A row of A adds its products in stored order from +0.0 (CsrMVBlock).  Every sum over k
+ * terms -- a row of a block times a k x k matrix, a k x k product, rr_j -- starts with its FIRST product and adds the others left to
+ * right, l = 0 .. k-1, structural zeros included:  (S M)[i][j] = ((S[i][0] M[0][j] + S[i][1] M[1][j]) + ...), X[i][j] = X[i][j] + (S M)[i][j],
+ * W[i][j] = Q[i][j] - (T alpha)[i][j], S[i][j] = Q[i][j] + sum_l S[i][l] zeta[j][l].  Only the upper triangle (a <= b) of a Gram matrix is
+ * summed, entry (a, b) = sum over the rows i of left[i][a] * right[i][b].  Cholesky, row i = 0 .. k-1:  d = G[i][i] - U[0][i]^2 - ... -
+ * U[i-1][i]^2 (left to right), U[i][i] = sqrt(d), U[i][j] = (G[i][j] - U[0][i] U[0][j] - ... - U[i-1][i] U[i-1][j]) / U[i][i] for j > i.
+ * Inverse V of an upper triangular U, column j:  V[j][j] = 1 / U[j][j] ;  for i = j-1 .. 0:  V[i][j] = -(U[i][i+1] V[i+1][j] + ... +
+ * U[i][j] V[j][j]) / U[i][i].  alpha[a][b] = alpha[b][a] = V[a][b] V[b][b] + V[a][b+1] V[b][b+1] + ... + V[a][k-1] V[b][k-1] (a <= b, V = Ug^-1).
+ * In the default mode a Gram entry is a tree sum of per-workgroup partial sums in a fixed order (the same bits on every run); under
+ * dot_order = 1 it is one serial left-to-right sum over the rows, and the whole loop is then a fixed sequence of IEEE operations.
+ * Stopping: the four 2-norm rules of SolveEx, evaluated per column in step 4 on (rr_j, rr0_j) with the common counter.  The loop ends in
+ * the first iteration in which NO column's decision is "continue"; until then every column is updated (the search space is shared: nothing
+ * is frozen), and status[j] / residual[j] are those of that last iteration.  MGCG_RULE_HANDMADECL is refused: it needs max|r|, and R is
+ * never formed.
+ * Breakdown: a Cholesky pivot that is not finite and > 0 -- in R0^T R0 (dependent or zero initial residual columns: two equal right-hand
+ * sides, b_j = 0, an x_j that already solves its system), in S^T A S (the matrix is not positive definite) or in W^T W -- ends the call with
+ * MGCG_NONFINITE for every column.  The raw pivot is tested, no tolerance; there is no rank-revealing deflation.  x keeps the last completed
+ * iterate: the caller's x, bit for bit, for the first factorisation; the previous iteration's for S^T A S; for W^T W the x of step 3 of that
+ * iteration (a valid iterate whose residual norm is unknown).  MgcgGetLastError names the factorisation and the pivot index.  A caller whose
+ * right-hand sides may be dependent falls back to SolveBlockEx, whose columns are independent.
+ * Returns the worst column status (MGCG_NONFINITE > MGCG_MAXIT_EXCEEDED > MGCG_OK); MGCG_ERROR with a message, and nothing enqueued, for k
+ * outside 1 .. 8, a null handle, a vector that is too small, or the max-norm rule.  The matrix is always read as plain CSR, whatever the
+ * handle's compression mode; placement draw and x_defer do not apply. */
+int SolveBlockKrylov(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                     Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                     Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                     int elementsCount, int count, int k,
+                     double allowableResidual, int minIteration, int maxIteration, int rule,
+                     int* iteration, double residual[], int status[], double residualTrace[], int traceCapacity);
+
 /* Fixed number of CG iterations with no stop test and no host synchronisation inside (bench.py's
  * "steps"): runs `steps` more iterations of the recurrence held in x,r,p (call with restart != 0 first
  * to compute r = b - A x, p = r, rr).  comm may be NULL.  Returns the residual after the last step. */

@@ -1,0 +1,488 @@
+"""Shared-subspace block CG (SolveBlockKrylov, blockkrylov.ConjugateGradientBlockKrylovGpu): k right-hand sides in one block Krylov space.
+
+The yardstick is ``bcgrq_yardstick`` below: the loop of include/MgcgGpu.h in numpy float64, every product an array (or a Python float) of
+its own before the add that follows it, the k x k algebra in Python floats in the header's order, the row sums from the oracle's SpMV and
+the Gram entries from oracle.dot (serial left-to-right sums).  Under dot_order = 1 the HIP loop must EQUAL it; in the default mode only the
+summation order of the Gram entries (and of long rows) differs.
+
+Tolerances: the project's standing ones: traces within rtol 1e-10 while >= 1e-6 of their start, iterates within
+1e-10 max|x|."""
+import ctypes as C
+import dataclasses
+import math
+
+import numpy as np
+import pytest
+
+from conjugategradient_amd import _lib, problems
+from conjugategradient_amd.block import ConjugateGradientBlockGpu
+from conjugategradient_amd.blockkrylov import ConjugateGradientBlockKrylovGpu
+from conjugategradient_amd.solver import ApplicationException, ConjugateGradientSingleGpu
+from oracle import oracle as O
+from tests.test_gpu_jacobi import stop_decision
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-8
+MAX_IT = 2000
+FINITE_MAX = 1.79e308
+
+
+# --------------------------------------------------------------------------- the yardstick
+def _div(a, b):
+    with np.errstate(all="ignore"):
+        return float(np.float64(a) / np.float64(b))
+
+
+def cholesky_upper(G, k):
+    """G = U^T U from G's upper triangle; (U, -1) or (U, index of the first pivot that is not finite and > 0)."""
+    U = [[0.0] * k for _ in range(k)]
+    for i in range(k):
+        d = G[i][i]
+        for l in range(i):
+            t = U[l][i] * U[l][i]
+            d = d - t
+        if not (0.0 < d <= FINITE_MAX):
+            return U, i
+        u = math.sqrt(d)
+        U[i][i] = u
+        for j in range(i + 1, k):
+            s = G[i][j]
+            for l in range(i):
+                t = U[l][i] * U[l][j]
+                s = s - t
+            U[i][j] = _div(s, u)
+    return U, -1
+
+
+def invert_upper(U, k):
+    V = [[0.0] * k for _ in range(k)]
+    for j in range(k):
+        V[j][j] = _div(1.0, U[j][j])
+        for i in range(j - 1, -1, -1):
+            s = U[i][i + 1] * V[i + 1][j]
+            for l in range(i + 2, j + 1):
+                t = U[i][l] * V[l][j]
+                s = s + t
+            V[i][j] = _div(-s, U[i][i])
+    return V
+
+
+def small_matmul(A, B, k):
+    P = [[0.0] * k for _ in range(k)]
+    for a in range(k):
+        for b in range(k):
+            s = A[a][0] * B[0][b]
+            for l in range(1, k):
+                t = A[a][l] * B[l][b]
+                s = s + t
+            P[a][b] = s
+    return P
+
+
+def column_norm2(Cm, j, k):
+    s = Cm[0][j] * Cm[0][j]
+    for i in range(1, k):
+        t = Cm[i][j] * Cm[i][j]
+        s = s + t
+    return s
+
+
+def rows_times(A, m, k):
+    """(n, k) block times a k x k matrix: per entry the first product, then the adds, left to right."""
+    out = np.empty_like(A)
+    for j in range(k):
+        acc = A[:, 0] * m[0][j]
+        for l in range(1, k):
+            t = A[:, l] * m[l][j]
+            acc = acc + t
+        out[:, j] = acc
+    return out
+
+
+def gram(L, Rt, k, dot):
+    G = [[0.0] * k for _ in range(k)]
+    for a in range(k):
+        la = np.ascontiguousarray(L[:, a])
+        for b in range(a, k):
+            G[a][b] = dot(la, np.ascontiguousarray(Rt[:, b]))
+    return G
+
+
+def bcgrq_yardstick(csr, B, X0, rule=_lib.RULE_VIENNACL, tol=TOL, min_it=0, max_it=MAX_IT, dot=None):
+    """csr = (elements, columns, row offsets); B, X0: (k, n).  Returns dict(x (k, n), iteration, residual (k), status (k), trace (k, m),
+    failed: None or (which, pivot) with which = 1 R0^T R0, 2 S^T A S, 3 W^T W)."""
+    e, c, r = csr
+    dot = dot or O.dot
+    k, n = B.shape
+    spmv_block = lambda V: np.stack([O.spmv(e, c, r, np.ascontiguousarray(V[:, j])) for j in range(k)], axis=1)
+    X = np.zeros((n, k)) if rule == _lib.RULE_SIMPLE else np.ascontiguousarray(X0.T).copy()
+    out = dict(iteration=0, residual=np.zeros(k), status=np.full(k, _lib.NONFINITE, dtype=np.int32), trace=[[] for _ in range(k)], failed=None)
+    R = np.ascontiguousarray(B.T) - spmv_block(X)
+    U, bad = cholesky_upper(gram(R, R, k, dot), k)
+    if bad >= 0:
+        out.update(x=X.T.copy(), failed=(1, bad), trace=np.zeros((k, 0)))
+        return out
+    Cm = U
+    Q = rows_times(R, invert_upper(U, k), k)
+    S = Q.copy()
+    rr0 = [column_norm2(Cm, j, k) for j in range(k)]
+    it = 0
+    while True:
+        T = spmv_block(S)
+        Ug, bad = cholesky_upper(gram(S, T, k, dot), k)
+        if bad >= 0:
+            out["failed"] = (2, bad)
+            break
+        V = invert_upper(Ug, k)
+        alpha = [[0.0] * k for _ in range(k)]
+        for a in range(k):
+            for b in range(a, k):
+                s = V[a][b] * V[b][b]
+                for l in range(b + 1, k):
+                    t = V[a][l] * V[b][l]
+                    s = s + t
+                alpha[a][b] = alpha[b][a] = s
+        M = small_matmul(alpha, Cm, k)
+        X = X + rows_times(S, M, k)
+        W = Q - rows_times(T, alpha, k)
+        zeta, bad = cholesky_upper(gram(W, W, k, dot), k)
+        if bad >= 0:
+            out["failed"] = (3, bad)
+            break
+        zinv = invert_upper(zeta, k)
+        Cm = small_matmul(zeta, Cm, k)
+        go_on = False
+        for j in range(k):
+            res, shown, stop, status = stop_decision(rule, tol, min_it, max_it, it, column_norm2(Cm, j, k), 0.0, rr0[j])
+            out["trace"][j].append(shown)
+            out["residual"][j], out["status"][j] = res, status
+            go_on = go_on or not stop
+        if not go_on:
+            break
+        Q = rows_times(W, zinv, k)
+        zetaT = [[zeta[j][l] for j in range(k)] for l in range(k)]
+        S = Q + rows_times(S, zetaT, k)
+        it += 1
+    out.update(x=X.T.copy(), iteration=it, trace=np.array(out["trace"]))
+    return out
+
+
+# --------------------------------------------------------------------------- systems and right-hand sides
+def _system(csr, name):
+    e, c, r = csr
+    n = len(r) - 1
+    return problems.LinearSystem(np.asarray(e, dtype=np.float64), np.asarray(c, dtype=np.int32), np.asarray(r, dtype=np.int32), np.zeros(n), np.zeros(n), name)
+
+
+CSR = {
+    "poisson16": lambda: O.poisson_csr(16, 16, 16),
+    "grid7x9x11": lambda: O.poisson_csr(7, 9, 11),        # 693 rows: odd, no multiple of the 256-row tile; columns of X misaligned for k > 1
+    "mgcgmain3000": lambda: O.mgcgmain_csr(3000, 160),    # rows longer than 100
+    "poisson8": lambda: O.poisson_csr(8, 8, 8),
+    "poisson5": lambda: O.poisson_csr(5, 5, 5),
+}
+_csr = {}
+
+
+def csr_of(which):
+    if which not in _csr:
+        _csr[which] = CSR[which]()
+    return _csr[which]
+
+
+def columns(n, k, seed, x0=False):
+    """k seeded N(0,1) right-hand sides, the last one (k > 1) scaled by 1e-6; x0: a seeded non-zero start, scaled like its right-hand side.
+    (A start of size 1 for the 1e-6 column would make its solution 1e5 times smaller than the x it is accumulated in: the fp64 rounding
+    of x itself, 1e-16 |x0|, then lies above 1e-10 max|x| for ANY two summation orders, which says nothing about the loop.)"""
+    rng = np.random.default_rng(seed)
+    B = rng.standard_normal((k, n))
+    X = rng.standard_normal((k, n)) if x0 else np.zeros((k, n))
+    if k > 1:
+        B[k - 1] *= 1e-6
+        X[k - 1] *= 1e-6
+    return B, X
+
+
+_refs = {}
+
+
+def reference(which, k, seed, x0=False, rule=_lib.RULE_VIENNACL, tol=TOL, min_it=0, max_it=MAX_IT):
+    """The yardstick's run (serial Gram sums), computed once per case and never changed."""
+    key = (which, k, seed, x0, rule, tol, min_it, max_it)
+    if key not in _refs:
+        csr = csr_of(which)
+        B, X = columns(len(csr[2]) - 1, k, seed, x0)
+        ref = bcgrq_yardstick(csr, B, X, rule, tol, min_it, max_it)
+        for name in ("x", "trace", "residual", "status"):
+            ref[name].setflags(write=False)
+        _refs[key] = ref
+    return _refs[key]
+
+
+@pytest.fixture
+def dot_order(mgcg_env):
+    mgcg_env.setenv("MGCG_DOT_ORDER", "1")
+    yield
+    mgcg_env.delenv("MGCG_DOT_ORDER")
+
+
+def solve(which, B, X, rule=_lib.RULE_VIENNACL, tol=TOL, min_it=0, max_it=MAX_IT, trace=True, cls=ConjugateGradientBlockKrylovGpu, csr=None):
+    """One solve through the Python class; an iteration cap that was hit is a result here.  Returns (object after Read, exception or None)."""
+    csr = csr or csr_of(which)
+    s = _system(csr, which)
+    cg = cls(s.Count, int(np.diff(s.RowOffsets).max()), B.shape[0], min_it, max_it, tol, rule=rule).load(s, B, X)
+    cg.Initialize()
+    err = None
+    try:
+        cg.Solve(trace=trace)
+    except (ApplicationException, _lib.MgcgError) as ex:
+        err = ex
+    cg.Read()
+    return cg, err
+
+
+def assert_close_runs(cg, ref, k):
+    """Check 1's tolerances against the yardstick stopped at the same iteration."""
+    assert cg.Iteration == ref["iteration"], (cg.Iteration, ref["iteration"])
+    assert list(cg.status) == list(ref["status"])
+    for j in range(k):
+        got, want = np.asarray(cg.trace[j]), ref["trace"][j]
+        assert len(got) == len(want)
+        hi = want >= 1e-6 * want[0]
+        err = np.abs(got[hi] - want[hi]) / want[hi]
+        dist = np.abs(cg.X[j] - ref["x"][j]).max() / np.abs(ref["x"][j]).max()
+        print("column", j, "trace rel. error (strict band)", err.max(), "iterate distance", dist)
+        np.testing.assert_allclose(got[hi], want[hi], rtol=1e-10)
+        assert dist <= 1e-10
+
+
+def assert_decisive(ref, tol):
+    """The yardstick's deciding column misses / meets the tolerance by more than a relative 1e-6 at the stop and one iteration before it."""
+    last = ref["trace"][:, -1].max()
+    before = ref["trace"][:, -2].max()
+    assert last < tol * (1.0 - 1e-6) and before > tol * (1.0 + 1e-6), (before, last, tol)
+
+
+def true_residuals(csr, B, X):
+    e, c, r = csr
+    out = []
+    for j in range(B.shape[0]):
+        d = B[j] - O.spmv(e, c, r, np.ascontiguousarray(X[j]))
+        out.append(math.sqrt(O.dot(d, d)))
+    return np.array(out)
+
+
+CASES = [("poisson16", 1, 21, False), ("poisson16", 3, 22, True), ("poisson16", 8, 23, False),
+         ("grid7x9x11", 1, 24, False), ("grid7x9x11", 3, 25, False), ("grid7x9x11", 8, 26, True),
+         ("mgcgmain3000", 1, 27, False), ("mgcgmain3000", 3, 28, False), ("mgcgmain3000", 8, 29, False)]
+
+
+# --------------------------------------------------------------------------- 1. default mode, 2. the true residual
+@pytest.mark.parametrize("which,k,seed,x0", CASES)
+def test_default_mode_against_the_yardstick_and_true_residual(oracle, which, k, seed, x0):
+    csr = csr_of(which)
+    ref = reference(which, k, seed, x0)
+    assert ref["failed"] is None and (ref["status"] == _lib.OK).all() and ref["iteration"] >= 3
+    assert_decisive(ref, TOL)
+    B, X = columns(len(csr[2]) - 1, k, seed, x0)
+    cg, err = solve(which, B, X)
+    assert err is None, err
+    print(which, k, "iterations", cg.Iteration, ref["iteration"])
+    assert_close_runs(cg, ref, k)
+    true = true_residuals(csr, B, cg.X)
+    r0 = true_residuals(csr, B, X)
+    print("true residuals", true, "reported", cg.Residual)
+    assert (true <= 2.0 * cg.Residual).all(), (true, cg.Residual)
+    assert (cg.Residual < TOL * r0 * (1.0 + 1e-9)).all()          # RULE_VIENNACL: rr / rr0 < tol^2, rr0 the first residual's (1e-9: rr0 comes from C, not from a sum of its own)
+
+
+@pytest.mark.parametrize("rule", [_lib.RULE_NATIVE, _lib.RULE_CSHARP, _lib.RULE_SIMPLE])
+def test_the_other_two_norm_rules(oracle, rule):
+    which, k, seed = "poisson16", 3, 31
+    csr = csr_of(which)
+    n = len(csr[2]) - 1
+    B, X = columns(n, k, seed, x0=True)
+    r0 = true_residuals(csr, B, np.zeros_like(X) if rule == _lib.RULE_SIMPLE else X)
+    tol = 1e-8 * float(r0.max())                                  # absolute rules: 1e-8 of the largest first residual
+    ref = bcgrq_yardstick(csr, B, X, rule, tol)
+    assert ref["failed"] is None and (ref["status"] == _lib.OK).all()
+    assert_decisive(ref, tol)
+    cg, err = solve(which, B, X, rule=rule, tol=tol)
+    assert err is None, err
+    assert_close_runs(cg, ref, k)
+    assert (cg.Residual < tol).all()
+    assert (true_residuals(csr, B, cg.X) <= 2.0 * cg.Residual).all()
+
+
+# --------------------------------------------------------------------------- 3. the shared space is real
+def test_fewer_iterations_than_independent_recurrences(oracle):
+    which, k, seed = "poisson16", 8, 23
+    csr = csr_of(which)
+    B, X = columns(len(csr[2]) - 1, k, seed)
+    shared, err = solve(which, B, X)
+    assert err is None, err
+    independent, err = solve(which, B, X, cls=ConjugateGradientBlockGpu)
+    assert err is None, err
+    print("shared subspace", shared.Iteration, "independent", independent.Iteration)
+    assert shared.Iteration < int(independent.Iteration.min())
+
+
+# --------------------------------------------------------------------------- 4. k = 1 is CG
+@pytest.mark.parametrize("which,seed", [("poisson16", 21), ("grid7x9x11", 24)])
+def test_one_column_is_solve_ex(oracle, which, seed):
+    csr = csr_of(which)
+    B, X = columns(len(csr[2]) - 1, 1, seed)
+    cg, err = solve(which, B, X)
+    assert err is None, err
+    s = dataclasses.replace(_system(csr, which), b=B[0].copy(), x=X[0].copy())
+    one = ConjugateGradientSingleGpu(s.Count, 7, 0, MAX_IT, TOL, rule=_lib.RULE_VIENNACL).load(s)
+    one.Initialize()
+    one.Solve()
+    one.Read()
+    dist = np.abs(cg.X[0] - one.x).max() / np.abs(one.x).max()
+    print(which, "iterations", cg.Iteration, one.Iteration, "distance", dist)
+    assert cg.Iteration == one.Iteration
+    assert dist <= 1e-10
+    one.Dispose()
+
+
+# --------------------------------------------------------------------------- 5. dot_order = 1: bit equality; reproducibility
+@pytest.mark.parametrize("k", [1, 3, 8])
+@pytest.mark.parametrize("which", ["poisson8", "grid7x9x11"])
+def test_dot_order_one_equals_the_yardstick_bit_for_bit(oracle, dot_order, which, k):
+    seed = 40 + k
+    csr = csr_of(which)
+    ref = reference(which, k, seed, x0=(k == 3))
+    assert ref["failed"] is None and (ref["status"] == _lib.OK).all() and ref["iteration"] >= 3
+    B, X = columns(len(csr[2]) - 1, k, seed, x0=(k == 3))
+    cg, err = solve(which, B, X)
+    assert err is None, err
+    assert cg.Iteration == ref["iteration"], (cg.Iteration, ref["iteration"])
+    assert np.array_equal(cg.status, ref["status"]) and np.array_equal(cg.Residual, ref["residual"])
+    for j in range(k):
+        assert np.array_equal(cg.trace[j], ref["trace"][j]), j
+    assert np.array_equal(cg.X, ref["x"])
+
+
+def test_two_default_mode_solves_give_identical_bits(oracle):
+    which, k, seed = "grid7x9x11", 8, 26
+    B, X = columns(693, k, seed, x0=True)
+    a, err = solve(which, B, X)
+    assert err is None, err
+    b, err = solve(which, B, X)
+    assert err is None, err
+    assert a.Iteration == b.Iteration and np.array_equal(a.Residual, b.Residual) and np.array_equal(a.X, b.X)
+    assert all(np.array_equal(p, q) for p, q in zip(a.trace, b.trace))
+
+
+# --------------------------------------------------------------------------- 6. breakdown
+def _raw_solve(cg, n, k, nnz, tol=TOL, max_it=MAX_IT):
+    L = _lib.lib()
+    it, status = C.c_int(-5), np.full(8, -7, dtype=np.int32)
+    L.MgcgClearLastError()
+    st = L.SolveBlockKrylov(cg.cublas, cg.cusparse, cg.matDescr, cg.vectorA.Ptr, cg.vectorRowOffsets.Ptr, cg.vectorColumnIndeces.Ptr,
+                            cg.vectorX.Ptr, cg.vectorB.Ptr, cg.vectorAp.Ptr, cg.vectorP.Ptr, cg.vectorR.Ptr, nnz, n, k,
+                            tol, 0, max_it, _lib.RULE_VIENNACL, C.byref(it), None, status.ctypes.data_as(C.c_void_p), None, 0)
+    msg = _lib.last_error()
+    L.MgcgClearLastError()
+    return st, status[:k], msg
+
+
+@pytest.mark.parametrize("case", ["identical_columns", "zero_column", "exact_start"])
+def test_rank_deficient_start_is_a_numerical_status(oracle, case):
+    which, k = "poisson8", 3
+    csr = csr_of(which)
+    n = len(csr[2]) - 1
+    B, X = columns(n, k, 51, x0=True)
+    if case == "identical_columns":
+        B[2] = B[0]
+        X[2] = X[0]
+    elif case == "zero_column":
+        B[1] = 0.0
+        X[1] = 0.0
+    else:
+        X[1] = np.round(4.0 * np.random.default_rng(52).standard_normal(n))      # small integers: A x0 is exact, so R's column is exactly 0
+        B[1] = O.spmv(*csr, X[1])
+    s = _system(csr, which)
+    cg = ConjugateGradientBlockKrylovGpu(n, 7, k, 0, MAX_IT, TOL, rule=_lib.RULE_VIENNACL).load(s, B, X)
+    cg.Initialize()
+    st, status, msg = _raw_solve(cg, n, k, s.nnz)
+    print(case, st, status, msg)
+    assert st == _lib.NONFINITE and list(status) == [_lib.NONFINITE] * k
+    assert "first factorisation" in msg and "pivot" in msg
+    cg.Read()
+    assert np.array_equal(cg.X, X)                                   # the caller's x, bit for bit
+    with pytest.raises(_lib.MgcgError, match="first factorisation"):
+        cg.Solve()
+    assert list(cg.status) == [_lib.NONFINITE] * k
+    cg.Dispose()
+
+
+# --------------------------------------------------------------------------- 7. caps and rules
+def test_iteration_cap(oracle):
+    which, k, seed = "poisson16", 3, 22
+    csr = csr_of(which)
+    B, X = columns(len(csr[2]) - 1, k, seed, x0=True)
+    ref = bcgrq_yardstick(csr, B, X, max_it=4)                      # iterations 0 .. 5: the cap stops the loop at it = 5 > max_it
+    assert ref["iteration"] == 5 and (ref["status"] == _lib.MAXIT_EXCEEDED).all()
+    cg, err = solve(which, B, X, max_it=4)
+    assert isinstance(err, ApplicationException), err
+    assert_close_runs(cg, ref, k)
+
+
+def test_min_iteration_runs_past_convergence(oracle):
+    which, k, seed = "poisson5", 8, 61
+    csr = csr_of(which)
+    B, X = columns(125, k, seed)
+    free = bcgrq_yardstick(csr, B, X)
+    assert free["failed"] is None
+    forced = free["iteration"] + 20
+    cg, err = solve(which, B, X, min_it=forced - 1)                 # RULE_VIENNACL converges only when min_it < it
+    assert err is None, err
+    print("free", free["iteration"], "forced", cg.Iteration, "residuals", cg.Residual)
+    assert cg.Iteration == forced and (cg.status == _lib.OK).all()
+    assert (true_residuals(csr, B, cg.X) <= 2.0 * true_residuals(csr, B, free["x"])).all()
+
+
+def test_short_trace_does_not_overflow(oracle):
+    which, k, seed = "poisson16", 3, 22
+    csr = csr_of(which)
+    n = len(csr[2]) - 1
+    B, X = columns(n, k, seed, x0=True)
+    ref = reference(which, k, seed, True)
+    s = _system(csr, which)
+    cg = ConjugateGradientBlockKrylovGpu(n, 7, k, 0, MAX_IT, TOL, rule=_lib.RULE_VIENNACL).load(s, B, X)
+    cg.Initialize()
+    cap = 4
+    tr = np.full(k * cap + 8, -1.0)
+    it = C.c_int(0)
+    L = _lib.lib()
+    st = L.SolveBlockKrylov(cg.cublas, cg.cusparse, cg.matDescr, cg.vectorA.Ptr, cg.vectorRowOffsets.Ptr, cg.vectorColumnIndeces.Ptr,
+                            cg.vectorX.Ptr, cg.vectorB.Ptr, cg.vectorAp.Ptr, cg.vectorP.Ptr, cg.vectorR.Ptr, s.nnz, n, k,
+                            TOL, 0, MAX_IT, _lib.RULE_VIENNACL, C.byref(it), None, None, tr.ctypes.data_as(C.c_void_p), cap)
+    _lib.check("SolveBlockKrylov")
+    assert st == _lib.OK and it.value == ref["iteration"] > cap
+    assert (tr[k * cap:] == -1.0).all()
+    for j in range(k):
+        np.testing.assert_allclose(tr[j * cap: (j + 1) * cap], ref["trace"][j][:cap], rtol=1e-10)
+    cg.Dispose()
+
+
+# --------------------------------------------------------------------------- 8. the streaming-hint form
+def test_streaming_hint_form(oracle):
+    """3 000 001 rows (above the 3 M rows from which the passes take the non-temporal forms; odd: with k = 2 one element at a time -- the
+    16-byte streaming form runs in the k = 1 solve), capped at 6 iterations."""
+    from tests.test_gpu_jacobi import tridiagonal
+
+    n = 3_000_001
+    s, _ = tridiagonal(n)
+    csr = (s.Elements, s.ColumnIndeces, s.RowOffsets)
+    for k in (2, 1):
+        B, X = columns(n, k, 70 + k)
+        ref = bcgrq_yardstick(csr, B, X, max_it=4, dot=lambda a, b: float(a @ b))
+        assert ref["iteration"] == 5 and ref["failed"] is None
+        cg, err = solve("tridiagonal", B, X, max_it=4, csr=csr)
+        assert isinstance(err, ApplicationException), err
+        assert_close_runs(cg, ref, k)
+        cg.Dispose()
