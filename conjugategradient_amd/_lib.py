@@ -115,6 +115,9 @@ SIGNATURES = {
     "MgcgJacobiSetup": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "SolveJacobi": (_i, [_vp] * 12 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "SolveShifted": (_i, [_vp] * 12 + [_i, _i, _i, _vp, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "MgcgMixedSetup": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _pi]),
+    "CsrMVFloat": (None, [_vp] * 7 + [_i, _i]),
+    "SolveMixed": (_i, [_vp] * 12 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _pi, _vp, _i]),
     "SolveJacobiParallel": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "MgcgCommGetUniqueId": (_i, [_vp]),
     "MgcgRcclAvailable": (_i, []),

@@ -96,7 +96,7 @@ inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (voi
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
-void preload_kernels_bkrylov();
+void preload_kernels_bkrylov(); void preload_kernels_mixed();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -149,6 +149,18 @@ struct ShiftScalars {
     int iteration[kShiftMaxK], status[kShiftMaxK];
 };
 
+// What the mixed-precision loop (SolveMixed, kernels_mixed.hip) keeps next to CgScalars.  The live fields are written by the first workgroup
+// of the x/p pass or of the restart pass; the r pass freezes what the passes behind it read in every workgroup (fMaxrr, fWant, fBroken),
+// as it does with CgScalars' own frozen copies.
+struct MixedScalars {
+    double maxrr, fMaxrr;    // largest r.r since the last reliable update
+    int want, fWant;         // a reliable update is due at the next slot
+    int gate;                // what the update's three launches look at: nonzero = skip (closed by every r pass, opened by the x/p pass of a slot)
+    int updates;             // reliable updates done
+    int fBroken;             // p.Ap of this iteration is not finite and > 0
+    int pad;
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
@@ -174,6 +186,11 @@ struct Workspace {
     // entry of the upper triangle of an 8 x 8 Gram matrix, and the loop's small matrices
     double* gramPartials = nullptr;
     BkScalars* bkScalars = nullptr;
+    // mixed-precision CG (kernels_mixed.hip), allocated at its first call and grown when a larger system comes: the loop's scalars and the four
+    // fp32 work vectors xs, r32, p32, Ap32, each mixedStride floats from the last (a multiple of 4: every vector starts on a 16-byte boundary)
+    MixedScalars* mixedScalars = nullptr;
+    float* mixedVecs = nullptr;
+    long long mixedStride = 0;
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -182,6 +199,7 @@ struct Workspace {
     bool ensure_block();                         // blockPartials / blockScalars (kernels_block.hip)
     bool ensure_shift();                         // shiftScalars (kernels_shift.hip)
     bool ensure_bkrylov();                       // gramPartials / bkScalars (kernels_bkrylov.hip)
+    bool ensure_mixed(long long n);              // mixedScalars / mixedVecs for n rows (kernels_mixed.hip)
 };
 
 } // namespace mgcg
@@ -513,6 +531,28 @@ bool bk_read_results(Workspace* ws, int k, BkResult* out);
 // (kernels_block.hip: spmv_block_kernel's gather with the Gram epilogue); returns the number of partial sums per entry
 int launch_spmv_block_gram(hipStream_t s, int k, const double* elements, const int* rowOffsets, const int* columnIndeces,
                            const double* S, double* T, long long rows, double* gramPartials, const int* done);
+
+// Mixed-precision CG (SolveMixed; kernels_mixed.hip has the loop and its rounding contract).  e32: the matrix values as floats (MgcgMixedSetup).
+// y = A32 x in fp32, every row summed in stored order (lane = row form) or, for long rows outside dot_order = 1, per lane and then across the
+// lanes of the row; partials != nullptr: the per-workgroup partial sums of sum (double)x_i (double)y_i ride along (returns their count).
+int launch_spmv_float(hipStream_t s, const float* e32, const int* rowOffsets, const int* columnIndeces, const float* x, float* y, long long nnz, long long rows,
+                      double* partials, const int* done);
+void launch_mixed_convert(hipStream_t s, const double* elements, const int* rowOffsets, long long nnz, long long rows, float* e32, int* flags /* device {inexact, bad, first bad row} */);
+struct MixedRun {
+    Workspace* ws;
+    const float* e32; const int* rowOffsets; const int* columnIndeces;
+    long long n, nnz;
+    double* x; double* r;
+    float *xs, *r32, *p32, *Ap32;
+};
+// r32 = (float)r, p32 = r32, xs = 0 and the scalars in front of iteration 0 from the nPartials partial sums of r.r in ws->partials
+void mixed_enqueue_start(const MixedRun& R, const FinalizeArgs& f, int nPartials);
+// the three launches of one iteration (five under dot_order = 1)
+bool mixed_enqueue_iteration(const MixedRun& R, const FinalizeArgs& f);
+// the first and the last launch of a reliable update; the fp64 residual product goes between them, gated on mixed_gate(R)
+void mixed_enqueue_fold(const MixedRun& R);
+void mixed_enqueue_restart(const MixedRun& R, const FinalizeArgs& f, int nPartials);
+inline const int* mixed_gate(const MixedRun& R) { return &R.ws->mixedScalars->gate; }
 
 // dinv_i = 1 / a_ii for the Jacobi-preconditioned loop
 void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,

@@ -1094,6 +1094,67 @@ static int cg_solve_shifted(CgRun& R, double* ps, int k, const double* shifts, i
     return ok ? worst : MGCG_ERROR;
 }
 
+// ---------------------------------------------------------------- mixed-precision CG (SolveMixed)
+// An fp32 CG recurrence corrected by fp64 reliable updates (kernels_mixed.hip has the loop and its kernels).  The host's side is cg_drive:
+// an iteration is three launches, and behind every fourth iteration the three launches of an update are enqueued whether or not the device
+// will want one -- they look at a device gate and return at their first instruction when it is closed, so the host decides nothing and the
+// pipeline never drains.  The period is compiled in (kMixedUpdateEvery), not a knob: no knob may change a result.  The matrix is read as
+// plain CSR in both precisions, so no compressed form, no placement draw and no deferred x update.
+constexpr int kMixedUpdateEvery = 4;
+static int cg_solve_mixed(CgRun& R, const float* e32, int* iteration, double* residual, int* reliableUpdates, double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    // everything the call allocates, before anything is enqueued
+    if (!ws->ensure_mixed(n)) return MGCG_ERROR;
+    const int devTraceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
+    if (devTraceCap && !ws->ensure_trace(devTraceCap)) return MGCG_ERROR;
+    if (R.elementsCount >= 8) R.cfg.periodRows = spmv_period(R.cusparse, R.rowOffsets, R.columnIndeces, n, 0, &R.cfg.maxRow);
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    f.trace = devTraceCap ? ws->trace : nullptr; f.traceCap = devTraceCap;
+    MixedRun M{};
+    M.ws = ws; M.e32 = e32; M.rowOffsets = R.rowOffsets; M.columnIndeces = R.columnIndeces; M.n = n; M.nnz = R.elementsCount; M.x = R.x; M.r = R.r;
+    M.xs = ws->mixedVecs; M.r32 = M.xs + ws->mixedStride; M.p32 = M.r32 + ws->mixedStride; M.Ap32 = M.p32 + ws->mixedStride;
+    const bool refDots = dot_reference_order();
+    // r = b - A x and the partial sums of r.r: the fp64 product of the start and of every update (gate: a device int, nonzero = skip)
+    auto residual_product = [&](const int* gate) {
+        SpmvArgs a = cg_spmv_args(R, R.x, R.r);
+        a.b = R.b; a.partials = ws->partials; a.doneFlag = gate;
+        int nP = launch_spmv_auto(s, EPI_RESIDUAL_DOT, a, R.cfg, nullptr);
+        if (refDots) { launch_dot_serial(s, R.r, R.r, n, ws->partials, gate); nP = 1; }
+        return nP;
+    };
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
+    mixed_enqueue_start(M, f, residual_product(nullptr));
+    bool ok = MGCG_HIP(hipGetLastError());
+    long long hostIt = 0;
+    ok = ok && cg_drive(R, "SolveMixed", [&] {
+        if (!mixed_enqueue_iteration(M, f)) return false;
+        if (++hostIt % kMixedUpdateEvery == 0) {                                         // behind iterations 3, 7, 11, ...: the device's it % 4 == 3
+            mixed_enqueue_fold(M);
+            mixed_enqueue_restart(M, f, residual_product(mixed_gate(M)));
+        }
+        return MGCG_HIP(hipGetLastError());
+    });
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    HostMirror* m = ws->mirror;
+    const int status = m->status;
+    if (iteration) *iteration = m->iteration;
+    if (residual) *residual = m->residual;
+    MixedScalars h{};
+    ok = MGCG_HIP(hipMemcpy(&h, ws->mixedScalars, sizeof(h), hipMemcpyDeviceToHost));
+    if (ok && reliableUpdates) *reliableUpdates = h.updates;
+    if (ok && devTraceCap) {
+        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
+        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
+    }
+    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveMixed: did not converge: iteration %d exceeded maxIteration %d (true residual %g)", m->iteration, R.maxIt, m->residual);
+    if (status == MGCG_NONFINITE) set_error("SolveMixed: stopped at iteration %d: p.Ap is not finite and > 0, or the residual is not finite or beyond the fp32 range", m->iteration);
+    return ok ? status : MGCG_ERROR;
+}
+
 // ---------------------------------------------------------------- shared-subspace block CG (SolveBlockKrylov)
 // k right-hand sides in one block Krylov space (kernels_bkrylov.hip has the method and the kernels).  The matrix is read as plain CSR by the
 // block product, so no matrix set-up, no placement draw and no deferred x update; the host's side is cg_drive.  R.p, R.r and R.Ap hold S, Q, T.
@@ -1267,6 +1328,40 @@ int SolveShifted(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
         analysis_note_write(R.x, sizeof(double) * (size_t)kn);
         analysis_note_write(shiftedPVector->data, sizeof(double) * (size_t)kn);
         st = cg_solve_shifted(R, shiftedPVector->data, k, shifts, iteration, residual, status, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveMixed(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+               Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+               Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* elements32Vector,
+               int elementsCount, int count,
+               double allowableResidual, int minIteration, int maxIteration, int rule,
+               int* iteration, double* residual, int* reliableUpdates, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    // what needs no device is refused before one is asked for; nothing is enqueued for a call that fails here or in cg_call's checks
+    if (!cublas || !cusparse || !elements32Vector) { set_error("SolveMixed: null handle"); return MGCG_ERROR; }
+    if (rule == MGCG_RULE_HANDMADECL) {
+        set_error("SolveMixed: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the fp32 recurrence carries no max|r|");
+        return MGCG_ERROR;
+    }
+    if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) { set_error("SolveMixed: unknown stop rule %d", rule); return MGCG_ERROR; }
+    if (count < 1 || elementsCount < 0) { set_error("SolveMixed: bad sizes"); return MGCG_ERROR; }
+    if (elements32Vector->size < ((long long)elementsCount + 1) / 2) {
+        set_error("SolveMixed: the elements32 vector holds %lld doubles, the %d floats of MgcgMixedSetup need %lld", elements32Vector->size, elementsCount,
+                  ((long long)elementsCount + 1) / 2);
+        return MGCG_ERROR;
+    }
+    if (!device_state()) return MGCG_ERROR;
+    const CgCall c = { "SolveMixed", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, count, 0, elementsCount, 0, count - 1 };
+    int st = MGCG_ERROR;
+    cg_call(c, true, no_more_checks, [&](CgRun& R) {
+        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        analysis_note_write(R.x, sizeof(double) * (size_t)count);
+        analysis_note_write(R.r, sizeof(double) * (size_t)count);
+        st = cg_solve_mixed(R, (const float*)elements32Vector->data, iteration, residual, reliableUpdates, residualTrace, traceCapacity);
     });
     return st;
 }

@@ -577,6 +577,65 @@ int SolveBlockKrylov(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDe
                      double allowableResidual, int minIteration, int maxIteration, int rule,
                      int* iteration, double residual[], int status[], double residualTrace[], int traceCapacity);
 
+/* ---- Mixed-precision CG: an fp32 recurrence corrected by fp64 reliable updates (one rank, no preconditioner, plain CSR) ---- */
+/* The CG loop is bound by memory traffic, and an fp32 iteration moves 100 bytes per row of a 7-point matrix where the fp64 one moves 168.
+ * SolveMixed runs the recurrence in fp32 and, every few iterations, recomputes the true residual b - A x in fp64 from the fp64 matrix and
+ * folds the fp32 partial solution into the fp64 iterate (Sleijpen / van der Vorst reliable updates).  The search direction is kept across
+ * an update: the Krylov recurrence is not restarted.  The caller gets an fp64-accurate x and a stop test on a true fp64 residual.
+ *
+ * MgcgMixedSetup writes (float)a for each of the elementsCount stored values into elements32Vector: a caller-owned double Vector of at
+ * least (elementsCount + 1) / 2 entries, read as floats by SolveMixed (as dinvVector is MgcgJacobiSetup's).  *exact (may be NULL) is 1
+ * when every value converted without rounding, as the Poisson stencils' do.  A value that is not finite as a float (beyond 3.4e38, an
+ * infinity or a NaN) makes the call fail: it returns -1, MgcgGetLastError names the first row that holds one, and the vector must not be
+ * handed to a solve.  The check runs on the device and is read back once.  Returns 0 on success. */
+int MgcgMixedSetup(MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                   int elementsCount, int count, Vector* elements32Vector, int* exact);
+/* y = A32 x in fp32 on raw device pointers (what CsrMVBlock is to the block product): the product of SolveMixed's iteration, without its
+ * p.Ap epilogue.  Every product is rounded to float, never fused with the add.  Up to a mean row length of 20 a row is summed in stored order
+ * from +0.0f (bit-exact in every mode); longer rows are summed by 8, 16 or 32 lanes (lane l adds entries l, l + L, ... and the lanes'
+ * sums meet in a tree), or in stored order under dot_order = 1. */
+void CsrMVFloat(MgcgSparse* cusparse, MgcgMatDescr* matDescr, float* y, const float* elements32, const int* rowOffsets,
+                const int* columnIndeces, const float* x, int elementsCount, int count);
+/* SolveEx's arguments plus elements32Vector (what MgcgMixedSetup wrote) and *reliableUpdates (may be NULL: the number of updates done).
+ * xVector: fp64, the initial guess and the result (MGCG_RULE_SIMPLE starts from 0).  rVector receives the last true fp64 residual.
+ * ApVector and pVector are accepted for the class surface's sake and not touched.  The fp32 work vectors xs, r32, p32, Ap32 are the
+ * library's, on the handle's workspace, allocated before anything is enqueued.
+ * Operation order -- every product is rounded in its own format before the add that follows it, nothing is fused into an FMA:
+ *   start       r = b - A x in fp64 (SolveEx's residual product) ; rr0 = rr = maxrr = r.r ; r32 = (float)r ; p32 = r32 ; xs = 0 ; want = 0
+ *   iteration it
+ *     Ap32 = A32 p32        products rounded to float, a row summed in float (CsrMVFloat)
+ *     pAp = sum_i (double)p32_i * (double)Ap32_i                the terms are exact in fp64
+ *     alpha = rr / pAp in fp64 ; alpha32 = (float)alpha
+ *     xs = xs + (alpha32 * p32) ; r32 = r32 + ((-alpha32) * Ap32)                    in float
+ *     rn = sum_i (double)r32_i * (double)r32_i ; maxrr = max(maxrr, rn)
+ *     want rises when rn < 0.01 * maxrr, or when the stop rule (below) would end the loop on rn: converged, or the iteration limit
+ *   update slot -- only in iterations with it % 4 == 3, and only when want is up:
+ *     x = x + (double)xs ; xs = 0 ; r = b - A x with the fp64 matrix ; rn = r.r in fp64 ; r32 = (float)r ; maxrr = rn ;
+ *     *reliableUpdates + 1 ; want = 0 ; THE STOP RULE IS DECIDED HERE AND ONLY HERE, SolveEx's rule on the true rn
+ *   end         beta = rn / rr in fp64 ; beta32 = (float)beta ; p32 = r32 + (beta32 * p32) ; rr = rn
+ * The period 4 and the drop 0.01 (delta = 0.1) are compiled in; no knob changes a result.  In the default mode a sum is a tree sum of
+ * per-workgroup partial sums in a fixed order (the same bits on every run); under dot_order = 1 pAp, rn and the update's r.r are serial
+ * left-to-right sums and the whole loop is a fixed sequence of IEEE operations (tests/test_mixed_host.py has it in numpy).
+ * Stop rules: the four 2-norm rules of SolveEx, on (rn, rr0) of an update with that iteration's counter.  *iteration, *residual, the
+ * returned status and the trace entry of an iteration with an update are therefore always those of a true fp64 residual; an iteration
+ * without one records the recurrence's sqrt(rn) in the trace (sqrt(rn / rr0) under MGCG_RULE_VIENNACL).  Since only every fourth
+ * iteration can stop the loop, *iteration may lie up to 3 beyond the first iteration at which SolveEx's test would have passed, and
+ * MGCG_MAXIT_EXCEEDED is reported at the first slot behind maxIteration.
+ * MGCG_NONFINITE: p.Ap <= 0 or not finite (the matrix is not positive definite, or the residual is 0), or an alpha32 that is not finite
+ * (a p.Ap so small that alpha leaves the fp32 range), ends the loop in that iteration,
+ * before its updates -- x keeps its last folded iterate, r the last true residual, and *residual is the recurrence's; a true residual
+ * that is not finite, or whose 2-norm is not below 3.4028e38, the range in which every (float)r_i is finite, ends it in its update (the
+ * residual is not scaled before conversion).
+ * MGCG_ERROR with a message, and nothing enqueued, for MGCG_RULE_HANDMADECL (the recurrence carries no max|r|), an unknown rule, a null
+ * handle or a vector that is too small, elements32Vector included.  Out of scope: several ranks, preconditioners, the compressed matrix
+ * forms (the matrix is read as plain CSR in both precisions, whatever the handle's compression mode), x_defer and the placement draw. */
+int SolveMixed(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+               Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+               Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* elements32Vector,
+               int elementsCount, int count,
+               double allowableResidual, int minIteration, int maxIteration, int rule,
+               int* iteration, double* residual, int* reliableUpdates, double* residualTrace, int traceCapacity);
+
 /* Fixed number of CG iterations with no stop test and no host synchronisation inside (bench.py's
  * "steps"): runs `steps` more iterations of the recurrence held in x,r,p (call with restart != 0 first
  * to compute r = b - A x, p = r, rr).  comm may be NULL.  Returns the residual after the last step. */
