@@ -11,6 +11,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // Only the C ABI is exported from the shared object (-fvisibility=hidden for everything else).
@@ -37,6 +38,23 @@ constexpr int kPbTileShift = 14;     // propagation-blocking form (class 5, kern
 constexpr int kPbTileWidth = 1 << kPbTileShift;
 constexpr int kPbMaxTiles = 1024;    // ... at most this many (16.7 M columns: pass 2 holds a block's piece table in LDS) ...
 constexpr int kPbRoundCap = 9088;    // ... and rounds of this many entries of a row block (71 KB of LDS in pass 2)
+
+// fn(K) with the run-time column count k of 1 .. 8 as a compile-time constant (K.value).  The callers have checked the range; anything else takes 8.
+template <typename Fn>
+inline auto dispatch_k(int k, Fn fn)
+{
+    static_assert(kBlockMaxK == 8 && kShiftMaxK == 8, "one instantiation per column count");
+    switch (k) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 5: return fn(std::integral_constant<int, 5>{});
+    case 6: return fn(std::integral_constant<int, 6>{});
+    case 7: return fn(std::integral_constant<int, 7>{});
+    default: return fn(std::integral_constant<int, 8>{});
+    }
+}
 
 // ---------------------------------------------------------------- errors
 void set_error(const char* fmt, ...);
@@ -512,6 +530,22 @@ void launch_ring_copy_back(hipStream_t s, const CgScalars* sc, const RingArgs& g
 // f.trace: k traces of f.traceCap entries.
 void launch_update_shifted(hipStream_t s, int k, const FinalizeArgs& f, ShiftScalars* sh, const double* partials, const double* partialsInf, int nPartials,
                            double* x, double* p, const double* r, double* ps, long long n);
+
+// Block CG (SolveBlockEx; kernels_block.hip has the layout and the kernels).  x, b and r column-major, column j at j * n; p and Ap the row-interleaved
+// work blocks.  The loop's stop flag is its own (block_enqueue_snapshot copies it into a pinned int): block_enqueue_start clears it, and every kernel
+// of the loop returns at once when it is up.  block_enqueue_start: with MGCG_RULE_SIMPLE x = 0; r = b - A x, p = r and the per-column scalars.  block_enqueue_iteration: the five
+// launches of one iteration (seven under dot_order = 1); f carries the stop rule and k traces of f.traceCap entries.
+struct BlockRun {
+    Workspace* ws;
+    const double* elements; const int* rowOffsets; const int* columnIndeces;
+    long long n; int k; int rule;
+    double* x; const double* b; double *Ap, *p, *r;
+};
+struct BlockResult { int iteration[kBlockMaxK]; double residual[kBlockMaxK]; int status[kBlockMaxK]; };
+bool block_enqueue_start(const BlockRun& R);
+bool block_enqueue_iteration(const BlockRun& R, const FinalizeArgs& f);
+bool block_read_results(Workspace* ws, BlockResult* out);
+void block_enqueue_snapshot(Workspace* ws, volatile int* slot);
 
 // Shared-subspace block CG (SolveBlockKrylov; kernels_bkrylov.hip has the method).  X and B column-major, column j at j * n; S, Q and T the
 // row-interleaved work blocks.  The loop's stop flag is ws->scalars->done: bk_enqueue_start expects it cleared, and every kernel of the loop

@@ -483,14 +483,8 @@ static bool bk_enqueue_iteration_k(const BkRun& R, const FinalizeArgs& f)
     return MGCG_HIP(hipGetLastError());
 }
 
-#define BK_DISPATCH(fn, ...) \
-    switch (R.k) { \
-    case 1: return fn<1>(__VA_ARGS__); case 2: return fn<2>(__VA_ARGS__); case 3: return fn<3>(__VA_ARGS__); case 4: return fn<4>(__VA_ARGS__); \
-    case 5: return fn<5>(__VA_ARGS__); case 6: return fn<6>(__VA_ARGS__); case 7: return fn<7>(__VA_ARGS__); default: return fn<8>(__VA_ARGS__); }
-
-bool bk_enqueue_start(const BkRun& R) { static_assert(kBlockMaxK == 8, "one instantiation per column count"); BK_DISPATCH(bk_enqueue_start_k, R) }
-bool bk_enqueue_iteration(const BkRun& R, const FinalizeArgs& f) { BK_DISPATCH(bk_enqueue_iteration_k, R, f) }
-#undef BK_DISPATCH
+bool bk_enqueue_start(const BkRun& R) { return dispatch_k(R.k, [&](auto K) { return bk_enqueue_start_k<K.value>(R); }); }
+bool bk_enqueue_iteration(const BkRun& R, const FinalizeArgs& f) { return dispatch_k(R.k, [&](auto K) { return bk_enqueue_iteration_k<K.value>(R, f); }); }
 
 bool bk_read_results(Workspace* ws, int k, BkResult* out)
 {

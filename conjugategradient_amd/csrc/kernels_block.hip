@@ -276,17 +276,8 @@ int launch_spmv_block_gram(hipStream_t s, int k, const double* elements, const i
     BlockSpmvArgs a{};
     a.elements = elements; a.rowOffsets = rowOffsets; a.columnIndeces = columnIndeces;
     a.x = S; a.y = T; a.ld = rows; a.rows = (int)rows; a.partials = gramPartials; a.done = done;
-    const bool nt = rows >= 8000000;                   // (block_solve's rule)
-    switch (k) {
-    case 1: return spmv_block_gram<1>(s, a, nt);
-    case 2: return spmv_block_gram<2>(s, a, nt);
-    case 3: return spmv_block_gram<3>(s, a, nt);
-    case 4: return spmv_block_gram<4>(s, a, nt);
-    case 5: return spmv_block_gram<5>(s, a, nt);
-    case 6: return spmv_block_gram<6>(s, a, nt);
-    case 7: return spmv_block_gram<7>(s, a, nt);
-    default: return spmv_block_gram<8>(s, a, nt);
-    }
+    const bool nt = rows >= 8000000;                   // (the block loop's rule: block_nt)
+    return dispatch_k(k, [&](auto K) { return spmv_block_gram<K.value>(s, a, nt); });
 }
 
 // ------------------------------------------------------------------ vector passes
@@ -475,17 +466,11 @@ __global__ __launch_bounds__(kBlock) void block_finalize_kernel(BlockScalars* sc
 
 __global__ void block_snapshot_kernel(const BlockScalars* sc, volatile int* slot) { *slot = sc->done; }
 
-// ------------------------------------------------------------------ the loop
-struct BlockRun {
-    Workspace* ws;
-    const double* elements; const int* rowOffsets; const int* columnIndeces; int nnz;
-    long long n;
-    double *x; const double* b; double *Ap, *p, *r;
-    double tol; int minIt, maxIt, rule;
-};
+// ------------------------------------------------------------------ the loop's launches (its host side is cg_solve_block, solver.hip)
+static bool block_nt(const BlockRun& R) { return R.n >= 8000000; }   // the streaming hints of the CG loop's passes (vectors and matrix far beyond the caches)
 
 template <int K>
-static bool block_enqueue_init(const BlockRun& R, bool nt)
+static bool block_enqueue_start_k(const BlockRun& R)
 {
     hipStream_t s = R.ws->stream;
     double* P0 = R.ws->blockPartials;
@@ -493,7 +478,7 @@ static bool block_enqueue_init(const BlockRun& R, bool nt)
     BlockSpmvArgs a{};
     a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces;
     a.x = R.x; a.y = R.r; a.b = R.b; a.ld = R.n; a.rows = (int)R.n;
-    (void)launch_spmv_block<K>(s, BEPI_RESIDUAL, a, nt);                                   // r_j = b_j - A x_j
+    (void)launch_spmv_block<K>(s, BEPI_RESIDUAL, a, block_nt(R));                          // r_j = b_j - A x_j
     const int g = vec_grid(R.n);
     hipLaunchKernelGGL((block_copy_dot_kernel<K>), dim3(g), dim3(kBlock), 0, s, R.p, R.r, R.n, P0);   // p = r ; r.r
     int nP = g;
@@ -506,7 +491,7 @@ static bool block_enqueue_init(const BlockRun& R, bool nt)
 }
 
 template <int K>
-static bool block_enqueue_iteration(const BlockRun& R, bool nt, const FinalizeArgs& f)
+static bool block_enqueue_iteration_k(const BlockRun& R, const FinalizeArgs& f)
 {
     hipStream_t s = R.ws->stream;
     BlockScalars* sc = R.ws->blockScalars;
@@ -515,6 +500,7 @@ static bool block_enqueue_iteration(const BlockRun& R, bool nt, const FinalizeAr
     double* P2 = P1 + (size_t)kBlockMaxK * kMaxPartials;
     const bool ref = dot_reference_order();
     const bool inf = R.rule == MGCG_RULE_HANDMADECL;
+    const bool nt = block_nt(R);
     BlockSpmvArgs a{};
     a.elements = R.elements; a.rowOffsets = R.rowOffsets; a.columnIndeces = R.columnIndeces;
     a.x = R.p; a.y = R.Ap; a.ld = R.n; a.rows = (int)R.n; a.partials = P0; a.done = &sc->done;
@@ -534,67 +520,16 @@ static bool block_enqueue_iteration(const BlockRun& R, bool nt, const FinalizeAr
     return MGCG_HIP(hipGetLastError());
 }
 
-template <int K>
-static int block_solve(BlockRun& R, int iteration[], double residual[], int status[], double residualTrace[], int traceCapacity)
+bool block_enqueue_start(const BlockRun& R) { return dispatch_k(R.k, [&](auto K) { return block_enqueue_start_k<K.value>(R); }); }
+bool block_enqueue_iteration(const BlockRun& R, const FinalizeArgs& f) { return dispatch_k(R.k, [&](auto K) { return block_enqueue_iteration_k<K.value>(R, f); }); }
+void block_enqueue_snapshot(Workspace* ws, volatile int* slot) { hipLaunchKernelGGL(block_snapshot_kernel, dim3(1), dim3(1), 0, ws->stream, (const BlockScalars*)ws->blockScalars, slot); }
+
+bool block_read_results(Workspace* ws, BlockResult* out)
 {
-    Workspace* ws = R.ws;
-    hipStream_t s = ws->stream;
-    if (!ws->ensure_block()) return MGCG_ERROR;
-    const int devTraceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
-    if (devTraceCap && !ws->ensure_trace(K * devTraceCap)) return MGCG_ERROR;
-    const bool nt = R.n >= 8000000;                   // the streaming hints of the CG loop's passes (vectors and matrix far beyond the caches)
-    FinalizeArgs f{};
-    f.trace = devTraceCap ? ws->trace : nullptr; f.traceCap = devTraceCap;
-    f.tol = R.tol; f.minIt = R.minIt; f.maxIt = R.maxIt; f.rule = R.rule;
-    int checkEvery = 4;
-    { const int v = tuning().checkEvery.load(std::memory_order_relaxed); if (v >= 1) checkEvery = v; }
-    const long long hostCap = (long long)(R.maxIt > R.minIt ? R.maxIt : R.minIt) + 4;
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    volatile int* slots = (volatile int*)&ws->hostScalar[2];
-    bool ok = MGCG_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming)) && MGCG_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-    for (int i = 0; i < 4; ++i) slots[i] = 0;
-    ok = ok && block_enqueue_init<K>(R, nt);
-    long long enqueued = 0;
-    int chunk = 0;
-    bool finished = false;
-    while (ok && !finished) {                          // cg_solve's schedule: look at the chunk before the one just enqueued
-        for (int i = 0; ok && i < checkEvery; ++i) ok = block_enqueue_iteration<K>(R, nt, f);
-        enqueued += checkEvery;
-        hipLaunchKernelGGL(block_snapshot_kernel, dim3(1), dim3(1), 0, s, (const BlockScalars*)ws->blockScalars, &slots[chunk & 1]);
-        ok = ok && MGCG_HIP(hipEventRecord(ev[chunk & 1], s));
-        if (chunk > 0) {
-            ok = ok && MGCG_HIP(hipEventSynchronize(ev[(chunk - 1) & 1]));
-            if (ok && slots[(chunk - 1) & 1] != 0) finished = true;
-        }
-        if (!finished && enqueued > hostCap + 2LL * checkEvery) {
-            ok = ok && MGCG_HIP(hipStreamSynchronize(s));
-            if (ok && slots[chunk & 1] != 0) finished = true;
-            else { set_error("SolveBlockEx: the device never raised its stop flag after %lld iterations", enqueued); ok = false; }
-        }
-        ++chunk;
-    }
-    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    int worst = MGCG_OK;
-    if (ok) {
-        BlockScalars h;
-        ok = MGCG_HIP(hipMemcpy(&h, ws->blockScalars, sizeof(BlockScalars), hipMemcpyDeviceToHost));
-        for (int j = 0; ok && j < K; ++j) {
-            if (iteration) iteration[j] = h.iteration[j];
-            if (residual) residual[j] = h.residual[j];
-            if (status) status[j] = h.status[j];
-            if (h.status[j] == MGCG_NONFINITE) worst = MGCG_NONFINITE;
-            else if (h.status[j] == MGCG_MAXIT_EXCEEDED && worst == MGCG_OK) worst = MGCG_MAXIT_EXCEEDED;
-            if (devTraceCap) {
-                int nTrace = h.iteration[j] + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-                ok = MGCG_HIP(hipMemcpy(residualTrace + (size_t)j * traceCapacity, ws->trace + (size_t)j * devTraceCap, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-            }
-        }
-        if (ok && worst == MGCG_NONFINITE) set_error("SolveBlockEx: the residual of a column is not finite");
-        else if (ok && worst == MGCG_MAXIT_EXCEEDED) set_error("SolveBlockEx: a column did not converge within maxIteration %d", R.maxIt);
-    }
-    if (ev[0]) (void)hipEventDestroy(ev[0]);
-    if (ev[1]) (void)hipEventDestroy(ev[1]);
-    return ok ? worst : MGCG_ERROR;
+    BlockScalars h;
+    if (!MGCG_HIP(hipMemcpy(&h, ws->blockScalars, sizeof(h), hipMemcpyDeviceToHost))) return false;
+    memcpy(out->iteration, h.iteration, sizeof(h.iteration)); memcpy(out->residual, h.residual, sizeof(h.residual)); memcpy(out->status, h.status, sizeof(h.status));
+    return true;
 }
 
 template <int K>
@@ -614,50 +549,6 @@ using namespace mgcg;
 
 extern "C" {
 
-int SolveBlockEx(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
-                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
-                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
-                 int elementsCount, int count, int k,
-                 double allowableResidual, int minIteration, int maxIteration, int rule,
-                 int iteration[], double residual[], int status[], double residualTrace[], int traceCapacity)
-{
-    (void)matDescr;
-    if (!device_state()) return MGCG_ERROR;
-    if (!cublas || !cusparse) { set_error("SolveBlockEx: null handle"); return MGCG_ERROR; }
-    if (k < 1 || k > kBlockMaxK) { set_error("SolveBlockEx: k = %d right-hand sides, must be 1 .. %d", k, kBlockMaxK); return MGCG_ERROR; }
-    if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) { set_error("SolveBlockEx: unknown stop rule %d", rule); return MGCG_ERROR; }
-    Vector* vs[6] = { elementsVector, xVector, bVector, ApVector, pVector, rVector };
-    for (Vector* v : vs) if (!v) { set_error("SolveBlockEx: null vector handle"); return MGCG_ERROR; }
-    if (!rowOffsetsVector || !columnIndecesVector) { set_error("SolveBlockEx: null vector handle"); return MGCG_ERROR; }
-    if (elementsCount < 0 || count < 1) { set_error("SolveBlockEx: bad sizes"); return MGCG_ERROR; }
-    const long long kn = (long long)k * count;
-    if (elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount || rowOffsetsVector->size < (long long)count + 1 ||
-        xVector->size < kn || bVector->size < kn || ApVector->size < kn || pVector->size < kn || rVector->size < kn) {
-        set_error("SolveBlockEx: a device vector is smaller than the problem (x, b, Ap, p, r need k * count entries)"); return MGCG_ERROR;
-    }
-    if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) { set_error("SolveBlockEx: trace capacity too large"); return MGCG_ERROR; }
-    BlockRun R{};
-    R.ws = &cublas->ws;
-    R.elements = elementsVector->data; R.rowOffsets = rowOffsetsVector->data; R.columnIndeces = columnIndecesVector->data; R.nnz = elementsCount;
-    R.n = count;
-    R.x = xVector->data; R.b = bVector->data; R.Ap = ApVector->data; R.p = pVector->data; R.r = rVector->data;
-    R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
-    analysis_note_write(R.x, sizeof(double) * (size_t)kn);
-    analysis_note_write(R.r, sizeof(double) * (size_t)kn);
-    analysis_note_write(R.p, sizeof(double) * (size_t)kn);
-    analysis_note_write(R.Ap, sizeof(double) * (size_t)kn);
-    switch (k) {
-    case 1: return block_solve<1>(R, iteration, residual, status, residualTrace, traceCapacity);
-    case 2: return block_solve<2>(R, iteration, residual, status, residualTrace, traceCapacity);
-    case 3: return block_solve<3>(R, iteration, residual, status, residualTrace, traceCapacity);
-    case 4: return block_solve<4>(R, iteration, residual, status, residualTrace, traceCapacity);
-    case 5: return block_solve<5>(R, iteration, residual, status, residualTrace, traceCapacity);
-    case 6: return block_solve<6>(R, iteration, residual, status, residualTrace, traceCapacity);
-    case 7: return block_solve<7>(R, iteration, residual, status, residualTrace, traceCapacity);
-    default: return block_solve<8>(R, iteration, residual, status, residualTrace, traceCapacity);
-    }
-}
-
 void CsrMVBlock(MgcgSparse* cusparse, MgcgMatDescr* matDescr, double* y, const double* elements, const int* rowOffsets,
                 const int* columnIndeces, const double* x, int elementsCount, int count, int k)
 {
@@ -669,16 +560,7 @@ void CsrMVBlock(MgcgSparse* cusparse, MgcgMatDescr* matDescr, double* y, const d
     if (count == 0) return;
     analysis_note_write(y, sizeof(double) * (size_t)k * (size_t)count);
     hipStream_t s = cusparse->ws.stream;
-    switch (k) {
-    case 1: csrmv_block<1>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    case 2: csrmv_block<2>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    case 3: csrmv_block<3>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    case 4: csrmv_block<4>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    case 5: csrmv_block<5>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    case 6: csrmv_block<6>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    case 7: csrmv_block<7>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    default: csrmv_block<8>(s, y, elements, rowOffsets, columnIndeces, x, count); break;
-    }
+    dispatch_k(k, [&](auto K) { csrmv_block<K.value>(s, y, elements, rowOffsets, columnIndeces, x, count); });
     (void)MGCG_HIP(hipGetLastError());
 }
 

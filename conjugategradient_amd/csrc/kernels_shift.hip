@@ -194,17 +194,7 @@ void launch_update_shifted(hipStream_t s, int k, const FinalizeArgs& f, ShiftSca
                            double* x, double* p, const double* r, double* ps, long long n)
 {
     if (n <= 0) return;
-    static_assert(kShiftMaxK == 8, "one instantiation per column count");
-    switch (k) {
-    case 1: launch_update_shifted_k<1>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    case 2: launch_update_shifted_k<2>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    case 3: launch_update_shifted_k<3>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    case 4: launch_update_shifted_k<4>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    case 5: launch_update_shifted_k<5>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    case 6: launch_update_shifted_k<6>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    case 7: launch_update_shifted_k<7>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    default: launch_update_shifted_k<8>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); break;
-    }
+    dispatch_k(k, [&](auto K) { launch_update_shifted_k<K.value>(s, f, sh, partials, partialsInf, nPartials, x, p, r, ps, n); });
 }
 
 void preload_kernels_shift() { preload_code_object(reinterpret_cast<const void*>(&update_shifted_kernel<1, false, false>)); }

@@ -955,8 +955,9 @@ static bool cg_enqueue_iteration(CgRun& R, bool withStopTest)
 // The host's side of a device-resident loop.  It enqueues checkEvery iterations, a snapshot of the device's stop flag and an event, and then
 // looks at the snapshot of the chunk BEFORE the one just enqueued, so that the device never waits for the host.  A loop whose flag has not
 // risen a little beyond max(minIt, maxIt) iterations is an error (who names the loop in the message).  The stream is not drained here.
-template <typename Enqueue>
-static bool cg_drive(CgRun& R, const char* who, Enqueue enqueueIteration, long long* enqueuedOut = nullptr)
+// snapshot(slot) enqueues the launch that copies the loop's device stop flag into the pinned int *slot.
+template <typename Enqueue, typename Snapshot>
+static bool cg_drive_on(CgRun& R, const char* who, Enqueue enqueueIteration, Snapshot snapshot, long long* enqueuedOut = nullptr)
 {
     hipStream_t s = R.ws->stream;
     int checkEvery = 4;
@@ -972,7 +973,7 @@ static bool cg_drive(CgRun& R, const char* who, Enqueue enqueueIteration, long l
     while (ok && !finished) {
         for (int k = 0; ok && k < checkEvery; ++k) ok = enqueueIteration();
         enqueued += checkEvery;
-        hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(1), 0, s, R.ws->scalars, R.ws->mirror, &slots[chunk & 1]);
+        snapshot(&slots[chunk & 1]);
         ok = ok && MGCG_HIP(hipEventRecord(ev[chunk & 1], s));
         if (chunk > 0) {                                  // look at the chunk BEFORE the one just enqueued
             ok = ok && MGCG_HIP(hipEventSynchronize(ev[(chunk - 1) & 1]));
@@ -989,6 +990,14 @@ static bool cg_drive(CgRun& R, const char* who, Enqueue enqueueIteration, long l
     if (ev[1]) (void)hipEventDestroy(ev[1]);
     if (enqueuedOut) *enqueuedOut = enqueued;
     return ok;
+}
+// The loops whose stop flag is CgScalars::done: their snapshot also mirrors the residual.
+template <typename Enqueue>
+static bool cg_drive(CgRun& R, const char* who, Enqueue enqueueIteration, long long* enqueuedOut = nullptr)
+{
+    return cg_drive_on(R, who, enqueueIteration, [&](volatile int* slot) {
+        hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(1), 0, R.ws->stream, R.ws->scalars, R.ws->mirror, slot);
+    }, enqueuedOut);
 }
 
 static int cg_solve(CgRun& R, int* iteration, double* residual, double* residualTrace, int traceCapacity)
@@ -1037,6 +1046,42 @@ static int cg_solve(CgRun& R, int* iteration, double* residual, double* residual
     return ok ? status : MGCG_ERROR;
 }
 
+// ---------------------------------------------------------------- what the variant loops share
+// The device trace of a loop of k columns, each of the caller's capacity: room on the workspace, and f told where it is.  f.traceCap is 0 afterwards
+// when the caller wants no trace.
+static bool cg_trace_columns(Workspace* ws, int k, const double* residualTrace, int traceCapacity, FinalizeArgs& f)
+{
+    f.traceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
+    if (f.traceCap && !ws->ensure_trace(k * f.traceCap)) return false;
+    f.trace = f.traceCap ? ws->trace : nullptr;
+    return true;
+}
+
+// What a loop of k columns hands back: column j's iteration (hIteration null: the loop has one count for all), residual and status into the
+// caller's arrays (each may be null), and the first nTrace[j] (null: hIteration[j] + 1) entries of its device trace to residualTrace + j * traceCapacity.
+// Returns the worst status, NONFINITE over MAXIT_EXCEEDED over OK; *ok falls when a copy fails.
+static int cg_return_columns(Workspace* ws, int k, const int hIteration[], const double hResidual[], const int hStatus[], const int nTrace[], int devTraceCap,
+                             int iteration[], double residual[], int status[], double* residualTrace, int traceCapacity, bool* ok)
+{
+    int worst = MGCG_OK;
+    for (int j = 0; *ok && j < k; ++j) {
+        if (iteration && hIteration) iteration[j] = hIteration[j];
+        if (residual) residual[j] = hResidual[j];
+        if (status) status[j] = hStatus[j];
+        if (hStatus[j] == MGCG_NONFINITE) worst = MGCG_NONFINITE;
+        else if (hStatus[j] == MGCG_MAXIT_EXCEEDED && worst == MGCG_OK) worst = MGCG_MAXIT_EXCEEDED;
+        int n = nTrace ? nTrace[j] : hIteration[j] + 1; if (n > devTraceCap) n = devTraceCap;
+        if (n > 0) *ok = MGCG_HIP(hipMemcpy(residualTrace + (size_t)j * traceCapacity, ws->trace + (size_t)j * devTraceCap, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return worst;
+}
+// ... and the message that goes with the worst status (nonfinite: what MGCG_NONFINITE means in this loop)
+static void cg_columns_message(const char* who, int worst, const char* nonfinite, int maxIt)
+{
+    if (worst == MGCG_NONFINITE) set_error("%s: %s", who, nonfinite);
+    else if (worst == MGCG_MAXIT_EXCEEDED) set_error("%s: a column did not converge within maxIteration %d", who, maxIt);
+}
+
 // ---------------------------------------------------------------- multi-shift CG (SolveShifted)
 // One CG recurrence on A serves the k systems (A + sigma_j I) x_j = b (kernels_shift.hip has the method).  An iteration is the plain loop's
 // product and r update followed by the one fused pass launch_update_shifted: three launches, as SolveEx's.  x_j starts from 0, so r = b
@@ -1048,12 +1093,9 @@ static int cg_solve_shifted(CgRun& R, double* ps, int k, const double* shifts, i
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
     R.wantInf = (R.rule == MGCG_RULE_HANDMADECL);
-    if (!ws->ensure_shift()) return MGCG_ERROR;
-    const int devTraceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
-    if (devTraceCap && !ws->ensure_trace(k * devTraceCap)) return MGCG_ERROR;
-    cg_matrix_setup(R);
     FinalizeArgs f = cg_finalize_args(R, true, 0);
-    f.trace = devTraceCap ? ws->trace : nullptr; f.traceCap = devTraceCap;
+    if (!ws->ensure_shift() || !cg_trace_columns(ws, k, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    cg_matrix_setup(R);
 
     ShiftScalars h{};
     for (int j = 0; j < k; ++j) { h.sigma[j] = shifts[j]; h.st[0].zeta[j] = 1.0; h.st[0].zetaPrev[j] = 1.0; h.st[0].live[j] = 1; }
@@ -1076,21 +1118,10 @@ static int cg_solve_shifted(CgRun& R, double* ps, int k, const double* shifts, i
         return MGCG_HIP(hipGetLastError());
     });
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    int worst = MGCG_OK;
     ok = ok && MGCG_HIP(hipMemcpy(&h, ws->shiftScalars, sizeof(h), hipMemcpyDeviceToHost));
-    for (int j = 0; ok && j < k; ++j) {
-        if (iteration) iteration[j] = h.iteration[j];
-        if (residual) residual[j] = h.residual[j];
-        if (status) status[j] = h.status[j];
-        if (h.status[j] == MGCG_NONFINITE) worst = MGCG_NONFINITE;
-        else if (h.status[j] == MGCG_MAXIT_EXCEEDED && worst == MGCG_OK) worst = MGCG_MAXIT_EXCEEDED;
-        if (devTraceCap) {
-            int nTrace = h.iteration[j] + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-            ok = MGCG_HIP(hipMemcpy(residualTrace + (size_t)j * traceCapacity, ws->trace + (size_t)j * devTraceCap, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-        }
-    }
-    if (ok && worst == MGCG_NONFINITE) set_error("SolveShifted: a column broke down (p.Ap <= 0 or a scalar that is not finite)");
-    else if (ok && worst == MGCG_MAXIT_EXCEEDED) set_error("SolveShifted: a column did not converge within maxIteration %d", R.maxIt);
+    if (!ok) return MGCG_ERROR;
+    const int worst = cg_return_columns(ws, k, h.iteration, h.residual, h.status, nullptr, f.traceCap, iteration, residual, status, residualTrace, traceCapacity, &ok);
+    if (ok) cg_columns_message("SolveShifted", worst, "a column broke down (p.Ap <= 0 or a scalar that is not finite)", R.maxIt);
     return ok ? worst : MGCG_ERROR;
 }
 
@@ -1107,12 +1138,10 @@ static int cg_solve_mixed(CgRun& R, const float* e32, int* iteration, double* re
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
     // everything the call allocates, before anything is enqueued
-    if (!ws->ensure_mixed(n)) return MGCG_ERROR;
-    const int devTraceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
-    if (devTraceCap && !ws->ensure_trace(devTraceCap)) return MGCG_ERROR;
-    if (R.elementsCount >= 8) R.cfg.periodRows = spmv_period(R.cusparse, R.rowOffsets, R.columnIndeces, n, 0, &R.cfg.maxRow);
     FinalizeArgs f = cg_finalize_args(R, true, 0);
-    f.trace = devTraceCap ? ws->trace : nullptr; f.traceCap = devTraceCap;
+    if (!ws->ensure_mixed(n) || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    const int devTraceCap = f.traceCap;
+    if (R.elementsCount >= 8) R.cfg.periodRows = spmv_period(R.cusparse, R.rowOffsets, R.columnIndeces, n, 0, &R.cfg.maxRow);
     MixedRun M{};
     M.ws = ws; M.e32 = e32; M.rowOffsets = R.rowOffsets; M.columnIndeces = R.columnIndeces; M.n = n; M.nnz = R.elementsCount; M.x = R.x; M.r = R.r;
     M.xs = ws->mixedVecs; M.r32 = M.xs + ws->mixedStride; M.p32 = M.r32 + ws->mixedStride; M.Ap32 = M.p32 + ws->mixedStride;
@@ -1163,11 +1192,8 @@ static int cg_solve_bkrylov(CgRun& R, int k, int* iteration, double residual[], 
     Workspace* ws = R.ws;
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
-    if (!ws->ensure_bkrylov()) return MGCG_ERROR;
-    const int devTraceCap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
-    if (devTraceCap && !ws->ensure_trace(k * devTraceCap)) return MGCG_ERROR;
     FinalizeArgs f = cg_finalize_args(R, true, 0);
-    f.trace = devTraceCap ? ws->trace : nullptr; f.traceCap = devTraceCap;
+    if (!ws->ensure_bkrylov() || !cg_trace_columns(ws, k, residualTrace, traceCapacity, f)) return MGCG_ERROR;
     const BkRun B = { ws, R.elements, R.rowOffsets, R.columnIndeces, n, k, R.x, R.b, R.p, R.r, R.Ap };
     hipLaunchKernelGGL(clear_done_kernel, dim3(1), dim3(1), 0, s, ws->scalars);
     if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, (long long)k * n);       // SimpleConjugateGradient.cu:53, per column (as SolveBlockEx)
@@ -1177,25 +1203,36 @@ static int cg_solve_bkrylov(CgRun& R, int k, int* iteration, double residual[], 
     BkResult h{};
     ok = ok && bk_read_results(ws, k, &h);
     if (!ok) return MGCG_ERROR;
-    int worst = MGCG_OK;
     if (iteration) *iteration = h.iteration;
-    for (int j = 0; j < k; ++j) {
-        if (residual) residual[j] = h.residual[j];
-        if (status) status[j] = h.status[j];
-        if (h.status[j] == MGCG_NONFINITE) worst = MGCG_NONFINITE;
-        else if (h.status[j] == MGCG_MAXIT_EXCEEDED && worst == MGCG_OK) worst = MGCG_MAXIT_EXCEEDED;
-        if (devTraceCap && h.failWhich != 1) {
-            int nTrace = h.iteration + (h.failWhich ? 0 : 1); if (nTrace > devTraceCap) nTrace = devTraceCap;
-            if (nTrace > 0) ok = MGCG_HIP(hipMemcpy(residualTrace + (size_t)j * traceCapacity, ws->trace + (size_t)j * devTraceCap, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost)) && ok;
-        }
-    }
+    int nTrace[kBlockMaxK];                            // a breakdown leaves no entry for its iteration; one in the first factorisation, none at all
+    for (int j = 0; j < k; ++j) nTrace[j] = h.failWhich == 1 ? 0 : h.iteration + (h.failWhich ? 0 : 1);
+    const int worst = cg_return_columns(ws, k, nullptr, h.residual, h.status, nTrace, f.traceCap, nullptr, residual, status, residualTrace, traceCapacity, &ok);
     if (h.failWhich) {
         static const char* const names[] = { "", "the first factorisation, of R0^T R0 (dependent or zero initial residual columns)", "the factorisation of S^T A S (is the matrix positive definite?)",
                                              "the factorisation of W^T W" };
         set_error("SolveBlockKrylov: breakdown in %s: pivot %d is not finite and > 0 (iteration %d); x keeps the last completed iterate -- fall back to SolveBlockEx",
                   names[h.failWhich], h.failPivot, h.iteration);
-    } else if (worst == MGCG_NONFINITE) set_error("SolveBlockKrylov: the residual of a column is not finite");
-    else if (worst == MGCG_MAXIT_EXCEEDED) set_error("SolveBlockKrylov: a column did not converge within maxIteration %d", R.maxIt);
+    } else cg_columns_message("SolveBlockKrylov", worst, "the residual of a column is not finite", R.maxIt);
+    return ok ? worst : MGCG_ERROR;
+}
+
+// ---------------------------------------------------------------- block CG (SolveBlockEx)
+// k independent CG recurrences that share the matrix pass (kernels_block.hip has the layout and the kernels).  The matrix is read as plain CSR by
+// the block product, so no matrix set-up, no placement draw and no deferred x update; the host's side is cg_drive_on with the snapshot of the loop's own stop flag.
+static int cg_solve_block(CgRun& R, int k, int iteration[], double residual[], int status[], double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    if (!ws->ensure_block() || !cg_trace_columns(ws, k, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    const BlockRun B = { ws, R.elements, R.rowOffsets, R.columnIndeces, R.nLocal, k, R.rule, R.x, R.b, R.Ap, R.p, R.r };
+    bool ok = block_enqueue_start(B);
+    ok = ok && cg_drive_on(R, "SolveBlockEx", [&] { return block_enqueue_iteration(B, f); }, [&](volatile int* slot) { block_enqueue_snapshot(ws, slot); });
+    ok = MGCG_HIP(hipStreamSynchronize(ws->stream)) && ok;
+    BlockResult h;
+    ok = ok && block_read_results(ws, &h);
+    if (!ok) return MGCG_ERROR;
+    const int worst = cg_return_columns(ws, k, h.iteration, h.residual, h.status, nullptr, f.traceCap, iteration, residual, status, residualTrace, traceCapacity, &ok);
+    if (ok) cg_columns_message("SolveBlockEx", worst, "the residual of a column is not finite", R.maxIt);
     return ok ? worst : MGCG_ERROR;
 }
 
@@ -1247,6 +1284,33 @@ static bool cg_call(const CgCall& c, bool handles, Checks checks, Body body)
 }
 static bool no_more_checks() { return true; }
 
+// The call of a one-rank export: every row and every column is this rank's.
+static CgCall cg_call_one_rank(const char* who, MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elements, VectorInt* rowOffsets, VectorInt* columnIndeces,
+                               Vector* x, Vector* b, Vector* Ap, Vector* p, Vector* r, int elementsCount, int count)
+{
+    return { who, nullptr, cublas, cusparse, elements, rowOffsets, columnIndeces, x, b, Ap, p, r, count, count, 0, elementsCount, 0, count - 1 };
+}
+
+static void cg_set_stop(CgRun& R, double allowableResidual, int minIteration, int maxIteration, int rule)
+{
+    R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+}
+
+// What a variant solver refuses without a device: a null handle (the caller's verdict), k outside 1 .. kMax (noun: what k counts), a stop rule
+// that is unknown or, with maxNormWhy (why this loop cannot take it), the max-norm rule, no rows, and k traces beyond what an int can index.
+static bool cg_variant_args(const char* who, bool handles, int k, int kMax, const char* noun, int rule, const char* maxNormWhy, int count,
+                            const double* residualTrace, int traceCapacity)
+{
+    if (!handles) set_error("%s: null handle", who);
+    else if (k < 1 || k > kMax) set_error("%s: k = %d %s, must be 1 .. %d", who, k, noun, kMax);
+    else if (rule == MGCG_RULE_HANDMADECL && maxNormWhy) set_error("%s: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: %s", who, maxNormWhy);
+    else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("%s: unknown stop rule %d", who, rule);
+    else if (count < 1) set_error("%s: bad sizes", who);
+    else if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) set_error("%s: trace capacity too large", who);
+    else return true;
+    return false;
+}
+
 // SolveEx and SolveParallel
 static int solve_plain(const CgCall& c, double allowableResidual, int minIteration, int maxIteration, int rule,
                        int* iteration, double* residual, double* residualTrace, int traceCapacity)
@@ -1254,7 +1318,7 @@ static int solve_plain(const CgCall& c, double allowableResidual, int minIterati
     if (!device_state()) return MGCG_ERROR;
     int st = MGCG_ERROR;
     cg_call(c, true, no_more_checks, [&](CgRun& R) {
-        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
         st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
     });
     return st;
@@ -1276,8 +1340,7 @@ int SolveEx(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
             int* iteration, double* residual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    const CgCall c = { "SolveEx", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                       count, count, 0, elementsCount, 0, count - 1 };
+    const CgCall c = cg_call_one_rank("SolveEx", cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
     return solve_plain(c, allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
 }
 
@@ -1306,17 +1369,12 @@ int SolveShifted(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
 {
     (void)matDescr;
     // what needs no device is refused before one is asked for; nothing is enqueued for a call that fails here or in cg_call's checks
-    if (!cublas || !cusparse || !shiftedPVector) { set_error("SolveShifted: null handle"); return MGCG_ERROR; }
-    if (k < 1 || k > kShiftMaxK) { set_error("SolveShifted: k = %d shifts, must be 1 .. %d", k, kShiftMaxK); return MGCG_ERROR; }
+    if (!cg_variant_args("SolveShifted", cublas && cusparse && shiftedPVector, k, kShiftMaxK, "shifts", rule, nullptr, count, residualTrace, traceCapacity)) return MGCG_ERROR;
     if (!shifts) { set_error("SolveShifted: shifts is NULL"); return MGCG_ERROR; }
     for (int j = 0; j < k; ++j)
         if (!(shifts[j] >= 0.0 && shifts[j] <= 1.79e308)) { set_error("SolveShifted: shift %d is %g, must be finite and >= 0", j, shifts[j]); return MGCG_ERROR; }
-    if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) { set_error("SolveShifted: unknown stop rule %d", rule); return MGCG_ERROR; }
-    if (count < 1) { set_error("SolveShifted: bad sizes"); return MGCG_ERROR; }
-    if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) { set_error("SolveShifted: trace capacity too large"); return MGCG_ERROR; }
     if (!device_state()) return MGCG_ERROR;
-    const CgCall c = { "SolveShifted", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                       count, count, 0, elementsCount, 0, count - 1 };
+    const CgCall c = cg_call_one_rank("SolveShifted", cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
     const long long kn = (long long)k * count;
     auto checks = [&] {
         if (xVector->size < kn || shiftedPVector->size < kn) { set_error("SolveShifted: a device vector is smaller than the problem (x and the direction work space need k * count entries)"); return false; }
@@ -1324,7 +1382,7 @@ int SolveShifted(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
     };
     int st = MGCG_ERROR;
     cg_call(c, true, checks, [&](CgRun& R) {
-        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
         analysis_note_write(R.x, sizeof(double) * (size_t)kn);
         analysis_note_write(shiftedPVector->data, sizeof(double) * (size_t)kn);
         st = cg_solve_shifted(R, shiftedPVector->data, k, shifts, iteration, residual, status, residualTrace, traceCapacity);
@@ -1341,27 +1399,48 @@ int SolveMixed(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
 {
     (void)matDescr;
     // what needs no device is refused before one is asked for; nothing is enqueued for a call that fails here or in cg_call's checks
-    if (!cublas || !cusparse || !elements32Vector) { set_error("SolveMixed: null handle"); return MGCG_ERROR; }
-    if (rule == MGCG_RULE_HANDMADECL) {
-        set_error("SolveMixed: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the fp32 recurrence carries no max|r|");
-        return MGCG_ERROR;
-    }
-    if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) { set_error("SolveMixed: unknown stop rule %d", rule); return MGCG_ERROR; }
-    if (count < 1 || elementsCount < 0) { set_error("SolveMixed: bad sizes"); return MGCG_ERROR; }
+    if (!cg_variant_args("SolveMixed", cublas && cusparse && elements32Vector, 1, 1, "", rule, "the fp32 recurrence carries no max|r|", count, residualTrace, traceCapacity)) return MGCG_ERROR;
+    if (elementsCount < 0) { set_error("SolveMixed: bad sizes"); return MGCG_ERROR; }
     if (elements32Vector->size < ((long long)elementsCount + 1) / 2) {
         set_error("SolveMixed: the elements32 vector holds %lld doubles, the %d floats of MgcgMixedSetup need %lld", elements32Vector->size, elementsCount,
                   ((long long)elementsCount + 1) / 2);
         return MGCG_ERROR;
     }
     if (!device_state()) return MGCG_ERROR;
-    const CgCall c = { "SolveMixed", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                       count, count, 0, elementsCount, 0, count - 1 };
+    const CgCall c = cg_call_one_rank("SolveMixed", cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
     int st = MGCG_ERROR;
     cg_call(c, true, no_more_checks, [&](CgRun& R) {
-        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
         analysis_note_write(R.x, sizeof(double) * (size_t)count);
         analysis_note_write(R.r, sizeof(double) * (size_t)count);
         st = cg_solve_mixed(R, (const float*)elements32Vector->data, iteration, residual, reliableUpdates, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveBlockEx(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                 int elementsCount, int count, int k,
+                 double allowableResidual, int minIteration, int maxIteration, int rule,
+                 int iteration[], double residual[], int status[], double residualTrace[], int traceCapacity)
+{
+    (void)matDescr;
+    if (!device_state()) return MGCG_ERROR;            // (this export asks for the device first)
+    if (!cg_variant_args("SolveBlockEx", cublas && cusparse, k, kBlockMaxK, "right-hand sides", rule, nullptr, count, residualTrace, traceCapacity)) return MGCG_ERROR;
+    const CgCall c = cg_call_one_rank("SolveBlockEx", cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
+    const long long kn = (long long)k * count;
+    auto checks = [&] {
+        if (xVector->size < kn || bVector->size < kn || ApVector->size < kn || pVector->size < kn || rVector->size < kn) {
+            set_error("SolveBlockEx: a device vector is smaller than the problem (x, b, Ap, p, r need k * count entries)"); return false;
+        }
+        return true;
+    };
+    int st = MGCG_ERROR;
+    cg_call(c, true, checks, [&](CgRun& R) {
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        for (double* v : { R.x, R.r, R.p, R.Ap }) analysis_note_write(v, sizeof(double) * (size_t)kn);
+        st = cg_solve_block(R, k, iteration, residual, status, residualTrace, traceCapacity);
     });
     return st;
 }
@@ -1375,18 +1454,10 @@ int SolveBlockKrylov(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDe
 {
     (void)matDescr;
     // what needs no device is refused before one is asked for; nothing is enqueued for a call that fails here or in cg_call's checks
-    if (!cublas || !cusparse) { set_error("SolveBlockKrylov: null handle"); return MGCG_ERROR; }
-    if (k < 1 || k > kBlockMaxK) { set_error("SolveBlockKrylov: k = %d right-hand sides, must be 1 .. %d", k, kBlockMaxK); return MGCG_ERROR; }
-    if (rule == MGCG_RULE_HANDMADECL) {
-        set_error("SolveBlockKrylov: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: it needs max|r| and the residual block is never formed");
-        return MGCG_ERROR;
-    }
-    if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) { set_error("SolveBlockKrylov: unknown stop rule %d", rule); return MGCG_ERROR; }
-    if (count < 1) { set_error("SolveBlockKrylov: bad sizes"); return MGCG_ERROR; }
-    if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) { set_error("SolveBlockKrylov: trace capacity too large"); return MGCG_ERROR; }
+    if (!cg_variant_args("SolveBlockKrylov", cublas && cusparse, k, kBlockMaxK, "right-hand sides", rule, "it needs max|r| and the residual block is never formed",
+                         count, residualTrace, traceCapacity)) return MGCG_ERROR;
     if (!device_state()) return MGCG_ERROR;
-    const CgCall c = { "SolveBlockKrylov", nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
-                       count, count, 0, elementsCount, 0, count - 1 };
+    const CgCall c = cg_call_one_rank("SolveBlockKrylov", cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
     const long long kn = (long long)k * count;
     auto checks = [&] {
         if (xVector->size < kn || bVector->size < kn || ApVector->size < kn || pVector->size < kn || rVector->size < kn) {
@@ -1396,7 +1467,7 @@ int SolveBlockKrylov(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDe
     };
     int st = MGCG_ERROR;
     cg_call(c, true, checks, [&](CgRun& R) {
-        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
         for (double* v : { R.x, R.r, R.p, R.Ap }) analysis_note_write(v, sizeof(double) * (size_t)kn);
         st = cg_solve_bkrylov(R, k, iteration, residual, status, residualTrace, traceCapacity);
     });
@@ -1874,7 +1945,7 @@ int SolveMgParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, Mgcg
     int st = MGCG_ERROR;
     cg_call(c, mg && zVector, checks, [&](CgRun& R) {
         R.mg = mg; R.z = zVector->data;
-        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
         // deep-halo cycle: the loop keeps r in the hierarchy's extended buffer (room for the halo planes the cycle's one exchange brings) and the
         // caller's vector receives it when the solve is over
         const bool rExtended = R.multi && mg->deep && mg->rExt != nullptr;
@@ -1973,7 +2044,7 @@ int SolveJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, 
     int st = MGCG_ERROR;
     cg_call(c, dinvVector != nullptr, checks, [&](CgRun& R) {
         R.dinv = dinvVector->data;
-        R.tol = allowableResidual; R.minIt = minIteration; R.maxIt = maxIteration; R.rule = rule;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
         st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
     });
     return st;

@@ -1,4 +1,5 @@
 """Helpers shared by the -m gpu tests: everything goes through the C ABI."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -39,6 +40,56 @@ def ivec(a):
     if a.shape[0]:
         v.CopyFrom(a, a.shape[0])
     return v
+
+
+@contextlib.contextmanager
+def tuning(**knobs):
+    """Library knobs (MgcgSetTuning names) set for the block's duration and put back in a finally."""
+    L = _lib.lib()
+    old = {}
+    try:
+        for name, value in knobs.items():
+            was = C.c_int(0)
+            assert L.MgcgGetTuning(name.encode(), C.byref(was)) == 0, name
+            old[name] = was.value
+            assert L.MgcgSetTuning(name.encode(), value) == 0, name
+        yield
+    finally:
+        for name, value in old.items():
+            L.MgcgSetTuning(name.encode(), value)
+
+
+def same_bits(a, b):
+    """Equal bit for bit (NaN payloads and the sign of zero included); lists and tuples entry by entry."""
+    if isinstance(a, (list, tuple)):
+        return isinstance(b, (list, tuple)) and len(a) == len(b) and all(same_bits(p, q) for p, q in zip(a, b))
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+CHECK_EVERY = (1, 4, 7)
+
+
+def same_under_every_chunking(run, dot_order):
+    """run() -> dict of results.  How many iterations the host enqueues ahead of the stop flag (knob check_every) must not change one bit
+    of them; returns the results."""
+    runs = []
+    for every in CHECK_EVERY:
+        with tuning(check_every=every, dot_order=dot_order):
+            runs.append(run())
+    for every, other in zip(CHECK_EVERY[1:], runs[1:]):
+        assert other.keys() == runs[0].keys()
+        for key in runs[0]:
+            assert same_bits(other[key], runs[0][key]), (key, every, other[key], runs[0][key])
+    return runs[0]
+
+
+def cap_inside_a_chunk(lowest, highest):
+    """An iteration cap in [0, highest) near the middle of [lowest, highest] whose stopping iteration (index cap + 1, the cap + 2nd enqueued) is
+    the last of a chunk under neither check_every = 4 nor 7."""
+    cap = next(c for c in range((lowest + highest) // 2, -1, -1) if (c + 2) % 4 and (c + 2) % 7)
+    assert cap < highest, (lowest, highest)
+    return cap
 
 
 class DeviceCsr:

@@ -14,7 +14,7 @@ from conjugategradient_amd.block import ConjugateGradientBlockGpu
 from conjugategradient_amd.parallel import ConjugateGradientRankGpu
 from conjugategradient_amd.solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble
 from oracle import oracle as O
-from tests.gpu_util import Handles, assert_iterate_close, assert_trace_close, dvec, ivec
+from tests.gpu_util import Handles, assert_iterate_close, assert_trace_close, cap_inside_a_chunk, dvec, ivec, same_bits, same_under_every_chunking
 
 pytestmark = pytest.mark.gpu
 
@@ -276,3 +276,80 @@ def test_python_class_equals_single_solves_on_golden_systems(dot_order, name, bu
         assert cg.Iteration[j] == one.Iteration and cg.Residual[j] == one.Residual and cg.Status[j] == one.status == _lib.OK, j
         assert np.array_equal(cg.trace[j], one.trace), j
         assert np.array_equal(cg.X[j], one.x), j
+
+
+# --------------------------------------------------------------------------- refusals, and the host's chunking (8^3 Poisson: 512 rows)
+def _raw_vectors(s, k, B, X):
+    n = s.Count
+    return dict(e=dvec(s.Elements[: s.nnz]), ro=ivec(s.RowOffsets), c=ivec(s.ColumnIndeces[: s.nnz]), x=dvec(X.reshape(-1)), b=dvec(B.reshape(-1)),
+                Ap=dvec(np.full(k * n, 7.0)), p=dvec(np.full(k * n, 7.0)), r=dvec(np.full(k * n, 7.0)))
+
+
+def _raw_block(h, v, s, k, rule=_lib.RULE_VIENNACL, **replace):
+    """One SolveBlockEx call through the C ABI.  replace: a vector by its key in v (None: a null handle), or count / elementsCount / traceCapacity."""
+    cap = MAX_IT + 8
+    a = dict(v, count=s.Count, elementsCount=s.nnz, traceCapacity=cap)
+    a.update(replace)
+    vec = lambda name: None if a[name] is None else a[name].Ptr
+    ptr = lambda arr: arr.ctypes.data_as(C.c_void_p)
+    it, res, st, tr = np.full(8, -7, np.int32), np.full(8, -7.0), np.full(8, -7, np.int32), np.zeros(8 * cap)
+    L = _lib.lib()
+    L.MgcgClearLastError()
+    ret = L.SolveBlockEx(h.blas, h.sparse, h.descr, vec("e"), vec("ro"), vec("c"), vec("x"), vec("b"), vec("Ap"), vec("p"), vec("r"),
+                         a["elementsCount"], a["count"], k, TOL, 0, MAX_IT, rule, ptr(it), ptr(res), ptr(st), ptr(tr), a["traceCapacity"])
+    msg = _lib.last_error()
+    L.MgcgClearLastError()
+    kk = min(max(k, 0), 8)
+    return dict(ret=ret, message=msg, iteration=it[:kk], residual=res[:kk], status=st[:kk],
+                trace=[tr[j * cap: j * cap + max(int(it[j]), 0) + 1].copy() for j in range(kk)])
+
+
+def test_refused_calls_enqueue_nothing_and_leave_the_handles_as_new():
+    s = problems.poisson(8, 8, 8)
+    k, n = 3, s.Count
+    B, X = _columns(s, k)
+    h, v = Handles(), _raw_vectors(s, k, B, X)
+    smaller = "a device vector is smaller than the problem"
+    cases = [(dict(k=0), "k = 0 right-hand sides, must be 1 .. 8"), (dict(k=9), "k = 9 right-hand sides, must be 1 .. 8"),
+             (dict(rule=17), "unknown stop rule 17"), (dict(p=None), "null vector handle"), (dict(count=0), "bad sizes"),
+             (dict(elementsCount=-1), "bad sizes"), (dict(x=dvec(np.zeros(k * n - 1))), smaller), (dict(ro=ivec(s.RowOffsets[:n])), smaller),
+             (dict(traceCapacity=2**30), "trace capacity too large")]          # 3 * 2^30 > 2^31 - 1
+    start = {name: v[name].to_numpy(k * n) for name in ("x", "Ap", "p", "r")}
+    for kw, word in cases:
+        got = _raw_block(h, v, s, kw.pop("k", k), **kw)
+        assert got["ret"] == _lib.ERROR and "SolveBlockEx" in got["message"] and word in got["message"], (kw, got["message"])
+        for name, was in start.items():
+            assert np.array_equal(v[name].to_numpy(k * n), was), (kw, name)       # nothing was enqueued
+    after = _raw_block(h, v, s, k)
+    h2, v2 = Handles(), _raw_vectors(s, k, B, X)
+    fresh = _raw_block(h2, v2, s, k)
+    assert after["ret"] == fresh["ret"] == _lib.OK, (after["message"], fresh["message"])
+    for key in ("iteration", "residual", "status", "trace"):
+        assert same_bits(after[key], fresh[key]), key
+    assert same_bits(v["x"].to_numpy(k * n), v2["x"].to_numpy(k * n))
+    h.close()
+    h2.close()
+
+
+def _block_results(s, k, B, X, max_it):
+    cg, _ = _block(s, k, B, X, _lib.RULE_VIENNACL, max_it=max_it)
+    out = dict(x=cg.X, iteration=cg.Iteration, residual=cg.Residual, status=cg.Status, trace=cg.trace)
+    cg.Dispose()
+    return out
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("k", [1, 3, 8])
+def test_chunking_cannot_change_a_result(k, order):
+    """check_every = 1, 4, 7: the same bits, also when the iteration cap ends columns in the middle of a chunk."""
+    s = problems.poisson(8, 8, 8)
+    B, X = _columns(s, k)
+    free = same_under_every_chunking(lambda: _block_results(s, k, B, X, MAX_IT), order)
+    its = free["iteration"].tolist()
+    print("iterations", its)
+    assert (free["status"] == _lib.OK).all()
+    assert k == 1 or len(set(its)) > 1, its                  # the columns stop in different iterations
+    cap = cap_inside_a_chunk(min(its) if k > 1 else 0, max(its))
+    capped = same_under_every_chunking(lambda: _block_results(s, k, B, X, cap), order)
+    print("cap", cap, "status", capped["status"].tolist())
+    assert (capped["status"] == _lib.MAXIT_EXCEEDED).any() and capped["iteration"].max() == cap + 1

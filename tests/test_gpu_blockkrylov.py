@@ -19,6 +19,7 @@ from conjugategradient_amd.block import ConjugateGradientBlockGpu
 from conjugategradient_amd.blockkrylov import ConjugateGradientBlockKrylovGpu
 from conjugategradient_amd.solver import ApplicationException, ConjugateGradientSingleGpu
 from oracle import oracle as O
+from tests.gpu_util import cap_inside_a_chunk, same_under_every_chunking
 from tests.test_gpu_jacobi import stop_decision
 
 pytestmark = pytest.mark.gpu
@@ -486,3 +487,23 @@ def test_streaming_hint_form(oracle):
         assert isinstance(err, ApplicationException), err
         assert_close_runs(cg, ref, k)
         cg.Dispose()
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_chunking_cannot_change_a_result(order):
+    """check_every = 1, 4, 7 on 8^3 Poisson, k = 3: the same bits, also when the iteration cap ends the block in the middle of a chunk."""
+    B, X = columns(512, 3, 31)
+
+    def run(max_it):
+        cg, _ = solve("poisson8", B, X, max_it=max_it)
+        out = dict(x=cg.X, iteration=cg.Iteration, residual=cg.Residual, status=cg.Status, trace=cg.trace)
+        cg.Dispose()
+        return out
+
+    free = same_under_every_chunking(lambda: run(MAX_IT), order)
+    print("iteration", free["iteration"])
+    assert (free["status"] == _lib.OK).all() and free["iteration"] > 4
+    cap = cap_inside_a_chunk(0, free["iteration"])
+    capped = same_under_every_chunking(lambda: run(cap), order)
+    print("cap", cap, "status", capped["status"].tolist())
+    assert (capped["status"] == _lib.MAXIT_EXCEEDED).any() and capped["iteration"] == cap + 1

@@ -16,7 +16,7 @@ from conjugategradient_amd import _lib, problems
 from conjugategradient_amd.mixed import ConjugateGradientMixedGpu
 from conjugategradient_amd.solver import ApplicationException, VectorDouble
 from oracle import oracle as O
-from tests.gpu_util import Handles, dvec, ivec
+from tests.gpu_util import Handles, cap_inside_a_chunk, dvec, ivec, same_under_every_chunking
 from tests.test_mixed_host import mixed_cg_oracle, row_sums
 
 pytestmark = pytest.mark.gpu
@@ -453,3 +453,23 @@ def test_class_raises_on_maximum_iterations(h):
         cg.Solve()
     assert cg.status == _lib.MAXIT_EXCEEDED and cg.Iteration == 7
     cg.Dispose()
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_chunking_cannot_change_a_result(h, order):
+    """check_every = 1, 4, 7 on 8^3 Poisson: the same bits, also when the iteration cap ends the loop in the middle of a chunk."""
+    d = DeviceSystem(h, system("poisson8"))
+    assert d.setup() == 0
+    keys = ("status", "iteration", "residual", "updates", "trace", "x", "r")
+
+    def run(max_it):
+        got = d.solve(_lib.RULE_VIENNACL, 1e-8, max_it=max_it)
+        return {key: got[key] for key in keys}
+
+    free = same_under_every_chunking(lambda: run(MAX_IT), order)
+    print("iteration", free["iteration"], "updates", free["updates"])
+    assert free["status"] == _lib.OK and free["iteration"] > 8
+    cap = cap_inside_a_chunk(0, free["iteration"])
+    capped = same_under_every_chunking(lambda: run(cap), order)
+    print("cap", cap, "iteration", capped["iteration"])
+    assert capped["status"] == _lib.MAXIT_EXCEEDED and cap < capped["iteration"] <= cap + 4       # (reported at the next update slot)

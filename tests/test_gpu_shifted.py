@@ -14,7 +14,7 @@ from conjugategradient_amd import _lib, problems
 from conjugategradient_amd.shifted import ConjugateGradientShiftedGpu
 from conjugategradient_amd.solver import ApplicationException, ConjugateGradientSingleGpu
 from oracle import oracle as O
-from tests.gpu_util import Handles, assert_iterate_close, assert_trace_close, dvec, ivec
+from tests.gpu_util import Handles, assert_iterate_close, assert_trace_close, cap_inside_a_chunk, dvec, ivec, same_under_every_chunking
 from tests.test_gpu_jacobi import stop_decision
 
 pytestmark = pytest.mark.gpu
@@ -446,3 +446,24 @@ def test_python_class_round_trip():
     cg.Read()
     assert np.array_equal(cg.x, first)
     cg.Dispose()
+
+
+# --------------------------------------------------------------------------- 8. the host's chunking
+@pytest.mark.parametrize("order", [0, 1])
+def test_chunking_cannot_change_a_result(order):
+    """check_every = 1, 4, 7 on 8^3 Poisson with 3 shifts: the same bits, also when the iteration cap ends columns in the middle of a chunk."""
+    s = problems.poisson(8, 8, 8)
+    shifts = shifts_for(s, 3)
+
+    def run(max_it):
+        cols = solve(s, shifts, _lib.RULE_VIENNACL, 1e-8, max_it=max_it)
+        return {key: [c[key] for c in cols] for key in ("x", "iteration", "residual", "status", "trace")}
+
+    free = same_under_every_chunking(lambda: run(MAX_IT), order)
+    its = free["iteration"]
+    print("iterations", its)
+    assert free["status"] == [_lib.OK] * 3 and len(set(its)) > 1, (free["status"], its)
+    cap = cap_inside_a_chunk(min(its), max(its))
+    capped = same_under_every_chunking(lambda: run(cap), order)
+    print("cap", cap, "status", capped["status"])
+    assert _lib.MAXIT_EXCEEDED in capped["status"] and max(capped["iteration"]) == cap + 1
