@@ -119,6 +119,8 @@ SIGNATURES = {
     "CsrMVFloat": (None, [_vp] * 7 + [_i, _i]),
     "SolveMixed": (_i, [_vp] * 12 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _pi, _vp, _i]),
     "SolveJacobiParallel": (_i, [_vp] * 13 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
+    "SolveSingleReduce": (_i, [_vp] * 13 + [_i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
+    "SolveSingleReduceParallel": (_i, [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "MgcgCommGetUniqueId": (_i, [_vp]),
     "MgcgRcclAvailable": (_i, []),
     "MgcgCommInitRank": (_vp, [_vp, _i, _i]),

@@ -114,7 +114,7 @@ inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (voi
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
-void preload_kernels_bkrylov(); void preload_kernels_mixed();
+void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -179,6 +179,14 @@ struct MixedScalars {
     int pad;
 };
 
+// What the single-reduction loop (SolveSingleReduce*, kernels_sreduce.hip) carries from one body to the next.  Body k reads st[k & 1] in every
+// workgroup of its pass while that pass's first workgroup writes st[(k + 1) & 1], as ShiftState does.  red: several ranks only -- this rank's
+// {delta, rr, gamma} ({delta, rr} without dinv), all-reduced in place between the launch that writes them and the pass that reads them.
+struct SreduceScalars {
+    double red[3];
+    struct State { double gamma, alpha; } st[2];     // gamma and alpha of the body before
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
@@ -209,6 +217,7 @@ struct Workspace {
     MixedScalars* mixedScalars = nullptr;
     float* mixedVecs = nullptr;
     long long mixedStride = 0;
+    SreduceScalars* sreduceScalars = nullptr;    // single-reduction CG (kernels_sreduce.hip), allocated at its first call and kept; its direction p takes ring[1]
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -218,6 +227,7 @@ struct Workspace {
     bool ensure_shift();                         // shiftScalars (kernels_shift.hip)
     bool ensure_bkrylov();                       // gramPartials / bkScalars (kernels_bkrylov.hip)
     bool ensure_mixed(long long n);              // mixedScalars / mixedVecs for n rows (kernels_mixed.hip)
+    bool ensure_sreduce();                       // sreduceScalars (kernels_sreduce.hip)
 };
 
 } // namespace mgcg
@@ -587,6 +597,22 @@ bool mixed_enqueue_iteration(const MixedRun& R, const FinalizeArgs& f);
 void mixed_enqueue_fold(const MixedRun& R);
 void mixed_enqueue_restart(const MixedRun& R, const FinalizeArgs& f, int nPartials);
 inline const int* mixed_gate(const MixedRun& R) { return &R.ws->mixedScalars->gate; }
+
+// Single-reduction CG (SolveSingleReduce*; kernels_sreduce.hip has the loop).  u: this rank's rows of the full-length buffer the product gathers
+// from (without dinv the residual lives there during the loop, and r is not touched); p: the direction; s = A p by recurrence; w = A u.
+// given: several ranks -- the sums arrive all-reduced in ws->sreduceScalars->red.  The partial sums of r.r (and of r.u with dinv) of parity q
+// live at sreduce_rr_partials(ws, q) (sreduce_gamma_partials): body k reads parity k + 1 and writes parity k, the start writes parity 1.
+struct SreduceRun {
+    Workspace* ws;
+    double *x, *p, *s, *r, *u, *w; const double* dinv;
+    long long n; bool given;
+};
+double* sreduce_rr_partials(Workspace* ws, int parity);
+double* sreduce_gamma_partials(Workspace* ws, int parity);
+// this rank's sums of body k into ws->sreduceScalars->red, in front of their one all-reduce (nDelta: the product's partial sums in ws->partials)
+void sreduce_enqueue_sums(const SreduceRun& R, int k, int nDelta, int nIn);
+// the pass of body k; returns the number of partial sums it leaves for body k + 1 (1 under dot_order = 1: two more launches, three with dinv)
+int sreduce_enqueue_pass(const SreduceRun& R, const FinalizeArgs& f, int k, int nDelta, int nIn);
 
 // dinv_i = 1 / a_ii for the Jacobi-preconditioned loop
 void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,

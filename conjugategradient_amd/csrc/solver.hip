@@ -1184,6 +1184,78 @@ static int cg_solve_mixed(CgRun& R, const float* e32, int* iteration, double* re
     return ok ? status : MGCG_ERROR;
 }
 
+// ---------------------------------------------------------------- single-reduction CG (SolveSingleReduce, SolveSingleReduceParallel)
+// Chronopoulos-Gear CG: the product in front of both sums, one reduction point per iteration (kernels_sreduce.hip has the loop and its pass).
+// The host's side is cg_drive: a body is the product and the pass (two launches), on several ranks the product, the three sums, their one
+// all-reduce and the pass.  The product is the plain loop's (cg_enqueue_product: halo exchange of the full-length buffer, which holds u here,
+// launch_spmv_auto with the partial sums of w.u), so compression modes and automatic column tiles apply unchanged; the overlap schedule
+// stays "in line", and the deferred x update and the placement draw do not apply.  R.Ap holds w, R.p u (full length), sVec s; the
+// direction p takes the first library slot of the deferred x update's ring.  Without dinv the residual lives in the rows' slice of R.p
+// while the loop runs and is copied into R.r at the end.
+static int cg_solve_sreduce(CgRun& R, double* sVec, int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    // everything the call allocates, before anything is enqueued
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    if (!ws->ensure_sreduce() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    if (!ws->ensure_ring(2, n > 0 ? n : 1)) { set_error("SolveSingleReduce: no room on the device for the direction vector (%lld entries)", n); return MGCG_ERROR; }
+    const int devTraceCap = f.traceCap;
+    cg_matrix_setup(R);
+    R.overlap = false;                                                                   // the exchange of u stays in line
+    CgScalars* sc = ws->scalars;
+    double* uLoc = R.p + R.offset;
+    const SreduceRun P = { ws, R.x, ws->ring[1], sVec, R.r, uLoc, R.Ap, R.dinv, n, R.multi };
+
+    // start: r = b - A x ; u = dinv r ; the partial sums of rr0 = r.r and gamma = r.u where body 0 looks for them ; the scalars
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
+    launch_copy(s, uLoc, R.x, n);
+    bool ok = halo_exchange(R.comm, R.halo, R.p, s);
+    if (ok) {
+        SpmvArgs a = cg_spmv_args(R, R.p, R.r);
+        a.b = R.b;
+        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
+    }
+    double* rrPartials = sreduce_rr_partials(ws, 1);
+    double* gPartials = R.dinv ? sreduce_gamma_partials(ws, 1) : nullptr;
+    int nIn = ok ? launch_copy_dot(s, uLoc, R.r, R.dinv, n, rrPartials, gPartials, nullptr) : 0;
+    if (ok && R.multi) {                                                                 // rr0 for the relative rule, as cg_enqueue_init
+        if (R.dinv) launch_reduce2_to(s, rrPartials, nIn, &sc->rrNew, gPartials, nIn, &sc->rzNew, nullptr);
+        else launch_reduce_to(s, rrPartials, nIn, &sc->rr, nullptr);
+        ok = comm_allreduce_sum(R.comm, R.dinv ? &sc->rrNew : &sc->rr, R.dinv ? 2 : 1, s);
+    }
+    if (ok) launch_init_scalars(s, rrPartials, gPartials, nIn, !R.multi, sc, ws->mirror);
+    ok = ok && MGCG_HIP(hipGetLastError());
+
+    int k = 0;
+    ok = ok && cg_drive(R, "SolveSingleReduce", [&] {
+        int nDelta = 0;
+        if (!cg_enqueue_product(R, R.p, &nDelta)) return false;                          // w = A u ; w.u
+        if (R.multi) {
+            sreduce_enqueue_sums(P, k, nDelta, nIn);
+            if (!comm_allreduce_sum(R.comm, ws->sreduceScalars->red, R.dinv ? 3 : 2, s)) return false;
+        }
+        nIn = sreduce_enqueue_pass(P, f, k, nDelta, nIn);
+        if (k < 0x7fffffff) ++k;
+        return MGCG_HIP(hipGetLastError());
+    });
+    if (ok && !R.dinv) launch_copy(s, R.r, uLoc, n);                                     // the residual into the caller's r
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    HostMirror* m = ws->mirror;
+    const int status = m->status;
+    if (iteration) *iteration = m->iteration;
+    if (residual) *residual = m->residual;
+    if (devTraceCap) {
+        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
+        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
+    }
+    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveSingleReduce: did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
+    if (status == MGCG_NONFINITE) set_error("SolveSingleReduce: stopped at iteration %d: w.u or its corrected form is not finite and > 0, or alpha or the residual is not finite", m->iteration);
+    return ok ? status : MGCG_ERROR;
+}
+
 // ---------------------------------------------------------------- shared-subspace block CG (SolveBlockKrylov)
 // k right-hand sides in one block Krylov space (kernels_bkrylov.hip has the method and the kernels).  The matrix is read as plain CSR by the
 // block product, so no matrix set-up, no placement draw and no deferred x update; the host's side is cg_drive.  R.p, R.r and R.Ap hold S, Q, T.
@@ -2060,6 +2132,58 @@ int SolveJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
     return SolveJacobiParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
                                xVector, bVector, ApVector, pVector, rVector, dinvVector, count, count, 0, elementsCount, 0, count - 1,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
+}
+
+// Single-reduction CG (cg_solve_sreduce above).  What needs no device is refused before one is asked for when there is nobody to agree with;
+// among several ranks a rank with unusable arguments travels in the halo plan's one all-reduce (cg_call) and every rank leaves with
+// MGCG_ERROR.  Whether dinvVector is given is NOT part of that agreement: every rank passes one, or none does.
+int SolveSingleReduceParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                              Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                              Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* sVector, Vector* dinvVector,
+                              int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                              double allowableResidual, int minIteration, int maxIteration, int rule,
+                              int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    const bool handles = cublas && cusparse && sVector;
+    auto checks = [&] {
+        if (rule == MGCG_RULE_HANDMADECL) set_error("SolveSingleReduce: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the pass carries no max|r|");
+        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("SolveSingleReduce: unknown stop rule %d", rule);
+        else if (sVector->size < countForDevice) set_error("SolveSingleReduce: the s vector holds %lld entries, the matrix has %d local rows", sVector->size, countForDevice);
+        else if (dinvVector && dinvVector->size < countForDevice) set_error("SolveSingleReduce: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice);
+        else return true;
+        return false;
+    };
+    if (MgcgCommSize(comm) <= 1) {
+        if (!handles) { set_error("SolveSingleReduce: null handle"); return MGCG_ERROR; }
+        if (!checks()) return MGCG_ERROR;
+    }
+    if (handles && !device_state()) return MGCG_ERROR;
+    const CgCall c = { "SolveSingleReduce", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    int st = MGCG_ERROR;
+    cg_call(c, handles, checks, [&](CgRun& R) {
+        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the loop, which reads nothing through
+        // it there -- the ranks must agree on the form, the all-reduce carries three sums or two
+        R.dinv = dinvVector ? (dinvVector->data ? dinvVector->data : R.ws->partials) : nullptr;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        for (double* v : { R.x, R.r, R.Ap, sVector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
+        analysis_note_write(R.p, sizeof(double) * (size_t)count);
+        st = cg_solve_sreduce(R, sVector->data, iteration, residual, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveSingleReduce(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                      Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                      Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* sVector, Vector* dinvVector,
+                      int elementsCount, int count,
+                      double allowableResidual, int minIteration, int maxIteration, int rule,
+                      int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    return SolveSingleReduceParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
+                                     xVector, bVector, ApVector, pVector, rVector, sVector, dinvVector, count, count, 0, elementsCount, 0, count - 1,
+                                     allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
 }
 
 } // extern "C"

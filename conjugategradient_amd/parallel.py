@@ -199,7 +199,7 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
     def Dispose(self):
         if getattr(self, "cublas", None):
             for v in (self.vectorElements, self.vectorColumnIndeces, self.vectorRowOffsets, self.vectorX, self.vectorB,
-                      self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None)):
+                      self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None), getattr(self, "vectorS", None)):
                 if v is not None:
                     v.Dispose()
             if self._own_comm and self.comm:
@@ -325,6 +325,35 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if st != _lib.OK:
             check("SolveJacobiParallel")
             raise MgcgError(f"SolveJacobiParallel failed with status {st}")
+
+    def SolveSingleReduce(self, trace: bool = False, jacobi: bool = False):
+        """Solve() on the single-reduction loop (SolveSingleReduceParallel): one all-reduce per iteration.  jacobi: with the diagonal
+        preconditioner (SetupJacobi() first).  Every rank passes the same ``jacobi``."""
+        self._ensure_comm()
+        p = self.part
+        if jacobi and (getattr(self, "vectorDinv", None) is None or getattr(self, "jacobiError", None) is not None):
+            raise MgcgError("SolveSingleReduce(jacobi=True): SetupJacobi() has not set the diagonal up")
+        if getattr(self, "vectorS", None) is None or self.vectorS.size < p.count:
+            self.vectorS = VectorDouble(p.count)
+        iteration, residual = C.c_int(0), C.c_double(0.0)
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        st = lib().SolveSingleReduceParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
+                                             self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                             self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorS.Ptr,
+                                             self.vectorDinv.Ptr if jacobi else None,
+                                             self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
+                                             self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
+                                             C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"single-reduction CG did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveSingleReduceParallel")
+            raise MgcgError(f"SolveSingleReduceParallel failed with status {st}")
 
     @staticmethod
     def LastOverlap():

@@ -493,6 +493,55 @@ int SolveJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, 
                         double allowableResidual, int minIteration, int maxIteration, int rule,
                         int* iteration, double* residual, double* residualTrace, int traceCapacity);
 
+/* ---- Single-reduction CG (Chronopoulos-Gear): the same Krylov method with ONE global sum per iteration (one rank or several) ---- */
+/* SolveEx / SolveJacobi with the product moved in front of both sums.  One rank: an iteration is the product and ONE fused vector pass
+ * (two launches where SolveEx has three).  Several ranks: the product, one small launch, one all-reduce of 3 doubles (2 without
+ * dinvVector) and the pass -- three launches and one all-reduce where SolveParallel has five and two.  The price is one more vector
+ * (s = A p, kept by recurrence) and 72 bytes per row of pass traffic against 64 (88 against 80 with dinvVector): a loop for
+ * latency-bound systems and for ranks, not for systems whose iteration is memory traffic.  Other bits than SolveEx's, the same method.
+ * Method (dinv = 1 / diag(A), or all ones when dinvVector is NULL):
+ *   start   r = b - A x ;  u = dinv r ;  rr0 = rr = r.r ;  gamma = r.u ;  w = A u ;  delta = w.u
+ *   body k  k = 0:  beta = 0 ;  alpha = gamma / delta
+ *           k > 0:  beta = gamma / gamma_old ;  t = beta*gamma ;  q = t / alpha_old ;  den = delta - q ;  alpha = gamma / den
+ *           p = u + beta p ;  s = w + beta s          (k = 0: p = u, s = w; the old p and s are not read)
+ *           x = x + alpha p ;  r = r + (-alpha) s ;  u = dinv r
+ *           gamma_old = gamma ; alpha_old = alpha ;  gamma = r.u ;  rr = r.r
+ *           w = A u ;  delta = w.u
+ * Rounding contract: every product goes into a double of its own before the add that follows it, nothing is fused; the scalars are
+ * evaluated in exactly the order written; per element bp = beta*p_i ; p_i = u_i + bp ; bs = beta*s_i ; s_i = w_i + bs ; ap = alpha*p_i ;
+ * x_i = x_i + ap ; as = (-alpha)*s_i ; r_i = r_i + as ; u_i = dinv_i*r_i; the terms of the sums are r_i*r_i and r_i*u_i of the rounded r
+ * and u, and w_i*u_i; without dinvVector u is r.  Under dot_order = 1 delta, gamma and rr are serial left-to-right sums and ranks add in
+ * rank order: the whole loop is then a fixed sequence of IEEE operations.
+ * Stop: the four 2-norm rules of SolveEx on the true (rr, rr0); MGCG_RULE_HANDMADECL is refused with MGCG_ERROR before anything is enqueued.
+ * The decision on body k's rr is taken at the one reduction point, behind the next product: one product at the very end is wasted, and x is
+ * the iterate whose residual was judged.  *iteration, *residual, the trace (entry k: body k's residual; sqrt(rr / rr0) under
+ * MGCG_RULE_VIENNACL) and the status mean what they mean for SolveEx.  MGCG_RULE_SIMPLE starts from x = 0.
+ * Breakdown: delta (k = 0) or den not finite or <= 0, or an alpha that is not finite, ends the loop with MGCG_NONFINITE before body k's
+ * updates: x keeps the last completed iterate, *iteration = k, and *residual and trace entry k repeat that iterate's residual.
+ *   ApVector, pVector, rVector, sVector   work space (count entries each; the layout is internal: w, u, r, s).  The direction p lives
+ *                   on the handle's workspace (one more vector of count entries, allocated at the first call and kept).  On return
+ *                   rVector holds the recurrence residual.
+ *   dinvVector      what MgcgJacobiSetup wrote, or NULL for the unpreconditioned loop
+ * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer) and the
+ * placement draw do not apply.  Out of scope: the V-cycle as preconditioner, the block, shifted and mixed variants, and hiding the
+ * all-reduce behind the product (pipelined CG). */
+int SolveSingleReduce(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                      Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                      Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* sVector, Vector* dinvVector /* may be NULL */,
+                      int elementsCount, int count,
+                      double allowableResidual, int minIteration, int maxIteration, int rule,
+                      int* iteration, double* residual, double* residualTrace, int traceCapacity);
+/* The same on a row partition, shaped after SolveJacobiParallel: pVector is full length (count entries; it holds u, whose halo is exchanged
+ * before every product, in line -- the overlap schedule is not used by this loop), the other vectors hold the local rows.  A rank without
+ * rows takes part in every collective.  Every rank passes a dinvVector or none does: that is not checked (the ranks would disagree on the
+ * length of the all-reduce); every other unusable argument on one rank makes every rank return MGCG_ERROR, as in SolveParallel. */
+int SolveSingleReduceParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                              Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                              Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* sVector, Vector* dinvVector /* may be NULL */,
+                              int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                              double allowableResidual, int minIteration, int maxIteration, int rule,
+                              int* iteration, double* residual, double* residualTrace, int traceCapacity);
+
 /* ---- Multi-shift CG: (A + shifts[j] I) x_j = b for k = 1 .. 8 shifts >= 0 from ONE CG recurrence on A (one rank, no preconditioner) ---- */
 /* Krylov spaces are shift-invariant: the residual of every shifted system is collinear with the base residual, r_j = zeta_j r, so an
  * iteration is SolveEx's product and r update plus ONE fused vector pass for all columns -- three launches, one matrix pass, whatever k
