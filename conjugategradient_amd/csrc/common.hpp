@@ -114,7 +114,7 @@ inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (voi
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
-void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce();
+void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -351,7 +351,9 @@ enum SpmvEpilogue {
     EPI_JACOBI = 3,  // y = xo + omega*(dinv*(b - A x))
     EPI_RESIDUAL_DOT = 4, // y = b - A x ; partial += y_i*y_i
     EPI_AXPBY_BETA = 5,  // internal: EPI_AXPBY with beta != 0 (reads y)
-    EPI_JACOBI_DOT = 6   // EPI_JACOBI ; partial += b_i * y_i   (last sweep of the V-cycle: r.z of the PCG loop rides along)
+    EPI_JACOBI_DOT = 6,  // EPI_JACOBI ; partial += b_i * y_i   (last sweep of the V-cycle: r.z of the PCG loop rides along)
+    EPI_CHEBYSHEV = 7,   // d = c1*d + c2*(dinv*(b - A x)) ; y = xo + d   (one step of the Chebyshev polynomial preconditioner, kernels_cheb.hip)
+    EPI_CHEBYSHEV_DOT = 8 // EPI_CHEBYSHEV ; partial += b_i * y_i   (the polynomial's last step: r.z of the loop rides along)
 };
 // Timing ablations that produce WRONG results exist only in lab builds of the library (make lab: -DMGCG_LAB).
 #ifdef MGCG_LAB
@@ -359,7 +361,9 @@ enum SpmvEpilogue {
 #else
 #define MGCG_ABLATE(a, bits) false
 #endif
-constexpr bool epi_has_dot(int e) { return e == EPI_DOT || e == EPI_RESIDUAL_DOT || e == EPI_JACOBI_DOT; }
+constexpr bool epi_has_dot(int e) { return e == EPI_DOT || e == EPI_RESIDUAL_DOT || e == EPI_JACOBI_DOT || e == EPI_CHEBYSHEV_DOT; }
+constexpr bool epi_is_jacobi(int e) { return e == EPI_JACOBI || e == EPI_JACOBI_DOT; }
+constexpr bool epi_is_chebyshev(int e) { return e == EPI_CHEBYSHEV || e == EPI_CHEBYSHEV_DOT; }
 
 struct SpmvArgs {
     const double* elements;
@@ -371,12 +375,14 @@ struct SpmvArgs {
     int rowCount;
     int columnCount;
     double alpha, beta;      // EPI_AXPBY
-    const double* w;         // EPI_DOT: weights (own slice of x); EPI_JACOBI: xo (own slice of x)
-    const double* b;         // EPI_RESIDUAL / EPI_JACOBI
-    const double* dinv;      // EPI_JACOBI
+    const double* w;         // EPI_DOT: weights (own slice of x); EPI_JACOBI / EPI_CHEBYSHEV: xo (own slice of x)
+    const double* b;         // EPI_RESIDUAL / EPI_JACOBI / EPI_CHEBYSHEV
+    const double* dinv;      // EPI_JACOBI / EPI_CHEBYSHEV
     double omega;            // EPI_JACOBI
-    int dinvUniform;         // EPI_JACOBI: every diagonal is the same; dinvScalar is used and the dinv array is not read
+    int dinvUniform;         // EPI_JACOBI / EPI_CHEBYSHEV: every diagonal is the same; dinvScalar is used and the dinv array is not read
     double dinvScalar;
+    double* d;               // EPI_CHEBYSHEV: the polynomial's increment, one entry per row, read and rewritten by the row's own lane
+    double c1, c2;           // EPI_CHEBYSHEV: this step's coefficients
     int xScaled;             // row-pattern and row-tile kernels: the multiplied vector is xOuter * (xInner * x[col]), formed per gather
     double xInner, xOuter;   //   (a first Jacobi sweep from zero folded into the residual pass of the V-cycle)
     // xScaled == 2 (row-tile kernel, Jacobi epilogues): ... + xCoarse[parent(col)] on top -- the piecewise-constant prolongation of the coarse
@@ -613,6 +619,22 @@ double* sreduce_gamma_partials(Workspace* ws, int parity);
 void sreduce_enqueue_sums(const SreduceRun& R, int k, int nDelta, int nIn);
 // the pass of body k; returns the number of partial sums it leaves for body k + 1 (1 under dot_order = 1: two more launches, three with dinv)
 int sreduce_enqueue_pass(const SreduceRun& R, const FinalizeArgs& f, int k, int nDelta, int nIn);
+
+// Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).
+// The start: d = it * (dinv r), z = d, the partial sums of r.r and -- withRz, degree 1 -- of r.z; returns their number (1 under dot_order = 1).
+int launch_cheb_start(hipStream_t s, const double* r, const double* dinv, double* d, double* z, long long n, double it,
+                      double* partials, double* partialsZ, bool withRz);
+// The scalars in front of iteration 0 from those sums (reduceFirst) or from the all-reduced {sc->rrNew, sc->rzNew}; an r.z that is not finite
+// and > 0 stops the loop here with MGCG_NONFINITE.
+void launch_cheb_init_scalars(hipStream_t s, const double* partials, int n, const double* partialsZ, int nZ, bool reduceFirst, const FinalizeArgs& f);
+// The first pass of an iteration: alpha = r.z / p.Ap (pApPartials as launch_update_r; a p.Ap that is not finite and > 0 stops the loop),
+// r += (-alpha) Ap, the partial sums of r.r, d = it * (dinv r), z = d and -- withRz -- the partial sums of r.z.
+int launch_cheb_first(hipStream_t s, const FinalizeArgs& f, double* r, const double* Ap, const double* dinv, double* d, double* z, long long n, double it,
+                      double* partials, double* partialsZ, bool withRz, const double* pApPartials, int nPAp);
+// Residual, stop test, the r.z breakdown test, beta and the hand-over of r.z; launch_update_xp follows.
+void launch_cheb_finalize(hipStream_t s, const double* partials, int n, const double* partialsZ, int nZ, bool reduceFirst, const FinalizeArgs& f);
+// out[0] = max over the rows of sum_k |a_ik| (times dinv_i), each row summed in stored order from +0.0; partials: room for kMaxGrid doubles, out: one more, elsewhere
+void launch_gershgorin(hipStream_t s, const double* elements, const int* rowOffsets, long long nnz, long long n, const double* dinv, double* partials, double* out);
 
 // dinv_i = 1 / a_ii for the Jacobi-preconditioned loop
 void launch_jacobi_setup(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long nnz, long long n, long long rowBase,

@@ -418,6 +418,8 @@ int launch_spmv_rows(hipStream_t s, int epilogue, const SpmvArgs& a, const DcsrV
     case EPI_RESIDUAL_DOT: return launch_rows_epi<EPI_RESIDUAL_DOT>(s, a, m, gridReq);
     case EPI_JACOBI:       return launch_rows_epi<EPI_JACOBI>(s, a, m, gridReq);
     case EPI_JACOBI_DOT:   return launch_rows_epi<EPI_JACOBI_DOT>(s, a, m, gridReq);
+    case EPI_CHEBYSHEV:    return launch_rows_epi<EPI_CHEBYSHEV>(s, a, m, gridReq);
+    case EPI_CHEBYSHEV_DOT: return launch_rows_epi<EPI_CHEBYSHEV_DOT>(s, a, m, gridReq);
     }
     return 0;
 }

@@ -52,7 +52,7 @@ template <int EPI, int XS>
 __device__ __forceinline__ RowsEpi tile_epi_prefetch(const SpmvArgs& a, int row)
 {
     // as rows_epi_prefetch, but without a conditional load (a branch around a load would make the waits uncounted)
-    RowsEpi o; o.w = 0.0; o.b = 0.0; o.dinv = 0.0; o.yold = 0.0;
+    RowsEpi o; o.w = 0.0; o.b = 0.0; o.dinv = 0.0; o.yold = 0.0; o.d = 0.0; o.row = row;
     if constexpr (XS == 2) {       // Jacobi sweep on x1 + P e formed on the fly (uniform diagonal): w is finished by tile_epi_own below
         o.b = a.b[row]; o.w = a.xCoarse[coarse_of(a, a.cRowBase + row)]; o.dinv = a.dinvScalar;
         return o;
@@ -60,8 +60,9 @@ __device__ __forceinline__ RowsEpi tile_epi_prefetch(const SpmvArgs& a, int row)
     if constexpr (EPI == EPI_AXPBY_BETA) o.yold = a.y[row];
     if constexpr (EPI == EPI_DOT) o.w = a.w[row];
     if constexpr (EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_DOT) o.b = a.b[row];
-    if constexpr (EPI == EPI_JACOBI || EPI == EPI_JACOBI_DOT) {
+    if constexpr (epi_is_jacobi(EPI) || epi_is_chebyshev(EPI)) {
         o.b = a.b[row]; o.w = a.w[row];
+        if constexpr (epi_is_chebyshev(EPI)) o.d = a.d[row];
         const double* dp = a.dinvUniform ? a.b : a.dinv;      // uniform diagonal: the array is not read (a.b stands in, same line as o.b)
         const double dl = dp[row];
         o.dinv = a.dinvUniform ? a.dinvScalar : dl;
@@ -345,6 +346,8 @@ int launch_spmv_rowtile(hipStream_t s, int epilogue, const SpmvArgs& a, int peri
     case EPI_RESIDUAL_DOT: return launch_rowtile_epi<EPI_RESIDUAL_DOT>(s, a, periodRows, gridReq, maxRow, ntWindow, gapAt, gapSkip);
     case EPI_JACOBI:       return launch_rowtile_epi<EPI_JACOBI>(s, a, periodRows, gridReq, maxRow, ntWindow, gapAt, gapSkip);
     case EPI_JACOBI_DOT:   return launch_rowtile_epi<EPI_JACOBI_DOT>(s, a, periodRows, gridReq, maxRow, ntWindow, gapAt, gapSkip);
+    case EPI_CHEBYSHEV:    return launch_rowtile_epi<EPI_CHEBYSHEV>(s, a, periodRows, gridReq, maxRow, ntWindow, gapAt, gapSkip);
+    case EPI_CHEBYSHEV_DOT: return launch_rowtile_epi<EPI_CHEBYSHEV_DOT>(s, a, periodRows, gridReq, maxRow, ntWindow, gapAt, gapSkip);
     }
     return 0;
 }

@@ -46,16 +46,17 @@ __device__ __forceinline__ double block_sum_256(double v, double* s_red)
 }
 
 // Epilogue operands of one row, loaded early (with the gathers) so the epilogue itself issues no load.
-struct EpiOperands { double w, b, dinv, yold; };
+struct EpiOperands { double w, b, dinv, yold, d; long long row; };   // d, row: the Chebyshev step, which stores d[row] itself
 
 template <int EPI>
 __device__ __forceinline__ EpiOperands epi_prefetch(const SpmvArgs& a, long long row)
 {
-    EpiOperands o; o.w = 0.0; o.b = 0.0; o.dinv = 0.0; o.yold = 0.0;
+    EpiOperands o; o.w = 0.0; o.b = 0.0; o.dinv = 0.0; o.yold = 0.0; o.d = 0.0; o.row = row;
     if constexpr (EPI == EPI_AXPBY_BETA) o.yold = a.y[row];
     if constexpr (EPI == EPI_DOT) o.w = a.w[row];
     if constexpr (EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_DOT) o.b = a.b[row];
-    if constexpr (EPI == EPI_JACOBI || EPI == EPI_JACOBI_DOT) { o.b = a.b[row]; o.dinv = a.dinvUniform ? a.dinvScalar : a.dinv[row]; o.w = a.w[row]; }
+    if constexpr (epi_is_jacobi(EPI) || epi_is_chebyshev(EPI)) { o.b = a.b[row]; o.dinv = a.dinvUniform ? a.dinvScalar : a.dinv[row]; o.w = a.w[row]; }
+    if constexpr (epi_is_chebyshev(EPI)) o.d = a.d[row];
     return o;
 }
 
@@ -80,6 +81,16 @@ __device__ __forceinline__ double spmv_epilogue_value(const SpmvArgs& a, double 
         double t = r * r;
         dotacc += t;
         return r;
+    } else if constexpr (epi_is_chebyshev(EPI)) {   // d = c1 d + c2 (dinv (r - A z)) ; z' = z + d, every product rounded on its own
+        double res = o.b - acc;
+        double t = o.dinv * res;
+        double p = a.c1 * o.d;
+        double q = a.c2 * t;
+        const double dn = p + q;
+        a.d[o.row] = dn;
+        const double v = o.w + dn;
+        if constexpr (EPI == EPI_CHEBYSHEV_DOT) { double u = o.b * v; dotacc += u; }
+        return v;
     } else {   // EPI_JACOBI, EPI_JACOBI_DOT
         double res = o.b - acc;
         double t = o.dinv * res;
@@ -553,6 +564,8 @@ int launch_spmv(hipStream_t s, int epilogue, const SpmvArgs& a, const SpmvConfig
     case EPI_RESIDUAL_DOT: return launch_spmv_epi<EPI_RESIDUAL_DOT>(s, a, cfg);
     case EPI_JACOBI:       return launch_spmv_epi<EPI_JACOBI>(s, a, cfg);
     case EPI_JACOBI_DOT:   return launch_spmv_epi<EPI_JACOBI_DOT>(s, a, cfg);
+    case EPI_CHEBYSHEV:    return launch_spmv_epi<EPI_CHEBYSHEV>(s, a, cfg);
+    case EPI_CHEBYSHEV_DOT: return launch_spmv_epi<EPI_CHEBYSHEV_DOT>(s, a, cfg);
     }
     return 0;
 }

@@ -1256,6 +1256,132 @@ static int cg_solve_sreduce(CgRun& R, double* sVec, int* iteration, double* resi
     return ok ? status : MGCG_ERROR;
 }
 
+// ---------------------------------------------------------------- Chebyshev-preconditioned CG (SolveChebyshev, SolveChebyshevParallel)
+// SolveJacobi's loop with z = p_m(D^-1 A) D^-1 r (kernels_cheb.hip has the method and the passes): the polynomial costs m - 1 products and no
+// global sum.  The host's side is cg_drive.  One iteration on one rank is m + 3 launches: the loop's product (cg_enqueue_product, so
+// compression modes and automatic column tiles apply to it), the fused first pass, m - 1 steps, the finalisation and the preconditioned
+// loop's x / p update.  Several ranks add a reduce and an all-reduce of p.Ap in front of the first pass and one reduce with ONE all-reduce
+// of {r.r, r.z} behind the polynomial (CgUpdate::PrecondRanks' pair), and exchange the halo of z in line before every step; the overlap
+// schedule, the deferred x update and the placement draw do not apply.  The steps read the matrix as plain CSR whatever the handle's
+// compression mode (launch_spmv, not launch_spmv_auto): the lossless forms would give the same bits.
+struct ChebPlan { int m; double it; double c1[16], c2[16]; };      // c1[j], c2[j]: step j = 1 .. m - 1
+
+// The coefficients, once per call, in the order include/MgcgGpu.h states (this file is built without contraction, as the kernels are).
+static ChebPlan cheb_plan(int degree, double lmin, double lmax)
+{
+    ChebPlan c{};
+    c.m = degree;
+    const double theta = (lmax + lmin) * 0.5, delta = (lmax - lmin) * 0.5, sigma = theta / delta;
+    double rho = 1.0 / sigma;
+    c.it = 1.0 / theta;
+    for (int j = 1; j < degree; ++j) {
+        const double next = 1.0 / (2.0 * sigma - rho);
+        c.c1[j] = next * rho; c.c2[j] = (2.0 * next) / delta;
+        rho = next;
+    }
+    return c;
+}
+
+// Steps 1 .. m - 1 behind the first pass, which left z in zA's rows: each gathers one full-length buffer and writes the rows of the other.
+// *zFinal: the buffer that holds z afterwards; *nZ: the number of r.z partial sums the last step left in ws->partials (untouched at m = 1).
+static bool cheb_enqueue_steps(CgRun& R, const ChebPlan& c, double* zA, double* zB, double* d, const int* done, double** zFinal, int* nZ)
+{
+    hipStream_t s = R.ws->stream;
+    double *in = zA, *out = zB;
+    for (int j = 1; j < c.m; ++j) {
+        if (!halo_exchange(R.comm, R.halo, in, s)) return false;
+        SpmvArgs a = cg_spmv_args(R, in, out + R.offset);
+        a.w = in + R.offset; a.b = R.r; a.d = d; a.c1 = c.c1[j]; a.c2 = c.c2[j];
+        a.dinv = R.dinv; a.dinvUniform = R.dinv ? 0 : 1; a.dinvScalar = 1.0;             // no diagonal: t = 1 * res, the same bits
+        a.partials = R.ws->partials; a.doneFlag = done;
+        const bool last = j == c.m - 1;
+        const int n = launch_spmv(s, last ? EPI_CHEBYSHEV_DOT : EPI_CHEBYSHEV, a, R.cfg);
+        if (last) *nZ = n;
+        double* t = in; in = out; out = t;
+    }
+    *zFinal = in;
+    if (c.m > 1 && dot_reference_order()) { launch_dot_serial(s, R.r, in + R.offset, R.nLocal, R.ws->partials, done); *nZ = 1; }   // validation mode: r.z once more, in the reference's order
+    return true;
+}
+
+static int cg_solve_chebyshev(CgRun& R, const ChebPlan& c, double* zA, double* zB, double* dVec, int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    FinalizeArgs f = cg_finalize_args(R, true, 2);
+    if (!cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    const int devTraceCap = f.traceCap;
+    cg_matrix_setup(R);
+    R.overlap = false;                                                                   // every exchange stays in line
+    CgScalars* sc = ws->scalars;
+    const int* done = &sc->done;
+    double* pLoc = R.p + R.offset;
+    // the first pass's partial sums of r.r (and, at degree 1, of r.z) take the third region of the buffer, as the r update's do; the last
+    // step's partial sums of r.z take the first, behind the product's of p.Ap, which the first pass has consumed by then
+    double* rrPartials = ws->partials + 2 * kMaxPartials;
+    double* rzFirst = rrPartials + kMaxPartials / 2;
+    const bool one = c.m == 1;
+    const double* rzPartials = one ? rzFirst : ws->partials;
+
+    // start: r = b - A x ; z = M r ; r.r and r.z ; the scalars (an r.z that is not > 0 stops the loop here) ; p = z
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
+    launch_copy(s, pLoc, R.x, n);
+    bool ok = halo_exchange(R.comm, R.halo, R.p, s);
+    if (ok) {
+        SpmvArgs a = cg_spmv_args(R, R.p, R.r);
+        a.b = R.b;
+        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
+        const int nrr = launch_cheb_start(s, R.r, R.dinv, dVec, zA + R.offset, n, c.it, rrPartials, rzFirst, one);
+        int nz = nrr;
+        double* zFin = zA;
+        ok = cheb_enqueue_steps(R, c, zA, zB, dVec, nullptr, &zFin, &nz);
+        if (ok && R.multi) {
+            launch_reduce2_to(s, rrPartials, nrr, &sc->rrNew, rzPartials, nz, &sc->rzNew, nullptr);
+            ok = comm_allreduce_sum(R.comm, &sc->rrNew, 2, s);
+        }
+        if (ok) {
+            launch_cheb_init_scalars(s, rrPartials, nrr, rzPartials, nz, !R.multi, f);
+            launch_copy(s, pLoc, zFin + R.offset, n);
+        }
+    }
+    ok = ok && MGCG_HIP(hipGetLastError());
+
+    ok = ok && cg_drive(R, "SolveChebyshev", [&] {
+        int nPAp = 0;
+        if (!cg_enqueue_product(R, R.p, &nPAp)) return false;                            // Ap = A p ; p.Ap
+        if (R.multi) {
+            launch_reduce_to(s, ws->partials, nPAp, &sc->pAp, done);
+            if (!comm_allreduce_sum(R.comm, &sc->pAp, 1, s)) return false;
+        }
+        const int nrr = launch_cheb_first(s, f, R.r, R.Ap, R.dinv, dVec, zA + R.offset, n, c.it, rrPartials, rzFirst, one,
+                                          R.multi ? nullptr : ws->partials, R.multi ? 0 : nPAp);
+        int nz = nrr;
+        double* zFin = zA;
+        if (!cheb_enqueue_steps(R, c, zA, zB, dVec, done, &zFin, &nz)) return false;
+        if (R.multi) {                                                                   // {rrNew, rzNew} are adjacent in CgScalars: one all-reduce
+            launch_reduce2_to(s, rrPartials, nrr, &sc->rrNew, rzPartials, nz, &sc->rzNew, done);
+            if (!comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;
+        }
+        launch_cheb_finalize(s, rrPartials, nrr, rzPartials, nz, !R.multi, f);
+        launch_update_xp(s, sc, R.x, pLoc, zFin + R.offset, n);                          // x += alpha p ; p = z + beta p
+        return MGCG_HIP(hipGetLastError());
+    });
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    HostMirror* m = ws->mirror;
+    const int status = m->status;
+    if (iteration) *iteration = m->iteration;
+    if (residual) *residual = m->residual;
+    if (devTraceCap) {
+        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
+        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
+    }
+    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveChebyshev: did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
+    if (status == MGCG_NONFINITE) set_error("SolveChebyshev: stopped at iteration %d: p.Ap or r.z is not finite and > 0 (an upper bound below the spectrum makes the polynomial indefinite), or the residual is not finite", m->iteration);
+    return ok ? status : MGCG_ERROR;
+}
+
 // ---------------------------------------------------------------- shared-subspace block CG (SolveBlockKrylov)
 // k right-hand sides in one block Krylov space (kernels_bkrylov.hip has the method and the kernels).  The matrix is read as plain CSR by the
 // block product, so no matrix set-up, no placement draw and no deferred x update; the host's side is cg_drive.  R.p, R.r and R.Ap hold S, Q, T.
@@ -2184,6 +2310,89 @@ int SolveSingleReduce(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matD
     return SolveSingleReduceParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
                                      xVector, bVector, ApVector, pVector, rVector, sVector, dinvVector, count, count, 0, elementsCount, 0, count - 1,
                                      allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
+}
+
+// Chebyshev-preconditioned CG (cg_solve_chebyshev above).  What needs no device is refused before one is asked for when there is nobody to agree
+// with; among several ranks a rank with unusable arguments travels in the halo plan's one all-reduce (cg_call) and every rank leaves with
+// MGCG_ERROR.  Degree, bounds and whether dinvVector is given are NOT part of that agreement: every rank passes the same.
+int SolveChebyshevParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                           Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                           Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector,
+                           Vector* zVector, Vector* z2Vector, Vector* dVector,
+                           int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                           int degree, double lambdaMin, double lambdaMax,
+                           double allowableResidual, int minIteration, int maxIteration, int rule,
+                           int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    const bool handles = cublas && cusparse && zVector && z2Vector && dVector;
+    auto checks = [&] {
+        if (degree < 1 || degree > 16) set_error("SolveChebyshev: degree %d, must be 1 .. 16", degree);
+        else if (!(lambdaMin > 0.0 && lambdaMin < lambdaMax && lambdaMax <= 1.79e308)) set_error("SolveChebyshev: the bounds (%g, %g) must be finite with 0 < lambdaMin < lambdaMax", lambdaMin, lambdaMax);
+        else if (rule == MGCG_RULE_HANDMADECL) set_error("SolveChebyshev: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the passes carry no max|r|");
+        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("SolveChebyshev: unknown stop rule %d", rule);
+        else if (zVector->size < count) set_error("SolveChebyshev: the z vector holds %lld entries, the matrix has %d columns", zVector->size, count);
+        else if (z2Vector->size < count) set_error("SolveChebyshev: the z2 vector holds %lld entries, the matrix has %d columns", z2Vector->size, count);
+        else if (dVector->size < countForDevice) set_error("SolveChebyshev: the d vector holds %lld entries, the matrix has %d local rows", dVector->size, countForDevice);
+        else if (dinvVector && dinvVector->size < countForDevice) set_error("SolveChebyshev: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice);
+        else return true;
+        return false;
+    };
+    if (MgcgCommSize(comm) <= 1) {
+        if (!handles) { set_error("SolveChebyshev: null handle"); return MGCG_ERROR; }
+        if (!checks()) return MGCG_ERROR;
+    }
+    if (handles && !device_state()) return MGCG_ERROR;
+    const CgCall c = { "SolveChebyshev", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    int st = MGCG_ERROR;
+    cg_call(c, handles, checks, [&](CgRun& R) {
+        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the passes, which read nothing through it there
+        R.dinv = dinvVector ? (dinvVector->data ? dinvVector->data : R.ws->partials) : nullptr;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        for (double* v : { R.x, R.r, R.Ap, dVector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
+        for (double* v : { R.p, zVector->data, z2Vector->data }) analysis_note_write(v, sizeof(double) * (size_t)count);
+        st = cg_solve_chebyshev(R, cheb_plan(degree, lambdaMin, lambdaMax), zVector->data, z2Vector->data, dVector->data, iteration, residual, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveChebyshev(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                   Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                   Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector,
+                   Vector* zVector, Vector* z2Vector, Vector* dVector,
+                   int elementsCount, int count, int degree, double lambdaMin, double lambdaMax,
+                   double allowableResidual, int minIteration, int maxIteration, int rule,
+                   int* iteration, double* residual, double* residualTrace, int traceCapacity)
+{
+    return SolveChebyshevParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
+                                  xVector, bVector, ApVector, pVector, rVector, dinvVector, zVector, z2Vector, dVector, count, count, 0, elementsCount, 0, count - 1,
+                                  degree, lambdaMin, lambdaMax, allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
+}
+
+// *bound = max over the local rows of sum_j |a_ij| (times dinv_i with a dinvVector): Gershgorin's upper bound of the spectrum of A (of D^-1 A).
+// One launch pair and one read-back; an empty slice gives 0.  Several ranks take the maximum of their bounds themselves.
+int MgcgGershgorinBound(MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        int elementsCount, int countForDevice, int offsetForDevice, Vector* dinvVector, double* bound)
+{
+    if (!cusparse || !elementsVector || !rowOffsetsVector || !columnIndecesVector || !bound) { set_error("MgcgGershgorinBound: null handle"); return -1; }
+    if (elementsCount < 0 || countForDevice < 0 || offsetForDevice < 0) { set_error("MgcgGershgorinBound: bad sizes"); return -1; }
+    if (elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount || rowOffsetsVector->size < (long long)countForDevice + 1) {
+        set_error("MgcgGershgorinBound: a device vector is smaller than the matrix"); return -1;
+    }
+    if (dinvVector && dinvVector->size < countForDevice) { set_error("MgcgGershgorinBound: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice); return -1; }
+    *bound = 0.0;
+    if (countForDevice == 0) return 0;
+    if (!device_state()) return -1;
+    hipStream_t s = cusparse->ws.stream;
+    double* partials = cusparse->ws.partials;
+    double* out = partials + kMaxPartials;
+    launch_gershgorin(s, elementsVector->data, rowOffsetsVector->data, elementsCount, countForDevice, dinvVector ? dinvVector->data : nullptr, partials, out);
+    double h = 0.0;
+    const bool ok = MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(&h, out, sizeof(double), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));   // the one read-back
+    if (!ok) return -1;
+    *bound = h;
+    return 0;
 }
 
 } // extern "C"

@@ -5,16 +5,17 @@
 
 namespace mgcg {
 
-struct RowsEpi { double w, b, dinv, yold; };
+struct RowsEpi { double w, b, dinv, yold, d; long long row; };   // d, row: the Chebyshev step, which stores d[row] itself
 
 template <int EPI>
 __device__ __forceinline__ RowsEpi rows_epi_prefetch(const SpmvArgs& a, long long row)
 {
-    RowsEpi o; o.w = 0.0; o.b = 0.0; o.dinv = 0.0; o.yold = 0.0;
+    RowsEpi o; o.w = 0.0; o.b = 0.0; o.dinv = 0.0; o.yold = 0.0; o.d = 0.0; o.row = row;
     if constexpr (EPI == EPI_AXPBY_BETA) o.yold = a.y[row];
     if constexpr (EPI == EPI_DOT) o.w = a.w[row];
     if constexpr (EPI == EPI_RESIDUAL || EPI == EPI_RESIDUAL_DOT) o.b = a.b[row];
-    if constexpr (EPI == EPI_JACOBI || EPI == EPI_JACOBI_DOT) { o.b = a.b[row]; o.dinv = a.dinvUniform ? a.dinvScalar : a.dinv[row]; o.w = a.w[row]; }
+    if constexpr (epi_is_jacobi(EPI) || epi_is_chebyshev(EPI)) { o.b = a.b[row]; o.dinv = a.dinvUniform ? a.dinvScalar : a.dinv[row]; o.w = a.w[row]; }
+    if constexpr (epi_is_chebyshev(EPI)) o.d = a.d[row];
     return o;
 }
 
@@ -26,6 +27,14 @@ __device__ __forceinline__ double rows_epilogue_value(const SpmvArgs& a, double 
     else if constexpr (EPI == EPI_DOT) { double t = o.w * acc; dotacc += t; return acc; }
     else if constexpr (EPI == EPI_RESIDUAL) return o.b - acc;
     else if constexpr (EPI == EPI_RESIDUAL_DOT) { double r = o.b - acc; double t = r * r; dotacc += t; return r; }
+    else if constexpr (epi_is_chebyshev(EPI)) {
+        // every product into a double of its own, then the add (the library is built without contraction): d = c1 d + c2 (dinv (r - A z)) ; z' = z + d
+        double res = o.b - acc; double t = o.dinv * res; double p = a.c1 * o.d; double q = a.c2 * t; const double dn = p + q;
+        a.d[o.row] = dn;
+        const double v = o.w + dn;
+        if constexpr (EPI == EPI_CHEBYSHEV_DOT) { double u = o.b * v; dotacc += u; }
+        return v;
+    }
     else {
         double res = o.b - acc; double t = o.dinv * res; double s = a.omega * t; const double v = o.w + s;
         if constexpr (EPI == EPI_JACOBI_DOT) { double q = o.b * v; dotacc += q; }

@@ -199,7 +199,8 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
     def Dispose(self):
         if getattr(self, "cublas", None):
             for v in (self.vectorElements, self.vectorColumnIndeces, self.vectorRowOffsets, self.vectorX, self.vectorB,
-                      self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None), getattr(self, "vectorS", None)):
+                      self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None), getattr(self, "vectorS", None),
+                      getattr(self, "vectorZ", None), getattr(self, "vectorZ2", None), getattr(self, "vectorD", None)):
                 if v is not None:
                     v.Dispose()
             if self._own_comm and self.comm:
@@ -354,6 +355,41 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if st != _lib.OK:
             check("SolveSingleReduceParallel")
             raise MgcgError(f"SolveSingleReduceParallel failed with status {st}")
+
+    def SolveChebyshev(self, trace: bool = False, jacobi: bool = False, degree: int = 4, bounds=None):
+        """Solve() on the Chebyshev-preconditioned loop (SolveChebyshevParallel).  bounds = (lambdaMin, lambdaMax) of A -- of D^-1 A with
+        jacobi=True (SetupJacobi() first) -- is required here: the bound of a partitioned matrix is the maximum over the ranks, which the
+        caller takes.  Every rank passes the same ``jacobi``, ``degree`` and ``bounds``."""
+        self._ensure_comm()
+        p = self.part
+        if bounds is None:
+            raise ValueError("SolveChebyshev: bounds = (lambdaMin, lambdaMax) is required on ranks")
+        lmin, lmax = float(bounds[0]), float(bounds[1])
+        if jacobi and (getattr(self, "vectorDinv", None) is None or getattr(self, "jacobiError", None) is not None):
+            raise MgcgError("SolveChebyshev(jacobi=True): SetupJacobi() has not set the diagonal up")
+        for name, size in (("vectorZ", self.Count), ("vectorZ2", self.Count), ("vectorD", p.count)):
+            if getattr(self, name, None) is None or getattr(self, name).size < size:
+                setattr(self, name, VectorDouble(size))
+        iteration, residual = C.c_int(0), C.c_double(0.0)
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        st = lib().SolveChebyshevParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
+                                          self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                          self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                          self.vectorDinv.Ptr if jacobi else None, self.vectorZ.Ptr, self.vectorZ2.Ptr, self.vectorD.Ptr,
+                                          self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
+                                          int(degree), lmin, lmax,
+                                          self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
+                                          C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"Chebyshev-preconditioned CG did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveChebyshevParallel")
+            raise MgcgError(f"SolveChebyshevParallel failed with status {st}")
 
     @staticmethod
     def LastOverlap():

@@ -542,6 +542,67 @@ int SolveSingleReduceParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusp
                               double allowableResidual, int minIteration, int maxIteration, int rule,
                               int* iteration, double* residual, double* residualTrace, int traceCapacity);
 
+/* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
+/* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
+ * MgcgJacobiSetup wrote) is given: Gershgorin's upper bound of the spectrum of A (of D^-1 A), rigorous, usually within a small factor
+ * of lambda_max for diagonally dominant matrices.  Each row is summed in stored order from +0.0 on the device; one read-back.  An
+ * empty local slice gives 0; several ranks take the maximum of their bounds themselves.  Returns 0 on success, -1 with a message. */
+int MgcgGershgorinBound(MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        int elementsCount, int countForDevice, int offsetForDevice, Vector* dinvVector /* may be NULL */, double* bound);
+/* SolveJacobi's loop with z = M r, M = p_m(B) D^-1 the Chebyshev polynomial of degree m - 1 in B = D^-1 A for the interval
+ * [lambdaMin, lambdaMax] (D = I, B = A when dinvVector is NULL).  One iteration carries m products and still two global sums: the
+ * polynomial needs no sum at all, and one of its steps is ONE launch (the product with the step fused into its epilogue).  One rank:
+ * m + 3 launches per iteration (product, first pass, m - 1 steps, finalisation, x / p update).
+ * Bounds and coefficients: 0 < lambdaMin < lambdaMax, both finite; degree m = 1 .. 16.  The host computes, once per call, in double
+ * precision and in exactly this order
+ *   theta = (lmax + lmin) * 0.5 ; delta = (lmax - lmin) * 0.5 ; sigma = theta / delta ; rho_0 = 1 / sigma ; it = 1 / theta
+ *   j = 1 .. m-1:  rho_j = 1 / (2*sigma - rho_{j-1}) ; c1_j = rho_j * rho_{j-1} ; c2_j = (2 * rho_j) / delta
+ * and hands the coefficients to the kernels as arguments.
+ * Applying z = M r (every product is rounded into a double of its own before the add that follows it, nothing is fused):
+ *   first   u_i = dinv_i * r_i (u_i = r_i without dinv) ; d_i = it * u_i ; z_i = d_i
+ *   step j  acc_i = row i of A z, summed in stored order from +0.0 ; res = r_i - acc_i ; t = dinv_i * res (t = res without dinv)
+ *           a = c1_j * d_i ; b = c2_j * t ; d_i = a + b ; z'_i = z_i + d_i          (z' is another buffer than z: rows gather z)
+ *   the terms of r.z are r_i * z_i of the last z.
+ * The outer loop: alpha = r.z / p.Ap ; r = r + (-alpha) Ap ; beta = r.z_new / r.z ; p = z + beta p ; x += alpha p, with SolveJacobi's
+ * rounding.  The stop rules, the trace, *iteration and *residual are SolveJacobi's and test the TRUE residual; MGCG_RULE_HANDMADECL is
+ * refused with MGCG_ERROR before anything is enqueued.  Under dot_order = 1 every sum is serial left to right and ranks add in rank order.
+ * With m = 1 and bounds that make theta exactly 1.0 (0.5 and 1.5, say) z is D^-1 r bit for bit and the call returns SolveJacobi's x,
+ * trace, iteration and residual exactly.
+ * Breakdown: a p.Ap or an r.z that is not finite and > 0 ends the loop with MGCG_NONFINITE before that iteration's updates.  x keeps
+ * the last completed iterate -- at the start the caller's x bit for bit (MGCG_RULE_SIMPLE: zero) -- *iteration is the iteration that
+ * could not run, and *residual and its trace entry repeat the last judged residual.  The r.z of iteration k + 1 is formed at the end of
+ * iteration k, behind k's stop test: when it breaks down, iteration k is complete (its x term applied, rVector its residual) and the
+ * call reports iteration k + 1.  An upper bound BELOW the true lambda_max can make M indefinite, and a negative r.z is how that shows:
+ * put a margin on an estimate that approaches lambda_max from below (a Lanczos value), or use MgcgGershgorinBound.  A lambdaMin above
+ * the true lambda_min only costs iterations.  b = 0 from x = 0 gives r.z = 0 and MGCG_NONFINITE at iteration 0.
+ *   dinvVector      what MgcgJacobiSetup wrote, or NULL; with it the bounds are bounds of D^-1 A
+ *   zVector, z2Vector, dVector   work space with an internal layout (count entries each)
+ * The steps always read the matrix as plain CSR, whatever the handle's compression mode (the lossless forms give the same bits); the
+ * loop's own product p -> Ap is SolveEx's, so compression modes and the automatic column tiles apply to it.  The deferred x update
+ * (x_defer) and the placement draw do not apply.  Out of scope: the step in the column-tile and propagation-blocking forms, the
+ * V-cycle or the single-reduction loop combined with the polynomial, the block, shifted and mixed variants. */
+int SolveChebyshev(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                   Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                   Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector /* may be NULL */,
+                   Vector* zVector, Vector* z2Vector, Vector* dVector,
+                   int elementsCount, int count, int degree, double lambdaMin, double lambdaMax,
+                   double allowableResidual, int minIteration, int maxIteration, int rule,
+                   int* iteration, double* residual, double* residualTrace, int traceCapacity);
+/* The same on a row partition, shaped after SolveJacobiParallel.  pVector, zVector and z2Vector are full length (count entries): rows
+ * gather them, and the halo of z is exchanged in line before every step (the overlap schedule is not used by this loop); dVector and the
+ * other vectors hold the local rows.  p.Ap travels in one all-reduce, r.r and r.z in ONE all-reduce of two doubles behind the
+ * polynomial: the stop decision of an iteration is taken behind its polynomial, which costs one wasted application at the very end,
+ * and x is the judged iterate.  A rank without rows takes part in every collective.  Every rank must pass the same degree and bounds,
+ * and a dinvVector or none: that is not checked.  Every other unusable argument on one rank makes every rank return MGCG_ERROR. */
+int SolveChebyshevParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                           Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                           Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector /* may be NULL */,
+                           Vector* zVector, Vector* z2Vector, Vector* dVector,
+                           int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                           int degree, double lambdaMin, double lambdaMax,
+                           double allowableResidual, int minIteration, int maxIteration, int rule,
+                           int* iteration, double* residual, double* residualTrace, int traceCapacity);
+
 /* ---- Multi-shift CG: (A + shifts[j] I) x_j = b for k = 1 .. 8 shifts >= 0 from ONE CG recurrence on A (one rank, no preconditioner) ---- */
 /* Krylov spaces are shift-invariant: the residual of every shifted system is collinear with the base residual, r_j = zeta_j r, so an
  * iteration is SolveEx's product and r update plus ONE fused vector pass for all columns -- three launches, one matrix pass, whatever k
