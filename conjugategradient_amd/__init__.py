@@ -4,6 +4,7 @@
 ``solver``    LinerEquations / ConjugateGradient / ...SingleGpu / ...ParallelGpu (reference class surface)
 ``parallel``  one-process-per-GPU driver (RCCL inside the library; torch.distributed bootstrap)
 ``multigrid`` the V-cycle preconditioner the reference named but never wrote
+``amg``       the same V-cycle for ANY CSR matrix: aggregates from the matrix graph (MgSetupAggregation) or from the caller
 ``jacobi``    Jacobi-preconditioned CG for general CSR matrices (the call the ViennaCL front-end left commented out)
 ``singlereduce`` single-reduction (Chronopoulos-Gear) CG: one global sum and two launches per iteration, with or without the diagonal
 ``chebyshev`` Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, m products and two global sums per iteration
@@ -12,4 +13,4 @@
 ``mixed``     mixed-precision CG: an fp32 recurrence corrected by fp64 reliable updates, fp64-accurate x and stop test
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "jacobi", "singlereduce", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "jacobi", "singlereduce", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]

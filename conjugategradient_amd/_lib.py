@@ -102,6 +102,9 @@ SIGNATURES = {
     "CsrMVBlock": (None, [_vp] * 7 + [_i, _i, _i]),
     "MgSetup": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _i, _d]),
     "MgSetupParallel": (_vp, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _d]),
+    "MgSetupAggregation": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _i, _d, _i, _i, _d]),
+    "MgSetupAggregates": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _i, _i, _d]),
+    "MgLevelCopyAggregates": (_i, [_vp, _i, _vp]),
     "MgDestroy": (None, [_vp]),
     "MgSetInterpolation": (_i, [_vp, _i]),
     "MgLevels": (_i, [_vp]),

@@ -1,0 +1,75 @@
+"""Aggregation multigrid (``MgSetupAggregation`` / ``MgSetupAggregates``): the V-cycle preconditioner of ``multigrid`` for any CSR matrix.
+
+The hierarchy is the one of ``ConjugateGradientMgGpu`` -- piecewise-constant transfer, coarse operators sigma * P^T A P, weighted Jacobi --
+with the aggregates taken from the matrix graph by a deterministic parallel matching (include/MgcgGpu.h writes the algorithm out;
+tests/test_amg_host.py states it in numpy) instead of 2x2x2 boxes of a grid, so the matrix needs no grid and no row order: a permuted
+stencil, a mesh or particle matrix, a graph Laplacian with jumping weights.  ``aggregates`` hands the library the caller's own maps.
+One GPU; ``omega`` is the caller's (omega * lambda_max(D^-1 A) < 2 keeps the preconditioner positive definite).  No arithmetic on
+vectors happens here.
+"""
+from __future__ import annotations
+
+
+import numpy as np
+
+from . import _lib
+from ._lib import MgcgError, check, lib
+from .multigrid import ConjugateGradientMgGpu
+from .solver import _ptr
+
+
+class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
+    """ConjugateGradientMgGpu without ``grid``: ``Apply``, ``Solve(trace=...)``, ``level_csr`` and ``level_dinv`` are the parent's.
+
+    ``aggregates``: None (the library's matching: ``passes`` passes per level at strength threshold ``theta``, at most ``levels`` levels,
+    none built from a level of ``minCoarse`` rows or fewer) or a list of per-level maps, ``aggregates[l][i]`` = the aggregate of row i of
+    level l; the hierarchy then has ``len(aggregates) + 1`` levels and the last map's largest id + 1 rows on its last level."""
+
+    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual,
+                 levels: int = 8, passes: int = 3, theta: float = 0.25, minCoarse: int = 64, omega: float = 0.8, nu: int = 1, nuCoarse: int = 4,
+                 sigma: float = 0.5, aggregates=None, rule=_lib.RULE_CSHARP):
+        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, (count, 1, 1),
+                         levels=levels, omega=omega, nu=nu, nuCoarse=nuCoarse, sigma=sigma, rule=rule)
+        self.passes, self.theta, self.minCoarse = int(passes), float(theta), int(minCoarse)
+        self.aggregates = None if aggregates is None else [np.ascontiguousarray(m, dtype=np.int32) for m in aggregates]
+
+    def InitializePoisson(self, grid, b_value: float = 1.0, x_value: float = 0.0):
+        """The parent's device generator for the 5/7-point matrix of ``grid`` (the hierarchy is built from the matrix alone)."""
+        saved, self.grid = self.grid, tuple(int(g) for g in grid)
+        try:
+            super().InitializePoisson(b_value, x_value)
+        finally:
+            self.grid = saved
+
+    def Setup(self):
+        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
+        L = lib()
+        if self.mg:
+            L.MgDestroy(self.mg)
+            self.mg = None
+        matrix = (self.cublas, self.cusparse, self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr, nonzeroCount, self.Count)
+        if self.aggregates is None:
+            name = "MgSetupAggregation"
+            self.mg = L.MgSetupAggregation(*matrix, int(self.levels_requested), self.passes, self.theta, self.minCoarse,
+                                           self.omega, self.nu, self.nuCoarse, self.sigma)
+        else:
+            name = "MgSetupAggregates"
+            maps = self.aggregates
+            if maps and len(maps[0]) != self.Count:
+                raise MgcgError(f"aggregates[0] holds {len(maps[0])} ids, the matrix has {self.Count} rows")
+            rows = [self.Count] + [len(m) for m in maps[1:]] + ([int(maps[-1].max()) + 1] if maps else [])
+            levelRows = np.asarray(rows, dtype=np.int32)
+            flat = np.ascontiguousarray(np.concatenate(maps), dtype=np.int32) if maps else np.zeros(1, dtype=np.int32)
+            self.mg = L.MgSetupAggregates(*matrix, len(rows), _ptr(levelRows), _ptr(flat), self.omega, self.nu, self.nuCoarse, self.sigma)
+        check(name)
+        if not self.mg:
+            raise MgcgError(f"{name} returned NULL")
+        self.levels = L.MgLevels(self.mg)
+
+    def level_aggregates(self, l: int) -> np.ndarray:
+        """The map of level ``l`` to level ``l + 1`` (MgcgError on the last level)."""
+        m = np.empty(lib().MgLevelRows(self.mg, l), dtype=np.int32)
+        if lib().MgLevelCopyAggregates(self.mg, l, _ptr(m)) != 0:
+            check("MgLevelCopyAggregates")
+            raise MgcgError("MgLevelCopyAggregates failed")
+        return m

@@ -113,7 +113,7 @@ bool select_device_only();       // hipSetDevice for the calling thread's device
 inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (void)hipFuncGetAttributes(&at, kernel); }
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
-void preload_kernels_mg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
+void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
 void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb();
 
 // Device scalars of one CG run (lives in the handle's workspace).
@@ -697,6 +697,23 @@ void launch_rebase(hipStream_t s, int* rowOffsets, long long n, int base);
 long long poisson_nnz_host(int nx, int ny, int nz, int zBegin, int zEnd);
 void launch_minmax_int(hipStream_t s, const int* v, long long n, int* out2 /* device int[2] */);
 void launch_halo_rows(hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long n, long long offset, int* out2 /* {0, n} */);
+
+// ---------------------------------------------------------------- aggregation multigrid kernels (kernels_amg.hip)
+// the cycle's indexed transfer: bc[I] = serial sum of r over members[aggOffsets[I] .. aggOffsets[I+1]) from +0.0; x[i] += e[agg[i]]
+void launch_amg_restrict(hipStream_t s, long long nc, const int* aggOffsets, const int* members, const double* r, double* bc, const int* done);
+void launch_amg_prolong_add(hipStream_t s, long long n, const int* agg, double* x, const double* e, const int* done);
+// *badRow (pre-set to INT_MAX) = the smallest row whose diagonal is not stored, not finite or not positive
+void launch_amg_check_diagonal(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long n, int* badRow);
+// one matching pass: the row maxima once, then rounds (pick + match; flags2 pre-set to {0, 0}: {some row picked, some pair formed}); match pre-set to -1
+void launch_amg_row_max(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long n, double* rowMax);
+void launch_amg_match_round(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, long long n, double theta,
+                            const double* rowMax, int* match, int* pick, int* flags2);
+// sigma * P^T A P for a map: count pass (unique coarse columns per row, left sorted in the row's scratch segment), then the fill pass
+void launch_amg_galerkin_count(hipStream_t s, long long nc, const int* aggOffsets, const int* members, const int* rowOffsets, const int* columnIndeces,
+                               const int* agg, const int* expandOffsets, int* scratch, int* counts);
+void launch_amg_galerkin_fill(hipStream_t s, long long nc, const int* aggOffsets, const int* members, const double* elements, const int* rowOffsets,
+                              const int* columnIndeces, const int* agg, const int* expandOffsets, const int* scratch, const int* rowOffsetsC, double sigma,
+                              double* elementsC, int* columnIndecesC);
 
 // ---------------------------------------------------------------- RCCL (dlopen'ed)
 struct CommImpl;

@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include <algorithm>
 #include <chrono>
+#include <functional>
 
 namespace mgcg {
 
@@ -45,6 +46,11 @@ struct MgLevel {
     HaloPlan* bHalo = nullptr;
     double* extElements = nullptr; int* extRowOffsets = nullptr; int* extColumnIndeces = nullptr; double* extDinv = nullptr;
     long long extRows = 0, extNnz = 0, extBase = 0;   // rows of the extended slab, its nonzeros, global index of its first row
+    // Aggregation hierarchy (MgSetupAggregation / MgSetupAggregates; one rank), every level but the last: the map to the next level and its
+    // inverted index.  Such a level is a "grid" of n x 1 x 1 cells, and a level that has a map never reaches the grid-addressed kernels.
+    int* agg = nullptr;                    // n: row -> aggregate
+    int* aggOffsets = nullptr;             // rows of the next level + 1
+    int* aggMembers = nullptr;             // n: the members of aggregate I, ascending, at [aggOffsets[I], aggOffsets[I + 1])
 };
 
 } // namespace mgcg
@@ -76,6 +82,7 @@ struct MgcgMg {
     double* rExt = nullptr;                // plane + n + plane doubles; the loop's r = rExt + plane
     bool deepFolds = false;                // levels >= 1 form x_1 and x_1 + P e per gather too (uniform diagonals, power-of-two nx and ny)
     bool skipHalo = false;                 // the next SpMV-shaped pass finds its halo planes already in place (deep-halo cycle: formed locally)
+    bool algebraic = false;                // built from aggregates of the matrix graph, not from a grid (also when it has a single level)
 };
 
 namespace mgcg {
@@ -346,6 +353,21 @@ static bool mg_vcycle(MgcgMg* mg, int l, const double* b, double* x0, double* x1
     if (l == mg->levels - 1) return mg_smooth(mg, L, b, x0, x1, mg->nuCoarse, true, done, result, l == 0);
     MgLevel& C = mg->lv[l + 1];
     double* cur = nullptr;
+    if (L.agg != nullptr) {
+        // a level of an aggregation hierarchy: the stored cycle with the indexed transfer (the folded forms address parents by bit fields
+        // of grid indices).  One rank: nothing travels.
+        if (!mg_smooth(mg, L, b, x0, x1, mg->nu, true, done, &cur)) return false;
+        double* spare = (cur == x0) ? x1 : x0;
+        SpmvArgs ar{};
+        ar.elements = L.elements; ar.rowOffsets = L.rowOffsets; ar.columnIndeces = L.columnIndeces; ar.x = cur; ar.y = L.r;
+        ar.elementsCount = (int)L.nnz; ar.rowCount = (int)L.n; ar.columnCount = (int)L.nGlobal; ar.b = b; ar.doneFlag = done;
+        if (!mg_spmv(mg, L, EPI_RESIDUAL, ar, cur)) return false;                              // r = b - A x
+        launch_amg_restrict(mg->stream, C.n, L.aggOffsets, L.aggMembers, L.r, C.b, done);      // b_c = P^T r
+        double* ec = nullptr;
+        if (!mg_vcycle(mg, l + 1, C.b, C.xa, C.xb, done, &ec)) return false;
+        launch_amg_prolong_add(mg->stream, L.n, L.agg, cur, ec, done);                         // x += P e
+        return mg_smooth(mg, L, b, cur, spare, mg->nu, false, done, result, l == 0);
+    }
     // V(1,*) on one rank with a uniform diagonal: the first sweep x1 = omega (d0 b) is not stored; the residual pass forms x1[col] per
     // gather (row-pattern form, or the row-tile kernel on plain CSR) and the prolongation forms x1[i] again when it adds the correction
     const bool linear = mg->interp == 1;
@@ -2045,6 +2067,281 @@ MgcgMg* MgSetup(MgcgBlas* cublas, MgcgSparse* cusparse,
                            nx, ny, nz, 0, nz, levels, omega, nu, nuCoarse, sigma);
 }
 
+// ---------------------------------------------------------------- aggregation multigrid: set-up
+// The hierarchy of MgSetupParallel with the aggregates taken from the matrix graph (or from the caller) instead of 2x2x2 boxes of a grid; the
+// algorithm is written out in include/MgcgGpu.h.  Index bookkeeping -- the scan of a map into aggregate numbers, its counting sort into member
+// lists, the scans of row lengths, one flag pair per matching round -- runs on the host, as MgSetupParallel's scan does; every matrix value is
+// formed on the device and none travels to the host.
+namespace mgcg {
+
+struct AmgDeviceMap { int* agg = nullptr; int* aggOffsets = nullptr; int* members = nullptr; };
+static void amg_free(AmgDeviceMap& m)
+{
+    if (m.agg) (void)hipFree(m.agg);
+    if (m.aggOffsets) (void)hipFree(m.aggOffsets);
+    if (m.members) (void)hipFree(m.members);
+    m = AmgDeviceMap();
+}
+struct AmgMatrix { double* elements = nullptr; int* rowOffsets = nullptr; int* columnIndeces = nullptr; long long n = 0, nnz = 0; };
+static void amg_free(AmgMatrix& m)
+{
+    if (m.elements) (void)hipFree(m.elements);
+    if (m.rowOffsets) (void)hipFree(m.rowOffsets);
+    if (m.columnIndeces) (void)hipFree(m.columnIndeces);
+    m = AmgMatrix();
+}
+
+// out = sigma * P^T A P for the map `map` (row -> aggregate, nc aggregates, none empty) in the contract's order; *dev receives the map and its
+// inverted index on the device (the caller frees both results, also after a failure)
+static bool amg_galerkin(hipStream_t s, const AmgMatrix& A, const std::vector<int>& map, int nc, double sigma, AmgMatrix* out, AmgDeviceMap* dev)
+{
+    const size_t n = (size_t)A.n;
+    std::vector<int> ro(n + 1), offs((size_t)nc + 1, 0), members(n), expand((size_t)nc + 1, 0);
+    if (!MGCG_HIP(hipMemcpyAsync(ro.data(), A.rowOffsets, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s)) || !MGCG_HIP(hipStreamSynchronize(s))) return false;
+    for (size_t i = 0; i < n; ++i) offs[(size_t)map[i] + 1]++;
+    for (int I = 0; I < nc; ++I) offs[(size_t)I + 1] += offs[(size_t)I];
+    {
+        std::vector<int> at(offs.begin(), offs.end() - 1);
+        for (size_t i = 0; i < n; ++i) members[(size_t)at[(size_t)map[i]]++] = (int)i;                  // ascending within every aggregate
+    }
+    long long run = 0;
+    for (int I = 0; I < nc; ++I) {
+        for (int m = offs[(size_t)I]; m < offs[(size_t)I + 1]; ++m) { const size_t i = (size_t)members[(size_t)m]; run += ro[i + 1] - ro[i]; }
+        expand[(size_t)I + 1] = (int)run;
+    }
+    const size_t scratchLen = (size_t)(run > 0 ? run : 1), ncAlloc = (size_t)(nc > 0 ? nc : 1);
+    int *dExpand = nullptr, *scratch = nullptr, *counts = nullptr;
+    out->n = nc;
+    bool ok = MGCG_HIP(hipMalloc((void**)&dev->agg, sizeof(int) * (n > 0 ? n : 1))) && MGCG_HIP(hipMalloc((void**)&dev->aggOffsets, sizeof(int) * ((size_t)nc + 1))) &&
+              MGCG_HIP(hipMalloc((void**)&dev->members, sizeof(int) * (n > 0 ? n : 1))) && MGCG_HIP(hipMalloc((void**)&dExpand, sizeof(int) * ((size_t)nc + 1))) &&
+              MGCG_HIP(hipMalloc((void**)&scratch, sizeof(int) * scratchLen)) && MGCG_HIP(hipMalloc((void**)&counts, sizeof(int) * ncAlloc)) &&
+              MGCG_HIP(hipMalloc((void**)&out->rowOffsets, sizeof(int) * ((size_t)nc + 1)));
+    ok = ok && MGCG_HIP(hipMemcpyAsync(dev->agg, map.data(), sizeof(int) * n, hipMemcpyHostToDevice, s)) &&
+         MGCG_HIP(hipMemcpyAsync(dev->aggOffsets, offs.data(), sizeof(int) * ((size_t)nc + 1), hipMemcpyHostToDevice, s)) &&
+         MGCG_HIP(hipMemcpyAsync(dev->members, members.data(), sizeof(int) * n, hipMemcpyHostToDevice, s)) &&
+         MGCG_HIP(hipMemcpyAsync(dExpand, expand.data(), sizeof(int) * ((size_t)nc + 1), hipMemcpyHostToDevice, s));
+    std::vector<int> roC((size_t)nc + 1, 0);
+    if (ok) {
+        launch_amg_galerkin_count(s, nc, dev->aggOffsets, dev->members, A.rowOffsets, A.columnIndeces, dev->agg, dExpand, scratch, counts);
+        ok = MGCG_HIP(hipMemcpyAsync(roC.data() + 1, counts, sizeof(int) * (size_t)nc, hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    }
+    if (ok) {
+        long long total = 0;
+        for (int I = 1; I <= nc; ++I) { total += roC[(size_t)I]; roC[(size_t)I] = (int)total; }
+        out->nnz = total;
+        const size_t nzAlloc = (size_t)(total > 0 ? total : 1);
+        ok = MGCG_HIP(hipMemcpyAsync(out->rowOffsets, roC.data(), sizeof(int) * ((size_t)nc + 1), hipMemcpyHostToDevice, s)) &&
+             MGCG_HIP(hipMalloc((void**)&out->elements, sizeof(double) * nzAlloc)) && MGCG_HIP(hipMalloc((void**)&out->columnIndeces, sizeof(int) * nzAlloc));
+        if (ok) launch_amg_galerkin_fill(s, nc, dev->aggOffsets, dev->members, A.elements, A.rowOffsets, A.columnIndeces, dev->agg, dExpand, scratch,
+                                         out->rowOffsets, sigma, out->elements, out->columnIndeces);
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;           // (the host staging vectors must outlive the copies)
+    if (dExpand) (void)hipFree(dExpand);
+    if (scratch) (void)hipFree(scratch);
+    if (counts) (void)hipFree(counts);
+    return ok;
+}
+
+// One matching pass on A: map[i] = the aggregate of row i (pairs and singletons, numbered by their smallest member), *nc = how many
+static bool amg_matching_pass(hipStream_t s, const AmgMatrix& A, double theta, std::vector<int>& map, int* nc)
+{
+    const size_t n = (size_t)A.n, nAlloc = n > 0 ? n : 1;
+    double* rowMax = nullptr; int *match = nullptr, *pick = nullptr, *flags = nullptr;
+    bool ok = MGCG_HIP(hipMalloc((void**)&rowMax, sizeof(double) * nAlloc)) && MGCG_HIP(hipMalloc((void**)&match, sizeof(int) * nAlloc)) &&
+              MGCG_HIP(hipMalloc((void**)&pick, sizeof(int) * nAlloc)) && MGCG_HIP(hipMalloc((void**)&flags, 2 * sizeof(int))) &&
+              MGCG_HIP(hipMemsetAsync(match, 0xff, sizeof(int) * nAlloc, s));
+    if (ok) launch_amg_row_max(s, A.elements, A.rowOffsets, A.columnIndeces, A.n, rowMax);
+    // a round pairs at least the largest remaining edge of a symmetric matrix, so n / 2 rounds is the most there can be; a round in which rows
+    // picked and none paired (an unsymmetric matrix: not checked) ends the pass as well
+    for (long long round = 0; ok && n > 0 && round <= (long long)n / 2; ++round) {
+        int h[2] = { 0, 0 };
+        ok = MGCG_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), s));
+        if (ok) launch_amg_match_round(s, A.elements, A.rowOffsets, A.columnIndeces, A.n, theta, rowMax, match, pick, flags);
+        ok = ok && MGCG_HIP(hipMemcpyAsync(h, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+        if (!h[0] || !h[1]) break;
+    }
+    std::vector<int> m(n);
+    ok = ok && (n == 0 || (MGCG_HIP(hipMemcpyAsync(m.data(), match, sizeof(int) * n, hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s))));
+    if (rowMax) (void)hipFree(rowMax);
+    if (match) (void)hipFree(match);
+    if (pick) (void)hipFree(pick);
+    if (flags) (void)hipFree(flags);
+    if (!ok) return false;
+    map.assign(n, 0);
+    int next = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int j = m[i];
+        if (j >= 0 && (size_t)j < i) map[i] = map[(size_t)j];     // the smaller member has numbered the pair
+        else map[i] = next++;
+    }
+    *nc = next;
+    return true;
+}
+
+// The map of one level: `passes` matching passes, pass p > 1 on the unscaled Galerkin matrix of pass p - 1, composed
+static bool amg_level_map(hipStream_t s, const AmgMatrix& A, int passes, double theta, std::vector<int>& map, int* nc)
+{
+    AmgMatrix cur = A, owned;
+    bool ok = true;
+    for (int p = 1; ok && p <= passes; ++p) {
+        std::vector<int> m; int c = 0;
+        ok = amg_matching_pass(s, cur, theta, m, &c);
+        if (!ok) break;
+        if (p == 1) map = m;
+        else for (int& v : map) v = m[(size_t)v];
+        *nc = c;
+        if (c == cur.n || p == passes) break;             // nothing matched: every later pass would see the same graph
+        AmgMatrix next; AmgDeviceMap dm;
+        ok = amg_galerkin(s, cur, m, c, 1.0, &next, &dm);
+        amg_free(dm);
+        amg_free(owned);
+        owned = next; cur = next;
+    }
+    amg_free(owned);
+    return ok;
+}
+
+// nextMap(l, A_l, map, &nc): 1 = `map` holds level l's aggregates (nc of them), 0 = the hierarchy ends with level l, -1 = error (message set)
+typedef std::function<int(int, const AmgMatrix&, std::vector<int>&, int*)> AmgNextMap;
+static MgcgMg* amg_setup(const char* who, MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                         int elementsCount, int count, int levels, double omega, int nu, int nuCoarse, double sigma, const AmgNextMap& nextMap)
+{
+    DeviceState* d = device_state();
+    if (!d) return nullptr;
+    hipStream_t s = d->stream;
+    MgcgMg* mg = new MgcgMg();
+    mg->omega = omega; mg->nu = nu; mg->nuCoarse = nuCoarse; mg->sigma = sigma; mg->stream = s; mg->cfg = cfg_of(cusparse);
+    mg->cfg.kernel = 0;   // every level picks its kernel from its own nnz/row
+    mg->algebraic = true;
+    int* dflag = nullptr;
+    bool ok = MGCG_HIP(hipMalloc((void**)&dflag, sizeof(int)));
+    AmgMatrix A; A.elements = elementsVector->data; A.rowOffsets = rowOffsetsVector->data; A.columnIndeces = columnIndecesVector->data; A.n = count; A.nnz = elementsCount;
+    for (int l = 0; ok && l < levels; ++l) {
+        MgLevel L;
+        L.nx = (int)A.n; L.ny = 1; L.nz = 1; L.z0 = 0; L.z1 = 1;
+        L.n = A.n; L.nGlobal = A.n; L.offset = 0; L.nnz = A.nnz;
+        L.elements = A.elements; L.rowOffsets = A.rowOffsets; L.columnIndeces = A.columnIndeces; L.ownsMatrix = l > 0;
+        int bad = 0x7fffffff;
+        ok = MGCG_HIP(hipMemcpyAsync(dflag, &bad, sizeof(int), hipMemcpyHostToDevice, s));
+        if (ok) launch_amg_check_diagonal(s, L.elements, L.rowOffsets, L.columnIndeces, L.n, dflag);
+        ok = ok && MGCG_HIP(hipMemcpyAsync(&bad, dflag, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+        if (ok && bad != 0x7fffffff) { set_error("%s: level %d, row %d: the diagonal must be stored, finite and > 0", who, l, bad); ok = false; }
+        ok = ok && MGCG_HIP(hipMalloc((void**)&L.dinv, sizeof(double) * (size_t)L.n));
+        ok = ok && MGCG_HIP(hipMalloc((void**)&L.xa, sizeof(double) * (size_t)L.n));
+        ok = ok && MGCG_HIP(hipMalloc((void**)&L.r, sizeof(double) * (size_t)L.n));
+        if (l > 0) ok = ok && MGCG_HIP(hipMalloc((void**)&L.xb, sizeof(double) * (size_t)L.n)) && MGCG_HIP(hipMalloc((void**)&L.b, sizeof(double) * (size_t)L.n));
+        if (ok) launch_extract_dinv(s, L.elements, L.rowOffsets, L.columnIndeces, L.n, 0, L.dinv);
+        if (ok) {                                         // constant-coefficient operators: one diagonal for all rows (as MgSetupParallel)
+            int differs = 1;
+            ok = MGCG_HIP(hipMemsetAsync(dflag, 0, sizeof(int), s));
+            if (ok) launch_uniform_check(s, L.dinv, L.n, dflag);
+            ok = ok && MGCG_HIP(hipMemcpyAsync(&differs, dflag, sizeof(int), hipMemcpyDeviceToHost, s)) &&
+                 MGCG_HIP(hipMemcpyAsync(&L.dinvScalar, L.dinv, sizeof(double), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+            L.dinvUniform = ok && differs == 0;
+        }
+        if (ok) L.dcsr = dcsr_lookup(cusparse, L.elements, L.rowOffsets, L.columnIndeces, L.n, L.nnz, 0);
+        L.cfg = mg->cfg;
+        if (ok && L.nnz >= 8) (void)spmv_period(cusparse, L.rowOffsets, L.columnIndeces, L.n, 0, &L.cfg.maxRow);
+        L.cfg.periodRows = 0;                             // no grid plane: the banded schedule has nothing to go by
+        mg->lv.push_back(L);                              // (also a level that failed: MgDestroy frees what it had allocated)
+        if (!ok) break;
+        mg->levels = (int)mg->lv.size();
+        if (l + 1 >= levels) break;
+        std::vector<int> map; int nc = 0;
+        const int made = nextMap(l, A, map, &nc);
+        if (made < 0) { ok = false; break; }
+        if (made == 0) break;
+        AmgMatrix C; AmgDeviceMap dm;
+        ok = amg_galerkin(s, A, map, nc, sigma, &C, &dm);
+        MgLevel& F = mg->lv.back();
+        F.agg = dm.agg; F.aggOffsets = dm.aggOffsets; F.aggMembers = dm.members;
+        if (!ok) { amg_free(C); break; }
+        if (C.nnz >= 0x7fffffffLL) { set_error("%s: level %d exceeds int32 offsets", who, l + 1); amg_free(C); ok = false; break; }
+        A = C;                                            // the next turn of the loop hands it to its level (which MgDestroy frees, built or not)
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (dflag) (void)hipFree(dflag);
+    if (!ok || mg->levels == 0) { MgDestroy(mg); return nullptr; }
+    return mg;
+}
+
+static bool amg_common_arguments(const char* who, MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                                 int elementsCount, int count, int levels, int nu, int nuCoarse)
+{
+    if (!cublas || !cusparse || !elementsVector || !rowOffsetsVector || !columnIndecesVector) { set_error("%s: null handle", who); return false; }
+    if (levels < 1) { set_error("%s: levels %d, must be >= 1", who, levels); return false; }
+    if (count < 1 || elementsCount < 0 || nu < 1 || nuCoarse < 1) { set_error("%s: bad parameters (count %d, elementsCount %d, nu %d, nuCoarse %d)", who, count, elementsCount, nu, nuCoarse); return false; }
+    if (rowOffsetsVector->size < (long long)count + 1 || elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount) {
+        set_error("%s: matrix vectors too small (%lld values, %lld offsets, %lld columns for %d entries in %d rows)", who, (long long)elementsVector->size,
+                  (long long)rowOffsetsVector->size, (long long)columnIndecesVector->size, elementsCount, count);
+        return false;
+    }
+    return true;
+}
+
+} // namespace mgcg
+
+MgcgMg* MgSetupAggregation(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                           int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
+                           double omega, int nu, int nuCoarse, double sigma)
+{
+    const char* who = "MgSetupAggregation";
+    if (!amg_common_arguments(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, nu, nuCoarse)) return nullptr;
+    if (passes < 1 || passes > 4) { set_error("%s: passes %d, must be 1 .. 4", who, passes); return nullptr; }
+    if (!(theta > 0.0 && theta <= 1.0)) { set_error("%s: theta %g, must be in (0, 1]", who, theta); return nullptr; }
+    DeviceState* d = device_state();
+    if (!d) return nullptr;
+    hipStream_t s = d->stream;
+    auto nextMap = [&](int, const AmgMatrix& A, std::vector<int>& map, int* nc) -> int {
+        if (A.n <= minCoarse) return 0;
+        if (!amg_level_map(s, A, passes, theta, map, nc)) return -1;
+        return (4LL * *nc > 3LL * A.n) ? 0 : 1;           // the next level would keep more than 3/4 of the rows ("nothing matched" included)
+    };
+    return amg_setup(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, omega, nu, nuCoarse, sigma, nextMap);
+}
+
+MgcgMg* MgSetupAggregates(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                          int elementsCount, int count, int levels, const int levelRows[], const int aggregateOf[],
+                          double omega, int nu, int nuCoarse, double sigma)
+{
+    const char* who = "MgSetupAggregates";
+    if (!amg_common_arguments(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, nu, nuCoarse)) return nullptr;
+    if (!levelRows || (levels > 1 && !aggregateOf)) { set_error("%s: null handle", who); return nullptr; }
+    if (levelRows[0] != count) { set_error("%s: levelRows[0] is %d, the matrix has %d rows", who, levelRows[0], count); return nullptr; }
+    std::vector<long long> first((size_t)levels, 0);      // where level l's map begins in aggregateOf
+    for (int l = 0; l + 1 < levels; ++l) {
+        const int n = levelRows[l], nc = levelRows[l + 1];
+        if (nc < 1 || nc > n) { set_error("%s: levelRows[%d] is %d, must be 1 .. %d", who, l + 1, nc, n); return nullptr; }
+        const int* map = aggregateOf + first[(size_t)l];
+        std::vector<char> seen((size_t)nc, 0);
+        for (int i = 0; i < n; ++i) {
+            if (map[i] < 0 || map[i] >= nc) { set_error("%s: level %d, row %d: aggregate id %d out of range (the next level has %d rows)", who, l, i, map[i], nc); return nullptr; }
+            seen[(size_t)map[i]] = 1;
+        }
+        for (int I = 0; I < nc; ++I)
+            if (!seen[(size_t)I]) { set_error("%s: level %d: aggregate %d is empty", who, l, I); return nullptr; }
+        first[(size_t)l + 1] = first[(size_t)l] + n;
+    }
+    auto nextMap = [&](int l, const AmgMatrix& A, std::vector<int>& map, int* nc) -> int {
+        if (A.n != levelRows[l]) { set_error("%s: level %d has %lld rows, levelRows says %d", who, l, A.n, levelRows[l]); return -1; }
+        const int* m = aggregateOf + first[(size_t)l];
+        map.assign(m, m + levelRows[l]);
+        *nc = levelRows[l + 1];
+        return 1;
+    };
+    return amg_setup(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, omega, nu, nuCoarse, sigma, nextMap);
+}
+
+int MgLevelCopyAggregates(const MgcgMg* mg, int level, int aggregateOf[])
+{
+    if (!mg || !aggregateOf) { set_error("MgLevelCopyAggregates: null argument"); return -1; }
+    if (!mg->algebraic) { set_error("MgLevelCopyAggregates: a geometric hierarchy has no stored aggregates"); return -1; }
+    if (level < 0 || level >= mg->levels - 1 || mg->lv[(size_t)level].agg == nullptr) { set_error("MgLevelCopyAggregates: level %d has no map (the hierarchy has %d levels)", level, mg->levels); return -1; }
+    const MgLevel& L = mg->lv[(size_t)level];
+    (void)hipStreamSynchronize(mg->stream);
+    return MGCG_HIP(hipMemcpy(aggregateOf, L.agg, sizeof(int) * (size_t)L.n, hipMemcpyDeviceToHost)) ? 0 : -1;
+}
+
 void MgDestroy(MgcgMg* mg)
 {
     if (!mg) return;
@@ -2056,6 +2353,9 @@ void MgDestroy(MgcgMg* mg)
             if (L.rowOffsets) { analysis_note_write(L.rowOffsets, sizeof(int) * (size_t)(L.n + 1)); (void)hipFree(L.rowOffsets); }
             if (L.columnIndeces) { analysis_note_write(L.columnIndeces, sizeof(int) * (size_t)(L.nnz > 0 ? L.nnz : 1)); (void)hipFree(L.columnIndeces); }
         }
+        if (L.agg) (void)hipFree(L.agg);
+        if (L.aggOffsets) (void)hipFree(L.aggOffsets);
+        if (L.aggMembers) (void)hipFree(L.aggMembers);
         if (L.dinv) (void)hipFree(L.dinv);
         if (L.xa) (void)hipFree(L.xa);
         if (L.xb) (void)hipFree(L.xb);
@@ -2076,6 +2376,7 @@ void MgDestroy(MgcgMg* mg)
 int MgSetInterpolation(MgcgMg* mg, int mode)
 {
     if (!mg || (mode != 0 && mode != 1)) { set_error("MgSetInterpolation: mode must be 0 (piecewise constant) or 1 (cell-centred linear)"); return -1; }
+    if (mode == 1 && mg->algebraic) { set_error("MgSetInterpolation: the linear transfer needs a grid; this hierarchy was built from aggregates"); return -1; }
     if (!device_state()) return -1;
     if (mode == 1 && mg->multi) {
         // collective: every rank builds, level by level, the plan that brings one grid plane from each z-neighbour

@@ -359,6 +359,56 @@ MgcgMg* MgSetupParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
                         Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                         int elementsCount, int nx, int ny, int nz, int zBegin, int zEnd,
                         int levels, double omega, int nu, int nuCoarse, double sigma);
+/* Aggregation multigrid: the same hierarchy -- piecewise-constant P, R = P^T, A_c = sigma*P^T A P, weighted-Jacobi V(nu,nu), nuCoarse
+ * sweeps on the last level -- for ANY CSR matrix with a positive stored diagonal: the aggregates come from the matrix graph instead of
+ * 2x2x2 boxes of a grid.  One rank.  MgApply, SolveMg, MgLevels, MgLevelRows, MgLevelNnz, MgLevelCopyCsr, MgLevelCopyDinv and MgDestroy
+ * work on the result; MgSetInterpolation(mg, 1) returns -1 (the linear transfer needs a grid) and SolveMgParallel on a communicator of
+ * several ranks refuses it.  The set-up is deterministic and defined by the data alone:
+ *
+ * One MATCHING PASS on a matrix B of n rows (assumed symmetric; not checked):
+ *   1. a stored entry k of row i with column j != i and value < 0 couples i and j with weight w = -value; entries >= 0 and the diagonal
+ *      do not couple.
+ *   2. m_i = the largest w of row i, 0 if there is none.
+ *   3. row i holds the candidate edge {i, j} iff w >= theta*m_i and w >= theta*m_j (w from row i).
+ *   4. the tie-break key of an edge, 32-bit unsigned arithmetic, lo = min(i, j), hi = max(i, j):
+ *        h = lo*0x9E3779B1 + hi*0x85EBCA77; h ^= h >> 15; h *= 0x2C1B3C6D; h ^= h >> 12; h *= 0x297A2D39; h ^= h >> 15
+ *   5. a round: every unmatched row picks the neighbour with the lexicographically largest (w, h, j) among those of its candidate edges
+ *      whose other end is unmatched; rows that pick each other are matched.  Rounds repeat until no row has such an edge left (or, on an
+ *      unsymmetric matrix, until a round matches nobody).  The host reads one flag pair per round.
+ *   6. unmatched rows become singletons; aggregates are numbered by their smallest member, ascending.
+ * One LEVEL takes `passes` (1..4; 3 gives aggregates of up to 8 rows, the size of the 2x2x2 box) matching passes: pass 1 on the level's
+ * matrix, pass p > 1 on the unscaled Galerkin matrix (sigma = 1) of pass p - 1 (skipped once a pass matches nothing); the level's map is
+ * their composition.  The next level's matrix is sigma*P^T A P of the level's own matrix with the composed map.
+ * GALERKIN CONTRACT: coarse row I takes its members in ascending fine index and each member's entries in stored order; every value is
+ * added to the accumulator of its coarse column, starting from +0.0; columns are emitted in ascending order, each as sigma*acc.  (The
+ * order of MgSetup's Galerkin pass: box aggregates reproduce MgSetup's hierarchy and its V-cycle bit for bit.)  No matrix value travels
+ * to the host; index bookkeeping (scans, the counting sort of a map into member lists) runs there.
+ * The hierarchy ENDS with level l when `levels` is reached, when level l has <= minCoarse rows, or when the next level would keep more
+ * than 3/4 of level l's rows ("nothing matched" included: a matrix without a negative off-diagonal entry gives ONE level, whose cycle is
+ * nuCoarse Jacobi sweeps).  Every level's diagonal must be stored, finite and > 0: else NULL, the error names the level and the row.
+ * In the cycle a level with a map runs the stored path: nu sweeps, r = b - A x, b_c[I] = the serial sum of r over I's members in ascending
+ * order from +0.0, the next level, x[i] += e[agg[i]], nu sweeps.
+ * Set-up (maps, level matrices, D^-1) is the same bits in every mode.  In the sweeps and the residual pass a level whose rows hold 20 entries
+ * or fewer on average sums every row in stored order; longer rows are summed by several lanes whose partial sums meet in a tree, or in stored
+ * order under dot_order = 1 -- as everywhere in the library.  Under dot_order = 1 M^-1 r is one fixed sequence of IEEE operations.
+ * omega is the caller's (one value for all levels, not range-checked): omega*lambda_max(D^-1 A) < 2 on every level is the caller's
+ * condition for a symmetric POSITIVE DEFINITE preconditioner (6/7 and 4/5 are MgSetup's values for the 7- and 5-point stencils).
+ * Returns NULL with MgcgGetLastError() on bad arguments (a null handle, levels < 1, passes outside 1..4, theta outside (0, 1], vectors
+ * that are too small: refused before a device is asked for). */
+MgcgMg* MgSetupAggregation(MgcgBlas* cublas, MgcgSparse* cusparse,
+                           Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                           int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
+                           double omega, int nu, int nuCoarse, double sigma);
+/* The same hierarchy from the caller's aggregates (host arrays): levelRows[0 .. levels-1] are the rows of every level (levelRows[0] =
+ * count), aggregateOf holds the maps of levels 0 .. levels-2 one after the other (levelRows[l] ids in [0, levelRows[l+1]) each).  Exactly
+ * `levels` levels are built.  An id out of range or an empty aggregate is refused (NULL, MgcgGetLastError()). */
+MgcgMg* MgSetupAggregates(MgcgBlas* cublas, MgcgSparse* cusparse,
+                          Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                          int elementsCount, int count, int levels, const int levelRows[], const int aggregateOf[],
+                          double omega, int nu, int nuCoarse, double sigma);
+/* aggregateOf[0 .. MgLevelRows(level)-1] = the map of `level` to the next one.  Returns 0; -1 with MgcgGetLastError() on a geometric
+ * hierarchy (MgSetup / MgSetupParallel) or on the last level. */
+int     MgLevelCopyAggregates(const MgcgMg* mg, int level, int aggregateOf[]);
 void    MgDestroy(MgcgMg* mg);
 /* Transfer operators of the V-cycle: 0 (default) piecewise-constant P, 1 cell-centred linear P (per coarsened dimension
  * a child takes 3/4 of its parent and 1/4 of the parent's neighbour on the child's side), R = P^T in both; the coarse
