@@ -1,6 +1,7 @@
 """Aggregation multigrid on the host side (no GPU needed): the numpy yardstick of tests/test_gpu_amg.py lives here and is checked against
 scipy's P^T A P, against the partition properties the matching promises and -- with 2x2x2 box maps -- against the geometric CPU oracle;
-the library exports the three entry points and refuses bad arguments before it asks for a device.
+the library exports the three entry points and refuses bad arguments before it asks for a device.  The systems that a sorted scipy matrix
+cannot express -- reversed rows, duplicates, one-way entries, irregular maps -- are built here from raw arrays and checked on the CPU first.
 
 The yardstick is the algorithm of include/MgcgGpu.h (MgSetupAggregation) in np.float64 and 32-bit unsigned integers: the matching pass
 round by round, the composed maps, the Galerkin product in the contract's order (members ascending, entries in stored order, every value
@@ -13,7 +14,7 @@ import numpy as np
 import pytest
 
 from conjugategradient_amd import _lib, problems
-from tests.test_mixed_host import row_sums
+from tests.test_mixed_host import row_sums, serial_sum
 
 U32 = np.uint64(0xFFFFFFFF)
 
@@ -32,8 +33,8 @@ def edge_key(i, j):
     return h
 
 
-def matching_pass(e, c, ro, theta):
-    """(map, aggregates): one matching pass, aggregates numbered by their smallest member."""
+def candidate_edges(e, c, ro, theta):
+    """(i, j, w) of every stored entry that is a candidate edge of its row: a negative off-diagonal entry with w >= theta m_i and theta m_j."""
     n = len(ro) - 1
     rows = np.repeat(np.arange(n), np.diff(ro))
     c = np.asarray(c, dtype=np.int64)
@@ -42,7 +43,13 @@ def matching_pass(e, c, ro, theta):
     m = np.zeros(n)
     np.maximum.at(m, rows[couples], w[couples])
     candidate = couples & (w >= theta * m[rows]) & (w >= theta * m[c])
-    ri, cj, wk = rows[candidate], c[candidate], w[candidate]
+    return rows[candidate], c[candidate], w[candidate]
+
+
+def matching_pass(e, c, ro, theta):
+    """(map, aggregates): one matching pass, aggregates numbered by their smallest member."""
+    n = len(ro) - 1
+    ri, cj, wk = candidate_edges(e, c, ro, theta)
     hk = edge_key(ri, cj)
     match = np.full(n, -1, dtype=np.int64)
     while True:
@@ -129,7 +136,10 @@ class Hierarchy:
         if maps is not None:
             levels = len(maps) + 1
         for l in range(levels):
-            L = dict(e=e, c=c, ro=ro, dinv=diagonal_inverse(e, c, ro), map=None, nc=0)
+            try:
+                L = dict(e=e, c=c, ro=ro, dinv=diagonal_inverse(e, c, ro), map=None, nc=0)
+            except ValueError as err:
+                raise ValueError(f"level {l}, {err}") from None
             self.levels.append(L)
             n = len(ro) - 1
             if l + 1 >= levels:
@@ -174,31 +184,42 @@ class Hierarchy:
     def apply(self, r):
         return self._vcycle(0, np.asarray(r, dtype=np.float64))
 
-    def pcg(self, b, x0=None, tol=1e-8, max_it=500):
-        """The shell of oracle_pcg (oracle/mg_oracle.c) under RULE_CSHARP with min_iteration 0 -> dict(x, iteration, residual, trace)."""
+    def pcg(self, b, x0=None, tol=1e-8, max_it=500, dot=None, min_it=0):
+        """The shell of oracle_pcg (oracle/mg_oracle.c) under RULE_CSHARP -> dict(x, iteration, residual, status, trace).  ``dot`` forms every
+        sum of the loop (default: numpy's); with ``lambda a, b: serial_sum(a * b)`` it is the reference's serial left-to-right sum of the
+        rounded products, the order of the library under dot_order = 1.  ``min_it`` is the library's minIteration: no iteration below it
+        ends the loop on its residual or on the cap."""
+        dot = (lambda u, v: float(u @ v)) if dot is None else dot
         L = self.levels[0]
         x = np.zeros(len(b)) if x0 is None else np.array(x0, dtype=np.float64)
         r = b - row_sums(L["e"], L["c"], L["ro"], x)
         z = self.apply(r)
         p = z.copy()
-        rz = float(r @ z)
+        rz = dot(r, z)
         trace = []
         it = 0
         while True:
             Ap = row_sums(L["e"], L["c"], L["ro"], p)
-            alpha = rz / float(p @ Ap)
+            alpha = rz / dot(p, Ap)
             x = x + alpha * p
             r = r - alpha * Ap
-            res = math.sqrt(float(r @ r))
+            res = math.sqrt(dot(r, r))
             trace.append(res)
-            if it > max_it or res < tol or not math.isfinite(res):
+            if (it >= min_it and (it > max_it or res < tol)) or not math.isfinite(res):
                 break
             z = self.apply(r)
-            rz_new = float(r @ z)
+            rz_new = dot(r, z)
             p = z + (rz_new / rz) * p
             rz = rz_new
             it += 1
-        return dict(x=x, iteration=it, residual=res, trace=np.array(trace))
+        converged = min_it <= it <= max_it and res < tol
+        status = _lib.OK if converged else _lib.MAXIT_EXCEEDED if it >= min_it and it > max_it else _lib.NONFINITE
+        return dict(x=x, iteration=it, residual=res, status=status, trace=np.array(trace))
+
+
+def serial_dot(a, b):
+    """The dot product of the library under dot_order = 1: the rounded products added strictly left to right from +0.0."""
+    return serial_sum(a * b)
 
 
 # --------------------------------------------------------------------------- the systems of the two test files
@@ -265,13 +286,132 @@ def csr_of(s):
     return np.asarray(s.Elements[: s.nnz], dtype=np.float64), np.asarray(s.ColumnIndeces[: s.nnz]), np.asarray(s.RowOffsets)
 
 
+# --------------------------------------------------------------------------- systems that system_of cannot make: built from raw arrays
+def _raw(s, e, c, ro, name):
+    """A LinearSystem of raw CSR arrays in exactly this stored order, with s's right-hand side."""
+    n = len(ro) - 1
+    return problems.LinearSystem(np.ascontiguousarray(e, dtype=np.float64), np.ascontiguousarray(c, dtype=np.int32), np.ascontiguousarray(ro, dtype=np.int32),
+                                 np.zeros(n), np.array(s.b, dtype=np.float64), name)
+
+
+def reversed_rows(s):
+    """Every row's entries in reverse stored order: the diagonal moves, no row is sorted ascending."""
+    e, c, ro = csr_of(s)
+    rows = np.repeat(np.arange(s.Count), np.diff(ro))
+    order = np.lexsort((-np.arange(s.nnz), rows))
+    return _raw(s, e[order], c[order], ro, s.name + "-reversed")
+
+
+def diagonal_first(s):
+    """Every row with its diagonal first and the other entries by ascending column behind it."""
+    e, c, ro = csr_of(s)
+    rows = np.repeat(np.arange(s.Count), np.diff(ro))
+    order = np.lexsort((c, c != rows, rows))
+    return _raw(s, e[order], c[order], ro, s.name + "-diagonal-first")
+
+
+def with_duplicates(s):
+    """Every off-diagonal entry v stored as the two adjacent entries 0.25 v and 0.75 v, and an explicit 0.0 of the row's own column behind
+    the (one) diagonal entry: the diagonal stays the FIRST stored entry of column i."""
+    e, c, ro = csr_of(s)
+    rows = np.repeat(np.arange(s.Count), np.diff(ro))
+    diagonal = c == rows
+    assert np.array_equal(np.bincount(rows[diagonal], minlength=s.Count), np.ones(s.Count, dtype=np.int64))
+    e2 = np.stack([np.where(diagonal, e, 0.25 * e), np.where(diagonal, 0.0, 0.75 * e)], axis=1).ravel()
+    return _raw(s, e2, np.repeat(c, 2), 2 * ro.astype(np.int64), s.name + "-duplicates")
+
+
+def one_way(s, rows=150, weight=-2000.0, seed=2):
+    """A symmetric M-matrix plus `rows` entries (i, (i + 37) mod n) of value `weight` that have no mirror entry, each stored at the end of its
+    row, the row's diagonal raised by |weight|: every row stays diagonally dominant, the matrix is no longer symmetric."""
+    e, c, ro = csr_of(s)
+    n = s.Count
+    where = np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+    row_of = np.repeat(np.arange(n), np.diff(ro))
+    e = e.copy()
+    at = np.nonzero((c == row_of) & np.isin(row_of, where))[0]
+    assert len(at) == rows
+    e[at] += abs(weight)
+    end = np.asarray(ro, dtype=np.int64)[where + 1]           # insert behind the last entry of each chosen row
+    e2, c2 = np.insert(e, end, weight), np.insert(c, end, (where + 37) % n)
+    extra = np.zeros(n, dtype=np.int64)
+    extra[where] = 1
+    return _raw(s, e2, c2, np.r_[0, np.cumsum(np.diff(ro) + extra)], s.name + "-one-way")
+
+
+def dominant_graph(n, seed):
+    """The weights of graph_laplacian with the diagonal of arrowhead: 1.25 x the off-diagonal row sum, a strictly dominant M-matrix."""
+    import scipy.sparse as sp
+
+    L = graph_laplacian(n, seed, shift=0.0).to_scipy()
+    W = sp.diags(L.diagonal()) - L
+    return system_of(sp.diags(1.25 * np.asarray(W.sum(axis=1)).ravel()) - W, f"dominant-graph-{n}")
+
+
+def path_graph(n, seed, decades=0.0):
+    """A path of n rows (tridiagonal) with edge weights U(0.5, 2) (times 10^U(0, decades)) and the diagonal 1.25 x the off-diagonal row sum,
+    columns ascending.  With decades = 0 every edge passes the strength threshold 0.25; with 2 the threshold decides."""
+    rng = np.random.default_rng(seed)
+    w = rng.uniform(0.5, 2.0, n - 1)
+    if decades:
+        w = w * 10.0 ** rng.uniform(0.0, decades, n - 1)
+    left, right = np.r_[0.0, w], np.r_[w, 0.0]
+    e = np.stack([-left, 1.25 * (left + right), -right], axis=1).ravel()
+    i = np.arange(n)
+    c = np.stack([i - 1, i, i + 1], axis=1).ravel()
+    keep = (c >= 0) & (c < n)
+    ro = np.r_[0, np.cumsum(keep.reshape(n, 3).sum(axis=1))]
+    s = problems.LinearSystem(e[keep], c[keep].astype(np.int32), ro.astype(np.int32), np.zeros(n), np.ones(n), f"path-{n}")
+    return s
+
+
+def irregular_maps(n, seed=11):
+    """Three maps no grid would give.  Level 0: aggregates of sizes drawn from 1 .. 40, their ids a random permutation (not numbered by
+    first member), their members scattered over the rows by another; level 1: permutation % 5; level 2: one aggregate of everything."""
+    rng = np.random.default_rng(seed)
+    sizes = []
+    while sum(sizes) < n:
+        sizes.append(min(int(rng.integers(1, 41)), n - sum(sizes)))
+    ids = rng.permutation(len(sizes))
+    m0 = np.empty(n, dtype=np.int32)
+    m0[rng.permutation(n)] = np.repeat(ids, sizes)
+    m1 = (rng.permutation(len(sizes)) % 5).astype(np.int32)
+    assert len(sizes) >= 5
+    return [m0, m1, np.zeros(5, dtype=np.int32)]
+
+
+def pairs_with_a_negative_coarse_diagonal(blocks=100):
+    """`blocks` diagonal blocks [[1, -2], [-2, 1]]: level 0 is fine, every pair is matched, the coarse diagonal sigma (1 - 2 - 2 + 1) < 0."""
+    n = 2 * blocks
+    i = np.arange(n)
+    e = np.where(i % 2 == 0, [[1.0], [-2.0]], [[-2.0], [1.0]]).T.ravel()
+    c = np.stack([i - i % 2, i - i % 2 + 1], axis=1).ravel()
+    return problems.LinearSystem(e, c.astype(np.int32), (2 * np.arange(n + 1)).astype(np.int32), np.zeros(n), np.ones(n), "negative-pairs")
+
+
+def zero_before_the_diagonal(s, row):
+    """s with an explicit 0.0 of column `row` stored at the head of that row: the first stored entry of the column, hence the diagonal."""
+    e, c, ro = csr_of(s)
+    at = int(ro[row])
+    extra = np.zeros(s.Count, dtype=np.int64)
+    extra[row] = 1
+    return _raw(s, np.insert(e, at, 0.0), np.insert(c, at, row), np.r_[0, np.cumsum(np.diff(ro) + extra)], s.name + "-zero-first")
+
+
+def rows_per_level(H):
+    return [len(L["ro"]) - 1 for L in H.levels]
+
+
 # --------------------------------------------------------------------------- the yardstick against independent statements
 def _ptap(s, amap, nc, sigma):
     import scipy.sparse as sp
 
     n = s.Count
     P = sp.csr_matrix((np.ones(n), (np.arange(n), amap)), shape=(n, nc))
-    C_ = (P.T @ s.to_scipy() @ P).tocsr() * sigma
+    # from copies: csr_matrix.sum_duplicates() works in place on arrays it shares and would rewrite the system's own offsets
+    A = sp.csr_matrix((np.array(s.Elements[: s.nnz]), np.array(s.ColumnIndeces[: s.nnz]), np.array(s.RowOffsets)), shape=(n, n))
+    A.sum_duplicates()
+    C_ = (P.T @ A @ P).tocsr() * sigma
     C_.sort_indices()
     return C_
 
@@ -372,6 +512,166 @@ def test_yardstick_cycle_is_symmetric_and_cuts_iterations():
     assert np.linalg.norm(s.b - A @ out["x"]) < 2e-8 and out["iteration"] < 30
     with pytest.raises(ValueError, match="row 0"):
         diagonal_inverse(np.array([1.0, 2.0]), np.array([1, 1]), np.array([0, 1, 2]))
+
+
+# --------------------------------------------------------------------------- the serial-dot loop and the raw-array systems
+@pytest.mark.parametrize("dims", [(8, 12, 4), (16, 16, 16)])
+def test_serial_dot_pcg_equals_the_geometric_oracle_bit_for_bit(oracle, dims):
+    """The yardstick loop of the GPU solve tests, validated first: with box maps and serial dots it IS oracle_pcg."""
+    s = problems.poisson(*dims)
+    s.b[:] = np.random.default_rng(3).standard_normal(s.Count)
+    M = oracle.Multigrid(s, levels=3)
+    H = Hierarchy(*csr_of(s), omega=M.omega, maps=box_maps(s.grid, 3))
+    assert len(H.levels) == M.levels == 3
+    for min_it, max_it in ((0, 400), (25, 400), (0, 5)):
+        ref = M.pcg(rule=oracle.RULE_CSHARP, min_iteration=min_it, max_iteration=max_it, trace=True)
+        out = H.pcg(np.asarray(s.b), max_it=max_it, dot=serial_dot, min_it=min_it)
+        assert (out["iteration"], out["status"]) == (ref["iteration"], ref["status"]), (min_it, max_it)
+        assert out["trace"].tobytes() == ref["trace"].tobytes() and out["x"].tobytes() == ref["x"].tobytes()
+    assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 6
+    # the default dot is today's loop: another order of summation, the same iteration count
+    assert H.pcg(np.asarray(s.b))["iteration"] == M.pcg(rule=oracle.RULE_CSHARP, trace=True)["iteration"]
+
+
+BUILT = {
+    "reversed": lambda: reversed_rows(permuted(problems.poisson(10, 10, 10), 7)),
+    "diagonal-first": lambda: diagonal_first(permuted(problems.poisson(10, 10, 10), 7)),
+    "duplicates": lambda: with_duplicates(graph_laplacian(8, 3)),
+    "one-way": lambda: one_way(graph_laplacian(10, 3)),
+    "dominant-graph": lambda: dominant_graph(10, 3),
+    "path": lambda: path_graph(1077, 5),
+    "path-wide": lambda: path_graph(1077, 5, decades=2.0),
+}
+
+
+@pytest.mark.parametrize("name", list(BUILT))
+def test_galerkin_of_the_built_systems_equals_scipy_ptap(name):
+    s = BUILT[name]()
+    e, c, ro = csr_of(s)
+    offsets = np.array(ro)
+    for passes in (1, 3):
+        amap, nc, _ = level_map(e, c, ro, passes, 0.25)
+        cases = [(amap, nc)] + ([(irregular_maps(s.Count)[0], len(irregular_maps(s.Count)[1]))] if passes == 1 else [])
+        for m, count in cases:
+            ge, gc, gro = galerkin(e, c, ro, m, count, 0.5)
+            ref = _ptap(s, m, count, 0.5)
+            assert np.array_equal(gro, ref.indptr) and np.array_equal(gc, ref.indices), (name, passes)
+            assert np.abs(ge - ref.data).max() <= 1e-13 * np.abs(ref.data).max()
+    assert np.array_equal(s.RowOffsets, offsets)               # (the comparison left the system alone)
+
+
+def test_reversed_rows_give_the_maps_of_the_sorted_matrix():
+    s = permuted(problems.poisson(10, 10, 10), 7)
+    H = Hierarchy(*csr_of(s), levels=3)
+    assert len(H.levels) == 3
+    for other in (reversed_rows(s), diagonal_first(s)):
+        e, c, ro = csr_of(other)
+        rows = np.repeat(np.arange(s.Count), np.diff(ro))
+        first = ro[:-1]
+        assert np.array_equal(ro, s.RowOffsets) and not np.array_equal(c, s.ColumnIndeces[: s.nnz])
+        if other.name.endswith("reversed"):
+            assert np.any(c[first] != np.arange(s.Count)) and np.all(np.diff(c)[np.diff(rows) == 0] < 0)
+        else:
+            assert np.all(c[first] == np.arange(s.Count))
+        assert (other.to_scipy() != s.to_scipy()).nnz == 0
+        G = Hierarchy(e, c, ro, levels=3)
+        print(other.name, rows_per_level(G))
+        assert rows_per_level(G) == rows_per_level(H)
+        for L, K in zip(G.levels, H.levels):
+            assert (L["map"] is None and K["map"] is None) or np.array_equal(L["map"], K["map"])
+            # integer values: the order of summation cannot change a bit, the sorted coarse rows are the same rows
+            assert np.array_equal(L["ro"], K["ro"]) and np.array_equal(L["dinv"], K["dinv"])
+
+
+def test_duplicate_entries_coarsen_and_keep_the_first_diagonal():
+    base = graph_laplacian(8, 3)
+    s = with_duplicates(base)
+    assert s.nnz == 2 * base.nnz
+    e, c, ro = csr_of(s)
+    assert np.array_equal(diagonal_inverse(e, c, ro), diagonal_inverse(*csr_of(base)))        # the 0.0 behind it is not the diagonal
+    assert np.abs(s.to_scipy() - base.to_scipy()).max() <= 2.0 ** -52 * np.abs(base.Elements).max()
+    H = Hierarchy(e, c, ro)
+    print("duplicates", rows_per_level(H))
+    assert len(H.levels) >= 3
+    # a level matrix is duplicate-free whatever went in
+    for L in H.levels[1:]:
+        rows = np.repeat(np.arange(len(L["ro"]) - 1), np.diff(L["ro"]))
+        assert np.all((np.diff(L["c"]) > 0) | (np.diff(rows) > 0))
+
+
+def test_one_way_entries_end_a_pass_by_the_round_that_pairs_nobody():
+    base = graph_laplacian(10, 3)
+    s = one_way(base)
+    assert s.nnz == base.nnz + 150
+    A = s.to_scipy()
+    assert (A != A.T).nnz == 300 and np.all(A @ np.ones(s.Count) > 0) and A.diagonal().min() > 0     # unsymmetric, rows dominant
+    e, c, ro = csr_of(s)
+    m, nc = matching_pass(e, c, ro, 0.25)
+    m_sym, nc_sym = matching_pass(*csr_of(base), 0.25)
+    H = Hierarchy(e, c, ro)
+    print("one-way", rows_per_level(H), "aggregates of pass 1:", nc, "symmetric:", nc_sym)
+    assert len(H.levels) >= 2
+    assert nc != nc_sym and not np.array_equal(m, m_sym)
+    # candidate edges still live between singletons: rows went on picking, so only the "nobody paired" exit can have ended the pass
+    i, j, _ = candidate_edges(e, c, ro, 0.25)
+    single = np.bincount(m, minlength=nc)[m] == 1
+    live = int((single[i] & single[j]).sum())
+    print("live candidate edges at the end of the pass:", live)
+    assert live > 0
+    i, j, _ = candidate_edges(*csr_of(base), 0.25)
+    single = np.bincount(m_sym, minlength=nc_sym)[m_sym] == 1
+    assert int((single[i] & single[j]).sum()) == 0               # the symmetric matrix ends with nothing left to pick
+
+
+def test_irregular_maps_build_a_hierarchy_with_long_coarse_rows():
+    s = dominant_graph(10, 3)
+    maps = irregular_maps(s.Count)
+    sizes = np.bincount(maps[0])
+    firsts = np.full(len(sizes), s.Count)
+    np.minimum.at(firsts, maps[0], np.arange(s.Count))
+    assert sizes.min() >= 1 and sizes.max() > 16 and len(set(sizes)) > 5 and np.any(np.diff(firsts) < 0)
+    H = Hierarchy(*csr_of(s), maps=maps)
+    print("irregular", rows_per_level(H), "entries per row on level 1:", len(H.levels[1]["e"]) / len(sizes))
+    assert rows_per_level(H) == [s.Count, len(sizes), 5, 1]
+    assert len(H.levels[1]["e"]) > 20 * len(sizes)               # the library sums such rows by several lanes in the default mode
+    rng = np.random.default_rng(9)
+    u, v = rng.standard_normal(s.Count), rng.standard_normal(s.Count)
+    a, b = float(u @ H.apply(v)), float(v @ H.apply(u))
+    assert abs(a - b) <= 1e-12 * abs(a)
+    out = H.pcg(np.asarray(s.b))
+    print("iterations", out["iteration"])
+    assert out["status"] == _lib.OK and out["iteration"] < 60 and np.linalg.norm(s.b - s.to_scipy() @ out["x"]) < 2e-8
+    # the identity map with sigma = 1: level 1 is the matrix itself, bit for bit
+    e, c, ro = csr_of(s)
+    I = Hierarchy(e, c, ro, sigma=1.0, maps=[np.arange(s.Count)])
+    L = I.levels[1]
+    assert np.array_equal(L["ro"], ro) and np.array_equal(L["c"], c) and L["e"].tobytes() == e.tobytes()
+
+
+def test_the_yardstick_refuses_what_the_header_refuses():
+    s = problems.poisson(6, 5, 4)
+    with pytest.raises(ValueError, match="^row 17$"):
+        diagonal_inverse(*csr_of(zero_before_the_diagonal(s, 17)))
+    with pytest.raises(ValueError, match="^level 0, row 17$"):
+        Hierarchy(*csr_of(zero_before_the_diagonal(s, 17)))
+    p = pairs_with_a_negative_coarse_diagonal()
+    e, c, ro = csr_of(p)
+    m, nc = matching_pass(e, c, ro, 0.25)
+    assert np.array_equal(m, np.arange(200) // 2) and nc == 100
+    assert np.all(galerkin(e, c, ro, m, nc, 0.5)[0] == -1.0)
+    with pytest.raises(ValueError, match="^level 1, row 0$"):
+        Hierarchy(e, c, ro)
+    with pytest.raises(ValueError, match="^level 1, row 0$"):
+        Hierarchy(e, c, ro, maps=[m])
+
+
+@pytest.mark.parametrize("n,rows", [(1, [1]), (2, [2, 1]), (3, [3, 1]), (5, [5, 1])])
+def test_tiny_matrices_coarsen_to_one_row(n, rows):
+    s = problems.poisson(n, 1, 1)
+    H = Hierarchy(*csr_of(s), minCoarse=0)
+    assert rows_per_level(H) == rows
+    out = H.pcg(np.asarray(s.b))
+    assert out["status"] == _lib.OK and np.linalg.norm(s.b - s.to_scipy() @ out["x"]) < 2e-8
 
 
 # --------------------------------------------------------------------------- the library without a device
