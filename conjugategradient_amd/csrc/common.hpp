@@ -114,7 +114,7 @@ inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (voi
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
-void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb();
+void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -187,6 +187,16 @@ struct SreduceScalars {
     struct State { double gamma, alpha; } st[2];     // gamma and alpha of the body before
 };
 
+// What the MINRES loop (SolveMinres*, kernels_minres.hip) carries from one body to the next.  Body k reads st[k & 1] in every workgroup of its
+// two passes while the second pass's first workgroup writes st[(k + 1) & 1], as SreduceScalars does.  red: {delta, y.y, the closing r.r} --
+// delta is left there by the first pass for the second (one rank) or all-reduced in place (several ranks, y.y too).  fDone: CgScalars::done
+// as the first pass of a body found it; the second pass, which raises `done` itself while its other workgroups may still start, looks here.
+struct MinresScalars {
+    double red[3];
+    int fDone, pad;
+    struct State { double beta, cs, sn, dbar, eps, phibar; } st[2];
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
@@ -218,6 +228,7 @@ struct Workspace {
     float* mixedVecs = nullptr;
     long long mixedStride = 0;
     SreduceScalars* sreduceScalars = nullptr;    // single-reduction CG (kernels_sreduce.hip), allocated at its first call and kept; its direction p takes ring[1]
+    MinresScalars* minresScalars = nullptr;      // MINRES (kernels_minres.hip), allocated at its first call and kept
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -228,6 +239,7 @@ struct Workspace {
     bool ensure_bkrylov();                       // gramPartials / bkScalars (kernels_bkrylov.hip)
     bool ensure_mixed(long long n);              // mixedScalars / mixedVecs for n rows (kernels_mixed.hip)
     bool ensure_sreduce();                       // sreduceScalars (kernels_sreduce.hip)
+    bool ensure_minres();                        // minresScalars (kernels_minres.hip)
 };
 
 } // namespace mgcg
@@ -619,6 +631,25 @@ double* sreduce_gamma_partials(Workspace* ws, int parity);
 void sreduce_enqueue_sums(const SreduceRun& R, int k, int nDelta, int nIn);
 // the pass of body k; returns the number of partial sums it leaves for body k + 1 (1 under dot_order = 1: two more launches, three with dinv)
 int sreduce_enqueue_pass(const SreduceRun& R, const FinalizeArgs& f, int k, int nDelta, int nIn);
+
+// MINRES (SolveMinres*; kernels_minres.hip has the loop, include/MgcgGpu.h the method).  v, vprev: this rank's rows of the two Lanczos buffers
+// of body k (the host rotates them; pass A forms y over vprev, pass B vnext over y); w1, w2: the two direction buffers (pass B writes w over
+// w1, the host rotates); q = A v.  given: several ranks -- delta and y.y arrive all-reduced in ws->minresScalars->red[0], red[1].
+struct MinresRun {
+    Workspace* ws;
+    double *x, *v, *vprev, *w1, *w2; const double* q;
+    long long n; double shift; bool given;
+};
+double* minres_yy_partials(Workspace* ws);
+// r = t + shift x with the partial sums of r.r in minres_yy_partials(ws) (start and closing pass); returns their number (1 under dot_order = 1)
+int minres_enqueue_residual(Workspace* ws, const double* t, const double* x, double* r, long long n, double shift);
+// the scalars in front of body 0 from those sums (reduceFirst) or from the all-reduced red[1]; r.r not finite or zero stops the loop here
+// with MGCG_NONFINITE at iteration 0; then v = r * (1 / beta1) in place
+void minres_enqueue_start(Workspace* ws, const FinalizeArgs& f, int nPartials, bool reduceFirst, double* v, long long n);
+// pass A of body k; returns the number of partial sums of y.y it leaves (1 under dot_order = 1: one more launch)
+int minres_enqueue_lanczos(const MinresRun& R, int k, int nDelta);
+// pass B of body k
+void minres_enqueue_update(const MinresRun& R, const FinalizeArgs& f, int k, int nYY);
 
 // Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).
 // The start: d = it * (dinv r), z = d, the partial sums of r.r and -- withRz, degree 1 -- of r.z; returns their number (1 under dot_order = 1).

@@ -1278,6 +1278,95 @@ static int cg_solve_sreduce(CgRun& R, double* sVec, int* iteration, double* resi
     return ok ? status : MGCG_ERROR;
 }
 
+// ---------------------------------------------------------------- MINRES (SolveMinres, SolveMinresParallel)
+// Paige and Saunders' MINRES for (A - shift I) x = b, A symmetric of any inertia (include/MgcgGpu.h has the method, kernels_minres.hip the two
+// passes).  The host's side is cg_drive: a body is the product and the two passes (three launches), on several ranks the product, a fold and an
+// all-reduce of delta, pass A, a fold and an all-reduce of y.y, pass B.  The product is the plain loop's (cg_enqueue_product: halo exchange of
+// the full-length buffer that holds v, launch_spmv_auto with the partial sums of v.q), so compression modes and automatic column tiles apply
+// unchanged; the overlap schedule stays "in line", and the deferred x update and the placement draw do not apply.  The caller's p and r are the
+// two full-length Lanczos buffers, rotated per body by pointer; w1Vec and w2Vec the two direction buffers, rotated the same way; R.Ap holds q.
+// One more product behind the loop leaves the true residual b - (A - shift I) x in the first nLocal entries of the caller's r.
+static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift, int* iteration, double* residual, double* trueResidual,
+                           double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    // everything the call allocates, before anything is enqueued
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    if (!ws->ensure_minres() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    const int devTraceCap = f.traceCap;
+    cg_matrix_setup(R);
+    R.overlap = false;                                                                   // the exchange of v stays in line
+    MinresScalars* ms = ws->minresScalars;
+    const int* done = &ws->scalars->done;
+    double* const bufP = R.p; double* const bufR = R.r;                                  // the caller's two full-length buffers
+    double* yyPartials = minres_yy_partials(ws);
+
+    // t = b - A x through bufP, then r = t + shift x into out's first n entries with its r.r in red[slot] (several ranks: all-reduced)
+    auto residual_pass = [&](double* out, int slot, int* nOut) {
+        launch_copy(s, bufP + R.offset, R.x, n);
+        if (!halo_exchange(R.comm, R.halo, bufP, s)) return false;
+        SpmvArgs a = cg_spmv_args(R, bufP, R.Ap);
+        a.b = R.b;
+        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
+        *nOut = minres_enqueue_residual(ws, R.Ap, R.x, out, n, shift);
+        if (R.multi || slot == 2) launch_reduce_to(s, yyPartials, *nOut, &ms->red[slot], nullptr);
+        return !R.multi || comm_allreduce_sum(R.comm, &ms->red[slot], 1, s);
+    };
+
+    // start: v = r0 / || r0 || in the rows' slice of bufR; bufP, which held x for the product, is body 0's vprev (not read there)
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
+    int nIn = 0;
+    bool ok = residual_pass(bufR + R.offset, 1, &nIn);
+    if (ok) minres_enqueue_start(ws, f, nIn, !R.multi, bufR + R.offset, n);
+    ok = ok && MGCG_HIP(hipGetLastError());
+
+    double *v = bufR, *vprev = bufP, *w1 = w1Vec, *w2 = w2Vec;
+    int k = 0;
+    ok = ok && cg_drive(R, "SolveMinres", [&] {
+        int nDelta = 0;
+        R.p = v;                                                                         // the buffer whose halo the product exchanges
+        if (!cg_enqueue_product(R, v, &nDelta)) return false;                            // q = A v ; v.q
+        const MinresRun P = { ws, R.x, v + R.offset, vprev + R.offset, w1, w2, R.Ap, n, shift, R.multi };
+        if (R.multi) {
+            launch_reduce_to(s, ws->partials, nDelta, &ms->red[0], done);
+            if (!comm_allreduce_sum(R.comm, &ms->red[0], 1, s)) return false;
+        }
+        const int nYY = minres_enqueue_lanczos(P, k, nDelta);                            // y over vprev ; y.y
+        if (R.multi) {
+            launch_reduce_to(s, yyPartials, nYY, &ms->red[1], done);
+            if (!comm_allreduce_sum(R.comm, &ms->red[1], 1, s)) return false;
+        }
+        minres_enqueue_update(P, f, k, nYY);                                             // w over w1 ; x ; vnext over y
+        std::swap(v, vprev); std::swap(w1, w2);                                          // (vprev, v) := (v, vnext) ; (w1, w2) := (w2, w)
+        if (k < 0x7fffffff) ++k;
+        return MGCG_HIP(hipGetLastError());
+    });
+    R.p = bufP;
+    // the closing product: the true residual into the caller's r, whatever the parity of the rotation
+    double rrTrue = 0.0;
+    if (ok) {
+        int nOut = 0;
+        ok = residual_pass(bufR, 2, &nOut) && MGCG_HIP(hipGetLastError());
+        ok = ok && MGCG_HIP(hipMemcpyAsync(&rrTrue, &ms->red[2], sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    HostMirror* m = ws->mirror;
+    const int status = m->status;
+    if (iteration) *iteration = m->iteration;
+    if (residual) *residual = m->residual;
+    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
+    if (devTraceCap) {
+        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
+        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
+    }
+    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveMinres: did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
+    if (status == MGCG_NONFINITE) set_error("SolveMinres: stopped at iteration %d: the first residual is zero or not finite, or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)", m->iteration);
+    return ok ? status : MGCG_ERROR;
+}
+
 // ---------------------------------------------------------------- Chebyshev-preconditioned CG (SolveChebyshev, SolveChebyshevParallel)
 // SolveJacobi's loop with z = p_m(D^-1 A) D^-1 r (kernels_cheb.hip has the method and the passes): the polynomial costs m - 1 products and no
 // global sum.  The host's side is cg_drive.  One iteration on one rank is m + 3 launches: the loop's product (cg_enqueue_product, so
@@ -2611,6 +2700,57 @@ int SolveSingleReduce(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matD
     return SolveSingleReduceParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
                                      xVector, bVector, ApVector, pVector, rVector, sVector, dinvVector, count, count, 0, elementsCount, 0, count - 1,
                                      allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
+}
+
+// MINRES (cg_solve_minres above).  What needs no device is refused before one is asked for when there is nobody to agree with; among several
+// ranks a rank with unusable arguments travels in the halo plan's one all-reduce (cg_call) and every rank leaves with MGCG_ERROR.  The shift
+// is NOT part of that agreement: every rank passes the same.
+int SolveMinresParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                        Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* w1Vector, Vector* w2Vector,
+                        int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ, double shift,
+                        double allowableResidual, int minIteration, int maxIteration, int rule,
+                        int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    const bool handles = cublas && cusparse && w1Vector && w2Vector;
+    auto checks = [&] {
+        if (!(std::fabs(shift) <= 1.79e308)) set_error("SolveMinres: the shift is not finite");
+        else if (rule == MGCG_RULE_HANDMADECL) set_error("SolveMinres: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the recurrence carries no max|r|");
+        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("SolveMinres: unknown stop rule %d", rule);
+        else if (w1Vector->size < countForDevice) set_error("SolveMinres: the w1 vector holds %lld entries, the matrix has %d local rows", w1Vector->size, countForDevice);
+        else if (w2Vector->size < countForDevice) set_error("SolveMinres: the w2 vector holds %lld entries, the matrix has %d local rows", w2Vector->size, countForDevice);
+        else if (rVector && rVector->size < count) set_error("SolveMinres: the r vector holds %lld entries, the matrix has %d columns (both Lanczos buffers are full length)", rVector->size, count);
+        else return true;
+        return false;
+    };
+    if (MgcgCommSize(comm) <= 1) {
+        if (!handles) { set_error("SolveMinres: null handle"); return MGCG_ERROR; }
+        if (!checks()) return MGCG_ERROR;
+    }
+    if (handles && !device_state()) return MGCG_ERROR;
+    const CgCall c = { "SolveMinres", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    int st = MGCG_ERROR;
+    cg_call(c, handles, checks, [&](CgRun& R) {
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        for (double* v : { R.x, R.Ap, w1Vector->data, w2Vector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
+        for (double* v : { R.p, R.r }) analysis_note_write(v, sizeof(double) * (size_t)count);
+        st = cg_solve_minres(R, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* w1Vector, Vector* w2Vector,
+                int elementsCount, int count, double shift,
+                double allowableResidual, int minIteration, int maxIteration, int rule,
+                int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    return SolveMinresParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
+                               xVector, bVector, ApVector, pVector, rVector, w1Vector, w2Vector, count, count, 0, elementsCount, 0, count - 1, shift,
+                               allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
 // Chebyshev-preconditioned CG (cg_solve_chebyshev above).  What needs no device is refused before one is asked for when there is nobody to agree

@@ -200,7 +200,8 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if getattr(self, "cublas", None):
             for v in (self.vectorElements, self.vectorColumnIndeces, self.vectorRowOffsets, self.vectorX, self.vectorB,
                       self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None), getattr(self, "vectorS", None),
-                      getattr(self, "vectorZ", None), getattr(self, "vectorZ2", None), getattr(self, "vectorD", None)):
+                      getattr(self, "vectorZ", None), getattr(self, "vectorZ2", None), getattr(self, "vectorD", None),
+                      getattr(self, "vectorW1", None), getattr(self, "vectorW2", None)):
                 if v is not None:
                     v.Dispose()
             if self._own_comm and self.comm:
@@ -355,6 +356,39 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if st != _lib.OK:
             check("SolveSingleReduceParallel")
             raise MgcgError(f"SolveSingleReduceParallel failed with status {st}")
+
+    def SolveMinres(self, trace: bool = False, shift: float = 0.0):
+        """Solve (A - shift I) x = b with MINRES (SolveMinresParallel): A symmetric, definite or not.  Two all-reduces per iteration, as
+        Solve().  Both Lanczos buffers are full length: vectorR is reallocated to ``Count`` entries at the first call; afterwards its first
+        ``part.count`` entries hold this rank's rows of the true residual and ``TrueResidual`` its global 2-norm.  Every rank passes the
+        same ``shift``."""
+        self._ensure_comm()
+        p = self.part
+        if self.vectorR.size < self.Count:
+            self.vectorR.Dispose()
+            self.vectorR = VectorDouble(self.Count)
+        for name in ("vectorW1", "vectorW2"):
+            if getattr(self, name, None) is None or getattr(self, name).size < p.count:
+                setattr(self, name, VectorDouble(p.count))
+        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        st = lib().SolveMinresParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
+                                       self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                       self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                       self.vectorW1.Ptr, self.vectorW2.Ptr,
+                                       self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ, float(shift),
+                                       self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
+                                       C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"MINRES did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveMinresParallel")
+            raise MgcgError(f"SolveMinresParallel failed with status {st}")
 
     def SolveChebyshev(self, trace: bool = False, jacobi: bool = False, degree: int = 4, bounds=None):
         """Solve() on the Chebyshev-preconditioned loop (SolveChebyshevParallel).  bounds = (lambdaMin, lambdaMax) of A -- of D^-1 A with

@@ -592,6 +592,71 @@ int SolveSingleReduceParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusp
                               double allowableResidual, int minIteration, int maxIteration, int rule,
                               int* iteration, double* residual, double* residualTrace, int traceCapacity);
 
+/* ---- MINRES: symmetric indefinite and shifted systems (A - shift I) x = b (one rank or several) ---- */
+/* Paige and Saunders' minimum-residual method.  A is symmetric CSR of any inertia, shift is finite and of any sign (0: plain MINRES).
+ * Every other solver here needs a positive definite matrix and returns MGCG_NONFINITE when p.Ap <= 0; this one does not.  It runs the
+ * Lanczos recurrence of CG at the plain loop's cost structure -- one product and two global sums per iteration -- and minimises || r ||_2,
+ * the very norm every stop rule of this library judges, over the Krylov space: on a definite matrix it never needs more iterations than CG
+ * to the same rule, and its residual trace never increases.  The Lanczos vectors of A - shift I are those of A, so the shift never
+ * touches a vector inside the loop: it enters the scalar alpha only.  One rank: three launches per iteration (the product and two fused
+ * vector passes, 32 and 64 bytes per row).
+ * Method:
+ *   start   (MGCG_RULE_SIMPLE: x := 0)
+ *           t = b - A x  (row i of A x summed as the product sums it, then b_i - acc) ;  r_i = t_i + shift*x_i ;  rr0 = r.r ;  beta1 = sqrt(rr0)
+ *           rr0 not finite or == 0  ->  MGCG_NONFINITE at iteration 0, x untouched
+ *           v = r*(1/beta1) ;  beta = 0 ;  cs = -1 ;  sn = 0 ;  dbar = 0 ;  eps = 0 ;  phibar = beta1 ;  trace[0] = beta1 (sqrt(rr0/rr0) under
+ *           MGCG_RULE_VIENNACL)
+ *   body k  q = A v ;  delta = v.q
+ *   pass A  y_i = (q_i - delta*v_i) - beta*vprev_i      (k = 0: the beta term is not formed, vprev is not read) ;  yy = y.y
+ *   pass B  alpha = delta - shift ;  betan = sqrt(yy)
+ *           oldeps = eps ;  dl = cs*dbar + sn*alpha ;  gbar = sn*dbar - cs*alpha ;  eps = sn*betan ;  dbar = -(cs*betan)
+ *           gamma = sqrt(gbar*gbar + betan*betan) ;  ig = 1/gamma ;  cs = gbar*ig ;  sn = betan*ig ;  phi = cs*phibar ;  phibar = sn*phibar
+ *           gamma, ig or phi not finite, or gamma == 0  ->  MGCG_NONFINITE reported for iteration k + 1, x and the directions unchanged by this body
+ *           w_i = ((v_i - oldeps*w1_i) - dl*w2_i)*ig    (k = 0: w1, w2 not read; k = 1: w1 not read) ;  x_i = x_i + phi*w_i
+ *           vnext_i = y_i*(1/betan)                     (not formed when betan == 0)
+ *           rr = phibar*phibar is judged by the rule's stop test against rr0 as the residual of iteration k + 1
+ *           betan == 0: the Krylov space is exhausted; the loop ends after this body with the rule's status if it stops, else MGCG_OK
+ *           (vprev, v) := (v, vnext) ;  (w1, w2) := (w2, w) ;  beta := betan
+ *   end     one more product: t = b - A x ;  r_i = t_i + shift*x_i into rVector ;  *trueResidual = sqrt(r.r)
+ * Rounding contract: every product goes into a double of its own before the add or subtraction that follows it, nothing is fused; the
+ * scalars are evaluated in exactly the order written (1/beta1, 1/betan and ig are formed once and multiplied); the terms of the sums are
+ * v_i*q_i, y_i*y_i and r_i*r_i of the rounded y and r.  Under dot_order = 1 every sum is serial left to right and ranks add in rank order:
+ * the whole loop is then a fixed sequence of IEEE operations (tests/test_minres_host.py restates it in numpy).
+ * Stop: the four 2-norm rules of SolveEx on (rr, rr0) with rr the recurrence's phibar^2; MGCG_RULE_HANDMADECL is refused (the recurrence
+ * carries no max|r|).  *iteration, *residual and the trace (entry 0: the first residual; entry k + 1: |phibar| after body k; sqrt(rr / rr0)
+ * under MGCG_RULE_VIENNACL) show the recurrence's figure.  phibar can drift from the true residual -- forced past convergence on a 300-row tridiagonal system
+ * it underflows to 0 after n iterations where b - A x is 6e-15 -- and a caller of an indefinite solver needs the true figure: the closing
+ * product runs whenever the loop ended without MGCG_ERROR, breakdown included, and *trueResidual (may be NULL) is || b - (A - shift I) x ||_2.
+ * A breakdown (shift an eigenvalue met by the Krylov space, or values that are not finite) repeats the last judged residual in *residual
+ * and its trace entry.
+ *   ApVector        work space (count entries): q
+ *   pVector, rVector  the two Lanczos buffers, rotated by pointer per body (count entries each).  On return the first count entries of
+ *                   rVector hold the true residual, whatever the parity of the rotation
+ *   w1Vector, w2Vector   work space (count entries each): the two direction buffers, rotated the same way
+ * Refused with MGCG_ERROR, a message and nothing enqueued: a shift that is not finite, MGCG_RULE_HANDMADECL, an unknown rule, a null
+ * handle, a vector that is too small.
+ * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer), the placement
+ * draw and the overlap schedule do not apply.  Out of scope: preconditioning, the block, mixed and multigrid combinations, the C++ twin
+ * under host/, and MINRES-QLP for singular systems. */
+int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* w1Vector, Vector* w2Vector,
+                int elementsCount, int count, double shift,
+                double allowableResidual, int minIteration, int maxIteration, int rule,
+                int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+/* The same on a row partition, shaped after SolveSingleReduceParallel.  BOTH Lanczos buffers, pVector and rVector, are full length (count
+ * entries): rows gather v, whose halo is exchanged in line before every product (the overlap schedule is not used by this loop); the other
+ * vectors hold the local rows.  delta and yy each travel in one all-reduce of one double (two per iteration, as in SolveParallel), the
+ * closing r.r in one more.  On return the first countForDevice entries of rVector hold this rank's rows of the true residual, and
+ * *trueResidual is the global figure on every rank.  A rank without rows takes part in every collective.  Every rank passes the same
+ * shift: that is not checked; every other unusable argument on one rank makes every rank return MGCG_ERROR, as in SolveParallel. */
+int SolveMinresParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                        Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* w1Vector, Vector* w2Vector,
+                        int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ, double shift,
+                        double allowableResidual, int minIteration, int maxIteration, int rule,
+                        int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
  * MgcgJacobiSetup wrote) is given: Gershgorin's upper bound of the spectrum of A (of D^-1 A), rigorous, usually within a small factor
