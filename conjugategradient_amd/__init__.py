@@ -7,7 +7,8 @@
 ``amg``       the same V-cycle for ANY CSR matrix: aggregates from the matrix graph (MgSetupAggregation) or from the caller
 ``jacobi``    Jacobi-preconditioned CG for general CSR matrices (the call the ViennaCL front-end left commented out)
 ``singlereduce`` single-reduction (Chronopoulos-Gear) CG: one global sum and two launches per iteration, with or without the diagonal
-``minres``   MINRES for symmetric indefinite and shifted systems (A - shift I) x = b: the solver for what the CG loops refuse
+``minres``   MINRES for symmetric indefinite and shifted systems (A - shift I) x = b: the solver for what the CG loops refuse,
+             plain or preconditioned by the diagonal (the V-cycle form is a method of the ``multigrid`` / ``amg`` classes)
 ``chebyshev`` Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, m products and two global sums per iteration
 ``shifted``   multi-shift CG: (A + s_j I) x_j = b for up to 8 shifts from one CG recurrence on A
 ``blockkrylov`` shared-subspace block CG: up to 8 right-hand sides in one block Krylov space (fewer iterations than ``block``)

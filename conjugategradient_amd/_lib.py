@@ -126,6 +126,9 @@ SIGNATURES = {
     "SolveSingleReduceParallel": (_i, [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "SolveMinres": (_i, [_vp] * 13 + [_i, _i, _d, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
     "SolveMinresParallel": (_i, [_vp] * 14 + [_i, _i, _i, _i, _i, _i, _d, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
+    "SolveMinresJacobi": (_i, [_vp] * 15 + [_i, _i, _d, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
+    "SolveMinresJacobiParallel": (_i, [_vp] * 16 + [_i, _i, _i, _i, _i, _i, _d, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
+    "SolveMinresMg": (_i, [_vp] * 16 + [_i, _i, _d, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
     "MgcgGershgorinBound": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _pd]),
     "SolveChebyshev": (_i, [_vp] * 15 + [_i, _i, _i, _d, _d, _d, _i, _i, _i, _pi, _pd, _vp, _i]),
     "SolveChebyshevParallel": (_i, [_vp] * 16 + [_i, _i, _i, _i, _i, _i, _i, _d, _d, _d, _i, _i, _i, _pi, _pd, _vp, _i]),

@@ -114,7 +114,7 @@ inline void preload_code_object(const void* kernel) { hipFuncAttributes at; (voi
 void preload_ops(); void preload_solver(); void preload_comm(); void preload_kernels_spmv(); void preload_kernels_rows();
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
-void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres();
+void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres(); void preload_kernels_pminres();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -191,10 +191,13 @@ struct SreduceScalars {
 // two passes while the second pass's first workgroup writes st[(k + 1) & 1], as SreduceScalars does.  red: {delta, y.y, the closing r.r} --
 // delta is left there by the first pass for the second (one rank) or all-reduced in place (several ranks, y.y too).  fDone: CgScalars::done
 // as the first pass of a body found it; the second pass, which raises `done` itself while its other workgroups may still start, looks here.
+// The preconditioned loop (SolveMinresJacobi*, SolveMinresMg; kernels_pminres.hip) uses the same block: red = {v.q, v.v, the closing r.r, r.z, the
+// first r.z as the start found it} -- {v.q, v.v} adjacent, so that they travel in one all-reduce of two doubles -- and State::oldb, the beta
+// of the body before (the plain loop neither reads nor writes it).
 struct MinresScalars {
-    double red[3];
+    double red[5];
     int fDone, pad;
-    struct State { double beta, cs, sn, dbar, eps, phibar; } st[2];
+    struct State { double beta, cs, sn, dbar, eps, phibar, oldb; } st[2];
 };
 
 // ---------------------------------------------------------------- handles
@@ -650,6 +653,28 @@ void minres_enqueue_start(Workspace* ws, const FinalizeArgs& f, int nPartials, b
 int minres_enqueue_lanczos(const MinresRun& R, int k, int nDelta);
 // pass B of body k
 void minres_enqueue_update(const MinresRun& R, const FinalizeArgs& f, int k, int nYY);
+
+// Preconditioned MINRES (SolveMinresJacobi*, SolveMinresMg; kernels_pminres.hip has the loop, include/MgcgGpu.h the method).  v: this rank's rows
+// of the one full-length buffer (pass B writes the next v over it in place); r1, r2: the two residual buffers of body k (the host rotates them;
+// pass A forms rn over r1); w1, w2: the two direction buffers, as in MinresRun; q = A v.  dinv: the Jacobi form -- z = dinv * rn is formed per
+// element in both passes; else z: the vector that holds M^-1 rn when pass B runs.  given: several ranks -- {v.q, v.v} and r.z arrive all-reduced
+// in ws->minresScalars->red[0 .. 1] and red[3].
+struct PminresRun {
+    Workspace* ws;
+    double *x, *v, *r1, *w1; const double *r2, *w2, *q, *dinv, *z;
+    long long n; double shift; bool given;
+};
+double* pminres_rz_partials(Workspace* ws);
+double* pminres_vv_partials(Workspace* ws);
+// the start: r = t + shift x and -- dinv given -- the partial sums of r.z, z = dinv * r; returns their number (1 under dot_order = 1; 0 without dinv)
+int pminres_enqueue_residual(Workspace* ws, const double* t, const double* x, double* r, const double* dinv, long long n, double shift);
+// the scalars in front of body 0 from the partial sums of the first r.z (reduceFirst) or from the all-reduced red[3]; an r.z that is not finite
+// and > 0 stops the loop here with MGCG_NONFINITE at iteration 0; then v = z * (1 / beta1) and the partial sums of v.v; returns their number
+int pminres_enqueue_start(Workspace* ws, const FinalizeArgs& f, int nPartials, bool reduceFirst, double* v, const double* r, const double* dinv, const double* z, long long n);
+// pass A of body k (nVq, nVv: the partial sums of v.q in ws->partials and of v.v); returns the number of partial sums of r.z it leaves (0 without dinv)
+int pminres_enqueue_lanczos(const PminresRun& R, int k, int nVq, int nVv);
+// pass B of body k; returns the number of partial sums of v.v it leaves
+int pminres_enqueue_update(const PminresRun& R, const FinalizeArgs& f, int k, int nRz);
 
 // Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).
 // The start: d = it * (dinv r), z = d, the partial sums of r.r and -- withRz, degree 1 -- of r.z; returns their number (1 under dot_order = 1).

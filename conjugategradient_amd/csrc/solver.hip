@@ -1367,6 +1367,113 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
     return ok ? status : MGCG_ERROR;
 }
 
+// ---------------------------------------------------------------- preconditioned MINRES (SolveMinresJacobi, SolveMinresJacobiParallel, SolveMinresMg)
+// MINRES with a symmetric positive definite preconditioner M (include/MgcgGpu.h has the method, kernels_pminres.hip the two passes): R.dinv --
+// z = dinv r formed per element inside the passes -- or R.mg with R.z, the V-cycle enqueued between them with one dot launch for r.z (one rank).
+// The host's side is cg_drive, and the product is the plain loop's, as in cg_solve_minres.  A body on several ranks (Jacobi only): the product, a
+// fold and ONE all-reduce of the adjacent pair {v.q, v.v}, pass A, a fold and an all-reduce of r.z, pass B: two all-reduces, as the plain loop.
+// R.p holds v, the one full-length buffer (pass B writes the next v over it in place); the caller's r and r1Vec are the two residual buffers,
+// rotated per body by pointer; w1Vec and w2Vec the two direction buffers, rotated the same way; R.Ap holds q.  One more product behind the loop
+// leaves the true residual b - (A - shift I) x in the caller's r, whatever the parity of the rotation.
+static int cg_solve_pminres(CgRun& R, const char* who, double* r1Vec, double* w1Vec, double* w2Vec, double shift, int* iteration, double* residual, double* trueResidual,
+                            double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    // everything the call allocates, before anything is enqueued
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    if (!ws->ensure_minres() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    const int devTraceCap = f.traceCap;
+    cg_matrix_setup(R);
+    R.overlap = false;                                                                   // the exchange of v stays in line
+    MinresScalars* ms = ws->minresScalars;
+    const int* done = &ws->scalars->done;
+    double* const bufR = R.r;                                                            // the caller's r
+    double* vLoc = R.p + R.offset;
+    double* rzPartials = pminres_rz_partials(ws);
+
+    // t = b - A x through the buffer of v (full length: its halo is exchanged), into R.Ap
+    auto residual_product = [&] {
+        launch_copy(s, vLoc, R.x, n);
+        if (!halo_exchange(R.comm, R.halo, R.p, s)) return false;
+        SpmvArgs a = cg_spmv_args(R, R.p, R.Ap);
+        a.b = R.b;
+        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
+        return true;
+    };
+    // z = M^-1 r into R.z and the partial sums of r.z (the V-cycle form)
+    auto cycle = [&](const double* r, const int* gate, int* nRz) {
+        if (!mg_apply(R.mg, r, R.z, gate)) return false;
+        *nRz = launch_dot_partials(s, r, R.z, n, rzPartials);
+        return true;
+    };
+
+    // start: r2 = b - (A - shift I) x in the caller's r ; bz = r2 . M^-1 r2 ; v = M^-1 r2 / sqrt(bz) ; v.v
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
+    int nRz = 0, nVv = 0;
+    bool ok = residual_product();
+    if (ok) nRz = pminres_enqueue_residual(ws, R.Ap, R.x, bufR, R.dinv, n, shift);
+    if (ok && R.mg) ok = cycle(bufR, nullptr, &nRz);
+    if (ok && R.multi) {
+        launch_reduce_to(s, rzPartials, nRz, &ms->red[3], nullptr);
+        ok = comm_allreduce_sum(R.comm, &ms->red[3], 1, s);
+    }
+    if (ok) nVv = pminres_enqueue_start(ws, f, nRz, !R.multi, vLoc, bufR, R.dinv, R.z, n);
+    ok = ok && MGCG_HIP(hipGetLastError());
+
+    double *r2 = bufR, *r1 = r1Vec, *w1 = w1Vec, *w2 = w2Vec;
+    int k = 0;
+    ok = ok && cg_drive(R, who, [&] {
+        int nVq = 0;
+        if (!cg_enqueue_product(R, R.p, &nVq)) return false;                             // q = A v ; v.q
+        const PminresRun P = { ws, R.x, vLoc, r1, w1, r2, w2, R.Ap, R.dinv, R.z, n, shift, R.multi };
+        if (R.multi) {
+            launch_reduce2_to(s, ws->partials, nVq, &ms->red[0], pminres_vv_partials(ws), nVv, &ms->red[1], done);
+            if (!comm_allreduce_sum(R.comm, &ms->red[0], 2, s)) return false;            // {v.q, v.v}: one all-reduce of two doubles
+        }
+        int nZ = pminres_enqueue_lanczos(P, k, nVq, nVv);                                // rn over r1 ; Jacobi: rn.z
+        if (R.mg && !cycle(r1, done, &nZ)) return false;                                 // z = M^-1 rn ; rn.z
+        if (R.multi) {
+            launch_reduce_to(s, rzPartials, nZ, &ms->red[3], done);
+            if (!comm_allreduce_sum(R.comm, &ms->red[3], 1, s)) return false;
+        }
+        nVv = pminres_enqueue_update(P, f, k, nZ);                                       // w over w1 ; x ; the next v in place ; v.v
+        std::swap(r1, r2); std::swap(w1, w2);                                            // (r1, r2) := (r2, rn) ; (w1, w2) := (w2, w)
+        if (k < 0x7fffffff) ++k;
+        return MGCG_HIP(hipGetLastError());
+    });
+    // the closing product: the true residual into the caller's r
+    double rrTrue = 0.0, bz = 0.0;
+    if (ok) {
+        ok = residual_product();
+        if (ok) {
+            const int nOut = minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift);
+            launch_reduce_to(s, minres_yy_partials(ws), nOut, &ms->red[2], nullptr);
+            ok = (!R.multi || comm_allreduce_sum(R.comm, &ms->red[2], 1, s)) && MGCG_HIP(hipGetLastError());
+        }
+        ok = ok && MGCG_HIP(hipMemcpyAsync(&rrTrue, &ms->red[2], sizeof(double), hipMemcpyDeviceToHost, s));
+        ok = ok && MGCG_HIP(hipMemcpyAsync(&bz, &ms->red[4], sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    HostMirror* m = ws->mirror;
+    const int status = m->status;
+    if (iteration) *iteration = m->iteration;
+    if (residual) *residual = m->residual;
+    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
+    if (devTraceCap) {
+        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
+        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
+    }
+    if (status == MGCG_MAXIT_EXCEEDED) set_error("%s: did not converge: iteration %d exceeded maxIteration %d (residual %g in the M^-1 norm)", who, m->iteration, R.maxIt, m->residual);
+    if (status == MGCG_NONFINITE) {
+        if (m->iteration == 0 && bz < 0.0) set_error("%s: stopped at iteration 0: the preconditioner is not positive definite (r . M^-1 r = %g for the first residual)", who, bz);
+        else set_error("%s: stopped at iteration %d: the first residual is zero or not finite, r . M^-1 r is negative or not finite (a preconditioner that is not positive definite), or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)", who, m->iteration);
+    }
+    return ok ? status : MGCG_ERROR;
+}
+
 // ---------------------------------------------------------------- Chebyshev-preconditioned CG (SolveChebyshev, SolveChebyshevParallel)
 // SolveJacobi's loop with z = p_m(D^-1 A) D^-1 r (kernels_cheb.hip has the method and the passes): the polynomial costs m - 1 products and no
 // global sum.  The host's side is cg_drive.  One iteration on one rank is m + 3 launches: the loop's product (cg_enqueue_product, so
@@ -2751,6 +2858,100 @@ int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
     return SolveMinresParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
                                xVector, bVector, ApVector, pVector, rVector, w1Vector, w2Vector, count, count, 0, elementsCount, 0, count - 1, shift,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+// Preconditioned MINRES (cg_solve_pminres above).  Refusals as in SolveMinresParallel; a rank whose diagonal set-up failed calls with a null
+// dinvVector and every rank leaves with MGCG_ERROR, as in SolveJacobiParallel.  The shift is NOT part of that agreement.
+static bool pminres_common_checks(const char* who, double shift, int rule, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector, int countForDevice)
+{
+    if (!(std::fabs(shift) <= 1.79e308)) set_error("%s: the shift is not finite", who);
+    else if (rule == MGCG_RULE_HANDMADECL) set_error("%s: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the recurrence carries no max|r|", who);
+    else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("%s: unknown stop rule %d", who, rule);
+    else if (r1Vector->size < countForDevice) set_error("%s: the r1 vector holds %lld entries, the matrix has %d local rows", who, r1Vector->size, countForDevice);
+    else if (w1Vector->size < countForDevice) set_error("%s: the w1 vector holds %lld entries, the matrix has %d local rows", who, w1Vector->size, countForDevice);
+    else if (w2Vector->size < countForDevice) set_error("%s: the w2 vector holds %lld entries, the matrix has %d local rows", who, w2Vector->size, countForDevice);
+    else return true;
+    return false;
+}
+
+int SolveMinresJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                              Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                              Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector,
+                              Vector* dinvVector,
+                              int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ, double shift,
+                              double allowableResidual, int minIteration, int maxIteration, int rule,
+                              int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    const char* who = "SolveMinresJacobi";
+    const bool handles = cublas && cusparse && r1Vector && w1Vector && w2Vector && dinvVector;
+    auto checks = [&] {
+        if (!pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, countForDevice)) return false;
+        if (dinvVector->size < countForDevice) { set_error("%s: the dinv vector holds %lld entries, the matrix has %d local rows", who, dinvVector->size, countForDevice); return false; }
+        return true;
+    };
+    if (MgcgCommSize(comm) <= 1) {
+        if (!handles) { set_error("%s: null handle", who); return MGCG_ERROR; }
+        if (!checks()) return MGCG_ERROR;
+    }
+    if (handles && !device_state()) return MGCG_ERROR;
+    const CgCall c = { who, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    int st = MGCG_ERROR;
+    cg_call(c, handles, checks, [&](CgRun& R) {
+        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the loop, which reads nothing through it there
+        R.dinv = dinvVector->data ? dinvVector->data : R.ws->partials;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        for (double* v : { R.x, R.Ap, R.r, r1Vector->data, w1Vector->data, w2Vector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
+        analysis_note_write(R.p, sizeof(double) * (size_t)count);
+        st = cg_solve_pminres(R, who, r1Vector->data, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveMinresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                      Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                      Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector,
+                      Vector* dinvVector,
+                      int elementsCount, int count, double shift,
+                      double allowableResidual, int minIteration, int maxIteration, int rule,
+                      int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    return SolveMinresJacobiParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
+                                     xVector, bVector, ApVector, pVector, rVector, r1Vector, w1Vector, w2Vector, dinvVector, count, count, 0, elementsCount, 0, count - 1, shift,
+                                     allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                  Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                  Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector,
+                  Vector* zVector,
+                  int elementsCount, int count, double shift,
+                  double allowableResidual, int minIteration, int maxIteration, int rule,
+                  int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    const char* who = "SolveMinresMg";
+    if (!cublas || !cusparse || !mg || !r1Vector || !w1Vector || !w2Vector || !zVector) { set_error("%s: null handle", who); return MGCG_ERROR; }
+    auto checks = [&] {
+        if (!pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, count)) return false;
+        if (zVector->size < count) { set_error("%s: the z vector holds %lld entries, the matrix has %d rows", who, zVector->size, count); return false; }
+        if (mg->nranks != 1 || mg->multi) { set_error("%s: the hierarchy was built for %d rank(s)%s; the V-cycle form runs on one rank", who, mg->nranks, mg->multi ? " on the several-ranks path" : ""); return false; }
+        if (mg->levels < 1 || mg->lv[0].n != count) { set_error("%s: the hierarchy has %lld rows on level 0, the matrix has %d", who, mg->levels < 1 ? 0LL : (long long)mg->lv[0].n, count); return false; }
+        return true;
+    };
+    if (!checks()) return MGCG_ERROR;
+    if (!device_state()) return MGCG_ERROR;
+    const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
+    int st = MGCG_ERROR;
+    cg_call(c, true, no_more_checks, [&](CgRun& R) {
+        if (R.multi) { set_error("%s: the V-cycle form runs on one rank", who); return; }
+        R.mg = mg; R.z = zVector->data;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        for (double* v : { R.x, R.Ap, R.r, R.p, r1Vector->data, w1Vector->data, w2Vector->data, R.z }) analysis_note_write(v, sizeof(double) * (size_t)count);
+        st = cg_solve_pminres(R, who, r1Vector->data, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    });
+    return st;
 }
 
 // Chebyshev-preconditioned CG (cg_solve_chebyshev above).  What needs no device is refused before one is asked for when there is nobody to agree

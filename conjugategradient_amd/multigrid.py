@@ -39,6 +39,10 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
             self.mg = None
         if getattr(self, "vectorZ", None) is not None:
             self.vectorZ.Dispose()
+        for name in ("vectorW1", "vectorW2", "vectorR1"):         # SolveMinres's work space, if it ran
+            if getattr(self, name, None) is not None:
+                getattr(self, name).Dispose()
+                setattr(self, name, None)
         super().Dispose()
 
     def Initialize(self):
@@ -119,3 +123,33 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         if st != _lib.OK:
             check("SolveMg")
             raise MgcgError(f"SolveMg failed with status {st}")
+
+    def SolveMinres(self, shift: float = 0.0, trace: bool = False):
+        """Solve (A - shift I) x = b with MINRES preconditioned by this hierarchy's V-cycle (SolveMinresMg): A symmetric, definite or not.
+        The hierarchy is ``self.mg`` whatever matrix it was built from (only its row count is checked); ``w1``, ``w2`` and ``r1`` are
+        allocated at the first call.  ``Iteration``, ``Residual`` and ``trace`` show the residual in the M^-1 norm, sqrt(r . M^-1 r),
+        which is what the stop rule judges; ``TrueResidual`` is the plain 2-norm || b - (A - shift I) x ||_2 of the closing product, and
+        ``vectorR`` holds that vector."""
+        for name in ("vectorW1", "vectorW2", "vectorR1"):
+            if getattr(self, name, None) is None:
+                setattr(self, name, VectorDouble(self.Count))
+        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
+        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        rule = _lib.RULE_CSHARP if self.rule is None else self.rule
+        st = lib().SolveMinresMg(self.cublas, self.cusparse, self.matDescr, self.mg,
+                                 self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                 self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorR1.Ptr,
+                                 self.vectorW1.Ptr, self.vectorW2.Ptr, self.vectorZ.Ptr,
+                                 nonzeroCount, self.Count, float(shift), self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
+                                 C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"V-cycle-preconditioned MINRES did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveMinresMg")
+            raise MgcgError(f"SolveMinresMg failed with status {st}")

@@ -201,7 +201,7 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
             for v in (self.vectorElements, self.vectorColumnIndeces, self.vectorRowOffsets, self.vectorX, self.vectorB,
                       self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None), getattr(self, "vectorS", None),
                       getattr(self, "vectorZ", None), getattr(self, "vectorZ2", None), getattr(self, "vectorD", None),
-                      getattr(self, "vectorW1", None), getattr(self, "vectorW2", None)):
+                      getattr(self, "vectorW1", None), getattr(self, "vectorW2", None), getattr(self, "vectorR1", None)):
                 if v is not None:
                     v.Dispose()
             if self._own_comm and self.comm:
@@ -389,6 +389,37 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if st != _lib.OK:
             check("SolveMinresParallel")
             raise MgcgError(f"SolveMinresParallel failed with status {st}")
+
+    def SolveMinresJacobi(self, trace: bool = False, shift: float = 0.0):
+        """SolveMinres() with the Jacobi preconditioner (SolveMinresJacobiParallel); SetupJacobi() first.  Only v (vectorP) is full length.
+        ``Residual`` and the trace are the residual in the M^-1 norm, sqrt(r . M^-1 r), which the stop rule judges; ``TrueResidual`` is the
+        global 2-norm of b - (A - shift I) x, whose local rows are left in vectorR.  A rank whose SetupJacobi() failed still enters the
+        native call, with no dinv vector: every rank gets MGCG_ERROR.  Every rank passes the same ``shift``."""
+        self._ensure_comm()
+        p = self.part
+        usable = getattr(self, "vectorDinv", None) is not None and getattr(self, "jacobiError", None) is None
+        for name in ("vectorW1", "vectorW2", "vectorR1"):
+            if getattr(self, name, None) is None or getattr(self, name).size < p.count:
+                setattr(self, name, VectorDouble(p.count))
+        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        st = lib().SolveMinresJacobiParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
+                                             self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                             self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorR1.Ptr,
+                                             self.vectorW1.Ptr, self.vectorW2.Ptr, self.vectorDinv.Ptr if usable else None,
+                                             self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ, float(shift),
+                                             self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
+                                             C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"Jacobi-preconditioned MINRES did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveMinresJacobiParallel")
+            raise MgcgError(f"SolveMinresJacobiParallel failed with status {st}")
 
     def SolveChebyshev(self, trace: bool = False, jacobi: bool = False, degree: int = 4, bounds=None):
         """Solve() on the Chebyshev-preconditioned loop (SolveChebyshevParallel).  bounds = (lambdaMin, lambdaMax) of A -- of D^-1 A with

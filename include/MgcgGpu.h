@@ -636,8 +636,8 @@ int SolveSingleReduceParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusp
  * Refused with MGCG_ERROR, a message and nothing enqueued: a shift that is not finite, MGCG_RULE_HANDMADECL, an unknown rule, a null
  * handle, a vector that is too small.
  * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer), the placement
- * draw and the overlap schedule do not apply.  Out of scope: preconditioning, the block, mixed and multigrid combinations, the C++ twin
- * under host/, and MINRES-QLP for singular systems. */
+ * draw and the overlap schedule do not apply.  Preconditioning: SolveMinresJacobi and SolveMinresMg below.  Out of scope: the block and mixed
+ * combinations, the C++ twin under host/, and MINRES-QLP for singular systems. */
 int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* w1Vector, Vector* w2Vector,
@@ -656,6 +656,84 @@ int SolveMinresParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, 
                         int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ, double shift,
                         double allowableResidual, int minIteration, int maxIteration, int rule,
                         int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
+/* ---- preconditioned MINRES: (A - shift I) x = b with the diagonal or the V-cycle as preconditioner ---- */
+/* Paige and Saunders' MINRES with a symmetric POSITIVE DEFINITE preconditioner M, for the systems SolveMinres takes: A symmetric CSR of any
+ * inertia, shift finite and of any sign.  M is the diagonal of MgcgJacobiSetup (SolveMinresJacobi*: z = dinv*r is formed per element inside
+ * the passes, there is no z vector) or the V-cycle of any one-rank hierarchy -- MgSetup, MgSetupAggregation, MgSetupAggregates -- whose
+ * level 0 has `count` rows (SolveMinresMg: what SolveMg enqueues, r -> zVector).  The hierarchy need not be built from the solved matrix: a
+ * caller may build it for A + |shift| I, which is positive definite where A - shift I is not; only the row count is checked.  One
+ * application of M^-1 per iteration, still two global sums.  Below z means M^-1 applied.
+ * Method:
+ *   start   (MGCG_RULE_SIMPLE: x := 0)
+ *           t = b - A x  (as in SolveMinres) ;  r2_i = t_i + shift*x_i ;  z = M^-1 r2 ;  bz = r2.z
+ *           bz not finite or <= 0  ->  MGCG_NONFINITE at iteration 0, x untouched (a negative bz: the message says that the preconditioner is
+ *           not positive definite)
+ *           beta = beta1 = sqrt(bz) ;  v = z*(1/beta1) ;  vv = v.v ;  oldb = 0 ;  cs = -1 ;  sn = 0 ;  dbar = 0 ;  eps = 0 ;  phibar = beta1 ;
+ *           trace[0] = beta1 (sqrt(bz/bz) under MGCG_RULE_VIENNACL)
+ *   body k  q = A v ;  vq = v.q                                   (the plain loop's product)
+ *   pass A  alpha = vq - shift*vv ;  c1 = beta/oldb (k > 0) ;  c2 = alpha/beta            (the two quotients are formed once per body)
+ *           y_i = q_i - shift*v_i                                 (shift == 0: the term is not formed, v is not read)
+ *           y_i = y_i - c1*r1_i                                   (k = 0: not formed, r1 is not read)
+ *           rn_i = y_i - c2*r2_i ,  written over r1
+ *           Jacobi: z_i = dinv_i*rn_i is formed per element ;  rz = sum rn_i*z_i
+ *           V-cycle: the hierarchy's cycle rn -> zVector, then one dot launch for rz = rn.z
+ *   pass B  rz < 0 or not finite  ->  MGCG_NONFINITE reported for iteration k + 1, x and the directions unchanged by this body
+ *           betan = sqrt(rz) ;  SolveMinres's rotation with this alpha and betan, operation for operation, with its breakdown test
+ *           w_i = ((v_i - oldeps*w1_i) - dl*w2_i)*ig over w1 ;  x_i = x_i + phi*w_i
+ *           v_i := z_i*(1/betan) IN PLACE                         (Jacobi: z_i formed again from rn_i and dinv_i ;  not formed when betan == 0)
+ *           vv = sum v_i*v_i of the new v
+ *           rr = phibar*phibar is judged against bz as the residual of iteration k + 1 ;  betan == 0 ends the loop as in SolveMinres
+ *           (r1, r2) := (r2, rn) ;  (w1, w2) := (w2, w) ;  oldb := beta ;  beta := betan
+ *   end     SolveMinres's closing product: b - (A - shift I) x into rVector, its 2-norm in *trueResidual
+ * Rounding contract: SolveMinres's -- every product (shift*vv, shift*v_i, c1*r1_i, c2*r2_i, dinv_i*rn_i, rn_i*z_i, z_i*(1/betan), v_i*v_i, ...)
+ * goes into a double of its own before the add or subtraction that follows it, nothing is fused, the scalars are evaluated in the order
+ * written.  Under dot_order = 1 every sum is serial left to right and ranks add in rank order (tests/test_pminres_host.py restates the loop
+ * in numpy); the V-cycle is MgApply's fixed sequence of operations in either mode.
+ * WHAT THE STOP RULE JUDGES: phibar is || r || in the M^-1 NORM, sqrt(r . M^-1 r) -- the quantity preconditioned MINRES minimises -- not the
+ * 2-norm.  The four 2-norm rules of SolveEx are applied to (phibar^2, beta1^2 = bz); *iteration, *residual and the trace show that figure
+ * (it never increases); MGCG_RULE_HANDMADECL is refused.  *trueResidual (may be NULL) remains the plain 2-norm || b - (A - shift I) x ||_2
+ * from the closing product, which runs whenever the loop ended without MGCG_ERROR.  The two norms differ by the conditioning of M: a
+ * caller who needs the 2-norm below a level looks at *trueResidual (on this project's test systems the relative true residual was up to
+ * 2.2 x the relative phibar at the stop).  A 2-norm recurrence of the true residual would cost one more vector; it is not carried.
+ *   ApVector        work space (count entries): q
+ *   pVector         v, the one full-length buffer (count entries), overwritten in place by pass B
+ *   rVector, r1Vector   the two residual buffers, rotated by pointer per body (local rows).  On return rVector holds the true residual,
+ *                   whatever the parity of the rotation
+ *   w1Vector, w2Vector   the two direction buffers, rotated the same way (local rows)
+ *   dinvVector      what MgcgJacobiSetup wrote (local rows) ;  zVector: work space of the V-cycle form (count entries)
+ * One rank, Jacobi: three launches per iteration; the two passes move 48 (40 with shift == 0) and 72 bytes per row.  V-cycle: the cycle
+ * and one dot launch more.
+ * Refused with MGCG_ERROR, a message and nothing enqueued: everything SolveMinres refuses; a null dinvVector, mg or zVector; an r1, z or
+ * dinv vector that is too small; a hierarchy whose level 0 does not have `count` rows; a hierarchy of several ranks.
+ * Out of scope: the V-cycle on several ranks, Chebyshev as M, a true 2-norm stop, the block and mixed variants, the C++ twin under host/. */
+int SolveMinresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                      Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                      Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector,
+                      Vector* dinvVector,
+                      int elementsCount, int count, double shift,
+                      double allowableResidual, int minIteration, int maxIteration, int rule,
+                      int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+/* The same on a row partition, shaped after SolveMinresParallel.  Only pVector (v) is full length and has its halo exchanged, in line before
+ * every product; every other vector holds the local rows.  {vq, vv} travel in ONE all-reduce of two doubles and rz in one more (two per
+ * iteration, as in SolveParallel), the first bz and the closing r.r in one each.  A rank without rows takes part in every collective.  A
+ * rank whose dinvVector is NULL (its MgcgJacobiSetup failed) makes every rank return MGCG_ERROR, as in SolveJacobiParallel; every rank
+ * passes the same shift: that is not checked. */
+int SolveMinresJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                              Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                              Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector,
+                              Vector* dinvVector,
+                              int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ, double shift,
+                              double allowableResidual, int minIteration, int maxIteration, int rule,
+                              int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+/* The V-cycle form (one rank). */
+int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                  Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                  Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector,
+                  Vector* zVector,
+                  int elementsCount, int count, double shift,
+                  double allowableResidual, int minIteration, int maxIteration, int rule,
+                  int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what

@@ -1,0 +1,579 @@
+"""Preconditioned MINRES on the GPU (SolveMinresJacobi, SolveMinresJacobiParallel, SolveMinresMg, minres.MinimalResidualJacobiGpu,
+ConjugateGradientMgGpu.SolveMinres / ConjugateGradientAmgGpu.SolveMinres, ConjugateGradientRankGpu.SolveMinresJacobi).
+
+The reference for every comparison is ``pminres_oracle`` (tests/test_pminres_host.py): the header's loop in numpy with serial sums, with
+``dinv * r`` or the numpy V-cycle ``Hierarchy.apply`` (tests/test_amg_host.py) as M^-1.  Under dot_order = 1 the HIP loop is a fixed
+sequence of IEEE operations and status, iteration, residual, TrueResidual, trace and ALL of x and r must EQUAL it; in the default mode
+only the summation order of the sums (and of long rows) differs."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from conjugategradient_amd import _lib, problems
+from conjugategradient_amd.amg import ConjugateGradientAmgGpu
+from conjugategradient_amd.minres import MinimalResidualJacobiGpu
+from conjugategradient_amd.multigrid import ConjugateGradientMgGpu
+from conjugategradient_amd.parallel import ConjugateGradientMgRankGpu, ConjugateGradientRankGpu
+from conjugategradient_amd.solver import ApplicationException, _ptr
+from tests.gpu_util import dvec
+from tests.test_amg_host import Hierarchy, box_maps, csr_of
+from tests.test_gpu_jacobi import run_ranks
+from tests.test_pminres_host import jacobi_of, m_norm, numpy_residual_vector, pminres_oracle, preconditioner, psystem
+from tests.test_sreduce_host import tridiagonal, with_b
+
+pytestmark = pytest.mark.gpu
+
+RULES = [_lib.RULE_NATIVE, _lib.RULE_CSHARP, _lib.RULE_SIMPLE, _lib.RULE_VIENNACL]
+MAX_IT = 3000
+JACOBI_CASES = [("viennacl4000", 0.0), ("viennacl4000", 60.0), ("random_spd5000", 0.0), ("random_spd5000", 1.5), ("graph12", 0.0), ("graph12", 20.0)]
+RULE_CASES = [(n, sh, r) for n, sh in JACOBI_CASES for r in RULES]      # every (system, shift) under the four 2-norm rules
+_cache = {}
+
+
+def maxnz(s):
+    return int(np.diff(s.RowOffsets).max())
+
+
+def box_cycle(name, levels=3):
+    """The yardstick of the geometric hierarchy of MgSetup (levels = 3, the class's omega): box maps (tests/test_gpu_amg.py shows them equal)."""
+    key = ("box", name, levels)
+    if key not in _cache:
+        s = psystem(name)
+        nz = s.grid[2]
+        _cache[key] = Hierarchy(*csr_of(s), omega=6.0 / 7.0 if nz > 1 else 4.0 / 5.0, maps=box_maps(s.grid, levels)).apply
+    return _cache[key]
+
+
+def minv_of(name, kind):
+    return box_cycle(name) if kind == "box" else preconditioner(name, kind)
+
+
+def tolerance(name, kind, rule, rel=1e-8):
+    """The relative rule: rel; the absolute rules: rel of the first residual's M^-1 norm (every system here starts from x = 0: r0 = b)."""
+    s = psystem(name)
+    assert not s.x.any()
+    return rel if rule == _lib.RULE_VIENNACL else rel * m_norm(minv_of(name, kind), np.asarray(s.b))
+
+
+def reference(name, shift, kind, rule, tol, parts=None, **kw):
+    """The oracle's run, computed once per case and shared (nothing changes it)."""
+    key = ("ref", name, shift, kind, rule, tol, None if parts is None else tuple(parts), tuple(sorted(kw.items())))
+    if key not in _cache:
+        _cache[key] = pminres_oracle(psystem(name), shift, minv_of(name, kind), rule, tol, parts=parts, **{"max_it": MAX_IT, **kw})
+    return _cache[key]
+
+
+@pytest.fixture
+def dot_order(mgcg_env):
+    mgcg_env.setenv("MGCG_DOT_ORDER", "1")
+    yield
+    mgcg_env.delenv("MGCG_DOT_ORDER")
+
+
+def _finish(cg, solve):
+    """Run solve(); an iteration cap that was hit or a breakdown is a result here, not an exception."""
+    try:
+        solve()
+    except ApplicationException:
+        assert cg.status == _lib.MAXIT_EXCEEDED
+    except _lib.MgcgError:
+        assert cg.status == _lib.NONFINITE
+    cg.Read()
+    r = np.empty(cg.Count)
+    cg.vectorR.CopyTo(r, cg.Count, 0)
+    out = dict(x=cg.x.copy(), r=r, iteration=cg.Iteration, residual=cg.Residual, true_residual=cg.TrueResidual, status=cg.status, trace=cg.trace)
+    cg.Dispose()
+    return out
+
+
+def solve(s, shift, rule, tol, min_it=0, max_it=MAX_IT, compression=None, trace_capacity=None, prepare=None):
+    """One Jacobi solve through the Python class.  prepare(cg): after Initialize()."""
+    cg = MinimalResidualJacobiGpu(s.Count, maxnz(s), min_it, max_it, tol, rule=rule, shift=shift).load(s)
+    if compression is not None:
+        _lib.lib().MgcgSetMatrixCompression(cg.cusparse, compression)
+    cg.Initialize()
+    if prepare is not None:
+        prepare(cg)
+    return _finish(cg, lambda: cg.Solve(trace=True, traceCapacity=trace_capacity))
+
+
+def vcycle_solve(s, kind, shift, rule, tol, min_it=0, max_it=MAX_IT, prepare=None, hierarchy_of=None):
+    """One V-cycle solve through the Python classes: kind 'box' (MgSetup on s.grid) or 'vcycle' (MgSetupAggregation, the defaults).
+    hierarchy_of: the system the hierarchy is built from when it is not s."""
+    def make(system):
+        if kind == "box":
+            cg = ConjugateGradientMgGpu(system.Count, maxnz(system), min_it, max_it, tol, system.grid, levels=3, rule=rule).load(system)
+        else:
+            cg = ConjugateGradientAmgGpu(system.Count, maxnz(system), min_it, max_it, tol, rule=rule).load(system)
+        cg.Initialize()
+        return cg
+
+    cg = make(s)
+    other = make(hierarchy_of) if hierarchy_of is not None else None
+    own = cg.mg
+    if other is not None:
+        cg.mg = other.mg
+    if prepare is not None:
+        prepare(cg)
+
+    def run():
+        try:
+            cg.SolveMinres(shift=shift, trace=True)
+        finally:
+            cg.mg = own
+
+    out = _finish(cg, run)
+    if other is not None:
+        other.Dispose()
+    return out
+
+
+def same(a, b):
+    return a == b or (math.isnan(a) and math.isnan(b))
+
+
+def assert_equal_runs(got, ref):
+    assert got["status"] == ref["status"], (got["status"], ref["status"])
+    assert got["iteration"] == ref["iteration"], (got["iteration"], ref["iteration"])
+    assert same(got["residual"], ref["residual"]), (got["residual"], ref["residual"])
+    assert same(got["true_residual"], ref["true_residual"]), (got["true_residual"], ref["true_residual"])
+    assert np.array_equal(got["trace"], ref["trace"], equal_nan=True)
+    assert np.array_equal(got["x"], ref["x"], equal_nan=True)
+    assert np.array_equal(got["r"], ref["r"], equal_nan=True)
+
+
+# --------------------------------------------------------------------------- 1. Jacobi: bit equality with the oracle
+@pytest.mark.parametrize("which,shift,rule", RULE_CASES)
+def test_jacobi_equals_the_oracle_bit_for_bit(dot_order, which, shift, rule):
+    s = psystem(which)
+    tol = tolerance(which, "jacobi", rule)
+    ref = reference(which, shift, "jacobi", rule, tol)
+    assert ref["status"] == _lib.OK and ref["iteration"] >= 3, ref["iteration"]
+    got = solve(s, shift, rule, tol)
+    print(which, shift, rule, "iterations", got["iteration"], ref["iteration"], "residual", got["residual"], ref["residual"],
+          "true", got["true_residual"], ref["true_residual"])
+    assert_equal_runs(got, ref)
+
+
+@pytest.mark.parametrize("shift", [0.0, 0.01])
+@pytest.mark.parametrize("n", [1, 2, 3, 257, 511, 4097])
+def test_small_and_odd_sizes_equal_the_oracle(dot_order, n, shift):
+    """The odd tail, one workgroup plus tail, both branches of chunk_pairs; shift == 0 and != 0: both template arms."""
+    s, _ = tridiagonal(n)
+    minv = jacobi_of(s)
+    tol = 1e-10 * m_norm(minv, np.asarray(s.b))
+    ref = pminres_oracle(s, shift, minv, _lib.RULE_CSHARP, tol)
+    assert ref["status"] == _lib.OK
+    assert_equal_runs(solve(s, shift, _lib.RULE_CSHARP, tol), ref)
+
+
+def test_a_nonzero_initial_guess(dot_order):
+    s = psystem("random_spd5000")
+    start = with_b(s, s.b, "spd-x0")
+    start.x[:] = 0.5 * np.cos(0.01 * np.arange(s.Count))
+    tol = tolerance("random_spd5000", "jacobi", _lib.RULE_CSHARP)
+    ref = pminres_oracle(start, 1.5, preconditioner("random_spd5000", "jacobi"), _lib.RULE_CSHARP, tol, max_it=MAX_IT)
+    assert ref["status"] == _lib.OK and ref["iteration"] >= 3
+    assert_equal_runs(solve(start, 1.5, _lib.RULE_CSHARP, tol), ref)
+    # ... which MGCG_RULE_SIMPLE ignores
+    assert_equal_runs(solve(start, 1.5, _lib.RULE_SIMPLE, tol), reference("random_spd5000", 1.5, "jacobi", _lib.RULE_SIMPLE, tol))
+
+
+def test_min_iteration_beyond_convergence(dot_order):
+    s, _ = tridiagonal(300)
+    minv = jacobi_of(s)
+    tol = 1e-6 * m_norm(minv, np.asarray(s.b))
+    free = pminres_oracle(s, 0.01, minv, _lib.RULE_CSHARP, tol)
+    held = pminres_oracle(s, 0.01, minv, _lib.RULE_CSHARP, tol, min_it=free["iteration"] + 6)
+    assert free["status"] == held["status"] == _lib.OK and held["iteration"] == free["iteration"] + 6
+    assert_equal_runs(solve(s, 0.01, _lib.RULE_CSHARP, tol, min_it=free["iteration"] + 6), held)
+
+
+def test_iteration_cap_equals_the_oracle_and_raises(dot_order):
+    s = psystem("random_spd5000")
+    ref = reference("random_spd5000", 1.5, "jacobi", _lib.RULE_CSHARP, 0.0, max_it=3)
+    assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 4
+    assert_equal_runs(solve(s, 1.5, _lib.RULE_CSHARP, 0.0, max_it=3), ref)
+    cg = MinimalResidualJacobiGpu(s.Count, maxnz(s), 0, 3, 0.0, rule=_lib.RULE_CSHARP, shift=1.5).load(s)
+    cg.Initialize()
+    with pytest.raises(ApplicationException, match="MaxIteration=3"):
+        cg.Solve()
+    assert cg.Iteration == 4 and cg.status == _lib.MAXIT_EXCEEDED
+    cg.Dispose()
+
+
+def test_a_trace_shorter_than_the_run(dot_order):
+    s = psystem("random_spd5000")
+    tol = tolerance("random_spd5000", "jacobi", _lib.RULE_CSHARP)
+    ref = dict(reference("random_spd5000", 1.5, "jacobi", _lib.RULE_CSHARP, tol))
+    assert ref["iteration"] + 1 > 5
+    ref["trace"] = ref["trace"][:5]
+    assert_equal_runs(solve(s, 1.5, _lib.RULE_CSHARP, tol, trace_capacity=5), ref)
+
+
+def test_every_compression_mode_gives_the_mode_0_bits(dot_order):
+    s = psystem("graph12")
+    tol = tolerance("graph12", "jacobi", _lib.RULE_CSHARP, rel=1e-3)
+    runs = [solve(s, 20.0, _lib.RULE_CSHARP, tol, compression=mode)
+            for mode in (_lib.COMPRESSION_OFF, _lib.COMPRESSION_BEST, _lib.COMPRESSION_CODES, _lib.COMPRESSION_PB)]
+    ref = reference("graph12", 20.0, "jacobi", _lib.RULE_CSHARP, tol)
+    assert ref["status"] == _lib.OK and ref["iteration"] >= 3
+    assert_equal_runs(runs[0], ref)
+    for other in runs[1:]:
+        assert_equal_runs(other, runs[0])
+
+
+def test_garbage_in_the_work_space_does_not_reach_the_result(dot_order):
+    """NaN in all six work vectors (q, v, the two residual buffers, the two direction buffers)."""
+    s = psystem("random_spd5000")
+    tol = tolerance("random_spd5000", "jacobi", _lib.RULE_CSHARP)
+    nan = np.full(s.Count, np.nan)
+
+    def prepare(cg):
+        for v in (cg.vectorAp, cg.vectorP, cg.vectorR, cg.vectorR1, cg.vectorW1, cg.vectorW2):
+            v.CopyFrom(nan, s.Count)
+
+    assert_equal_runs(solve(s, 1.5, _lib.RULE_CSHARP, tol, prepare=prepare), reference("random_spd5000", 1.5, "jacobi", _lib.RULE_CSHARP, tol))
+
+
+def test_corner_cases_equal_the_oracle(dot_order):
+    """A zero right-hand side (NONFINITE at iteration 0) and a shift that makes the matrix singular on the Krylov space (body 0 breaks down)."""
+    t, _ = tridiagonal(50)
+    zero = with_b(t, np.zeros(50), "b0")
+    for rule in (_lib.RULE_CSHARP, _lib.RULE_VIENNACL):
+        ref = pminres_oracle(zero, 0.01, jacobi_of(t), rule, 1e-12)
+        assert ref["status"] == _lib.NONFINITE and ref["iteration"] == 0
+        assert_equal_runs(solve(zero, 0.01, rule, 1e-12), ref)
+    from tests.test_minres_host import singular2
+
+    s = singular2()
+    ref = pminres_oracle(s, 1.0, jacobi_of(s), _lib.RULE_CSHARP, 1e-12)
+    assert ref["status"] == _lib.NONFINITE and ref["iteration"] == 1 and np.array_equal(ref["x"], s.x)
+    assert_equal_runs(solve(s, 1.0, _lib.RULE_CSHARP, 1e-12), ref)
+
+
+def test_a_preconditioner_that_is_not_positive_definite_is_named(dot_order):
+    """dinv = -1 everywhere: NONFINITE at iteration 0, x as the caller left it, and the message says what is wrong with M."""
+    s = psystem("random_spd5000")
+    start = with_b(s, s.b, "x0")
+    start.x[:] = 0.25
+    ref = pminres_oracle(start, 1.5, lambda r: -1.0 * r, _lib.RULE_CSHARP, 1e-8)
+    assert ref["status"] == _lib.NONFINITE and ref["iteration"] == 0 and np.array_equal(ref["x"], start.x)
+    cg = MinimalResidualJacobiGpu(s.Count, maxnz(s), 0, 100, 1e-8, rule=_lib.RULE_CSHARP, shift=1.5).load(start)
+    cg.Initialize()
+    cg.vectorDinv.CopyFrom(np.full(s.Count, -1.0), s.Count)
+    with pytest.raises(_lib.MgcgError, match="not positive definite"):
+        cg.Solve(trace=True)
+    assert_equal_runs(_finish(cg, lambda: None), ref)
+
+
+STREAMING_ROWS = 3_000_001      # the smallest row count at which the passes take their streaming-hint form (n > 3 000 000); odd: the tail element runs
+
+
+def test_streaming_hint_form_equals_the_oracle(dot_order):
+    """Three bodies, tolerance 0, so that both sides stop at the iteration cap."""
+    s = tridiagonal(STREAMING_ROWS)[0]
+    ref = pminres_oracle(s, 0.01, jacobi_of(s), _lib.RULE_CSHARP, 0.0, max_it=2)
+    assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 3
+    assert_equal_runs(solve(s, 0.01, _lib.RULE_CSHARP, 0.0, max_it=2), ref)
+
+
+# --------------------------------------------------------------------------- 2. the V-cycle
+VCYCLE_CASES = [("poisson16", "box", 0.0), ("poisson16", "box", 0.5), ("graph12", "vcycle", 0.0), ("graph12", "vcycle", 20.0)]
+
+
+@pytest.mark.parametrize("which,kind,shift", VCYCLE_CASES)
+def test_vcycle_equals_the_oracle_bit_for_bit(dot_order, which, kind, shift):
+    """MgSetup on the 16^3 Poisson matrix and MgSetupAggregation on the graph Laplacian against Hierarchy.apply."""
+    s = psystem(which)
+    tol = tolerance(which, kind, _lib.RULE_CSHARP)
+    ref = reference(which, shift, kind, _lib.RULE_CSHARP, tol)
+    assert ref["status"] == _lib.OK and ref["iteration"] >= 3, ref["iteration"]
+    got = vcycle_solve(s, kind, shift, _lib.RULE_CSHARP, tol)
+    print(which, kind, shift, "iterations", got["iteration"], ref["iteration"], "residual", got["residual"], ref["residual"])
+    assert_equal_runs(got, ref)
+
+
+def _plus(s, sigma):
+    """A + sigma I: the stored diagonal entries moved."""
+    e = np.array(s.Elements[: s.nnz], dtype=np.float64)
+    rows = np.repeat(np.arange(s.Count), np.diff(s.RowOffsets))
+    e[np.asarray(s.ColumnIndeces[: s.nnz]) == rows] += sigma
+    return problems.LinearSystem(e, s.ColumnIndeces[: s.nnz], s.RowOffsets, np.zeros(s.Count), s.b, s.name + "-plus", s.grid)
+
+
+def test_a_hierarchy_of_a_plus_sigma_preconditions_a_minus_sigma(dot_order):
+    """The hierarchy is built from A + 0.5 I (positive definite) and used on A - 0.5 I: only its row count is checked.  NaN in zVector and
+    in the other work vectors on the way."""
+    s = psystem("poisson16")
+    up = _plus(s, 0.5)
+    minv = Hierarchy(*csr_of(up), omega=6.0 / 7.0, maps=box_maps(s.grid, 3)).apply
+    tol = 1e-8 * m_norm(minv, np.asarray(s.b))
+    ref = pminres_oracle(s, 0.5, minv, _lib.RULE_CSHARP, tol, max_it=MAX_IT)
+    assert ref["status"] == _lib.OK and ref["iteration"] >= 3
+    nan = np.full(s.Count, np.nan)
+
+    def prepare(cg):
+        for name in ("vectorW1", "vectorW2", "vectorR1"):
+            setattr(cg, name, dvec(nan))
+        for v in (cg.vectorZ, cg.vectorAp, cg.vectorP, cg.vectorR):
+            v.CopyFrom(nan, s.Count)
+
+    assert_equal_runs(vcycle_solve(s, "box", 0.5, _lib.RULE_CSHARP, tol, prepare=prepare, hierarchy_of=up), ref)
+
+
+def test_the_multigrid_classes_raise_at_the_cap_and_refuse_a_hierarchy_of_another_size(dot_order):
+    s = psystem("poisson16")
+    ref = reference("poisson16", 0.5, "box", _lib.RULE_CSHARP, 0.0, max_it=3)
+    assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 4
+    assert_equal_runs(vcycle_solve(s, "box", 0.5, _lib.RULE_CSHARP, 0.0, max_it=3), ref)
+    cg = ConjugateGradientMgGpu(s.Count, 7, 0, 3, 0.0, s.grid, levels=3).load(s)
+    cg.Initialize()
+    with pytest.raises(ApplicationException, match="MaxIteration=3"):
+        cg.SolveMinres(shift=0.5)
+    # a hierarchy whose level 0 has another row count
+    small = problems.poisson(8, 8, 8)
+    other = ConjugateGradientMgGpu(small.Count, 7, 0, 3, 0.0, small.grid, levels=2).load(small)
+    other.Initialize()
+    own, cg.mg = cg.mg, other.mg
+    try:
+        with pytest.raises(_lib.MgcgError, match="512 rows on level 0, the matrix has 4096"):
+            cg.SolveMinres(shift=0.5)
+    finally:
+        cg.mg = own
+    other.Dispose()
+    cg.Dispose()
+
+
+# --------------------------------------------------------------------------- 3. the classes against the C calls
+def test_the_classes_give_the_c_calls_results(dot_order):
+    L = _lib.lib()
+    s = psystem("random_spd5000")
+    tol = tolerance("random_spd5000", "jacobi", _lib.RULE_CSHARP)
+    nnz = int(s.RowOffsets[s.Count])
+
+    def c_call(cg, name, *extra):
+        it, res, true = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        tr = np.zeros(MAX_IT + 8)
+        cg.vectorX.CopyFrom(np.ascontiguousarray(s.x), s.Count)
+        head = (cg.cublas, cg.cusparse, cg.matDescr) + extra[:1] if name == "SolveMinresMg" else (cg.cublas, cg.cusparse, cg.matDescr)
+        st = getattr(L, name)(*head, cg.vectorA.Ptr, cg.vectorRowOffsets.Ptr, cg.vectorColumnIndeces.Ptr,
+                              cg.vectorX.Ptr, cg.vectorB.Ptr, cg.vectorAp.Ptr, cg.vectorP.Ptr, cg.vectorR.Ptr, cg.vectorR1.Ptr, cg.vectorW1.Ptr, cg.vectorW2.Ptr,
+                              extra[-1], nnz, s.Count, 1.5, tol, 0, MAX_IT, _lib.RULE_CSHARP, C.byref(it), C.byref(res), C.byref(true), _ptr(tr), len(tr))
+        x, r = np.empty(s.Count), np.empty(s.Count)
+        cg.vectorX.CopyTo(x, s.Count, 0)
+        cg.vectorR.CopyTo(r, s.Count, 0)
+        return dict(x=x, r=r, iteration=it.value, residual=res.value, true_residual=true.value, status=st, trace=tr[: it.value + 1].copy())
+
+    cg = MinimalResidualJacobiGpu(s.Count, maxnz(s), 0, MAX_IT, tol, rule=_lib.RULE_CSHARP, shift=1.5).load(s)
+    cg.Initialize()
+    direct = c_call(cg, "SolveMinresJacobi", cg.vectorDinv.Ptr)
+    cg.Dispose()
+    assert direct["status"] == _lib.OK
+    assert_equal_runs(solve(s, 1.5, _lib.RULE_CSHARP, tol), direct)
+
+    for which, kind in (("graph12", "vcycle"), ("poisson16", "box")):
+        s = psystem(which)
+        tol = tolerance(which, kind, _lib.RULE_CSHARP)
+        nnz = int(s.RowOffsets[s.Count])
+        if kind == "box":
+            cg = ConjugateGradientMgGpu(s.Count, maxnz(s), 0, MAX_IT, tol, s.grid, levels=3).load(s)
+        else:
+            cg = ConjugateGradientAmgGpu(s.Count, maxnz(s), 0, MAX_IT, tol).load(s)
+        cg.Initialize()
+        for name in ("vectorW1", "vectorW2", "vectorR1"):
+            setattr(cg, name, dvec(np.zeros(s.Count)))
+        direct = c_call(cg, "SolveMinresMg", cg.mg, cg.vectorZ.Ptr)
+        cg.Dispose()
+        assert direct["status"] == _lib.OK and direct["iteration"] >= 3
+        assert_equal_runs(vcycle_solve(s, kind, 1.5, _lib.RULE_CSHARP, tol), direct)
+
+
+# --------------------------------------------------------------------------- 4. default mode
+# The cases are those on which the ORACLE ITSELF, measured on the CPU at these tolerances with its serial sums replaced by numpy's pairwise
+# ones, moves by no more than half of what a margin allows -- the HIP loop's order of summation is a third one.  Its own movement:
+#   shift 0, relative 1e-13 (count serial / pairwise, x relative 2-norm distance)
+#     viennacl4000 Jacobi 13 / 13, 2.9e-16 ;  random_spd5000 Jacobi 23 / 23, 2.6e-15 ;  poisson16 geometric 28 / 28, 3.6e-16      -> taken
+#     graph12 Jacobi 360 / 302 ;  graph12 aggregation 84 / 85 (the whole margin of one iteration)                                -> not taken
+#   shift != 0, relative 1e-8 (count serial / pairwise)
+#     viennacl4000 60 Jacobi 63 / 62 ;  random_spd5000 1.5 Jacobi 19 / 19 ;  poisson16 0.5 geometric 46 / 46 ;
+#     graph12 5 aggregation (4 eigenvalues below the shift) 64 / 64                                                             -> taken
+#     graph12 20 Jacobi 1039 / 985 (5.2 %) ;  graph12 20 aggregation 294 / 275 (6.5 %): more than half of the 10 %                -> not taken
+# (the bit-for-bit tests above cover every one of them under dot_order = 1)
+DEFAULT_ZERO = [("viennacl4000", "jacobi"), ("random_spd5000", "jacobi"), ("poisson16", "box")]
+DEFAULT_SHIFTED = [("viennacl4000", "jacobi", 60.0), ("random_spd5000", "jacobi", 1.5), ("graph12", "vcycle", 5.0), ("poisson16", "box", 0.5)]
+
+
+def _default_solve(s, kind, shift, tol):
+    if kind == "jacobi":
+        return solve(s, shift, _lib.RULE_CSHARP, tol)
+    return vcycle_solve(s, kind, shift, _lib.RULE_CSHARP, tol)
+
+
+@pytest.mark.parametrize("which,kind", DEFAULT_ZERO)
+def test_default_dot_order_stays_within_1e_10_of_the_oracle(which, kind):
+    """shift 0, tolerance 1e-13 of the first residual, so that the one iteration the two runs may differ by moves x by far less than the
+    bound.  The comment above has the oracle's own movement between serial and pairwise sums at this tolerance."""
+    s = psystem(which)
+    tol = tolerance(which, kind, _lib.RULE_CSHARP, rel=1e-13)
+    ref = reference(which, 0.0, kind, _lib.RULE_CSHARP, tol)
+    got = _default_solve(s, kind, 0.0, tol)
+    distance = float(np.linalg.norm(got["x"] - ref["x"]) / np.linalg.norm(ref["x"]))
+    print(which, kind, "iterations", got["iteration"], ref["iteration"], "distance", distance)
+    assert got["status"] == ref["status"] == _lib.OK
+    assert abs(got["iteration"] - ref["iteration"]) <= 1
+    assert distance <= 1e-10
+
+
+@pytest.mark.parametrize("which,kind,shift", DEFAULT_SHIFTED)
+def test_default_dot_order_solves_the_indefinite_systems(which, kind, shift):
+    """The margins of tests/test_gpu_minres.py, taken over because the recurrence has the same sensitivity: status OK, the count within 10 %
+    of the oracle's, the numpy residual of x in the M^-1 norm at most 2 x the stop level (the oracle's is <= 1.0 x; the factor 2 is for
+    the drift of phibar under another summation order).  The comment above has the oracle's own movement."""
+    s = psystem(which)
+    minv = minv_of(which, kind)
+    tol = tolerance(which, kind, _lib.RULE_CSHARP)
+    ref = reference(which, shift, kind, _lib.RULE_CSHARP, tol)
+    got = _default_solve(s, kind, shift, tol)
+    r = numpy_residual_vector(s, shift, got["x"])
+    true_m = m_norm(minv, r)
+    print(which, kind, shift, "iterations", got["iteration"], ref["iteration"], "recurrence", got["residual"], "TrueResidual", got["true_residual"],
+          "numpy residual in the M^-1 norm", true_m, "=", true_m / tol, "x the stop level")
+    assert got["status"] == ref["status"] == _lib.OK
+    assert true_m <= 2.0 * tol
+    assert abs(got["iteration"] - ref["iteration"]) <= 0.1 * ref["iteration"]
+    # what the call reports as the true residual is the 2-norm of that vector, up to the rounding of the closing product
+    m = maxnz(s)
+    absx = np.abs(got["x"])
+    rows = np.repeat(np.arange(s.Count), np.diff(s.RowOffsets))
+    scale = np.bincount(rows, weights=np.abs(s.Elements[: s.nnz]) * absx[s.ColumnIndeces[: s.nnz]], minlength=s.Count) + np.abs(s.b) + abs(shift) * absx
+    assert abs(got["true_residual"] - float(np.linalg.norm(r))) <= (m + 2) * np.finfo(np.float64).eps * float(np.linalg.norm(scale))
+
+
+@pytest.mark.parametrize("serial", [False, True], ids=["default", "dot_order"])
+def test_the_trace_read_back_never_increases(mgcg_env, serial):
+    if serial:
+        mgcg_env.setenv("MGCG_DOT_ORDER", "1")
+    s = psystem("random_spd5000")
+    got = solve(s, 1.5, _lib.RULE_CSHARP, tolerance("random_spd5000", "jacobi", _lib.RULE_CSHARP))
+    assert got["status"] == _lib.OK and len(got["trace"]) == got["iteration"] + 1 >= 4
+    assert (np.diff(got["trace"]) <= 0.0).all()
+
+
+# --------------------------------------------------------------------------- 5. ranks (Jacobi)
+def _rank_solve(s, world, shift, rule, tol, max_it=MAX_IT, break_rank=None):
+    def make_rank(rank, comm):
+        cg = ConjugateGradientRankGpu(s.Count, maxnz(s), 0, max_it, tol, rank=rank, world=world, comm=comm, rule=rule, device=rank).load(s)
+        cg.Initialize()
+        cg.SetupJacobi()
+        if rank == break_rank:
+            cg.jacobiError = _lib.MgcgError("stands for a failed set-up")
+        try:
+            cg.SolveMinresJacobi(trace=True, shift=shift)
+        except _lib.MgcgError as e:
+            if break_rank is None:
+                raise
+            cg.Dispose()
+            return dict(status=cg.status, message=str(e))
+        cg.Read()
+        p = cg.part
+        r = np.zeros(max(p.count, 1))
+        if p.count:
+            cg.vectorR.CopyTo(r, p.count, 0)
+        out = dict(offset=p.offset, count=p.count, x=cg.x[p.offset: p.offset + p.count].copy(), r=r[: p.count], iteration=cg.Iteration,
+                   residual=cg.Residual, true_residual=cg.TrueResidual, status=cg.status, trace=cg.trace)
+        cg.Dispose()
+        return out
+
+    return run_ranks(world, make_rank)
+
+
+def _assert_ranks_equal(res, ref, parts):
+    x, r = np.zeros(parts[-1]), np.zeros(parts[-1])
+    for k in res:
+        x[k["offset"]: k["offset"] + k["count"]] = k["x"]
+        r[k["offset"]: k["offset"] + k["count"]] = k["r"]
+        assert k["status"] == ref["status"] and k["iteration"] == ref["iteration"] and k["residual"] == ref["residual"]
+        assert k["true_residual"] == ref["true_residual"]
+        assert np.array_equal(k["trace"], ref["trace"])
+    assert [k["offset"] for k in res] == parts[:-1]
+    assert np.array_equal(x, ref["x"])
+    assert np.array_equal(r, ref["r"])
+
+
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("which,shift", [("viennacl4000", 60.0), ("random_spd5000", 1.5)])
+def test_ranks_equal_the_oracle_with_its_sums_cut_at_their_rows(mgcg_env, dot_order, which, shift, world):
+    mgcg_env.setenv("MGCG_VIRTUAL_DEVICES", str(world))
+    s = psystem(which)
+    tol = tolerance(which, "jacobi", _lib.RULE_CSHARP)
+    parts = problems.partition_offsets(s.Count, world)
+    ref = reference(which, shift, "jacobi", _lib.RULE_CSHARP, tol, parts=parts)
+    assert ref["status"] == _lib.OK and ref["iteration"] >= 3
+    _assert_ranks_equal(_rank_solve(s, world, shift, _lib.RULE_CSHARP, tol), ref, parts)
+
+
+def test_a_rank_without_rows_takes_part(mgcg_env, dot_order):
+    world = 4
+    mgcg_env.setenv("MGCG_VIRTUAL_DEVICES", str(world))
+    s = problems.mgcg_main(3, 160)                      # 3 rows over 4 ranks: offsets [0, 0, 0, 0, 3]
+    parts = problems.partition_offsets(s.Count, world)
+    assert parts == [0, 0, 0, 0, 3]
+    ref = pminres_oracle(s, 0.25, jacobi_of(s), _lib.RULE_CSHARP, 1e-8, max_it=50, parts=parts)
+    assert ref["status"] == _lib.OK
+    res = _rank_solve(s, world, 0.25, _lib.RULE_CSHARP, 1e-8, max_it=50)
+    assert [k["count"] for k in res] == [0, 0, 0, 3]
+    _assert_ranks_equal(res, ref, parts)
+
+
+def test_a_rank_without_a_diagonal_makes_every_rank_return_an_error(mgcg_env):
+    world = 2
+    mgcg_env.setenv("MGCG_VIRTUAL_DEVICES", str(world))
+    s = psystem("random_spd5000")
+    res = _rank_solve(s, world, 1.5, _lib.RULE_CSHARP, 1e-8, break_rank=1)
+    assert [k["status"] for k in res] == [_lib.ERROR, _lib.ERROR]
+    assert "null handle" in res[1]["message"]
+
+
+def test_the_forced_several_ranks_path_on_one_rank_equals_the_one_rank_loop(mgcg_env, dot_order):
+    """MGCG_FORCE_MULTIRANK: a one-rank RCCL communicator takes the fold / all-reduce / GIVEN-pass path with a real ncclAllReduce on the
+    stream; the sums are the one-rank loop's, so are the bits.  A hierarchy built on that path is one of several ranks to SolveMinresMg,
+    which refuses it."""
+    L = _lib.lib()
+    L.SetDevice(0)
+    buf = (C.c_char * 128)()
+    assert L.MgcgCommGetUniqueId(buf) == 0, _lib.last_error()
+    comm = L.MgcgCommInitRank(buf, 1, 0)
+    assert comm, _lib.last_error()
+    mgcg_env.setenv("MGCG_FORCE_MULTIRANK", "1")
+    s = psystem("random_spd5000")
+    tol = tolerance("random_spd5000", "jacobi", _lib.RULE_CSHARP)
+    cg = ConjugateGradientRankGpu(s.Count, maxnz(s), 0, MAX_IT, tol, rank=0, world=1, comm=comm, rule=_lib.RULE_CSHARP, device=0).load(s)
+    cg.Initialize()
+    cg.SetupJacobi()
+    cg.SolveMinresJacobi(trace=True, shift=1.5)
+    cg.Read()
+    r = np.zeros(s.Count)
+    cg.vectorR.CopyTo(r, s.Count, 0)
+    got = dict(x=cg.x.copy(), r=r, iteration=cg.Iteration, residual=cg.Residual, true_residual=cg.TrueResidual, status=cg.status, trace=cg.trace)
+    cg.Dispose()
+    assert_equal_runs(got, reference("random_spd5000", 1.5, "jacobi", _lib.RULE_CSHARP, tol))
+
+    p = psystem("poisson16")
+    mg = ConjugateGradientMgRankGpu(p.Count, 7, 0, 10, 1e-8, p.grid, rank=0, world=1, comm=comm, device=0).load(p)
+    mg.Initialize()
+    mg.Setup()
+    work = [dvec(np.zeros(p.Count)) for _ in range(4)]
+    it, res = C.c_int(0), C.c_double(0.0)
+    L.MgcgClearLastError()
+    st = L.SolveMinresMg(mg.cublas, mg.cusparse, mg.matDescr, mg.mg, mg.vectorElements.Ptr, mg.vectorRowOffsets.Ptr, mg.vectorColumnIndeces.Ptr,
+                         mg.vectorX.Ptr, mg.vectorB.Ptr, mg.vectorAp.Ptr, mg.vectorP.Ptr, mg.vectorR.Ptr, work[0].Ptr, work[1].Ptr, work[2].Ptr, work[3].Ptr,
+                         int(p.RowOffsets[p.Count]), p.Count, 0.5, 1e-8, 0, 10, _lib.RULE_CSHARP, C.byref(it), C.byref(res), None, None, 0)
+    assert st == _lib.ERROR and "the V-cycle form runs on one rank" in _lib.last_error()
+    L.MgcgClearLastError()
+    for v in work:
+        v.Dispose()
+    mg.Dispose()
+    L.MgcgCommDestroy(comm)
