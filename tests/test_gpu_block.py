@@ -13,7 +13,7 @@ from conjugategradient_amd import _lib, problems
 from conjugategradient_amd.block import ConjugateGradientBlockGpu
 from conjugategradient_amd.parallel import ConjugateGradientRankGpu
 from conjugategradient_amd.solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble
-from oracle import oracle as O
+from tests import block_cases as BC
 from tests.gpu_util import Handles, assert_iterate_close, assert_trace_close, cap_inside_a_chunk, dvec, ivec, same_bits, same_under_every_chunking
 
 pytestmark = pytest.mark.gpu
@@ -78,24 +78,7 @@ def test_csrmv_block_equals_the_oracle_per_column(oracle, which):
     h.close()
 
 
-def _columns(s, k, seed=11):
-    """k columns cycling through b = 1, seeded random b, b scaled by 1e-6, b = A x* with a nonzero start x."""
-    rng = np.random.default_rng(seed)
-    n = s.Count
-    B, X = np.zeros((k, n)), np.zeros((k, n))
-    for j in range(k):
-        kind = j % 4
-        if kind == 0:
-            B[j] = 1.0 + 0.25 * (j // 4)
-        elif kind == 1:
-            B[j] = rng.standard_normal(n)
-        elif kind == 2:
-            B[j] = 1e-6 * (1.0 + 0.5 * rng.random(n))
-        else:
-            xs = rng.standard_normal(n)
-            B[j] = O.spmv(s.Elements, s.ColumnIndeces, s.RowOffsets, xs)
-            X[j] = rng.standard_normal(n)
-    return B, X
+_columns = BC.columns
 
 
 def _block(s, k, B, X, rule, max_it=MAX_IT, min_it=0, tol=TOL):
@@ -353,3 +336,372 @@ def test_chunking_cannot_change_a_result(k, order):
     capped = same_under_every_chunking(lambda: _block_results(s, k, B, X, cap), order)
     print("cap", cap, "status", capped["status"].tolist())
     assert (capped["status"] == _lib.MAXIT_EXCEEDED).any() and capped["iteration"].max() == cap + 1
+
+
+# =========================================================================== every path, every k: the k-column product and the passes
+# (tests/block_cases.py: ragged_spd mixes the product's fast, staged-slow and unstaged wavefronts in every 256-row tile)
+@pytest.fixture(scope="module")
+def handles():
+    h = Handles()
+    yield h
+    h.close()
+
+
+_cases = {}
+
+
+def ragged(n):
+    """ragged_spd(n) and its device copy, built once per module."""
+    if n not in _cases:
+        s = BC.ragged_spd(n)
+        cls = BC.span_classes(s.RowOffsets)
+        assert set(cls.tolist()) == {BC.FAST, BC.STAGED_SLOW, BC.UNSTAGED}
+        _cases[n] = (s, BC.DeviceBlock(s))
+    return _cases[n]
+
+
+def _assert_product(oracle, s, X, Y, what):
+    for j in range(X.shape[0]):
+        ref = oracle.spmv(s.Elements, s.ColumnIndeces, s.RowOffsets, X[j])
+        assert same_bits(Y[j], ref), (what, X.shape[0], j, np.nonzero(Y[j] != ref)[0][:8])
+
+
+# --------------------------------------------------------------------------- CsrMVBlock (the plain epilogue)
+@pytest.mark.parametrize("seed", range(BC.FUZZ_SEEDS))
+def test_csrmv_block_random_shapes(handles, oracle, seed):
+    """The row-tile kernel's fuzz shapes (test_csrmv_rowtile_random_shapes: the same generator, sizes, densities, empty rows, reversed rows
+    and nnz residues) with k = seed mod 8 + 1 columns: every column the oracle's stored-order product, bit for bit."""
+    assert BC.FUZZ_SEEDS < 8 or {BC.fuzz_k(i) for i in range(BC.FUZZ_SEEDS)} == set(range(1, 9))      # the seeds of a run hit every k
+    s, n, per_row, rng = BC.random_shape(seed)
+    k = BC.fuzz_k(seed)
+    X = rng.standard_normal((k, n))
+    A = BC.DeviceBlock(s)
+    _assert_product(oracle, s, X, A.product(handles, X), (seed, n, per_row))
+    A.dispose()
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257])
+def test_csrmv_block_tiny_and_edge_sizes(handles, oracle, n):
+    """Below, at and above a wavefront and a tile, for every k, into a y full of NaN; plus a matrix of fewer than 8 entries and one of
+    empty rows only, whose product is +0.0 in every bit."""
+    import scipy.sparse as sp
+
+    M = (sp.random(n, n, density=min(1.0, 5.0 / n), random_state=n, format="csr") + sp.eye(n, format="csr") * (n % 3 == 0)).tocsr()
+    M.sort_indices()
+    few = sp.csr_matrix((np.array([2.0, -3.0, 0.5]), (np.array([0, 0, n - 1]), np.array([n - 1, 0, n // 2]))), shape=(n, n))
+    few.sum_duplicates()
+    none = sp.csr_matrix((n, n))
+    rng = np.random.default_rng(n)
+    for name, M in (("random", M), ("few", few), ("none", none)):
+        s = problems.LinearSystem(M.data.astype(np.float64), M.indices.astype(np.int32), M.indptr.astype(np.int32), np.zeros(n), np.zeros(n), name)
+        assert name != "few" or 0 < s.nnz < 8
+        assert name != "none" or s.nnz == 0
+        A = BC.DeviceBlock(s)
+        for k in range(1, 9):
+            X = rng.standard_normal((k, n))
+            Y = A.product(handles, X)
+            _assert_product(oracle, s, X, Y, (name, n))
+            if name == "none":
+                assert same_bits(Y, np.zeros((k, n)))
+        A.dispose()
+
+
+@pytest.mark.parametrize("n", [1350, 600_006, 600_134])
+def test_csrmv_block_on_every_path(handles, oracle, n):
+    """ragged_spd, k = 1 .. 8.  1350 rows: six tiles, the last one with two wavefronts that own no row.
+
+    600 006 rows: the tile loop is launched with min(2 * 256 CUs, tiles) = 512 workgroups, so it takes a second trip above
+    512 * 256 = 131 072 rows; the passes of the block loop run at most kMaxGrid = 2048 workgroups of 256 threads and stride above
+    524 288 rows.  600 006 is past both, even, and 198 mod 256: its last tile (number 2343, the fifth trip of workgroup 295) has three full
+    wavefronts and one of 6 rows.  600 134 is the next row count that is 70 mod 256: there the last tile, again on a fifth trip, has two
+    wavefronts that own no row."""
+    s, A = ragged(n)
+    rng = np.random.default_rng(n)
+    for k in range(1, 9):
+        X = rng.standard_normal((k, n))
+        X[0, ::7] = -0.0
+        _assert_product(oracle, s, X, A.product(handles, X), n)
+
+
+@pytest.mark.parametrize("which", ["ragged1351", "grid13x11x5"])
+def test_csrmv_block_unaligned_subarrays(handles, oracle, which):
+    """The matrix arrays one element, x and y one and two elements into larger vectors (test_csrmv_unaligned_subarrays), with an odd
+    count: one element in, columns 0, 2, ... of x and y are 8-byte aligned only; two elements in, columns 1, 3, ... are.  The elements
+    around y stay as they were."""
+    s = BC.ragged_spd(1351) if which == "ragged1351" else problems.poisson(13, 11, 5)
+    n, nnz = s.Count, s.nnz
+    assert n % 2 == 1
+    L = _lib.lib()
+    e = dvec(np.concatenate([[9.0], s.Elements[:nnz]]))
+    c = ivec(np.concatenate([[0], s.ColumnIndeces[:nnz]]))
+    r = ivec(s.RowOffsets)
+    rng = np.random.default_rng(4)
+    for k in range(1, 9):
+        X = rng.standard_normal((k, n))
+        for lead in (1, 2):
+            vx, vy = dvec(np.concatenate([np.full(lead, 5.0), X.reshape(-1), [5.0]])), dvec(np.full(k * n + lead + 1, -3.0))
+            L.CsrMVBlock(handles.sparse, handles.descr, vy.ToRawPtr() + 8 * lead, e.ToRawPtr() + 8, r.ToRawPtr(), c.ToRawPtr() + 4, vx.ToRawPtr() + 8 * lead,
+                         nnz, n, k)
+            _lib.check("CsrMVBlock")
+            out = vy.to_numpy(k * n + lead + 1)
+            assert (out[:lead] == -3.0).all() and out[-1] == -3.0
+            _assert_product(oracle, s, X, out[lead:-1].reshape(k, n), (which, lead))
+            vx.Dispose()
+            vy.Dispose()
+
+
+@pytest.mark.parametrize("k", range(1, 9))
+def test_csrmv_block_drops_the_products_of_masked_slots(handles, oracle, k):
+    """inf, -inf and nan in x[0] and in the first stored column of six spans, in every second column of the block (and in the last):
+    rows that do not store a poisoned column stay finite -- a masked slot gathers column 0 and must drop the product, 0 * inf is NaN --
+    and every column equals the oracle's, NaN where it has NaN.  The other columns of the block stay finite everywhere."""
+    s, A = ragged(1350)
+    n = s.Count
+    X = np.random.default_rng(20 + k).standard_normal((k, n))
+    poisoned = sorted(set(range(0, k, 2)) | {k - 1})
+    clean = {j: BC.poison(s, X[j], seed=j) for j in poisoned}
+    Y = A.product(handles, X)
+    for j in range(k):
+        ref = oracle.spmv(s.Elements, s.ColumnIndeces, s.RowOffsets, X[j])
+        if j in clean:
+            BC.assert_poisoned_product(Y[j], ref, clean[j])
+        else:
+            assert np.isfinite(ref).all() and same_bits(Y[j], ref), j
+
+
+# --------------------------------------------------------------------------- SolveBlockEx: both epilogues and the three passes, every k
+_refs = {}
+ORDER = [0, 2, 3, 1, 4, 6, 7, 5]
+
+
+def mixed_columns(s, k, seed=11):
+    """The first k of BC.columns' eight in the order b = 1, 1e-6 b, A x* with a start, random b, ...: on the well-conditioned ragged_spd
+    b = 1 and a random b stop in the same iteration (the oracle's 21), the scaled column in iteration 8 and the one with a start in 22,
+    so that already k = 2 freezes a column long before the other ends."""
+    B, X = BC.columns(s, 8, seed=seed)
+    return B[ORDER[:k]].copy(), X[ORDER[:k]].copy()
+
+
+def oracle_columns(oracle, s, B, X, orule, tol=TOL, max_it=MAX_IT, key=None):
+    """The oracle's CG on every column, computed once per case (the columns of BC.columns do not depend on k) and never changed."""
+    out = []
+    for j in range(B.shape[0]):
+        kk = (key, s.name, j, orule, tol, max_it)
+        if key is None or kk not in _refs:
+            ref = _oracle_column(oracle, s, B[j], X[j], orule, max_it=max_it, tol=tol)
+            ref["x"].setflags(write=False)
+            ref["trace"].setflags(write=False)
+            if key is None:
+                out.append(ref)
+                continue
+            _refs[kk] = ref
+        out.append(_refs[kk])
+    return out
+
+
+def assert_columns_equal(got_x, iteration, residual, status, traces, refs):
+    for j, ref in enumerate(refs):
+        assert status[j] == ref["status"], (j, status, ref["status"])
+        assert iteration[j] == ref["iteration"], (j, iteration, ref["iteration"])
+        assert residual[j] == ref["residual"], j
+        assert np.array_equal(traces[j], ref["trace"]), j
+        assert np.array_equal(got_x[j], ref["x"]), (j, np.nonzero(got_x[j] != ref["x"])[0][:8])
+
+
+@pytest.mark.parametrize("k,orule,grule", [(k, "RULE_CSHARP", _lib.RULE_CSHARP) for k in range(1, 9)] +
+                         [(2, "RULE_HANDMADECL", _lib.RULE_HANDMADECL), (5, "RULE_HANDMADECL", _lib.RULE_HANDMADECL)])
+def test_block_on_every_path_equals_the_oracle_bit_for_bit(oracle, dot_order, k, orule, grule):
+    """ragged_spd(1350): the residual and the p.Ap epilogue on fast, staged-slow and unstaged wavefronts and the three passes for every k,
+    with columns that stop in different iterations (the frozen-column branches of every K); the max-norm rule is the pass's INF form."""
+    s, _ = ragged(1350)
+    B, X = mixed_columns(s, k)
+    cg, err = _block(s, k, B, X, grule)
+    assert err is None, err
+    refs = oracle_columns(oracle, s, B, X, orule, key="free")
+    assert all(ref["status"] == _lib.OK for ref in refs)
+    assert_columns_equal(cg.X, cg.Iteration, cg.Residual, cg.Status, cg.trace, refs)
+    print("iterations", cg.Iteration.tolist())
+    if k > 1:
+        assert len(set(cg.Iteration.tolist())) > 1, cg.Iteration
+    cg.Dispose()
+
+
+@pytest.mark.parametrize("k", [3, 6])
+def test_frozen_columns_keep_their_p_and_r(handles, dot_order, k):
+    """A column that stopped is written by no kernel again: when the last column ends, the direction p and the residual r of every
+    column are the bits that a solve of that column alone leaves behind (the oracle does not show its p and r; the one-column solve is
+    held to the oracle above)."""
+    s, A = ragged(1350)
+    B, X = mixed_columns(s, k)
+    got = A.solve(handles, B, X, _lib.RULE_CSHARP, TOL, 0, MAX_IT)
+    assert got["ret"] == _lib.OK and len(set(got["iteration"].tolist())) > 1, (got["message"], got["iteration"])
+    for j in range(k):
+        one = A.solve(handles, B[j: j + 1], X[j: j + 1], _lib.RULE_CSHARP, TOL, 0, MAX_IT)
+        assert one["ret"] == _lib.OK and one["iteration"][0] == got["iteration"][j], j
+        assert same_bits(one["x"][0], got["x"][j]) and same_bits(one["r"][0], got["r"][j]), j
+        assert same_bits(one["p"][0], got["p"][j]), (j, np.nonzero(one["p"][0] != got["p"][j])[0][:8])
+
+
+@pytest.mark.parametrize("k", [3, 6])
+def test_block_second_trips_equal_the_oracle(handles, oracle, dot_order, k):
+    """600 006 rows (test_csrmv_block_on_every_path says why), tolerance 0 and a cap of 5: both sides end at the cap.  The tile loop of both
+    epilogues and the grid-stride loops of the three passes take further trips, the last one partly filled."""
+    s, A = ragged(600_006)
+    B, X = mixed_columns(s, k)
+    got = A.solve(handles, B, X, _lib.RULE_CSHARP, 0.0, 0, 5)
+    assert got["ret"] == _lib.MAXIT_EXCEEDED, got["message"]
+    refs = oracle_columns(oracle, s, B, X, "RULE_CSHARP", tol=0.0, max_it=5, key="capped")
+    assert all(ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 6 for ref in refs)
+    cap = got["cap"]
+    traces = [got["trace"][j * cap: j * cap + got["iteration"][j] + 1] for j in range(k)]
+    assert_columns_equal(got["x"], got["iteration"], got["residual"], got["status"], traces, refs)
+
+
+@pytest.mark.parametrize("k", [2, 7])
+@pytest.mark.parametrize("n", [1, 2, 63, 65, 257])
+def test_block_small_and_odd_sizes_equal_the_oracle(oracle, dot_order, n, k):
+    """A dominant tridiagonal of less than a wavefront, one row more than a wavefront, one row more than a tile; odd n: columns 1, 3, ...
+    of x, b and r are 8-byte aligned only."""
+    from tests.test_gpu_jacobi import tridiagonal
+
+    s, _ = tridiagonal(n)
+    B, X = BC.columns(s, k)
+    cg, err = _block(s, k, B, X, _lib.RULE_CSHARP)
+    assert err is None, err
+    refs = oracle_columns(oracle, s, B, X, "RULE_CSHARP")
+    assert all(ref["status"] == _lib.OK for ref in refs)
+    assert_columns_equal(cg.X, cg.Iteration, cg.Residual, cg.Status, cg.trace, refs)
+    cg.Dispose()
+
+
+def test_a_trace_shorter_than_the_run(handles, oracle, dot_order):
+    """Capacity 4 per column: column j's first four entries at trace[4 j ...], nothing beyond 4 k, and a column that stops earlier
+    leaves the rest of its own four entries alone."""
+    s, A = ragged(1350)
+    k, cap = 5, 4
+    B, X = mixed_columns(s, k)
+    B[4] = np.where(np.arange(s.Count) == 0, 1e-9, 0.0)                     # below the tolerance after its first iteration: stops within the capacity
+    refs = oracle_columns(oracle, s, B, X, "RULE_CSHARP")
+    used = [min(ref["iteration"] + 1, cap) for ref in refs]
+    assert max(ref["iteration"] for ref in refs) + 1 > cap and min(used) < cap, [ref["iteration"] for ref in refs]
+    got = A.solve(handles, B, X, _lib.RULE_CSHARP, TOL, 0, MAX_IT, trace_capacity=cap)
+    assert got["ret"] == _lib.OK, got["message"]
+    tr = got["trace"]
+    assert (tr[k * cap:] == -1.0).all()
+    for j, ref in enumerate(refs):
+        assert np.array_equal(tr[j * cap: j * cap + used[j]], ref["trace"][:cap]), j
+        assert (tr[j * cap + used[j]: (j + 1) * cap] == -1.0).all(), j
+    assert_columns_equal(got["x"], got["iteration"], got["residual"], got["status"], [ref["trace"] for ref in refs], refs)
+
+
+@pytest.mark.parametrize("k,orule,grule", [(6, "RULE_CSHARP", _lib.RULE_CSHARP), (5, "RULE_HANDMADECL", _lib.RULE_HANDMADECL)])
+def test_garbage_in_the_work_space_does_not_reach_the_result(oracle, mgcg_env, k, orule, grule):
+    """NaN in the caller's Ap, p and r.  The partial sums live on the handle's workspace (3 regions of 8 columns of 8192 doubles),
+    allocated by the first solve of a new handle: a vector of that size full of NaN is freed just before, which is where the allocator
+    usually takes it from (nothing here can check that it did).  dot_order = 1: the oracle's bits; default mode (where the partial sums
+    of every workgroup are read): the bits of a solve that started from clean work vectors."""
+    s, A = ragged(1350)
+    B, X = mixed_columns(s, k)
+    nan_space = np.full(3 * 8 * 8192, np.nan)
+
+    def run(garbage):
+        h = Handles()
+        if garbage is not None:
+            dvec(nan_space).Dispose()
+        out = A.solve(h, B, X, grule, TOL, 0, MAX_IT, garbage=garbage)
+        h.close()
+        return out
+
+    clean, dirty = run(None), run(np.nan)
+    assert clean["ret"] == dirty["ret"] == _lib.OK, (clean["message"], dirty["message"])
+    for key in ("iteration", "residual", "status", "trace", "x"):
+        assert same_bits(clean[key], dirty[key]), key
+    mgcg_env.setenv("MGCG_DOT_ORDER", "1")
+    got = run(np.nan)
+    mgcg_env.delenv("MGCG_DOT_ORDER")
+    cap = got["cap"]
+    refs = oracle_columns(oracle, s, B, X, orule, key="free")
+    assert_columns_equal(got["x"], got["iteration"], got["residual"], got["status"], [got["trace"][j * cap: j * cap + got["iteration"][j] + 1] for j in range(k)], refs)
+
+
+@pytest.mark.parametrize("k", [2, 5])
+def test_block_default_mode_on_every_path(oracle, k):
+    """dot_order = 0 at tolerance 1e-6 (test_block_default_mode_within_the_north_star says why), the project's standing tolerances; the
+    oracle's own spread over the summation order of its dots (1 .. 4 devices' partial sums) widens the iterate's bound only where it
+    exceeds 1e-10, as assert_iterate_close documents."""
+    tol = 1e-6
+    s, _ = ragged(1350)
+    B, X = BC.columns(s, k, seed=5)
+    cg, err = _block(s, k, B, X, _lib.RULE_CSHARP, tol=tol)
+    assert err is None, err
+    for j in range(k):
+        print("column", j, "iterations", cg.Iteration[j], "trace", cg.trace[j][:3], cg.trace[j][-2:])
+        sj = dataclasses.replace(s, b=B[j].copy(), x=X[j].copy())
+        ref = _oracle_column(oracle, s, B[j], X[j], "RULE_CSHARP", tol=tol)
+        spread = [oracle.cg_parallel(sj, d, allowable_residual=tol, max_iteration=MAX_IT)["x"] for d in (2, 3, 4)]
+        assert cg.Iteration[j] == ref["iteration"], (j, cg.Iteration, ref["iteration"])
+        assert cg.Status[j] == _lib.OK
+        assert_trace_close(cg.trace[j], ref["trace"])
+        print("column", j, "distance, oracle spread", assert_iterate_close(cg.X[j], ref["x"], spread_refs=spread))
+    cg.Dispose()
+
+
+# --------------------------------------------------------------------------- the streaming forms, at the smallest size that takes them
+STREAMING_ROWS = 8_000_001       # the product and the block loop's passes take their non-temporal forms from 8 000 000 rows
+
+
+@pytest.fixture(scope="module")
+def streaming():
+    """The dominant tridiagonal plus hub rows and one span of more than 512 entries (the unstaged branch has non-temporal loads of its
+    own), built and sent to the device once."""
+    s = BC.streaming_system(STREAMING_ROWS)
+    cls = BC.span_classes(s.RowOffsets)
+    assert (cls == BC.UNSTAGED).sum() == 1 and (cls == BC.STAGED_SLOW).sum() >= 5 and BC.strictly_dominant(s)
+    A = BC.DeviceBlock(s)
+    yield s, A
+    A.dispose()
+
+
+def _streaming_columns(n, k, seed):
+    rng = np.random.default_rng(seed)
+    B = rng.standard_normal((k, n))
+    B[k - 1] *= 1e-3
+    return B, np.zeros((k, n))
+
+
+def test_streaming_product_equals_the_oracle(handles, oracle, streaming):
+    s, A = streaming
+    X = np.random.default_rng(8).standard_normal((3, s.Count))
+    _assert_product(oracle, s, X, A.product(handles, X), "streaming")
+
+
+@pytest.mark.parametrize("k,orule,grule", [(2, "RULE_HANDMADECL", _lib.RULE_HANDMADECL), (3, "RULE_CSHARP", _lib.RULE_CSHARP)])
+def test_streaming_block_solve_equals_the_oracle(handles, oracle, dot_order, streaming, k, orule, grule):
+    """Tolerance 0, cap 3: both sides end at the cap."""
+    s, A = streaming
+    B, X = _streaming_columns(s.Count, k, 80 + k)
+    got = A.solve(handles, B, X, grule, 0.0, 0, 3)
+    assert got["ret"] == _lib.MAXIT_EXCEEDED, got["message"]
+    refs = oracle_columns(oracle, s, B, X, orule, tol=0.0, max_it=3)
+    assert all(ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 4 for ref in refs)
+    cap = got["cap"]
+    assert_columns_equal(got["x"], got["iteration"], got["residual"], got["status"], [got["trace"][j * cap: j * cap + got["iteration"][j] + 1] for j in range(k)], refs)
+
+
+def test_streaming_gram_product_equals_the_yardstick(handles, oracle, dot_order, streaming):
+    """SolveBlockKrylov, k = 2, cap 2 (tolerance 0): the Gram epilogue's non-temporal form."""
+    from tests.test_gpu_blockkrylov import bcgrq_yardstick
+
+    s, A = streaming
+    k = 2
+    B, X = _streaming_columns(s.Count, k, 90)
+    ref = bcgrq_yardstick((s.Elements, s.ColumnIndeces, s.RowOffsets), B, X, rule=_lib.RULE_VIENNACL, tol=0.0, max_it=2)
+    assert ref["failed"] is None and ref["iteration"] == 3 and (ref["status"] == _lib.MAXIT_EXCEEDED).all()
+    got = A.solve(handles, B, X, _lib.RULE_VIENNACL, 0.0, 0, 2, krylov=True)
+    assert got["ret"] == _lib.MAXIT_EXCEEDED, got["message"]
+    assert got["iteration"] == ref["iteration"]
+    assert np.array_equal(got["status"], ref["status"]) and np.array_equal(got["residual"], ref["residual"])
+    cap = got["cap"]
+    for j in range(k):
+        assert np.array_equal(got["trace"][j * cap: j * cap + ref["iteration"] + 1], ref["trace"][j]), j
+    assert np.array_equal(got["x"], ref["x"])

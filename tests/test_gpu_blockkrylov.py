@@ -366,6 +366,31 @@ def test_dot_order_one_equals_the_yardstick_bit_for_bit(oracle, dot_order, which
     assert np.array_equal(cg.X, ref["x"])
 
 
+@pytest.mark.parametrize("k", [2, 4, 5, 6, 7])
+def test_gram_product_on_every_path_equals_the_yardstick(oracle, dot_order, k):
+    """tests/block_cases.py: ragged_spd(1350) mixes the product's fast, staged-slow and unstaged wavefronts in every tile and leaves two
+    wavefronts of the last tile without a row.  The Gram epilogue (and the interleaved gather of the slow paths) for the k that no other
+    system here runs."""
+    from tests.block_cases import ragged_spd
+
+    if "ragged_spd1350" not in _csr:
+        s = ragged_spd(1350)
+        _csr["ragged_spd1350"] = (s.Elements, s.ColumnIndeces, s.RowOffsets)
+    which, seed = "ragged_spd1350", 100 + k
+    csr = csr_of(which)
+    ref = reference(which, k, seed, x0=(k % 2 == 1))
+    assert ref["failed"] is None and (ref["status"] == _lib.OK).all() and ref["iteration"] >= 3
+    B, X = columns(1350, k, seed, x0=(k % 2 == 1))
+    cg, err = solve(which, B, X)
+    assert err is None, err
+    assert cg.Iteration == ref["iteration"], (cg.Iteration, ref["iteration"])
+    assert np.array_equal(cg.status, ref["status"]) and np.array_equal(cg.Residual, ref["residual"])
+    for j in range(k):
+        assert np.array_equal(cg.trace[j], ref["trace"][j]), j
+    assert np.array_equal(cg.X, ref["x"])
+    cg.Dispose()
+
+
 def test_two_default_mode_solves_give_identical_bits(oracle):
     which, k, seed = "grid7x9x11", 8, 26
     B, X = columns(693, k, seed, x0=True)

@@ -245,6 +245,23 @@ def test_product_equals_the_serial_float32_product(h, which):
         assert got[77] == 0.0 and not np.signbit(got[77])
 
 
+@pytest.mark.parametrize("which", ["ragged_spd1350", "poisson20x17x13"])
+def test_product_drops_the_products_of_masked_slots(h, which):
+    """inf, -inf, nan and the largest float in x (tests/block_cases.py: poison): the serial float32 product's values, NaN where it has NaN,
+    and every row that stores none of those columns finite.  Both matrices take the lane = row form (mean row length below 20)."""
+    from tests.block_cases import assert_poisoned_product, poison, ragged_spd
+
+    s = ragged_spd(1350) if which == "ragged_spd1350" else problems.poisson(20, 17, 13)
+    assert s.nnz <= 20 * s.Count
+    d = DeviceSystem(h, s)
+    assert d.setup() == 0
+    x = _x32(s.Count)
+    clean = poison(s, x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ref = serial_product(s, x)
+    assert_poisoned_product(d.product(x), ref, clean)
+
+
 @pytest.mark.parametrize("width", [24, 100, 300])       # 8, 16 and 32 lanes per row
 def test_long_rows_take_the_lanes_per_row_form(h, mgcg_env, width):
     """Positive terms, so that the rounding of a `width`-term float32 sum in any order is width * 2^-24 relative to the row's value."""

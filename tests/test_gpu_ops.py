@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conjugategradient_amd import _lib, problems
+from tests.block_cases import assert_poisoned_product, poison, ragged_spd, random_shape
 from tests.gpu_util import DeviceCsr, Handles, dvec, ivec
 
 pytestmark = pytest.mark.gpu
@@ -130,25 +131,8 @@ def test_csrmv_rowtile_random_shapes(h, oracle, seed):
     """Randomised shapes for the row-tile kernel: sizes around the tile and block boundaries, densities that mix the fast path
     (rows <= 7 / 8, spans <= 512) with slow blocks, empty rows, unsorted columns, nnz of every residue mod 4; CsrMV and the
     fused CsrMVDot against the oracle (product bit for bit, dot to summation order)."""
-    import scipy.sparse as sp
     L = _lib.lib()
-    rng = np.random.default_rng(1000 + seed)
-    n = int(rng.choice([200, 256, 300, 511, 512, 1000, 4096, 5000, 33333]))
-    per_row = float(rng.choice([0.5, 2.0, 5.0, 7.0, 9.0]))
-    k = rng.poisson(per_row, size=n)                            # row lengths; duplicates are merged below
-    rows = np.repeat(np.arange(n), k)
-    M = sp.coo_matrix((rng.standard_normal(rows.size), (rows, rng.integers(0, n, size=rows.size))), shape=(n, n)).tocsr()
-    if seed % 3 == 0:
-        M = M + sp.eye(n, format="csr")
-    M = M.tocsr()
-    M.sum_duplicates()
-    M.sort_indices()
-    data, indices, indptr = M.data.astype(np.float64), M.indices.astype(np.int32), M.indptr.astype(np.int32)
-    if seed % 2 == 1:                                           # unsorted columns: reverse every row
-        for i in range(n):
-            data[indptr[i]:indptr[i + 1]] = data[indptr[i]:indptr[i + 1]][::-1]
-            indices[indptr[i]:indptr[i + 1]] = indices[indptr[i]:indptr[i + 1]][::-1]
-    sysm = problems.LinearSystem(data, indices, indptr, np.zeros(n), np.zeros(n), "rnd")
+    sysm, n, per_row, rng = random_shape(seed)                  # (shared with the k-column product's fuzz test, tests/test_gpu_block.py)
     x, y0 = rng.standard_normal(n), rng.standard_normal(n)
     ref = oracle.spmv(sysm.Elements, sysm.ColumnIndeces, sysm.RowOffsets, x)
     A = DeviceCsr(sysm)
@@ -164,6 +148,52 @@ def test_csrmv_rowtile_random_shapes(h, oracle, seed):
         assert np.array_equal(vy.to_numpy(n), ref)
         want = float(np.dot(x, ref))
         assert abs(got - want) <= 1e-12 * max(1.0, float(np.abs(x * ref).sum()))
+
+
+POISONED = {"ragged_spd1350": lambda: ragged_spd(1350), "poisson20x17x13": lambda: problems.poisson(20, 17, 13)}
+
+
+def _poisoned(oracle, which):
+    """(system, x with inf, -inf, nan, the largest double and -0.0 in it, the oracle's product, the rows that store none of those columns)"""
+    s = POISONED[which]()
+    x = np.random.default_rng(31).standard_normal(s.Count)
+    clean = poison(s, x)
+    return s, x, oracle.spmv(s.Elements, s.ColumnIndeces, s.RowOffsets, x), clean
+
+
+@pytest.mark.parametrize("which", list(POISONED))
+def test_csrmv_drops_the_products_of_masked_slots(h, oracle, which):
+    """The fast paths of the lane = row kernels fill the slots a short row does not use with column 0 (or the span's first stored one) and
+    select the product away: with inf or nan in those columns of x, a kernel that multiplied by a zero mask instead would turn rows
+    that never store them into NaN.  Stored-order kernels: the oracle's bits, NaN where it has NaN; the lanes-per-row kernels reorder
+    their sums, so only: every row that stores no poisoned column is finite."""
+    s, x, ref, clean = _poisoned(oracle, which)
+    A = DeviceCsr(s)
+    for kernel in (1, 9, 10):
+        assert_poisoned_product(A.spmv(h, x, kernel=kernel), ref, clean)
+    for kernel in (3, 4, 5, 6, 7, 8):
+        assert_poisoned_product(A.spmv(h, x, kernel=kernel), ref, clean, exact=False)
+
+
+@pytest.mark.parametrize("mode", [1, 2, 3])
+@pytest.mark.parametrize("which,classes", [("poisson20x17x13", {1: 3, 2: 2, 3: 3}), ("ragged_spd1350", {1: None, 2: None, 3: None})])
+def test_lossless_forms_drop_the_products_of_masked_slots(oracle, which, classes, mode):
+    """The same check on the forms of MgcgSetMatrixCompression, with the class that ran: one byte per row (3) and per-nonzero codes (2)
+    for the stencil; the ragged matrix has no form (too many distinct rows and offsets, unsorted rows, x within one tile) and takes the
+    stored-order CSR kernel under every mode."""
+    L = _lib.lib()
+    s, x, ref, clean = _poisoned(oracle, which)
+    hh = Handles()
+    A = DeviceCsr(s)
+    L.MgcgSetMatrixCompression(hh.sparse, mode)
+    got = A.spmv(hh, x, kernel=None if classes[mode] is not None else 1)
+    d, v, r, n = C.c_int(), C.c_int(), C.c_longlong(), C.c_longlong()
+    cls = L.MgcgAnalysisInfo(hh.sparse, 0, C.byref(d), C.byref(v), C.byref(r), C.byref(n))
+    print(which, "mode", mode, "class", cls)
+    assert cls == classes[mode] if classes[mode] is not None else cls in (0, -1), cls
+    assert_poisoned_product(got, ref, clean)
+    L.MgcgAnalysisClear(hh.sparse)
+    hh.close()
 
 
 def test_csrmv_alpha_beta_and_edges(h, oracle):
