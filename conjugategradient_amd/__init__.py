@@ -9,10 +9,12 @@
 ``singlereduce`` single-reduction (Chronopoulos-Gear) CG: one global sum and two launches per iteration, with or without the diagonal
 ``minres``   MINRES for symmetric indefinite and shifted systems (A - shift I) x = b: the solver for what the CG loops refuse,
              plain or preconditioned by the diagonal (the V-cycle form is a method of the ``multigrid`` / ``amg`` classes)
+``bicgstab`` BiCGStab for NONSYMMETRIC systems A x = b (convection-diffusion, upwinded stencils, any CSR matrix), plain or
+             right-preconditioned by the diagonal
 ``chebyshev`` Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, m products and two global sums per iteration
 ``shifted``   multi-shift CG: (A + s_j I) x_j = b for up to 8 shifts from one CG recurrence on A
 ``blockkrylov`` shared-subspace block CG: up to 8 right-hand sides in one block Krylov space (fewer iterations than ``block``)
 ``mixed``     mixed-precision CG: an fp32 recurrence corrected by fp64 reliable updates, fp64-accurate x and stop test
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "jacobi", "singlereduce", "minres", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "jacobi", "singlereduce", "minres", "bicgstab", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]

@@ -1,0 +1,114 @@
+"""BiCGStab (``SolveBicgstab``, ``SolveBicgstabJacobi``): nonsymmetric systems A x = b.
+
+Every other loop of this package takes a symmetric matrix: on a convection-diffusion stencil, an upwinded operator or any CSR matrix with
+A != A^T the CG loops break down or return a wrong x, and MINRES is not defined.  BiCGStab (van der Vorst) needs only products with A --
+no transpose, no new matrix form -- and fixed storage: two products and three global sums per iteration.  It is right-preconditioned, so
+the residual it carries is that of the system itself and every stop rule judges its 2-norm, as everywhere else here.
+
+``BiConjugateGradientStabGpu`` has ``MinimalResidualGpu``'s class surface.  ``Iteration``, ``Residual`` and the trace show the
+recurrence's residual, which can drift from b - A x on a badly conditioned nonsymmetric matrix; ``TrueResidual`` is || b - A x ||_2 from
+one closing product, and ``ReadResidual()`` returns that vector.  ``BiConjugateGradientStabJacobiGpu`` is the same class with M = diag(A).
+Several ranks: ``ConjugateGradientRankGpu.SolveBicgstab`` / ``.SolveBicgstabJacobi``.  The max-norm stop rule is not supported.  No
+arithmetic happens in this module.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import MgcgError, check, lib
+from .jacobi import check_system_shapes, jacobi_setup
+from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+
+_WORK = ("vectorV", "vectorS", "vectorT", "vectorRhat")
+
+
+class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
+    """ConjugateGradientSingleGpu on the BiCGStab loop: same constructor, members, ``Iteration`` / ``Residual`` and
+    ``ApplicationException`` behaviour, for any CSR matrix."""
+
+    _export = "SolveBicgstab"
+    _what = "BiCGStab"
+
+    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None):
+        if rule == _lib.RULE_HANDMADECL:
+            raise ValueError(f"{type(self).__name__}: the max-norm rule (RULE_HANDMADECL) is not supported")
+        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
+        self.TrueResidual = float("nan")
+        for name in _WORK:
+            setattr(self, name, VectorDouble(count))
+        self._ready = False
+
+    def Dispose(self):
+        for name in _WORK + ("vectorDinv",):
+            if getattr(self, name, None) is not None:
+                getattr(self, name).Dispose()
+                setattr(self, name, None)
+        super().Dispose()
+
+    def Initialize(self):
+        self._ready = False
+        check_system_shapes(self.A, self.x, self.b, self.Count)
+        super().Initialize()
+        self._ready = True
+
+    def _more_vectors(self):
+        return ()
+
+    def Solve(self, trace: bool = False, traceCapacity: int | None = None):
+        """trace: keep the residual trace in ``self.trace``; traceCapacity: its length when the default (room for every iteration) is not wanted."""
+        if not self._ready:
+            raise MgcgError(f"{type(self).__name__}.Solve: Initialize() has not run")
+        nonzeroCount = int(self.A.RowOffsets[self.Count])
+        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
+        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
+        cap = (max(self.MaxIteration, self.MinIteration) + 8 if traceCapacity is None else int(traceCapacity)) if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        L = lib()
+        st = getattr(L, self._export)(self.cublas, self.cusparse, self.matDescr,
+                                      self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                      self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                      self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr, *self._more_vectors(),
+                                      nonzeroCount, self.Count,
+                                      self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
+                                      C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
+        if trace:
+            self.trace = tr[: min(self.Iteration + 1, cap)].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            L.MgcgClearLastError()
+            raise ApplicationException(f"{self._what} did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check(self._export)
+            raise MgcgError(f"{self._export} failed with status {st}")
+
+    def ReadResidual(self) -> np.ndarray:
+        """The true residual b - A x that the last Solve()'s closing product left in its work vector."""
+        r = np.empty(self.Count)
+        self.vectorR.CopyTo(r, self.Count, 0)
+        return r
+
+
+class BiConjugateGradientStabJacobiGpu(BiConjugateGradientStabGpu):
+    """BiConjugateGradientStabGpu with M = diag(A) as right preconditioner (SolveBicgstabJacobi): same constructor and members, and the
+    same residual -- that of A x = b in the 2-norm.  ``Initialize()`` also extracts and checks the diagonal (a row without a positive,
+    finite stored diagonal raises ``MgcgError`` there)."""
+
+    _export = "SolveBicgstabJacobi"
+    _what = "Jacobi-preconditioned BiCGStab"
+
+    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None):
+        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
+        self.vectorDinv = VectorDouble(count)
+
+    def Initialize(self):
+        super().Initialize()
+        self._ready = False
+        jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
+                     int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
+        self._ready = True
+
+    def _more_vectors(self):
+        return (self.vectorDinv.Ptr,)

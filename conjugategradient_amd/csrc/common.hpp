@@ -115,6 +115,7 @@ void preload_ops(); void preload_solver(); void preload_comm(); void preload_ker
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
 void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres(); void preload_kernels_pminres();
+void preload_kernels_bicgstab();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -200,6 +201,19 @@ struct MinresScalars {
     struct State { double beta, cs, sn, dbar, eps, phibar, oldb; } st[2];
 };
 
+// What the BiCGStab loop (SolveBicgstab*, kernels_bicgstab.hip) keeps on the device.  red: {sigma, theta, tau, rr, rhon, the closing r.r} -- several
+// ranks only for the first five, all-reduced in place; {theta, tau} and {rr, rhon} are adjacent, so that each pair travels in one all-reduce of
+// two doubles.  alpha is written by pass S and omega by pass X, each by its first workgroup, for the passes behind it.  rho: body k reads
+// rho[k & 1] in every workgroup of pass S and pass P while pass P's first workgroup writes rho[(k + 1) & 1], as SreduceScalars does.  fDone:
+// CgScalars::done as pass S found it; pass X and pass P look here, since pass P raises `done` itself.  brokeS, brokeX: the breakdown of sigma
+// (pass S) or omega (pass X), read by later launches only.
+struct BicgstabScalars {
+    double red[6];
+    double alpha, omega;
+    double rho[2];
+    int fDone, brokeS, brokeX, pad;
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
@@ -232,6 +246,7 @@ struct Workspace {
     long long mixedStride = 0;
     SreduceScalars* sreduceScalars = nullptr;    // single-reduction CG (kernels_sreduce.hip), allocated at its first call and kept; its direction p takes ring[1]
     MinresScalars* minresScalars = nullptr;      // MINRES (kernels_minres.hip), allocated at its first call and kept
+    BicgstabScalars* bicgstabScalars = nullptr;  // BiCGStab (kernels_bicgstab.hip), allocated at its first call and kept
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -243,6 +258,7 @@ struct Workspace {
     bool ensure_mixed(long long n);              // mixedScalars / mixedVecs for n rows (kernels_mixed.hip)
     bool ensure_sreduce();                       // sreduceScalars (kernels_sreduce.hip)
     bool ensure_minres();                        // minresScalars (kernels_minres.hip)
+    bool ensure_bicgstab();                      // bicgstabScalars (kernels_bicgstab.hip)
 };
 
 } // namespace mgcg
@@ -675,6 +691,34 @@ int pminres_enqueue_start(Workspace* ws, const FinalizeArgs& f, int nPartials, b
 int pminres_enqueue_lanczos(const PminresRun& R, int k, int nVq, int nVv);
 // pass B of body k; returns the number of partial sums of v.v it leaves
 int pminres_enqueue_update(const PminresRun& R, const FinalizeArgs& f, int k, int nRz);
+
+// BiCGStab (SolveBicgstab*; kernels_bicgstab.hip has the loop, include/MgcgGpu.h the method).  All pointers are this rank's rows.  phat, shat:
+// the rows' slices of the two full-length buffers the products gather from; without dinv they ARE p and s (phat == p, shat == s) and nothing
+// is stored twice.  With dinv s is written over r (s == r: the two are never alive together) and p lives in a buffer of its own.  v = A phat,
+// t = A shat.  given: several ranks -- the sums arrive all-reduced in ws->bicgstabScalars->red.
+struct BicgstabRun {
+    Workspace* ws;
+    double *x, *r, *p, *s, *phat, *shat, *v, *t, *rhat; const double* dinv;
+    long long n; bool given;
+};
+double* bicgstab_tau_partials(Workspace* ws);
+double* bicgstab_rr_partials(Workspace* ws);
+double* bicgstab_rho_partials(Workspace* ws);
+// the start behind r = b - A x: rhat = r, p = r, phat = dinv * r (with dinv) and the partial sums of r.r in bicgstab_rr_partials(ws); returns
+// their number (1 under dot_order = 1)
+int bicgstab_enqueue_start(const BicgstabRun& R);
+// the scalars in front of body 0 from those sums (reduceFirst) or from the all-reduced red[3]; r.r not finite or zero stops the loop here
+// with MGCG_NONFINITE at iteration 0
+void bicgstab_enqueue_init(Workspace* ws, const FinalizeArgs& f, int nPartials, bool reduceFirst);
+// pass S of body k (nSigma: the first product's partial sums of rhat.v in ws->partials): alpha, s, shat
+void bicgstab_enqueue_s(const BicgstabRun& R, const FinalizeArgs& f, int k, int nSigma);
+// the partial sums of t.t into bicgstab_tau_partials(ws); returns their number (1 under dot_order = 1)
+int bicgstab_enqueue_tau(const BicgstabRun& R);
+// pass X of body k (nTheta: the second product's partial sums of s.t in ws->partials): omega, x, r and the partial sums of r.r and rhat.r in
+// bicgstab_rr_partials(ws) and bicgstab_rho_partials(ws); returns their number, the same for both (1 under dot_order = 1)
+int bicgstab_enqueue_x(const BicgstabRun& R, const FinalizeArgs& f, int k, int nTheta, int nTau);
+// pass P of body k: the stop decision, beta, p, phat
+void bicgstab_enqueue_p(const BicgstabRun& R, const FinalizeArgs& f, int k, int nRr);
 
 // Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).
 // The start: d = it * (dinv r), z = d, the partial sums of r.r and -- withRz, degree 1 -- of r.z; returns their number (1 under dot_order = 1).

@@ -824,13 +824,14 @@ static bool cg_enqueue_init(CgRun& R, bool fixedSteps = false)
 }
 
 // The product step of one iteration: SyncP, Ap = A p with the partial sums of p.Ap in ws->partials[0 .. *nPAp).  pIn: the vector that
-// holds p_k (the caller's p, or a slot of the deferred x update's ring).
-static bool cg_enqueue_product(CgRun& R, double* pIn, int* nPAp)
+// holds p_k (the caller's p, or a slot of the deferred x update's ring).  w: the local rows of the vector the sum is taken with, w.Ap (null: p
+// itself, p.Ap; the BiCGStab loop sums rhat.v and s.t).
+static bool cg_enqueue_product(CgRun& R, double* pIn, int* nPAp, const double* w = nullptr)
 {
     hipStream_t s = R.ws->stream;
     const int* done = &R.ws->scalars->done;
     SpmvArgs a = cg_spmv_args(R, pIn, R.Ap);
-    a.w = pIn + R.offset; a.partials = R.ws->partials; a.doneFlag = done;
+    a.w = w ? w : pIn + R.offset; a.partials = R.ws->partials; a.doneFlag = done;
     int n;
     if (R.overlap) {
         // interior rows on the side stream while SyncP (:469) travels on the main stream, then the boundary rows
@@ -1364,6 +1365,106 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
     }
     if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveMinres: did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
     if (status == MGCG_NONFINITE) set_error("SolveMinres: stopped at iteration %d: the first residual is zero or not finite, or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)", m->iteration);
+    return ok ? status : MGCG_ERROR;
+}
+
+// ---------------------------------------------------------------- BiCGStab (SolveBicgstab*, SolveBicgstabJacobi*)
+// Van der Vorst's BiCGStab for A x = b, A any CSR matrix, right-preconditioned with M = I or M = diag(A) (R.dinv) (include/MgcgGpu.h has the
+// method, kernels_bicgstab.hip the passes).  The host's side is cg_drive: a body is two products and four passes (six launches), on several ranks
+// with a fold and an all-reduce behind each of its three reduction points: sigma, {theta, tau}, {rr, rhon}.  Both products are the plain loop's
+// (cg_enqueue_product: halo exchange of the full-length buffer in line, launch_spmv_auto with the partial sums of w.Ap), so compression modes and
+// automatic column tiles apply unchanged; the overlap schedule stays "in line", and the deferred x update and the placement draw do not apply.
+// The caller's p and s are the two full-length buffers the products gather from: phat and shat, which without a diagonal are p and s themselves.
+// With a diagonal s is written over r and p lives in the caller's Ap vector.  One more product behind the loop leaves the true residual b - A x in
+// the caller's r.
+static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sVec, double* tVec, double* rhatVec, int* iteration, double* residual, double* trueResidual,
+                             double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    // everything the call allocates, before anything is enqueued
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    if (!ws->ensure_bicgstab() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    const int devTraceCap = f.traceCap;
+    cg_matrix_setup(R);
+    R.overlap = false;                                                                   // the exchanges of phat and shat stay in line
+    BicgstabScalars* bs = ws->bicgstabScalars;
+    const int* done = &ws->scalars->done;
+    double* const bufP = R.p; double* const bufS = sVec; double* const work = R.Ap;      // the two full-length buffers; the caller's Ap
+    BicgstabRun P{};
+    P.ws = ws; P.x = R.x; P.r = R.r; P.v = vVec; P.t = tVec; P.rhat = rhatVec; P.dinv = R.dinv; P.n = n; P.given = R.multi;
+    P.phat = bufP + R.offset; P.shat = bufS + R.offset;
+    P.p = R.dinv ? work : P.phat; P.s = R.dinv ? R.r : P.shat;
+
+    // out = b - A x through bufP
+    auto residual_product = [&] {
+        launch_copy(s, bufP + R.offset, R.x, n);
+        if (!halo_exchange(R.comm, R.halo, bufP, s)) return false;
+        SpmvArgs a = cg_spmv_args(R, bufP, R.r);
+        a.b = R.b;
+        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
+        return true;
+    };
+    // this rank's sums (one or an adjacent pair) into red[slot ..], all-reduced in place
+    auto share = [&](const double* pA, int nA, const double* pB, int nB, int slot, const int* gate) {
+        if (pB) launch_reduce2_to(s, pA, nA, &bs->red[slot], pB, nB, &bs->red[slot + 1], gate);
+        else launch_reduce_to(s, pA, nA, &bs->red[slot], gate);
+        return comm_allreduce_sum(R.comm, &bs->red[slot], pB ? 2 : 1, s);
+    };
+
+    // start: r = b - A x ; rhat = r ; p = r ; phat = dinv r ; rho = rr0 = r.r
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
+    bool ok = residual_product();
+    if (ok) {
+        const int nRr = bicgstab_enqueue_start(P);
+        if (R.multi) ok = share(bicgstab_rr_partials(ws), nRr, nullptr, 0, 3, nullptr);
+        if (ok) bicgstab_enqueue_init(ws, f, nRr, !R.multi);
+    }
+    ok = ok && MGCG_HIP(hipGetLastError());
+
+    int k = 0;
+    ok = ok && cg_drive(R, who, [&] {
+        int nSigma = 0, nTheta = 0;
+        R.p = bufP; R.Ap = P.v;
+        if (!cg_enqueue_product(R, bufP, &nSigma, P.rhat)) return false;                 // v = A phat ; sigma = rhat.v
+        if (R.multi && !share(ws->partials, nSigma, nullptr, 0, 0, done)) return false;
+        bicgstab_enqueue_s(P, f, k, nSigma);                                             // alpha ; s ; shat
+        R.p = bufS; R.Ap = P.t;
+        if (!cg_enqueue_product(R, bufS, &nTheta, P.s)) return false;                    // t = A shat ; theta = s.t
+        const int nTau = bicgstab_enqueue_tau(P);                                        // tau = t.t
+        if (R.multi && !share(ws->partials, nTheta, bicgstab_tau_partials(ws), nTau, 1, done)) return false;
+        const int nRr = bicgstab_enqueue_x(P, f, k, nTheta, nTau);                       // omega ; x ; r ; rr, rhon
+        if (R.multi && !share(bicgstab_rr_partials(ws), nRr, bicgstab_rho_partials(ws), nRr, 3, done)) return false;
+        bicgstab_enqueue_p(P, f, k, nRr);                                                // the stop decision ; beta ; p ; phat
+        if (k < 0x7fffffff) ++k;
+        return MGCG_HIP(hipGetLastError());
+    });
+    R.p = bufP; R.Ap = work;
+    // the closing product: the true residual into the caller's r
+    double rrTrue = 0.0;
+    if (ok) {
+        ok = residual_product();
+        if (ok) {
+            const int nOut = launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws));
+            launch_reduce_to(s, bicgstab_rr_partials(ws), nOut, &bs->red[5], nullptr);
+            ok = (!R.multi || comm_allreduce_sum(R.comm, &bs->red[5], 1, s)) && MGCG_HIP(hipGetLastError());
+        }
+        ok = ok && MGCG_HIP(hipMemcpyAsync(&rrTrue, &bs->red[5], sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    HostMirror* m = ws->mirror;
+    const int status = m->status;
+    if (iteration) *iteration = m->iteration;
+    if (residual) *residual = m->residual;
+    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
+    if (devTraceCap) {
+        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
+        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
+    }
+    if (status == MGCG_MAXIT_EXCEEDED) set_error("%s: did not converge: iteration %d exceeded maxIteration %d (residual %g)", who, m->iteration, R.maxIt, m->residual);
+    if (status == MGCG_NONFINITE) set_error("%s: stopped at iteration %d: the first residual is zero or not finite, or the recurrence broke down (rhat.v, omega or rhat.r zero, or a value that is not finite)", who, m->iteration);
     return ok ? status : MGCG_ERROR;
 }
 
@@ -2858,6 +2959,103 @@ int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
     return SolveMinresParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
                                xVector, bVector, ApVector, pVector, rVector, w1Vector, w2Vector, count, count, 0, elementsCount, 0, count - 1, shift,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+// BiCGStab (cg_solve_bicgstab above).  Refusals as in SolveMinresParallel; with `jacobi` a rank whose diagonal set-up failed calls with a null
+// dinvVector and every rank leaves with MGCG_ERROR, as in SolveJacobiParallel.
+static int bicgstab_entry(const char* who, bool jacobi, MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
+                          Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                          Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                          Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector, Vector* dinvVector,
+                          int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                          double allowableResidual, int minIteration, int maxIteration, int rule,
+                          int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    const bool handles = cublas && cusparse && vVector && sVector && tVector && rhatVector && (!jacobi || dinvVector);
+    auto checks = [&] {
+        if (rule == MGCG_RULE_HANDMADECL) set_error("%s: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the loop carries no max|r|", who);
+        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("%s: unknown stop rule %d", who, rule);
+        else if (vVector->size < countForDevice) set_error("%s: the v vector holds %lld entries, the matrix has %d local rows", who, vVector->size, countForDevice);
+        else if (tVector->size < countForDevice) set_error("%s: the t vector holds %lld entries, the matrix has %d local rows", who, tVector->size, countForDevice);
+        else if (rhatVector->size < countForDevice) set_error("%s: the rhat vector holds %lld entries, the matrix has %d local rows", who, rhatVector->size, countForDevice);
+        else if (sVector->size < count) set_error("%s: the s vector holds %lld entries, the matrix has %d columns (p and s are full length)", who, sVector->size, count);
+        else if (jacobi && dinvVector->size < countForDevice) set_error("%s: the dinv vector holds %lld entries, the matrix has %d local rows", who, dinvVector->size, countForDevice);
+        else return true;
+        return false;
+    };
+    if (MgcgCommSize(comm) <= 1) {
+        if (!handles) { set_error("%s: null handle", who); return MGCG_ERROR; }
+        if (!checks()) return MGCG_ERROR;
+    }
+    if (handles && !device_state()) return MGCG_ERROR;
+    const CgCall c = { who, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                       count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
+    int st = MGCG_ERROR;
+    cg_call(c, handles, checks, [&](CgRun& R) {
+        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the loop, which reads nothing through it there
+        if (jacobi) R.dinv = dinvVector->data ? dinvVector->data : R.ws->partials;
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        for (double* v : { R.x, R.Ap, R.r, vVector->data, tVector->data, rhatVector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
+        for (double* v : { R.p, sVector->data }) analysis_note_write(v, sizeof(double) * (size_t)count);
+        st = cg_solve_bicgstab(R, who, vVector->data, sVector->data, tVector->data, rhatVector->data, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    });
+    return st;
+}
+
+int SolveBicgstabParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                          Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                          Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                          Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector,
+                          int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                          double allowableResidual, int minIteration, int maxIteration, int rule,
+                          int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return bicgstab_entry("SolveBicgstab", false, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+                          xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, nullptr,
+                          count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ,
+                          allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+int SolveBicgstab(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                  Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                  Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                  Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector,
+                  int elementsCount, int count,
+                  double allowableResidual, int minIteration, int maxIteration, int rule,
+                  int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    return SolveBicgstabParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
+                                 xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, count, count, 0, elementsCount, 0, count - 1,
+                                 allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+int SolveBicgstabJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                                Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector, Vector* dinvVector,
+                                int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                                double allowableResidual, int minIteration, int maxIteration, int rule,
+                                int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return bicgstab_entry("SolveBicgstabJacobi", true, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+                          xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, dinvVector,
+                          count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ,
+                          allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+int SolveBicgstabJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                        Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                        Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector, Vector* dinvVector,
+                        int elementsCount, int count,
+                        double allowableResidual, int minIteration, int maxIteration, int rule,
+                        int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    return SolveBicgstabJacobiParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
+                                       xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, dinvVector, count, count, 0, elementsCount, 0, count - 1,
+                                       allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
 // Preconditioned MINRES (cg_solve_pminres above).  Refusals as in SolveMinresParallel; a rank whose diagonal set-up failed calls with a null

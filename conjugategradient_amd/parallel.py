@@ -201,7 +201,8 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
             for v in (self.vectorElements, self.vectorColumnIndeces, self.vectorRowOffsets, self.vectorX, self.vectorB,
                       self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None), getattr(self, "vectorS", None),
                       getattr(self, "vectorZ", None), getattr(self, "vectorZ2", None), getattr(self, "vectorD", None),
-                      getattr(self, "vectorW1", None), getattr(self, "vectorW2", None), getattr(self, "vectorR1", None)):
+                      getattr(self, "vectorW1", None), getattr(self, "vectorW2", None), getattr(self, "vectorR1", None),
+                      getattr(self, "vectorV", None), getattr(self, "vectorT", None), getattr(self, "vectorRhat", None)):
                 if v is not None:
                     v.Dispose()
             if self._own_comm and self.comm:
@@ -420,6 +421,46 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if st != _lib.OK:
             check("SolveMinresJacobiParallel")
             raise MgcgError(f"SolveMinresJacobiParallel failed with status {st}")
+
+    def SolveBicgstab(self, trace: bool = False, jacobi: bool = False):
+        """Solve A x = b with BiCGStab (SolveBicgstabParallel): A any CSR matrix, symmetric or not.  Three all-reduces per iteration (of
+        1, 2 and 2 doubles).  vectorP and vectorS are full length; afterwards the first ``part.count`` entries of vectorR hold this rank's
+        rows of the true residual and ``TrueResidual`` its global 2-norm.  jacobi: right-preconditioned with the diagonal
+        (SolveBicgstabJacobiParallel; SetupJacobi() first) -- a rank whose SetupJacobi() failed still enters the native call, with no dinv
+        vector: every rank gets MGCG_ERROR.  Every rank passes the same ``jacobi``."""
+        self._ensure_comm()
+        p = self.part
+        usable = getattr(self, "vectorDinv", None) is not None and getattr(self, "jacobiError", None) is None
+        if getattr(self, "vectorS", None) is None or self.vectorS.size < self.Count:
+            self.vectorS = VectorDouble(self.Count)
+        for name in ("vectorV", "vectorT", "vectorRhat"):
+            if getattr(self, name, None) is None or getattr(self, name).size < p.count:
+                setattr(self, name, VectorDouble(p.count))
+        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        export = "SolveBicgstabJacobiParallel" if jacobi else "SolveBicgstabParallel"
+        more = ((self.vectorDinv.Ptr if usable else None),) if jacobi else ()
+        st = getattr(lib(), export)(self.comm, self.cublas, self.cusparse, self.matDescr,
+                                    self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                    self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                    self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr, *more,
+                                    self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
+                                    self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
+                                    C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"{'Jacobi-preconditioned ' if jacobi else ''}BiCGStab did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check(export)
+            raise MgcgError(f"{export} failed with status {st}")
+
+    def SolveBicgstabJacobi(self, trace: bool = False):
+        """SolveBicgstab() right-preconditioned with the diagonal (SolveBicgstabJacobiParallel); SetupJacobi() first."""
+        self.SolveBicgstab(trace=trace, jacobi=True)
 
     def SolveChebyshev(self, trace: bool = False, jacobi: bool = False, degree: int = 4, bounds=None):
         """Solve() on the Chebyshev-preconditioned loop (SolveChebyshevParallel).  bounds = (lambdaMin, lambdaMax) of A -- of D^-1 A with

@@ -207,6 +207,75 @@ def random_spd(n: int, mean_upper: float = 14.0, seed: int = 12345, sort_columns
                         np.zeros(n), b, f"random_spd{n}")
 
 
+def convection_diffusion(nx: int, ny: int, nz: int = 1, c=(0.0, 0.0, 0.0), upwind: bool = False) -> LinearSystem:
+    """Nonsymmetric 5-point (nz == 1) / 7-point convection-diffusion stencil on poisson()'s grid and ordering, c = (c_x, c_y[, c_z]) the
+    cell Peclet numbers.  Central differences: diagonal 2 per dimension, off-diagonals -1 - c_d towards the lower neighbour and -1 + c_d
+    towards the upper one.  upwind=True (first-order upwinding, c_d >= 0): diagonal 2 + 2 c_d per dimension, off-diagonals -1 - 2 c_d and
+    -1.  Columns ascending; b = A.1, x0 = 0.  c = 0 gives poisson()'s matrix."""
+    n = nx * ny * nz
+    assert n < 2**31
+    dims = 3 if nz > 1 else 2
+    c = [float(v) for v in c][:dims] + [0.0] * max(0, dims - len(c))
+    cx, cy, cz = c[0], c[1], (c[2] if dims == 3 else 0.0)
+    idx = np.arange(n, dtype=np.int64)
+    x = idx % nx
+    y = (idx // nx) % ny
+    z = idx // (nx * ny)
+    if upwind:
+        diag = sum(2.0 + 2.0 * v for v in c)
+        lower = lambda v: -1.0 - 2.0 * v
+        upper = lambda v: -1.0
+    else:
+        diag = 2.0 * dims
+        lower = lambda v: -1.0 - v
+        upper = lambda v: -1.0 + v
+    masks = [z > 0, y > 0, x > 0, np.ones(n, bool), x < nx - 1, y < ny - 1, z < nz - 1]
+    offs = [-nx * ny, -nx, -1, 0, 1, nx, nx * ny]
+    vals = [lower(cz), lower(cy), lower(cx), diag, upper(cx), upper(cy), upper(cz)]
+    cnt = np.zeros(n, dtype=np.int64)
+    for m in masks:
+        cnt += m
+    ro = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(cnt, out=ro[1:])
+    nnz = int(ro[-1])
+    col = np.empty(nnz, dtype=np.int32)
+    val = np.empty(nnz, dtype=np.float64)
+    pos = ro[:-1].copy()
+    for m, o, v in zip(masks, offs, vals):
+        p = pos[m]
+        col[p] = idx[m] + o
+        val[p] = v
+        pos += m
+    b = np.bincount(np.repeat(idx, cnt), weights=val, minlength=n)
+    return LinearSystem(val, col, ro.astype(np.int32), np.zeros(n), b,
+                        f"convdiff{nx}x{ny}x{nz}{'u' if upwind else 'c'}", grid=(nx, ny, nz))
+
+
+def random_nonsymmetric(n: int, per_row: int = 9, seed: int = 12345) -> LinearSystem:
+    """A random matrix with A != A^T and an uneven diagonal: per row per_row - 1 off-diagonal draws with columns uniform over the other
+    rows and values N(0,1), duplicates summed; diagonal = sum |off-diagonals| + U(0.5, 50) (strictly row dominant, hence nonsingular).
+    Columns ascending; b = A.1, x0 = 0."""
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(seed)
+    k = max(int(per_row) - 1, 0)
+    rows = np.repeat(np.arange(n, dtype=np.int64), k)
+    cols = rng.integers(0, max(n - 1, 1), size=rows.shape[0])
+    cols = cols + (cols >= rows)                       # uniform over the columns other than the row's own
+    vals = rng.standard_normal(rows.shape[0])
+    keep = cols < n                                    # (n == 1: no other column)
+    A = sp.coo_matrix((vals[keep], (rows[keep], cols[keep])), shape=(n, n)).tocsr()
+    A.sum_duplicates()
+    d = np.asarray(abs(A).sum(axis=1)).ravel() + rng.uniform(0.5, 50.0, size=n)
+    A = (A + sp.diags(d)).tocsr()
+    A.sort_indices()
+    b = A @ np.ones(n)
+    return LinearSystem(np.ascontiguousarray(A.data, dtype=np.float64),
+                        np.ascontiguousarray(A.indices, dtype=np.int32),
+                        np.ascontiguousarray(A.indptr, dtype=np.int32),
+                        np.zeros(n), b, f"random_nonsymmetric{n}")
+
+
 def partition_offsets(count: int, device_count: int, row_offsets=None, balance: str = "rows") -> list[int]:
     """Row-range partition of Mgcg/cuBlas/Mgcg/ConjugateGradientParallelGpu.cs:271-277:
     floor(count/device_count) rows each, the last device takes the remainder.

@@ -735,6 +735,85 @@ int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
                   double allowableResidual, int minIteration, int maxIteration, int rule,
                   int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
+/* ---- BiCGStab: nonsymmetric systems A x = b, plain and Jacobi-preconditioned (one rank or several) ---- */
+/* Van der Vorst's BiCGStab.  A is ANY CSR matrix: every other solver here takes a symmetric one, and on A != A^T the CG loops break down or
+ * return a wrong x and MINRES is not defined.  The method needs only A v (no transpose product, no new matrix form) and fixed storage.  It is
+ * right-preconditioned with M = I (SolveBicgstab*) or M = diag(A) (SolveBicgstabJacobi*, dinvVector from MgcgJacobiSetup, which refuses a row
+ * without a positive finite stored diagonal): r stays the residual of the system itself, and every stop rule judges its 2-norm, as
+ * everywhere else in the library.  A body costs two products and three global sums; one rank: six launches per body (two products, four
+ * vector passes of 24 + 8 + 56 + 32 = 120 bytes per row without the diagonal, 40 + 8 + 64 + 48 = 160 with it).
+ * Method: d_i is dinv_i when a diagonal is given and 1 otherwise; with d = 1 the multiplication is not performed and no hatted copy is stored.
+ *   start   (MGCG_RULE_SIMPLE: x := 0)
+ *           r = b - A x  (row i of A x summed as the product sums it, then b_i - acc) ;  rhat = r ;  p = r ;  phat_i = d_i*p_i ;  rho = rr0 = r.r
+ *           rr0 == 0 or not finite  ->  MGCG_NONFINITE at iteration 0, x untouched (as SolveMinres)
+ *   body k  v = A phat ;  sigma = rhat.v
+ *           sigma == 0 or not finite, or alpha = rho/sigma not finite  ->  MGCG_NONFINITE for iteration k + 1, x unchanged by this body
+ *           s_i = r_i - alpha*v_i ;  shat_i = d_i*s_i
+ *           t = A shat ;  theta = t.s ;  tau = t.t
+ *           omega = (tau == 0) ? 0 : theta/tau ;  omega not finite  ->  MGCG_NONFINITE for iteration k + 1, x unchanged by this body
+ *           x_i = (x_i + alpha*phat_i) + omega*shat_i ;  r_i = s_i - omega*t_i ;  rr = r.r ;  rhon = rhat.r
+ *           rr is judged by the rule's stop test against rr0 as the residual of iteration k + 1
+ *           not stopped and (omega == 0 or rhon == 0 or rhon not finite)  ->  MGCG_NONFINITE for iteration k + 1 (x IS this body's iterate)
+ *           beta = (rhon/rho)*(alpha/omega) ;  p_i = r_i + beta*(p_i - omega*v_i) ;  phat_i = d_i*p_i ;  rho = rhon
+ *   end     one more product: rVector = b - A x ;  *trueResidual = sqrt(r.r)      (whenever the loop ended without MGCG_ERROR)
+ * Rounding contract, the same as the other loops: every product (alpha*v_i, d_i*s_i, alpha*phat_i, omega*shat_i, omega*t_i, omega*v_i,
+ * beta*(p_i - omega*v_i), d_i*p_i, and the terms rhat_i*v_i, s_i*t_i, t_i*t_i, r_i*r_i, rhat_i*r_i of the rounded vectors) goes into a double
+ * of its own before the add or subtraction that follows it, nothing is fused; the scalars are evaluated in exactly the order written (the
+ * two quotients of beta are formed, then multiplied).  Under dot_order = 1 every sum is serial left to right and ranks add in rank order:
+ * the whole loop is then a fixed sequence of IEEE operations (tests/test_bicgstab_host.py restates it in numpy).
+ * Stop: the four 2-norm rules of SolveEx on (rr, rr0); MGCG_RULE_HANDMADECL is refused (the loop carries no max|r|).  *iteration, *residual
+ * and the trace (entry 0: the first residual; entry k + 1: sqrt(rr) after body k, sqrt(rr / rr0) under MGCG_RULE_VIENNACL) show the
+ * recurrence's figure; a breakdown repeats the last judged figure in *residual and its trace entry.  The recurrence's r can drift from
+ * b - A x (classical BiCGStab drift: on the tridiagonal matrix (-1.9, 2, -0.1) the recurrence reaches the level while the true residual has
+ * grown by tens of orders of magnitude), so the closing product runs whenever the loop ended without MGCG_ERROR, breakdown included, and
+ * *trueResidual (may be NULL) is || b - A x ||_2: a caller of a nonsymmetric solver looks there.
+ *   ApVector        with a diagonal: p, the unhatted direction (count entries) ;  without: not used by the loop
+ *   pVector         phat, the first buffer the products gather from (count entries) ;  without a diagonal p itself
+ *   rVector         r ;  with a diagonal s is written over it between pass S and pass X (the two are never alive together).  On return its
+ *                   first count entries hold the true residual b - A x
+ *   vVector, tVector   v = A phat and t = A shat (count entries each)
+ *   sVector         shat, the second buffer the products gather from (count entries) ;  without a diagonal s itself
+ *   rhatVector      the shadow residual, fixed after the start (count entries)
+ * Refused with MGCG_ERROR, a message and nothing enqueued: MGCG_RULE_HANDMADECL, an unknown rule, a null handle, a vector that is too small.
+ * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer), the placement
+ * draw and the overlap schedule do not apply.  Out of scope: the V-cycle as preconditioner (SolveBicgstabMg), BiCGStab(l), GMRES, residual
+ * replacement, the block and mixed combinations, the C++ twin under host/. */
+int SolveBicgstab(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                  Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                  Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                  Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector,
+                  int elementsCount, int count,
+                  double allowableResidual, int minIteration, int maxIteration, int rule,
+                  int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+int SolveBicgstabJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                        Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                        Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                        Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector, Vector* dinvVector,
+                        int elementsCount, int count,
+                        double allowableResidual, int minIteration, int maxIteration, int rule,
+                        int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+/* The same on a row partition, shaped after SolveMinresParallel.  pVector and sVector are full length (count entries): rows gather phat and
+ * shat, and each has its halo exchanged in line before its product (the overlap schedule is not used by this loop); every other vector
+ * holds the local rows (countForDevice entries).  A body has three reduction points: sigma, then {theta, tau}, then {rr, rhon} -- three
+ * all-reduces of 1, 2 and 2 adjacent doubles -- and the first and the closing r.r take one each.  On return the first countForDevice entries
+ * of rVector hold this rank's rows of the true residual, and *trueResidual is the global figure on every rank.  A rank without rows takes
+ * part in every collective.  An unusable argument on one rank (in the Jacobi form also a NULL dinvVector: its MgcgJacobiSetup failed) makes
+ * every rank return MGCG_ERROR, as in SolveParallel. */
+int SolveBicgstabParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                          Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                          Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                          Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector,
+                          int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                          double allowableResidual, int minIteration, int maxIteration, int rule,
+                          int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+int SolveBicgstabJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                                Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector, Vector* dinvVector,
+                                int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
+                                double allowableResidual, int minIteration, int maxIteration, int rule,
+                                int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
  * MgcgJacobiSetup wrote) is given: Gershgorin's upper bound of the spectrum of A (of D^-1 A), rigorous, usually within a small factor
