@@ -1105,6 +1105,97 @@ static void cg_columns_message(const char* who, int worst, const char* nonfinite
     else if (worst == MGCG_MAXIT_EXCEEDED) set_error("%s: a column did not converge within maxIteration %d", who, maxIt);
 }
 
+// What a one-column loop hands back once its stream has drained: iteration and residual from the mirror, the first min(iteration + 1,
+// devTraceCap) entries of the device trace, and the message of a status that is not MGCG_OK.  residualName and inNorm word the residual of
+// the MAXIT message ("residual" / "true residual", "" / " in the M^-1 norm"); nonfinite says what MGCG_NONFINITE means in this loop.
+// Returns the status, MGCG_ERROR when the trace's copy fails.
+static int cg_return_one(const CgRun& R, const char* who, int devTraceCap, int* iteration, double* residual, double* residualTrace,
+                         const char* residualName, const char* inNorm, const char* nonfinite)
+{
+    const HostMirror* m = R.ws->mirror;
+    const int it = m->iteration, status = m->status;
+    const double res = m->residual;
+    bool ok = true;
+    cg_return_columns(R.ws, 1, &it, &res, &status, nullptr, devTraceCap, iteration, residual, nullptr, residualTrace, devTraceCap, &ok);
+    if (status == MGCG_MAXIT_EXCEEDED) set_error("%s: did not converge: iteration %d exceeded maxIteration %d (%s %g%s)", who, it, R.maxIt, residualName, res, inNorm);
+    if (status == MGCG_NONFINITE) set_error("%s: stopped at iteration %d: %s", who, it, nonfinite);
+    return ok ? status : MGCG_ERROR;
+}
+
+// The prologue of a one-column loop that takes the plain loop's product, behind the caller's own ensure_* calls: the finalisation's
+// arguments and the device trace (the last allocation: nothing is enqueued before it), the matrix set-up, every exchange kept in line (no
+// overlap schedule), and x = 0 under MGCG_RULE_SIMPLE (SimpleConjugateGradient.cu:53).
+static bool cg_variant_begin(CgRun& R, int preconditioned, const double* residualTrace, int traceCapacity, FinalizeArgs* f)
+{
+    *f = cg_finalize_args(R, true, preconditioned);
+    if (!cg_trace_columns(R.ws, 1, residualTrace, traceCapacity, *f)) return false;
+    cg_matrix_setup(R);
+    R.overlap = false;
+    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(R.ws->stream, R.x, 0.0, R.nLocal);
+    return true;
+}
+
+// out = b - A x through a full-length buffer: x into the rows' slice of `full`, its halo exchanged in line, the product with the residual epilogue
+static bool cg_enqueue_residual(CgRun& R, double* full, double* out)
+{
+    hipStream_t s = R.ws->stream;
+    launch_copy(s, full + R.offset, R.x, R.nLocal);
+    if (!halo_exchange(R.comm, R.halo, full, s)) return false;
+    SpmvArgs a = cg_spmv_args(R, full, out);
+    a.b = R.b;
+    launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
+    return true;
+}
+
+// Several ranks: this rank's partial sums -- one array, or with pB a pair whose destinations are adjacent -- folded into dst (and dst + 1)
+// and all-reduced there in place.  One rank never comes here: its passes fold the partial sums themselves.
+static bool cg_share_sums(CgRun& R, const double* pA, int nA, const double* pB, int nB, double* dst, const int* gate)
+{
+    hipStream_t s = R.ws->stream;
+    if (pB) launch_reduce2_to(s, pA, nA, dst, pB, nB, dst + 1, gate);
+    else launch_reduce_to(s, pA, nA, dst, gate);
+    return comm_allreduce_sum(R.comm, dst, pB ? 2 : 1, s);
+}
+
+// The closing step of MINRES, preconditioned MINRES and BiCGStab, behind the loop: t = b - A x through `full` into `out`; form() makes the
+// true residual of t and leaves the partial sums of its r.r in `partials`, returning their count; the sum into *dst -- folded on one rank
+// too: no pass follows that would -- and all-reduced on several; *rrTrue is read back behind it and holds once the stream has drained.
+template <typename Form>
+static bool cg_enqueue_true_residual(CgRun& R, double* full, double* out, Form form, const double* partials, double* dst, double* rrTrue)
+{
+    hipStream_t s = R.ws->stream;
+    if (!cg_enqueue_residual(R, full, out)) return false;
+    const int nOut = form();
+    launch_reduce_to(s, partials, nOut, dst, nullptr);
+    if (R.multi && !comm_allreduce_sum(R.comm, dst, 1, s)) return false;
+    return MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(rrTrue, dst, sizeof(double), hipMemcpyDeviceToHost, s));
+}
+
+// The refusals and rules that the exports of the variants word alike.  A stop rule that is unknown or, with maxNormWhy (why this loop cannot
+// take it), the max-norm rule: true, refused.
+static bool cg_rule_refused(const char* who, int rule, const char* maxNormWhy)
+{
+    if (rule == MGCG_RULE_HANDMADECL && maxNormWhy) set_error("%s: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: %s", who, maxNormWhy);
+    else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("%s: unknown stop rule %d", who, rule);
+    else return false;
+    return true;
+}
+// A vector of fewer than `need` entries: true, refused.  of: what `need` counts ("local rows", "columns", "rows"), with a remark if there is one.
+static bool cg_vector_short(const char* who, const char* name, const Vector* v, int need, const char* of)
+{
+    if (v->size >= need) return false;
+    set_error("%s: the %s vector holds %lld entries, the matrix has %d %s", who, name, v->size, need, of);
+    return true;
+}
+// R.dinv of a loop that runs with the diagonal when the caller gives one.  A rank without rows has an empty dinv vector (no data): any
+// address says "with the diagonal" to the loop, which reads nothing through it there -- the ranks must agree on the form.
+static double* cg_dinv_address(const CgRun& R, const Vector* dinv) { return dinv ? (dinv->data ? dinv->data : R.ws->partials) : nullptr; }
+// These vectors are written by the call, n entries each (the matrix analysis must not trust a form that lies in one of them).
+static void cg_note_written(std::initializer_list<double*> vectors, long long n)
+{
+    for (double* v : vectors) analysis_note_write(v, sizeof(double) * (size_t)n);
+}
+
 // ---------------------------------------------------------------- multi-shift CG (SolveShifted)
 // One CG recurrence on A serves the k systems (A + sigma_j I) x_j = b (kernels_shift.hip has the method).  An iteration is the plain loop's
 // product and r update followed by the one fused pass launch_update_shifted: three launches, as SolveEx's.  x_j starts from 0, so r = b
@@ -1163,7 +1254,6 @@ static int cg_solve_mixed(CgRun& R, const float* e32, int* iteration, double* re
     // everything the call allocates, before anything is enqueued
     FinalizeArgs f = cg_finalize_args(R, true, 0);
     if (!ws->ensure_mixed(n) || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
-    const int devTraceCap = f.traceCap;
     if (R.elementsCount >= 8) R.cfg.periodRows = spmv_period(R.cusparse, R.rowOffsets, R.columnIndeces, n, 0, &R.cfg.maxRow);
     MixedRun M{};
     M.ws = ws; M.e32 = e32; M.rowOffsets = R.rowOffsets; M.columnIndeces = R.columnIndeces; M.n = n; M.nnz = R.elementsCount; M.x = R.x; M.r = R.r;
@@ -1190,21 +1280,12 @@ static int cg_solve_mixed(CgRun& R, const float* e32, int* iteration, double* re
         return MGCG_HIP(hipGetLastError());
     });
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    if (!ok) return MGCG_ERROR;
-    HostMirror* m = ws->mirror;
-    const int status = m->status;
-    if (iteration) *iteration = m->iteration;
-    if (residual) *residual = m->residual;
     MixedScalars h{};
-    ok = MGCG_HIP(hipMemcpy(&h, ws->mixedScalars, sizeof(h), hipMemcpyDeviceToHost));
-    if (ok && reliableUpdates) *reliableUpdates = h.updates;
-    if (ok && devTraceCap) {
-        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-    }
-    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveMixed: did not converge: iteration %d exceeded maxIteration %d (true residual %g)", m->iteration, R.maxIt, m->residual);
-    if (status == MGCG_NONFINITE) set_error("SolveMixed: stopped at iteration %d: p.Ap is not finite and > 0, or the residual is not finite or beyond the fp32 range", m->iteration);
-    return ok ? status : MGCG_ERROR;
+    ok = ok && MGCG_HIP(hipMemcpy(&h, ws->mixedScalars, sizeof(h), hipMemcpyDeviceToHost));
+    if (!ok) return MGCG_ERROR;
+    if (reliableUpdates) *reliableUpdates = h.updates;
+    return cg_return_one(R, "SolveMixed", f.traceCap, iteration, residual, residualTrace, "true residual", "",
+                         "p.Ap is not finite and > 0, or the residual is not finite or beyond the fp32 range");
 }
 
 // ---------------------------------------------------------------- single-reduction CG (SolveSingleReduce, SolveSingleReduceParallel)
@@ -1221,33 +1302,20 @@ static int cg_solve_sreduce(CgRun& R, double* sVec, int* iteration, double* resi
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
     // everything the call allocates, before anything is enqueued
-    FinalizeArgs f = cg_finalize_args(R, true, 0);
-    if (!ws->ensure_sreduce() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    FinalizeArgs f;
+    if (!ws->ensure_sreduce()) return MGCG_ERROR;
     if (!ws->ensure_ring(2, n > 0 ? n : 1)) { set_error("SolveSingleReduce: no room on the device for the direction vector (%lld entries)", n); return MGCG_ERROR; }
-    const int devTraceCap = f.traceCap;
-    cg_matrix_setup(R);
-    R.overlap = false;                                                                   // the exchange of u stays in line
+    if (!cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
     CgScalars* sc = ws->scalars;
     double* uLoc = R.p + R.offset;
     const SreduceRun P = { ws, R.x, ws->ring[1], sVec, R.r, uLoc, R.Ap, R.dinv, n, R.multi };
 
     // start: r = b - A x ; u = dinv r ; the partial sums of rr0 = r.r and gamma = r.u where body 0 looks for them ; the scalars
-    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
-    launch_copy(s, uLoc, R.x, n);
-    bool ok = halo_exchange(R.comm, R.halo, R.p, s);
-    if (ok) {
-        SpmvArgs a = cg_spmv_args(R, R.p, R.r);
-        a.b = R.b;
-        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
-    }
+    bool ok = cg_enqueue_residual(R, R.p, R.r);
     double* rrPartials = sreduce_rr_partials(ws, 1);
     double* gPartials = R.dinv ? sreduce_gamma_partials(ws, 1) : nullptr;
     int nIn = ok ? launch_copy_dot(s, uLoc, R.r, R.dinv, n, rrPartials, gPartials, nullptr) : 0;
-    if (ok && R.multi) {                                                                 // rr0 for the relative rule, as cg_enqueue_init
-        if (R.dinv) launch_reduce2_to(s, rrPartials, nIn, &sc->rrNew, gPartials, nIn, &sc->rzNew, nullptr);
-        else launch_reduce_to(s, rrPartials, nIn, &sc->rr, nullptr);
-        ok = comm_allreduce_sum(R.comm, R.dinv ? &sc->rrNew : &sc->rr, R.dinv ? 2 : 1, s);
-    }
+    if (ok && R.multi) ok = cg_share_sums(R, rrPartials, nIn, gPartials, nIn, R.dinv ? &sc->rrNew : &sc->rr, nullptr);   // rr0 for the relative rule, as cg_enqueue_init; {rrNew, rzNew} are adjacent
     if (ok) launch_init_scalars(s, rrPartials, gPartials, nIn, !R.multi, sc, ws->mirror);
     ok = ok && MGCG_HIP(hipGetLastError());
 
@@ -1266,17 +1334,8 @@ static int cg_solve_sreduce(CgRun& R, double* sVec, int* iteration, double* resi
     if (ok && !R.dinv) launch_copy(s, R.r, uLoc, n);                                     // the residual into the caller's r
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
     if (!ok) return MGCG_ERROR;
-    HostMirror* m = ws->mirror;
-    const int status = m->status;
-    if (iteration) *iteration = m->iteration;
-    if (residual) *residual = m->residual;
-    if (devTraceCap) {
-        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-    }
-    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveSingleReduce: did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
-    if (status == MGCG_NONFINITE) set_error("SolveSingleReduce: stopped at iteration %d: w.u or its corrected form is not finite and > 0, or alpha or the residual is not finite", m->iteration);
-    return ok ? status : MGCG_ERROR;
+    return cg_return_one(R, "SolveSingleReduce", f.traceCap, iteration, residual, residualTrace, "residual", "",
+                         "w.u or its corrected form is not finite and > 0, or alpha or the residual is not finite");
 }
 
 // ---------------------------------------------------------------- MINRES (SolveMinres, SolveMinresParallel)
@@ -1294,33 +1353,21 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
     // everything the call allocates, before anything is enqueued
-    FinalizeArgs f = cg_finalize_args(R, true, 0);
-    if (!ws->ensure_minres() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
-    const int devTraceCap = f.traceCap;
-    cg_matrix_setup(R);
-    R.overlap = false;                                                                   // the exchange of v stays in line
+    FinalizeArgs f;
+    if (!ws->ensure_minres() || !cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
     MinresScalars* ms = ws->minresScalars;
     const int* done = &ws->scalars->done;
     double* const bufP = R.p; double* const bufR = R.r;                                  // the caller's two full-length buffers
     double* yyPartials = minres_yy_partials(ws);
 
-    // t = b - A x through bufP, then r = t + shift x into out's first n entries with its r.r in red[slot] (several ranks: all-reduced)
-    auto residual_pass = [&](double* out, int slot, int* nOut) {
-        launch_copy(s, bufP + R.offset, R.x, n);
-        if (!halo_exchange(R.comm, R.halo, bufP, s)) return false;
-        SpmvArgs a = cg_spmv_args(R, bufP, R.Ap);
-        a.b = R.b;
-        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
-        *nOut = minres_enqueue_residual(ws, R.Ap, R.x, out, n, shift);
-        if (R.multi || slot == 2) launch_reduce_to(s, yyPartials, *nOut, &ms->red[slot], nullptr);
-        return !R.multi || comm_allreduce_sum(R.comm, &ms->red[slot], 1, s);
-    };
-
-    // start: v = r0 / || r0 || in the rows' slice of bufR; bufP, which held x for the product, is body 0's vprev (not read there)
-    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
-    int nIn = 0;
-    bool ok = residual_pass(bufR + R.offset, 1, &nIn);
-    if (ok) minres_enqueue_start(ws, f, nIn, !R.multi, bufR + R.offset, n);
+    // start: t = b - A x through bufP ; r0 = t + shift x and v = r0 / || r0 || in the rows' slice of bufR ; r0.r0 in red[1] (several ranks:
+    // all-reduced); bufP, which held x for the product, is body 0's vprev (not read there)
+    bool ok = cg_enqueue_residual(R, bufP, R.Ap);
+    if (ok) {
+        const int nIn = minres_enqueue_residual(ws, R.Ap, R.x, bufR + R.offset, n, shift);
+        if (R.multi) ok = cg_share_sums(R, yyPartials, nIn, nullptr, 0, &ms->red[1], nullptr);
+        if (ok) minres_enqueue_start(ws, f, nIn, !R.multi, bufR + R.offset, n);
+    }
     ok = ok && MGCG_HIP(hipGetLastError());
 
     double *v = bufR, *vprev = bufP, *w1 = w1Vec, *w2 = w2Vec;
@@ -1330,42 +1377,23 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
         R.p = v;                                                                         // the buffer whose halo the product exchanges
         if (!cg_enqueue_product(R, v, &nDelta)) return false;                            // q = A v ; v.q
         const MinresRun P = { ws, R.x, v + R.offset, vprev + R.offset, w1, w2, R.Ap, n, shift, R.multi };
-        if (R.multi) {
-            launch_reduce_to(s, ws->partials, nDelta, &ms->red[0], done);
-            if (!comm_allreduce_sum(R.comm, &ms->red[0], 1, s)) return false;
-        }
+        if (R.multi && !cg_share_sums(R, ws->partials, nDelta, nullptr, 0, &ms->red[0], done)) return false;
         const int nYY = minres_enqueue_lanczos(P, k, nDelta);                            // y over vprev ; y.y
-        if (R.multi) {
-            launch_reduce_to(s, yyPartials, nYY, &ms->red[1], done);
-            if (!comm_allreduce_sum(R.comm, &ms->red[1], 1, s)) return false;
-        }
+        if (R.multi && !cg_share_sums(R, yyPartials, nYY, nullptr, 0, &ms->red[1], done)) return false;
         minres_enqueue_update(P, f, k, nYY);                                             // w over w1 ; x ; vnext over y
         std::swap(v, vprev); std::swap(w1, w2);                                          // (vprev, v) := (v, vnext) ; (w1, w2) := (w2, w)
         if (k < 0x7fffffff) ++k;
         return MGCG_HIP(hipGetLastError());
     });
     R.p = bufP;
-    // the closing product: the true residual into the caller's r, whatever the parity of the rotation
+    // the closing product: the true residual t + shift x into the caller's r, whatever the parity of the rotation
     double rrTrue = 0.0;
-    if (ok) {
-        int nOut = 0;
-        ok = residual_pass(bufR, 2, &nOut) && MGCG_HIP(hipGetLastError());
-        ok = ok && MGCG_HIP(hipMemcpyAsync(&rrTrue, &ms->red[2], sizeof(double), hipMemcpyDeviceToHost, s));
-    }
+    ok = ok && cg_enqueue_true_residual(R, bufP, R.Ap, [&] { return minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift); }, yyPartials, &ms->red[2], &rrTrue);
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
     if (!ok) return MGCG_ERROR;
-    HostMirror* m = ws->mirror;
-    const int status = m->status;
-    if (iteration) *iteration = m->iteration;
-    if (residual) *residual = m->residual;
     if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    if (devTraceCap) {
-        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-    }
-    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveMinres: did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
-    if (status == MGCG_NONFINITE) set_error("SolveMinres: stopped at iteration %d: the first residual is zero or not finite, or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)", m->iteration);
-    return ok ? status : MGCG_ERROR;
+    return cg_return_one(R, "SolveMinres", f.traceCap, iteration, residual, residualTrace, "residual", "",
+                         "the first residual is zero or not finite, or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)");
 }
 
 // ---------------------------------------------------------------- BiCGStab (SolveBicgstab*, SolveBicgstabJacobi*)
@@ -1384,11 +1412,8 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
     // everything the call allocates, before anything is enqueued
-    FinalizeArgs f = cg_finalize_args(R, true, 0);
-    if (!ws->ensure_bicgstab() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
-    const int devTraceCap = f.traceCap;
-    cg_matrix_setup(R);
-    R.overlap = false;                                                                   // the exchanges of phat and shat stay in line
+    FinalizeArgs f;
+    if (!ws->ensure_bicgstab() || !cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
     BicgstabScalars* bs = ws->bicgstabScalars;
     const int* done = &ws->scalars->done;
     double* const bufP = R.p; double* const bufS = sVec; double* const work = R.Ap;      // the two full-length buffers; the caller's Ap
@@ -1397,28 +1422,11 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
     P.phat = bufP + R.offset; P.shat = bufS + R.offset;
     P.p = R.dinv ? work : P.phat; P.s = R.dinv ? R.r : P.shat;
 
-    // out = b - A x through bufP
-    auto residual_product = [&] {
-        launch_copy(s, bufP + R.offset, R.x, n);
-        if (!halo_exchange(R.comm, R.halo, bufP, s)) return false;
-        SpmvArgs a = cg_spmv_args(R, bufP, R.r);
-        a.b = R.b;
-        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
-        return true;
-    };
-    // this rank's sums (one or an adjacent pair) into red[slot ..], all-reduced in place
-    auto share = [&](const double* pA, int nA, const double* pB, int nB, int slot, const int* gate) {
-        if (pB) launch_reduce2_to(s, pA, nA, &bs->red[slot], pB, nB, &bs->red[slot + 1], gate);
-        else launch_reduce_to(s, pA, nA, &bs->red[slot], gate);
-        return comm_allreduce_sum(R.comm, &bs->red[slot], pB ? 2 : 1, s);
-    };
-
-    // start: r = b - A x ; rhat = r ; p = r ; phat = dinv r ; rho = rr0 = r.r
-    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
-    bool ok = residual_product();
+    // start: r = b - A x through bufP ; rhat = r ; p = r ; phat = dinv r ; rho = rr0 = r.r
+    bool ok = cg_enqueue_residual(R, bufP, R.r);
     if (ok) {
         const int nRr = bicgstab_enqueue_start(P);
-        if (R.multi) ok = share(bicgstab_rr_partials(ws), nRr, nullptr, 0, 3, nullptr);
+        if (R.multi) ok = cg_share_sums(R, bicgstab_rr_partials(ws), nRr, nullptr, 0, &bs->red[3], nullptr);
         if (ok) bicgstab_enqueue_init(ws, f, nRr, !R.multi);
     }
     ok = ok && MGCG_HIP(hipGetLastError());
@@ -1428,14 +1436,14 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
         int nSigma = 0, nTheta = 0;
         R.p = bufP; R.Ap = P.v;
         if (!cg_enqueue_product(R, bufP, &nSigma, P.rhat)) return false;                 // v = A phat ; sigma = rhat.v
-        if (R.multi && !share(ws->partials, nSigma, nullptr, 0, 0, done)) return false;
+        if (R.multi && !cg_share_sums(R, ws->partials, nSigma, nullptr, 0, &bs->red[0], done)) return false;
         bicgstab_enqueue_s(P, f, k, nSigma);                                             // alpha ; s ; shat
         R.p = bufS; R.Ap = P.t;
         if (!cg_enqueue_product(R, bufS, &nTheta, P.s)) return false;                    // t = A shat ; theta = s.t
         const int nTau = bicgstab_enqueue_tau(P);                                        // tau = t.t
-        if (R.multi && !share(ws->partials, nTheta, bicgstab_tau_partials(ws), nTau, 1, done)) return false;
+        if (R.multi && !cg_share_sums(R, ws->partials, nTheta, bicgstab_tau_partials(ws), nTau, &bs->red[1], done)) return false;
         const int nRr = bicgstab_enqueue_x(P, f, k, nTheta, nTau);                       // omega ; x ; r ; rr, rhon
-        if (R.multi && !share(bicgstab_rr_partials(ws), nRr, bicgstab_rho_partials(ws), nRr, 3, done)) return false;
+        if (R.multi && !cg_share_sums(R, bicgstab_rr_partials(ws), nRr, bicgstab_rho_partials(ws), nRr, &bs->red[3], done)) return false;
         bicgstab_enqueue_p(P, f, k, nRr);                                                // the stop decision ; beta ; p ; phat
         if (k < 0x7fffffff) ++k;
         return MGCG_HIP(hipGetLastError());
@@ -1443,29 +1451,12 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
     R.p = bufP; R.Ap = work;
     // the closing product: the true residual into the caller's r
     double rrTrue = 0.0;
-    if (ok) {
-        ok = residual_product();
-        if (ok) {
-            const int nOut = launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws));
-            launch_reduce_to(s, bicgstab_rr_partials(ws), nOut, &bs->red[5], nullptr);
-            ok = (!R.multi || comm_allreduce_sum(R.comm, &bs->red[5], 1, s)) && MGCG_HIP(hipGetLastError());
-        }
-        ok = ok && MGCG_HIP(hipMemcpyAsync(&rrTrue, &bs->red[5], sizeof(double), hipMemcpyDeviceToHost, s));
-    }
+    ok = ok && cg_enqueue_true_residual(R, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws)); }, bicgstab_rr_partials(ws), &bs->red[5], &rrTrue);
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
     if (!ok) return MGCG_ERROR;
-    HostMirror* m = ws->mirror;
-    const int status = m->status;
-    if (iteration) *iteration = m->iteration;
-    if (residual) *residual = m->residual;
     if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    if (devTraceCap) {
-        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-    }
-    if (status == MGCG_MAXIT_EXCEEDED) set_error("%s: did not converge: iteration %d exceeded maxIteration %d (residual %g)", who, m->iteration, R.maxIt, m->residual);
-    if (status == MGCG_NONFINITE) set_error("%s: stopped at iteration %d: the first residual is zero or not finite, or the recurrence broke down (rhat.v, omega or rhat.r zero, or a value that is not finite)", who, m->iteration);
-    return ok ? status : MGCG_ERROR;
+    return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", "",
+                         "the first residual is zero or not finite, or the recurrence broke down (rhat.v, omega or rhat.r zero, or a value that is not finite)");
 }
 
 // ---------------------------------------------------------------- preconditioned MINRES (SolveMinresJacobi, SolveMinresJacobiParallel, SolveMinresMg)
@@ -1483,26 +1474,14 @@ static int cg_solve_pminres(CgRun& R, const char* who, double* r1Vec, double* w1
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
     // everything the call allocates, before anything is enqueued
-    FinalizeArgs f = cg_finalize_args(R, true, 0);
-    if (!ws->ensure_minres() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
-    const int devTraceCap = f.traceCap;
-    cg_matrix_setup(R);
-    R.overlap = false;                                                                   // the exchange of v stays in line
+    FinalizeArgs f;
+    if (!ws->ensure_minres() || !cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
     MinresScalars* ms = ws->minresScalars;
     const int* done = &ws->scalars->done;
     double* const bufR = R.r;                                                            // the caller's r
     double* vLoc = R.p + R.offset;
     double* rzPartials = pminres_rz_partials(ws);
 
-    // t = b - A x through the buffer of v (full length: its halo is exchanged), into R.Ap
-    auto residual_product = [&] {
-        launch_copy(s, vLoc, R.x, n);
-        if (!halo_exchange(R.comm, R.halo, R.p, s)) return false;
-        SpmvArgs a = cg_spmv_args(R, R.p, R.Ap);
-        a.b = R.b;
-        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
-        return true;
-    };
     // z = M^-1 r into R.z and the partial sums of r.z (the V-cycle form)
     auto cycle = [&](const double* r, const int* gate, int* nRz) {
         if (!mg_apply(R.mg, r, R.z, gate)) return false;
@@ -1510,16 +1489,12 @@ static int cg_solve_pminres(CgRun& R, const char* who, double* r1Vec, double* w1
         return true;
     };
 
-    // start: r2 = b - (A - shift I) x in the caller's r ; bz = r2 . M^-1 r2 ; v = M^-1 r2 / sqrt(bz) ; v.v
-    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
+    // start: t = b - A x through the buffer of v, into R.Ap ; r2 = t + shift x in the caller's r ; bz = r2 . M^-1 r2 ; v = M^-1 r2 / sqrt(bz) ; v.v
     int nRz = 0, nVv = 0;
-    bool ok = residual_product();
+    bool ok = cg_enqueue_residual(R, R.p, R.Ap);
     if (ok) nRz = pminres_enqueue_residual(ws, R.Ap, R.x, bufR, R.dinv, n, shift);
     if (ok && R.mg) ok = cycle(bufR, nullptr, &nRz);
-    if (ok && R.multi) {
-        launch_reduce_to(s, rzPartials, nRz, &ms->red[3], nullptr);
-        ok = comm_allreduce_sum(R.comm, &ms->red[3], 1, s);
-    }
+    if (ok && R.multi) ok = cg_share_sums(R, rzPartials, nRz, nullptr, 0, &ms->red[3], nullptr);
     if (ok) nVv = pminres_enqueue_start(ws, f, nRz, !R.multi, vLoc, bufR, R.dinv, R.z, n);
     ok = ok && MGCG_HIP(hipGetLastError());
 
@@ -1529,16 +1504,10 @@ static int cg_solve_pminres(CgRun& R, const char* who, double* r1Vec, double* w1
         int nVq = 0;
         if (!cg_enqueue_product(R, R.p, &nVq)) return false;                             // q = A v ; v.q
         const PminresRun P = { ws, R.x, vLoc, r1, w1, r2, w2, R.Ap, R.dinv, R.z, n, shift, R.multi };
-        if (R.multi) {
-            launch_reduce2_to(s, ws->partials, nVq, &ms->red[0], pminres_vv_partials(ws), nVv, &ms->red[1], done);
-            if (!comm_allreduce_sum(R.comm, &ms->red[0], 2, s)) return false;            // {v.q, v.v}: one all-reduce of two doubles
-        }
+        if (R.multi && !cg_share_sums(R, ws->partials, nVq, pminres_vv_partials(ws), nVv, &ms->red[0], done)) return false;   // {v.q, v.v}: one all-reduce of two doubles
         int nZ = pminres_enqueue_lanczos(P, k, nVq, nVv);                                // rn over r1 ; Jacobi: rn.z
         if (R.mg && !cycle(r1, done, &nZ)) return false;                                 // z = M^-1 rn ; rn.z
-        if (R.multi) {
-            launch_reduce_to(s, rzPartials, nZ, &ms->red[3], done);
-            if (!comm_allreduce_sum(R.comm, &ms->red[3], 1, s)) return false;
-        }
+        if (R.multi && !cg_share_sums(R, rzPartials, nZ, nullptr, 0, &ms->red[3], done)) return false;
         nVv = pminres_enqueue_update(P, f, k, nZ);                                       // w over w1 ; x ; the next v in place ; v.v
         std::swap(r1, r2); std::swap(w1, w2);                                            // (r1, r2) := (r2, rn) ; (w1, w2) := (w2, w)
         if (k < 0x7fffffff) ++k;
@@ -1546,33 +1515,16 @@ static int cg_solve_pminres(CgRun& R, const char* who, double* r1Vec, double* w1
     });
     // the closing product: the true residual into the caller's r
     double rrTrue = 0.0, bz = 0.0;
-    if (ok) {
-        ok = residual_product();
-        if (ok) {
-            const int nOut = minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift);
-            launch_reduce_to(s, minres_yy_partials(ws), nOut, &ms->red[2], nullptr);
-            ok = (!R.multi || comm_allreduce_sum(R.comm, &ms->red[2], 1, s)) && MGCG_HIP(hipGetLastError());
-        }
-        ok = ok && MGCG_HIP(hipMemcpyAsync(&rrTrue, &ms->red[2], sizeof(double), hipMemcpyDeviceToHost, s));
-        ok = ok && MGCG_HIP(hipMemcpyAsync(&bz, &ms->red[4], sizeof(double), hipMemcpyDeviceToHost, s));
-    }
+    ok = ok && cg_enqueue_true_residual(R, R.p, R.Ap, [&] { return minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift); }, minres_yy_partials(ws), &ms->red[2], &rrTrue);
+    ok = ok && MGCG_HIP(hipMemcpyAsync(&bz, &ms->red[4], sizeof(double), hipMemcpyDeviceToHost, s));
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
     if (!ok) return MGCG_ERROR;
-    HostMirror* m = ws->mirror;
-    const int status = m->status;
-    if (iteration) *iteration = m->iteration;
-    if (residual) *residual = m->residual;
     if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    if (devTraceCap) {
-        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-    }
-    if (status == MGCG_MAXIT_EXCEEDED) set_error("%s: did not converge: iteration %d exceeded maxIteration %d (residual %g in the M^-1 norm)", who, m->iteration, R.maxIt, m->residual);
-    if (status == MGCG_NONFINITE) {
-        if (m->iteration == 0 && bz < 0.0) set_error("%s: stopped at iteration 0: the preconditioner is not positive definite (r . M^-1 r = %g for the first residual)", who, bz);
-        else set_error("%s: stopped at iteration %d: the first residual is zero or not finite, r . M^-1 r is negative or not finite (a preconditioner that is not positive definite), or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)", who, m->iteration);
-    }
-    return ok ? status : MGCG_ERROR;
+    const int status = cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", " in the M^-1 norm",
+                                     "the first residual is zero or not finite, r . M^-1 r is negative or not finite (a preconditioner that is not positive definite), or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)");
+    if (ws->mirror->status == MGCG_NONFINITE && ws->mirror->iteration == 0 && bz < 0.0)
+        set_error("%s: stopped at iteration 0: the preconditioner is not positive definite (r . M^-1 r = %g for the first residual)", who, bz);
+    return status;
 }
 
 // ---------------------------------------------------------------- Chebyshev-preconditioned CG (SolveChebyshev, SolveChebyshevParallel)
@@ -1628,11 +1580,8 @@ static int cg_solve_chebyshev(CgRun& R, const ChebPlan& c, double* zA, double* z
     Workspace* ws = R.ws;
     hipStream_t s = ws->stream;
     const long long n = R.nLocal;
-    FinalizeArgs f = cg_finalize_args(R, true, 2);
-    if (!cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
-    const int devTraceCap = f.traceCap;
-    cg_matrix_setup(R);
-    R.overlap = false;                                                                   // every exchange stays in line
+    FinalizeArgs f;
+    if (!cg_variant_begin(R, 2, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
     CgScalars* sc = ws->scalars;
     const int* done = &sc->done;
     double* pLoc = R.p + R.offset;
@@ -1644,21 +1593,13 @@ static int cg_solve_chebyshev(CgRun& R, const ChebPlan& c, double* zA, double* z
     const double* rzPartials = one ? rzFirst : ws->partials;
 
     // start: r = b - A x ; z = M r ; r.r and r.z ; the scalars (an r.z that is not > 0 stops the loop here) ; p = z
-    if (R.rule == MGCG_RULE_SIMPLE) launch_fill(s, R.x, 0.0, n);                         // SimpleConjugateGradient.cu:53
-    launch_copy(s, pLoc, R.x, n);
-    bool ok = halo_exchange(R.comm, R.halo, R.p, s);
+    bool ok = cg_enqueue_residual(R, R.p, R.r);
     if (ok) {
-        SpmvArgs a = cg_spmv_args(R, R.p, R.r);
-        a.b = R.b;
-        launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
         const int nrr = launch_cheb_start(s, R.r, R.dinv, dVec, zA + R.offset, n, c.it, rrPartials, rzFirst, one);
         int nz = nrr;
         double* zFin = zA;
         ok = cheb_enqueue_steps(R, c, zA, zB, dVec, nullptr, &zFin, &nz);
-        if (ok && R.multi) {
-            launch_reduce2_to(s, rrPartials, nrr, &sc->rrNew, rzPartials, nz, &sc->rzNew, nullptr);
-            ok = comm_allreduce_sum(R.comm, &sc->rrNew, 2, s);
-        }
+        if (ok && R.multi) ok = cg_share_sums(R, rrPartials, nrr, rzPartials, nz, &sc->rrNew, nullptr);
         if (ok) {
             launch_cheb_init_scalars(s, rrPartials, nrr, rzPartials, nz, !R.multi, f);
             launch_copy(s, pLoc, zFin + R.offset, n);
@@ -1669,36 +1610,21 @@ static int cg_solve_chebyshev(CgRun& R, const ChebPlan& c, double* zA, double* z
     ok = ok && cg_drive(R, "SolveChebyshev", [&] {
         int nPAp = 0;
         if (!cg_enqueue_product(R, R.p, &nPAp)) return false;                            // Ap = A p ; p.Ap
-        if (R.multi) {
-            launch_reduce_to(s, ws->partials, nPAp, &sc->pAp, done);
-            if (!comm_allreduce_sum(R.comm, &sc->pAp, 1, s)) return false;
-        }
+        if (R.multi && !cg_share_sums(R, ws->partials, nPAp, nullptr, 0, &sc->pAp, done)) return false;
         const int nrr = launch_cheb_first(s, f, R.r, R.Ap, R.dinv, dVec, zA + R.offset, n, c.it, rrPartials, rzFirst, one,
                                           R.multi ? nullptr : ws->partials, R.multi ? 0 : nPAp);
         int nz = nrr;
         double* zFin = zA;
         if (!cheb_enqueue_steps(R, c, zA, zB, dVec, done, &zFin, &nz)) return false;
-        if (R.multi) {                                                                   // {rrNew, rzNew} are adjacent in CgScalars: one all-reduce
-            launch_reduce2_to(s, rrPartials, nrr, &sc->rrNew, rzPartials, nz, &sc->rzNew, done);
-            if (!comm_allreduce_sum(R.comm, &sc->rrNew, 2, s)) return false;
-        }
+        if (R.multi && !cg_share_sums(R, rrPartials, nrr, rzPartials, nz, &sc->rrNew, done)) return false;   // {rrNew, rzNew} are adjacent in CgScalars: one all-reduce
         launch_cheb_finalize(s, rrPartials, nrr, rzPartials, nz, !R.multi, f);
         launch_update_xp(s, sc, R.x, pLoc, zFin + R.offset, n);                          // x += alpha p ; p = z + beta p
         return MGCG_HIP(hipGetLastError());
     });
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
     if (!ok) return MGCG_ERROR;
-    HostMirror* m = ws->mirror;
-    const int status = m->status;
-    if (iteration) *iteration = m->iteration;
-    if (residual) *residual = m->residual;
-    if (devTraceCap) {
-        int nTrace = m->iteration + 1; if (nTrace > devTraceCap) nTrace = devTraceCap;
-        ok = MGCG_HIP(hipMemcpy(residualTrace, ws->trace, sizeof(double) * (size_t)nTrace, hipMemcpyDeviceToHost));
-    }
-    if (status == MGCG_MAXIT_EXCEEDED) set_error("SolveChebyshev: did not converge: iteration %d exceeded maxIteration %d (residual %g)", m->iteration, R.maxIt, m->residual);
-    if (status == MGCG_NONFINITE) set_error("SolveChebyshev: stopped at iteration %d: p.Ap or r.z is not finite and > 0 (an upper bound below the spectrum makes the polynomial indefinite), or the residual is not finite", m->iteration);
-    return ok ? status : MGCG_ERROR;
+    return cg_return_one(R, "SolveChebyshev", f.traceCap, iteration, residual, residualTrace, "residual", "",
+                         "p.Ap or r.z is not finite and > 0 (an upper bound below the spectrum makes the polynomial indefinite), or the residual is not finite");
 }
 
 // ---------------------------------------------------------------- shared-subspace block CG (SolveBlockKrylov)
@@ -1820,12 +1746,35 @@ static bool cg_variant_args(const char* who, bool handles, int k, int kMax, cons
 {
     if (!handles) set_error("%s: null handle", who);
     else if (k < 1 || k > kMax) set_error("%s: k = %d %s, must be 1 .. %d", who, k, noun, kMax);
-    else if (rule == MGCG_RULE_HANDMADECL && maxNormWhy) set_error("%s: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: %s", who, maxNormWhy);
-    else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("%s: unknown stop rule %d", who, rule);
+    else if (cg_rule_refused(who, rule, maxNormWhy)) return false;
     else if (count < 1) set_error("%s: bad sizes", who);
     else if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) set_error("%s: trace capacity too large", who);
     else return true;
     return false;
+}
+
+// The entry path of the one-column variants' exports (single-reduction CG, MINRES, BiCGStab, preconditioned MINRES, Chebyshev CG), one rank
+// and several.  handles: the caller's verdict on the handles that only it takes; checks(): its refusals of its own arguments, which look at
+// nothing but those handles; body(R): the solve, whose status is returned.  What is refused where:
+//   one rank (no communicator, or one of size 1): there is nobody to agree with, so what needs no device is refused before one is asked for --
+//     a null handle first, then checks() -- and then the device;
+//   several ranks: nothing is refused in front of cg_call.  A rank with unusable arguments must not simply return: its verdict, checks()
+//     included, travels in the halo plan's one all-reduce and every rank leaves with MGCG_ERROR.  The device is asked for only with the
+//     handles in hand, which the plan of a refusing rank needs too.
+// A rank whose diagonal set-up failed calls with a null dinvVector where the export requires one: that is a null handle, refused by every rank.
+// NOT part of the agreement are the values every rank must pass alike -- a shift, a degree and its bounds, whether an optional dinvVector
+// is given: the exports say which.  Nothing is enqueued for a call that fails here or in cg_call's checks.
+template <typename Checks, typename Body>
+static int cg_variant_call(const CgCall& c, bool handles, Checks checks, Body body)
+{
+    if (MgcgCommSize(c.comm) <= 1) {
+        if (!handles) { set_error("%s: null handle", c.who); return MGCG_ERROR; }
+        if (!checks()) return MGCG_ERROR;
+    }
+    if (handles && !device_state()) return MGCG_ERROR;
+    int st = MGCG_ERROR;
+    cg_call(c, handles, checks, [&](CgRun& R) { st = body(R); });
+    return st;
 }
 
 // SolveEx and SolveParallel
@@ -1928,8 +1877,7 @@ int SolveMixed(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
     int st = MGCG_ERROR;
     cg_call(c, true, no_more_checks, [&](CgRun& R) {
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        analysis_note_write(R.x, sizeof(double) * (size_t)count);
-        analysis_note_write(R.r, sizeof(double) * (size_t)count);
+        cg_note_written({ R.x, R.r }, count);
         st = cg_solve_mixed(R, (const float*)elements32Vector->data, iteration, residual, reliableUpdates, residualTrace, traceCapacity);
     });
     return st;
@@ -2780,7 +2728,7 @@ int MgcgJacobiSetup(MgcgSparse* cusparse, Vector* elementsVector, VectorInt* row
     if (elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount || rowOffsetsVector->size < (long long)countForDevice + 1) {
         set_error("MgcgJacobiSetup: a device vector is smaller than the matrix"); return -1;
     }
-    if (dinvVector->size < countForDevice) { set_error("MgcgJacobiSetup: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice); return -1; }
+    if (cg_vector_short("MgcgJacobiSetup", "dinv", dinvVector, countForDevice, "local rows")) return -1;
     if (!device_state()) return -1;
     if (countForDevice == 0) return 0;
     hipStream_t s = cusparse->ws.stream;
@@ -2858,9 +2806,8 @@ int SolveJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
 }
 
-// Single-reduction CG (cg_solve_sreduce above).  What needs no device is refused before one is asked for when there is nobody to agree with;
-// among several ranks a rank with unusable arguments travels in the halo plan's one all-reduce (cg_call) and every rank leaves with
-// MGCG_ERROR.  Whether dinvVector is given is NOT part of that agreement: every rank passes one, or none does.
+// Single-reduction CG (cg_solve_sreduce above; refusals: cg_variant_call).  Whether dinvVector is given is NOT part of the ranks' agreement:
+// every rank passes one, or none does -- the all-reduce carries three sums or two.
 int SolveSingleReduceParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                               Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                               Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* sVector, Vector* dinvVector,
@@ -2869,33 +2816,20 @@ int SolveSingleReduceParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusp
                               int* iteration, double* residual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    const bool handles = cublas && cusparse && sVector;
-    auto checks = [&] {
-        if (rule == MGCG_RULE_HANDMADECL) set_error("SolveSingleReduce: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the pass carries no max|r|");
-        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("SolveSingleReduce: unknown stop rule %d", rule);
-        else if (sVector->size < countForDevice) set_error("SolveSingleReduce: the s vector holds %lld entries, the matrix has %d local rows", sVector->size, countForDevice);
-        else if (dinvVector && dinvVector->size < countForDevice) set_error("SolveSingleReduce: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice);
-        else return true;
-        return false;
-    };
-    if (MgcgCommSize(comm) <= 1) {
-        if (!handles) { set_error("SolveSingleReduce: null handle"); return MGCG_ERROR; }
-        if (!checks()) return MGCG_ERROR;
-    }
-    if (handles && !device_state()) return MGCG_ERROR;
-    const CgCall c = { "SolveSingleReduce", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+    const char* who = "SolveSingleReduce";
+    const CgCall c = { who, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
                        count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
-    int st = MGCG_ERROR;
-    cg_call(c, handles, checks, [&](CgRun& R) {
-        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the loop, which reads nothing through
-        // it there -- the ranks must agree on the form, the all-reduce carries three sums or two
-        R.dinv = dinvVector ? (dinvVector->data ? dinvVector->data : R.ws->partials) : nullptr;
+    auto checks = [&] {
+        return !cg_rule_refused(who, rule, "the pass carries no max|r|") && !cg_vector_short(who, "s", sVector, countForDevice, "local rows") &&
+               !(dinvVector && cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows"));
+    };
+    return cg_variant_call(c, cublas && cusparse && sVector, checks, [&](CgRun& R) {
+        R.dinv = cg_dinv_address(R, dinvVector);
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        for (double* v : { R.x, R.r, R.Ap, sVector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
-        analysis_note_write(R.p, sizeof(double) * (size_t)count);
-        st = cg_solve_sreduce(R, sVector->data, iteration, residual, residualTrace, traceCapacity);
+        cg_note_written({ R.x, R.r, R.Ap, sVector->data }, countForDevice);
+        cg_note_written({ R.p }, count);
+        return cg_solve_sreduce(R, sVector->data, iteration, residual, residualTrace, traceCapacity);
     });
-    return st;
 }
 
 int SolveSingleReduce(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -2910,9 +2844,7 @@ int SolveSingleReduce(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matD
                                      allowableResidual, minIteration, maxIteration, rule, iteration, residual, residualTrace, traceCapacity);
 }
 
-// MINRES (cg_solve_minres above).  What needs no device is refused before one is asked for when there is nobody to agree with; among several
-// ranks a rank with unusable arguments travels in the halo plan's one all-reduce (cg_call) and every rank leaves with MGCG_ERROR.  The shift
-// is NOT part of that agreement: every rank passes the same.
+// MINRES (cg_solve_minres above; refusals: cg_variant_call).  The shift is NOT part of the ranks' agreement: every rank passes the same.
 int SolveMinresParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                         Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                         Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* w1Vector, Vector* w2Vector,
@@ -2921,32 +2853,20 @@ int SolveMinresParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, 
                         int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    const bool handles = cublas && cusparse && w1Vector && w2Vector;
-    auto checks = [&] {
-        if (!(std::fabs(shift) <= 1.79e308)) set_error("SolveMinres: the shift is not finite");
-        else if (rule == MGCG_RULE_HANDMADECL) set_error("SolveMinres: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the recurrence carries no max|r|");
-        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("SolveMinres: unknown stop rule %d", rule);
-        else if (w1Vector->size < countForDevice) set_error("SolveMinres: the w1 vector holds %lld entries, the matrix has %d local rows", w1Vector->size, countForDevice);
-        else if (w2Vector->size < countForDevice) set_error("SolveMinres: the w2 vector holds %lld entries, the matrix has %d local rows", w2Vector->size, countForDevice);
-        else if (rVector && rVector->size < count) set_error("SolveMinres: the r vector holds %lld entries, the matrix has %d columns (both Lanczos buffers are full length)", rVector->size, count);
-        else return true;
-        return false;
-    };
-    if (MgcgCommSize(comm) <= 1) {
-        if (!handles) { set_error("SolveMinres: null handle"); return MGCG_ERROR; }
-        if (!checks()) return MGCG_ERROR;
-    }
-    if (handles && !device_state()) return MGCG_ERROR;
-    const CgCall c = { "SolveMinres", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+    const char* who = "SolveMinres";
+    const CgCall c = { who, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
                        count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
-    int st = MGCG_ERROR;
-    cg_call(c, handles, checks, [&](CgRun& R) {
+    auto checks = [&] {
+        if (!(std::fabs(shift) <= 1.79e308)) { set_error("%s: the shift is not finite", who); return false; }
+        return !cg_rule_refused(who, rule, "the recurrence carries no max|r|") && !cg_vector_short(who, "w1", w1Vector, countForDevice, "local rows") && !cg_vector_short(who, "w2", w2Vector, countForDevice, "local rows") &&
+               !(rVector && cg_vector_short(who, "r", rVector, count, "columns (both Lanczos buffers are full length)"));
+    };
+    return cg_variant_call(c, cublas && cusparse && w1Vector && w2Vector, checks, [&](CgRun& R) {
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        for (double* v : { R.x, R.Ap, w1Vector->data, w2Vector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
-        for (double* v : { R.p, R.r }) analysis_note_write(v, sizeof(double) * (size_t)count);
-        st = cg_solve_minres(R, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
+        cg_note_written({ R.x, R.Ap, w1Vector->data, w2Vector->data }, countForDevice);
+        cg_note_written({ R.p, R.r }, count);
+        return cg_solve_minres(R, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
     });
-    return st;
 }
 
 int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -2961,8 +2881,7 @@ int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
-// BiCGStab (cg_solve_bicgstab above).  Refusals as in SolveMinresParallel; with `jacobi` a rank whose diagonal set-up failed calls with a null
-// dinvVector and every rank leaves with MGCG_ERROR, as in SolveJacobiParallel.
+// BiCGStab (cg_solve_bicgstab above; refusals: cg_variant_call).  With `jacobi` dinvVector is a handle the export requires.
 static int bicgstab_entry(const char* who, bool jacobi, MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
                           Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                           Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
@@ -2971,35 +2890,21 @@ static int bicgstab_entry(const char* who, bool jacobi, MgcgComm* comm, MgcgBlas
                           double allowableResidual, int minIteration, int maxIteration, int rule,
                           int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
-    const bool handles = cublas && cusparse && vVector && sVector && tVector && rhatVector && (!jacobi || dinvVector);
-    auto checks = [&] {
-        if (rule == MGCG_RULE_HANDMADECL) set_error("%s: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the loop carries no max|r|", who);
-        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("%s: unknown stop rule %d", who, rule);
-        else if (vVector->size < countForDevice) set_error("%s: the v vector holds %lld entries, the matrix has %d local rows", who, vVector->size, countForDevice);
-        else if (tVector->size < countForDevice) set_error("%s: the t vector holds %lld entries, the matrix has %d local rows", who, tVector->size, countForDevice);
-        else if (rhatVector->size < countForDevice) set_error("%s: the rhat vector holds %lld entries, the matrix has %d local rows", who, rhatVector->size, countForDevice);
-        else if (sVector->size < count) set_error("%s: the s vector holds %lld entries, the matrix has %d columns (p and s are full length)", who, sVector->size, count);
-        else if (jacobi && dinvVector->size < countForDevice) set_error("%s: the dinv vector holds %lld entries, the matrix has %d local rows", who, dinvVector->size, countForDevice);
-        else return true;
-        return false;
-    };
-    if (MgcgCommSize(comm) <= 1) {
-        if (!handles) { set_error("%s: null handle", who); return MGCG_ERROR; }
-        if (!checks()) return MGCG_ERROR;
-    }
-    if (handles && !device_state()) return MGCG_ERROR;
     const CgCall c = { who, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
                        count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
-    int st = MGCG_ERROR;
-    cg_call(c, handles, checks, [&](CgRun& R) {
-        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the loop, which reads nothing through it there
-        if (jacobi) R.dinv = dinvVector->data ? dinvVector->data : R.ws->partials;
+    auto checks = [&] {
+        return !cg_rule_refused(who, rule, "the loop carries no max|r|") && !cg_vector_short(who, "v", vVector, countForDevice, "local rows") &&
+               !cg_vector_short(who, "t", tVector, countForDevice, "local rows") && !cg_vector_short(who, "rhat", rhatVector, countForDevice, "local rows") &&
+               !cg_vector_short(who, "s", sVector, count, "columns (p and s are full length)") &&
+               !(jacobi && cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows"));
+    };
+    return cg_variant_call(c, cublas && cusparse && vVector && sVector && tVector && rhatVector && (!jacobi || dinvVector), checks, [&](CgRun& R) {
+        if (jacobi) R.dinv = cg_dinv_address(R, dinvVector);
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        for (double* v : { R.x, R.Ap, R.r, vVector->data, tVector->data, rhatVector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
-        for (double* v : { R.p, sVector->data }) analysis_note_write(v, sizeof(double) * (size_t)count);
-        st = cg_solve_bicgstab(R, who, vVector->data, sVector->data, tVector->data, rhatVector->data, iteration, residual, trueResidual, residualTrace, traceCapacity);
+        cg_note_written({ R.x, R.Ap, R.r, vVector->data, tVector->data, rhatVector->data }, countForDevice);
+        cg_note_written({ R.p, sVector->data }, count);
+        return cg_solve_bicgstab(R, who, vVector->data, sVector->data, tVector->data, rhatVector->data, iteration, residual, trueResidual, residualTrace, traceCapacity);
     });
-    return st;
 }
 
 int SolveBicgstabParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -3058,18 +2963,13 @@ int SolveBicgstabJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* ma
                                        allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
-// Preconditioned MINRES (cg_solve_pminres above).  Refusals as in SolveMinresParallel; a rank whose diagonal set-up failed calls with a null
-// dinvVector and every rank leaves with MGCG_ERROR, as in SolveJacobiParallel.  The shift is NOT part of that agreement.
+// Preconditioned MINRES (cg_solve_pminres above; refusals: cg_variant_call).  dinvVector, the hierarchy and zVector are handles the exports
+// require.  The shift is NOT part of the ranks' agreement.
 static bool pminres_common_checks(const char* who, double shift, int rule, Vector* r1Vector, Vector* w1Vector, Vector* w2Vector, int countForDevice)
 {
-    if (!(std::fabs(shift) <= 1.79e308)) set_error("%s: the shift is not finite", who);
-    else if (rule == MGCG_RULE_HANDMADECL) set_error("%s: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the recurrence carries no max|r|", who);
-    else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("%s: unknown stop rule %d", who, rule);
-    else if (r1Vector->size < countForDevice) set_error("%s: the r1 vector holds %lld entries, the matrix has %d local rows", who, r1Vector->size, countForDevice);
-    else if (w1Vector->size < countForDevice) set_error("%s: the w1 vector holds %lld entries, the matrix has %d local rows", who, w1Vector->size, countForDevice);
-    else if (w2Vector->size < countForDevice) set_error("%s: the w2 vector holds %lld entries, the matrix has %d local rows", who, w2Vector->size, countForDevice);
-    else return true;
-    return false;
+    if (!(std::fabs(shift) <= 1.79e308)) { set_error("%s: the shift is not finite", who); return false; }
+    return !cg_rule_refused(who, rule, "the recurrence carries no max|r|") && !cg_vector_short(who, "r1", r1Vector, countForDevice, "local rows") &&
+           !cg_vector_short(who, "w1", w1Vector, countForDevice, "local rows") && !cg_vector_short(who, "w2", w2Vector, countForDevice, "local rows");
 }
 
 int SolveMinresJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -3082,29 +2982,18 @@ int SolveMinresJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusp
 {
     (void)matDescr;
     const char* who = "SolveMinresJacobi";
-    const bool handles = cublas && cusparse && r1Vector && w1Vector && w2Vector && dinvVector;
-    auto checks = [&] {
-        if (!pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, countForDevice)) return false;
-        if (dinvVector->size < countForDevice) { set_error("%s: the dinv vector holds %lld entries, the matrix has %d local rows", who, dinvVector->size, countForDevice); return false; }
-        return true;
-    };
-    if (MgcgCommSize(comm) <= 1) {
-        if (!handles) { set_error("%s: null handle", who); return MGCG_ERROR; }
-        if (!checks()) return MGCG_ERROR;
-    }
-    if (handles && !device_state()) return MGCG_ERROR;
     const CgCall c = { who, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
                        count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
-    int st = MGCG_ERROR;
-    cg_call(c, handles, checks, [&](CgRun& R) {
-        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the loop, which reads nothing through it there
-        R.dinv = dinvVector->data ? dinvVector->data : R.ws->partials;
+    auto checks = [&] {
+        return pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, countForDevice) && !cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows");
+    };
+    return cg_variant_call(c, cublas && cusparse && r1Vector && w1Vector && w2Vector && dinvVector, checks, [&](CgRun& R) {
+        R.dinv = cg_dinv_address(R, dinvVector);
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        for (double* v : { R.x, R.Ap, R.r, r1Vector->data, w1Vector->data, w2Vector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
-        analysis_note_write(R.p, sizeof(double) * (size_t)count);
-        st = cg_solve_pminres(R, who, r1Vector->data, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
+        cg_note_written({ R.x, R.Ap, R.r, r1Vector->data, w1Vector->data, w2Vector->data }, countForDevice);
+        cg_note_written({ R.p }, count);
+        return cg_solve_pminres(R, who, r1Vector->data, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
     });
-    return st;
 }
 
 int SolveMinresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -3130,31 +3019,25 @@ int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
 {
     (void)matDescr;
     const char* who = "SolveMinresMg";
-    if (!cublas || !cusparse || !mg || !r1Vector || !w1Vector || !w2Vector || !zVector) { set_error("%s: null handle", who); return MGCG_ERROR; }
+    const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
     auto checks = [&] {
-        if (!pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, count)) return false;
-        if (zVector->size < count) { set_error("%s: the z vector holds %lld entries, the matrix has %d rows", who, zVector->size, count); return false; }
+        if (!pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, count) || cg_vector_short(who, "z", zVector, count, "rows")) return false;
         if (mg->nranks != 1 || mg->multi) { set_error("%s: the hierarchy was built for %d rank(s)%s; the V-cycle form runs on one rank", who, mg->nranks, mg->multi ? " on the several-ranks path" : ""); return false; }
         if (mg->levels < 1 || mg->lv[0].n != count) { set_error("%s: the hierarchy has %lld rows on level 0, the matrix has %d", who, mg->levels < 1 ? 0LL : (long long)mg->lv[0].n, count); return false; }
         return true;
     };
-    if (!checks()) return MGCG_ERROR;
-    if (!device_state()) return MGCG_ERROR;
-    const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
-    int st = MGCG_ERROR;
-    cg_call(c, true, no_more_checks, [&](CgRun& R) {
-        if (R.multi) { set_error("%s: the V-cycle form runs on one rank", who); return; }
+    // one rank always: cg_variant_call refuses in front of the device, and cg_call's second look at checks() finds nothing new
+    return cg_variant_call(c, cublas && cusparse && mg && r1Vector && w1Vector && w2Vector && zVector, checks, [&](CgRun& R) {
+        if (R.multi) { set_error("%s: the V-cycle form runs on one rank", who); return (int)MGCG_ERROR; }
         R.mg = mg; R.z = zVector->data;
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        for (double* v : { R.x, R.Ap, R.r, R.p, r1Vector->data, w1Vector->data, w2Vector->data, R.z }) analysis_note_write(v, sizeof(double) * (size_t)count);
-        st = cg_solve_pminres(R, who, r1Vector->data, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
+        cg_note_written({ R.x, R.Ap, R.r, R.p, r1Vector->data, w1Vector->data, w2Vector->data, R.z }, count);
+        return cg_solve_pminres(R, who, r1Vector->data, w1Vector->data, w2Vector->data, shift, iteration, residual, trueResidual, residualTrace, traceCapacity);
     });
-    return st;
 }
 
-// Chebyshev-preconditioned CG (cg_solve_chebyshev above).  What needs no device is refused before one is asked for when there is nobody to agree
-// with; among several ranks a rank with unusable arguments travels in the halo plan's one all-reduce (cg_call) and every rank leaves with
-// MGCG_ERROR.  Degree, bounds and whether dinvVector is given are NOT part of that agreement: every rank passes the same.
+// Chebyshev-preconditioned CG (cg_solve_chebyshev above; refusals: cg_variant_call).  Degree, bounds and whether dinvVector is given are NOT part
+// of the ranks' agreement: every rank passes the same.
 int SolveChebyshevParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                            Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                            Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* dinvVector,
@@ -3165,36 +3048,22 @@ int SolveChebyshevParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cuspars
                            int* iteration, double* residual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    const bool handles = cublas && cusparse && zVector && z2Vector && dVector;
-    auto checks = [&] {
-        if (degree < 1 || degree > 16) set_error("SolveChebyshev: degree %d, must be 1 .. 16", degree);
-        else if (!(lambdaMin > 0.0 && lambdaMin < lambdaMax && lambdaMax <= 1.79e308)) set_error("SolveChebyshev: the bounds (%g, %g) must be finite with 0 < lambdaMin < lambdaMax", lambdaMin, lambdaMax);
-        else if (rule == MGCG_RULE_HANDMADECL) set_error("SolveChebyshev: the max-norm rule (MGCG_RULE_HANDMADECL) is not supported: the passes carry no max|r|");
-        else if (rule < MGCG_RULE_NATIVE || rule > MGCG_RULE_VIENNACL) set_error("SolveChebyshev: unknown stop rule %d", rule);
-        else if (zVector->size < count) set_error("SolveChebyshev: the z vector holds %lld entries, the matrix has %d columns", zVector->size, count);
-        else if (z2Vector->size < count) set_error("SolveChebyshev: the z2 vector holds %lld entries, the matrix has %d columns", z2Vector->size, count);
-        else if (dVector->size < countForDevice) set_error("SolveChebyshev: the d vector holds %lld entries, the matrix has %d local rows", dVector->size, countForDevice);
-        else if (dinvVector && dinvVector->size < countForDevice) set_error("SolveChebyshev: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice);
-        else return true;
-        return false;
-    };
-    if (MgcgCommSize(comm) <= 1) {
-        if (!handles) { set_error("SolveChebyshev: null handle"); return MGCG_ERROR; }
-        if (!checks()) return MGCG_ERROR;
-    }
-    if (handles && !device_state()) return MGCG_ERROR;
-    const CgCall c = { "SolveChebyshev", comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+    const char* who = "SolveChebyshev";
+    const CgCall c = { who, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
                        count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ };
-    int st = MGCG_ERROR;
-    cg_call(c, handles, checks, [&](CgRun& R) {
-        // a rank without rows has an empty dinv vector (no data): any address says "with the diagonal" to the passes, which read nothing through it there
-        R.dinv = dinvVector ? (dinvVector->data ? dinvVector->data : R.ws->partials) : nullptr;
+    auto checks = [&] {
+        if (degree < 1 || degree > 16) { set_error("%s: degree %d, must be 1 .. 16", who, degree); return false; }
+        if (!(lambdaMin > 0.0 && lambdaMin < lambdaMax && lambdaMax <= 1.79e308)) { set_error("%s: the bounds (%g, %g) must be finite with 0 < lambdaMin < lambdaMax", who, lambdaMin, lambdaMax); return false; }
+        return !cg_rule_refused(who, rule, "the passes carry no max|r|") && !cg_vector_short(who, "z", zVector, count, "columns") && !cg_vector_short(who, "z2", z2Vector, count, "columns") &&
+               !cg_vector_short(who, "d", dVector, countForDevice, "local rows") && !(dinvVector && cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows"));
+    };
+    return cg_variant_call(c, cublas && cusparse && zVector && z2Vector && dVector, checks, [&](CgRun& R) {
+        R.dinv = cg_dinv_address(R, dinvVector);
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        for (double* v : { R.x, R.r, R.Ap, dVector->data }) analysis_note_write(v, sizeof(double) * (size_t)countForDevice);
-        for (double* v : { R.p, zVector->data, z2Vector->data }) analysis_note_write(v, sizeof(double) * (size_t)count);
-        st = cg_solve_chebyshev(R, cheb_plan(degree, lambdaMin, lambdaMax), zVector->data, z2Vector->data, dVector->data, iteration, residual, residualTrace, traceCapacity);
+        cg_note_written({ R.x, R.r, R.Ap, dVector->data }, countForDevice);
+        cg_note_written({ R.p, zVector->data, z2Vector->data }, count);
+        return cg_solve_chebyshev(R, cheb_plan(degree, lambdaMin, lambdaMax), zVector->data, z2Vector->data, dVector->data, iteration, residual, residualTrace, traceCapacity);
     });
-    return st;
 }
 
 int SolveChebyshev(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -3220,7 +3089,7 @@ int MgcgGershgorinBound(MgcgSparse* cusparse, Vector* elementsVector, VectorInt*
     if (elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount || rowOffsetsVector->size < (long long)countForDevice + 1) {
         set_error("MgcgGershgorinBound: a device vector is smaller than the matrix"); return -1;
     }
-    if (dinvVector && dinvVector->size < countForDevice) { set_error("MgcgGershgorinBound: the dinv vector holds %lld entries, the matrix has %d local rows", dinvVector->size, countForDevice); return -1; }
+    if (dinvVector && cg_vector_short("MgcgGershgorinBound", "dinv", dinvVector, countForDevice, "local rows")) return -1;
     *bound = 0.0;
     if (countForDevice == 0) return 0;
     if (!device_state()) return -1;

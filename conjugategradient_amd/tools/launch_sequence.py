@@ -6,8 +6,10 @@
     python conjugategradient_amd/tools/launch_sequence.py table OUT > counts.json
 
 ``run``: 64^3 SolveEx with x_defer 8 and 1, CgSteps(20), a 64^3 MGCG solve and a 64^3 Jacobi-preconditioned solve, two loopback ranks
-plain, MGCG and Jacobi, four loopback ranks of which three hold no rows, plain and Jacobi.  The placement draw is off (its timing loops
-launch SpMVs by the free memory of the moment).
+plain, MGCG and Jacobi, four loopback ranks of which three hold no rows, plain and Jacobi; then one 64^3 solve of each one-column variant
+(mixed precision, single reduction, MINRES with a shift that makes the system indefinite, BiCGStab, Jacobi-preconditioned MINRES, Chebyshev
+CG of degree 4) and, on two loopback ranks at 32 x 32 x 16, the five of them that have a several-ranks form, with and without the diagonal
+where both exist.  The placement draw is off (its timing loops launch SpMVs by the free memory of the moment).
 ``table``: per-kernel call counts of the run's *kernel_stats.csv, as one JSON object sorted by name."""
 import csv
 import glob
@@ -138,7 +140,77 @@ def run():
     ranks_in_threads(4, empty_jacobi)
     done.append(("four ranks, three empty", its["empty", 3]))
     done.append(("four ranks, three empty, Jacobi", its["empty jacobi", 3]))
+    variants(done)
     print(json.dumps({"iterations": dict(done)}))
+
+
+SHIFT = 0.1             # above the first eigenvalues of both grids below (64^3: from 0.007; 32 x 32 x 16: 0.052, 0.079, ...): A - SHIFT I is indefinite
+BOUNDS = (0.4, 12.0)    # of the 7-point matrix; with the diagonal the same interval over 6
+
+
+def variants(done):
+    """One solve of each one-column variant on one rank, and of each several-ranks form on two loopback ranks."""
+    from conjugategradient_amd import _lib, problems
+    from conjugategradient_amd.bicgstab import BiConjugateGradientStabGpu, BiConjugateGradientStabJacobiGpu
+    from conjugategradient_amd.chebyshev import ConjugateGradientChebyshevGpu
+    from conjugategradient_amd.minres import MinimalResidualGpu, MinimalResidualJacobiGpu
+    from conjugategradient_amd.mixed import ConjugateGradientMixedGpu
+    from conjugategradient_amd.parallel import ConjugateGradientRankGpu
+    from conjugategradient_amd.singlereduce import ConjugateGradientSingleReduceGpu
+    from conjugategradient_amd.solver import ApplicationException
+
+    def counted(solve):                                         # a run that meets its iteration cap counts too
+        try:
+            solve()
+        except ApplicationException:
+            pass
+
+    s = problems.poisson(64, 64, 64)
+    args = (s.Count, 7, 0, 5000, 1e-8)
+    one_rank = [
+        ("mixed", lambda: ConjugateGradientMixedGpu(*args, rule=_lib.RULE_CSHARP)),
+        ("single reduction", lambda: ConjugateGradientSingleReduceGpu(*args, rule=_lib.RULE_CSHARP)),
+        ("single reduction Jacobi", lambda: ConjugateGradientSingleReduceGpu(*args, rule=_lib.RULE_CSHARP, jacobi=True)),
+        ("MINRES indefinite", lambda: MinimalResidualGpu(*args, rule=_lib.RULE_CSHARP, shift=SHIFT)),
+        ("MINRES Jacobi indefinite", lambda: MinimalResidualJacobiGpu(*args, rule=_lib.RULE_CSHARP, shift=SHIFT)),
+        ("BiCGStab", lambda: BiConjugateGradientStabGpu(*args, rule=_lib.RULE_CSHARP)),
+        ("BiCGStab Jacobi", lambda: BiConjugateGradientStabJacobiGpu(*args, rule=_lib.RULE_CSHARP)),
+        ("Chebyshev degree 4", lambda: ConjugateGradientChebyshevGpu(*args, rule=_lib.RULE_CSHARP, degree=4, bounds=BOUNDS)),
+        ("Chebyshev degree 4 Jacobi", lambda: ConjugateGradientChebyshevGpu(*args, rule=_lib.RULE_CSHARP, degree=4, jacobi=True, bounds=(BOUNDS[0] / 6, BOUNDS[1] / 6))),
+    ]
+    for name, make in one_rank:
+        cg = make().load(s)
+        cg.Initialize()
+        counted(cg.Solve)
+        done.append((name, cg.Iteration))
+        cg.Dispose()
+
+    t = problems.poisson(32, 32, 16)
+    two_ranks = [
+        ("single reduction", False, lambda cg: cg.SolveSingleReduce()),
+        ("single reduction Jacobi", True, lambda cg: cg.SolveSingleReduce(jacobi=True)),
+        ("MINRES indefinite", False, lambda cg: cg.SolveMinres(shift=SHIFT)),
+        ("MINRES Jacobi indefinite", True, lambda cg: cg.SolveMinresJacobi(shift=SHIFT)),
+        ("BiCGStab", False, lambda cg: cg.SolveBicgstab()),
+        ("BiCGStab Jacobi", True, lambda cg: cg.SolveBicgstabJacobi()),
+        ("Chebyshev degree 4", False, lambda cg: cg.SolveChebyshev(degree=4, bounds=BOUNDS)),
+        ("Chebyshev degree 4 Jacobi", True, lambda cg: cg.SolveChebyshev(jacobi=True, degree=4, bounds=(BOUNDS[0] / 6, BOUNDS[1] / 6))),
+    ]
+    for name, diagonal, solve in two_ranks:
+        its = {}
+
+        def rank_body(rank, comm):
+            cg = ConjugateGradientRankGpu(t.Count, 7, 0, 2000, 1e-8, rank=rank, world=2, comm=comm, device=rank).load(t)
+            cg.Initialize()
+            if diagonal:
+                cg.SetupJacobi()
+            counted(lambda: solve(cg))
+            its[rank] = cg.Iteration
+            cg.Dispose()
+
+        ranks_in_threads(2, rank_body)
+        assert its[0] == its[1], (name, its)
+        done.append(("two ranks " + name, its[0]))
 
 
 def table(out):

@@ -59,6 +59,36 @@ def tuning(**knobs):
             L.MgcgSetTuning(name.encode(), value)
 
 
+@contextlib.contextmanager
+def library_messages():
+    """The messages the library left on this thread during the block, whole and in order.  The Python classes consume a message before
+    they raise -- they clear it when an iteration cap was hit, and put it behind "Export: " in their MgcgError otherwise -- so each one is
+    recorded on its way out, when it is cleared."""
+    L = _lib.lib()
+    seen, clear = [], L.MgcgClearLastError
+
+    def recording_clear():
+        if _lib.last_error():
+            seen.append(_lib.last_error())
+        clear()
+
+    L.MgcgClearLastError = recording_clear
+    try:
+        yield seen
+    finally:
+        L.MgcgClearLastError = clear
+
+
+def maxit_message(who, run, max_it, residual="residual", norm=""):
+    """The library's message of a run that met its iteration cap, rebuilt from what the run returned (%g, as the library prints it)."""
+    return "%s: did not converge: iteration %d exceeded maxIteration %d (%s %g%s)" % (who, run["iteration"], max_it, residual, run["residual"], norm)
+
+
+def nonfinite_message(who, run, what):
+    """The library's message of a run that ended with NONFINITE; what: the loop's own text of what that means."""
+    return "%s: stopped at iteration %d: %s" % (who, run["iteration"], what)
+
+
 def same_bits(a, b):
     """Equal bit for bit (NaN payloads and the sign of zero included); lists and tuples entry by entry."""
     if isinstance(a, (list, tuple)):

@@ -15,7 +15,7 @@ from conjugategradient_amd import _lib, problems
 from conjugategradient_amd.bicgstab import BiConjugateGradientStabGpu, BiConjugateGradientStabJacobiGpu
 from conjugategradient_amd.parallel import ConjugateGradientRankGpu
 from conjugategradient_amd.solver import ApplicationException, ConjugateGradientSingleGpu
-from tests.gpu_util import dvec
+from tests.gpu_util import dvec, library_messages, maxit_message, nonfinite_message
 from tests.test_bicgstab_host import (CASES, bicgstab_oracle, nonsymmetric_tridiagonal, numpy_true_residual, rho_zero2, sigma_zero2,
                                       system)
 from tests.test_gpu_jacobi import run_ranks
@@ -28,6 +28,9 @@ FORMS = [False, True]
 FORM_IDS = ["plain", "jacobi"]
 MAX_IT = 3000
 _oracles = {}
+WHO = {False: "SolveBicgstab", True: "SolveBicgstabJacobi"}
+# what MGCG_NONFINITE means in this loop, as the library words it (csrc/solver.hip: cg_solve_bicgstab)
+NONFINITE = "the first residual is zero or not finite, or the recurrence broke down (rhat.v, omega or rhat.r zero, or a value that is not finite)"
 
 
 def reference(name, rhs, jacobi, rule, tol, parts=None, **kw):
@@ -67,15 +70,16 @@ def solve(s, jacobi, rule, tol, min_it=0, max_it=MAX_IT, compression=None, trace
     cg.Initialize()
     if prepare is not None:
         prepare(cg)
-    try:
-        cg.Solve(trace=True, traceCapacity=trace_capacity)
-    except ApplicationException:
-        assert cg.status == _lib.MAXIT_EXCEEDED
-    except _lib.MgcgError:
-        assert cg.status == _lib.NONFINITE
+    with library_messages() as said:
+        try:
+            cg.Solve(trace=True, traceCapacity=trace_capacity)
+        except ApplicationException:
+            assert cg.status == _lib.MAXIT_EXCEEDED
+        except _lib.MgcgError:
+            assert cg.status == _lib.NONFINITE
     cg.Read()
     out = dict(x=cg.x.copy(), r=cg.ReadResidual(), iteration=cg.Iteration, residual=cg.Residual, true_residual=cg.TrueResidual,
-               status=cg.status, trace=cg.trace)
+               status=cg.status, trace=cg.trace, messages=list(said))
     cg.Dispose()
     return out
 
@@ -148,7 +152,9 @@ def test_min_iteration_beyond_convergence(dot_order, jacobi):
 def test_iteration_cap_equals_the_oracle(dot_order, jacobi):
     ref = reference("convdiff16", "randn", jacobi, _lib.RULE_CSHARP, 0.0, max_it=3)
     assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 4
-    assert_equal_runs(solve(system("convdiff16", "randn")[0], jacobi, _lib.RULE_CSHARP, 0.0, max_it=3), ref)
+    got = solve(system("convdiff16", "randn")[0], jacobi, _lib.RULE_CSHARP, 0.0, max_it=3)
+    assert_equal_runs(got, ref)
+    assert got["messages"] == [maxit_message(WHO[jacobi], got, 3)]          # "SolveBicgstab: did not converge: iteration 4 exceeded maxIteration 3 (residual ...)"
 
 
 def test_the_iteration_cap_raises_application_exception(dot_order):
@@ -232,7 +238,9 @@ def test_sigma_zero_gives_nonfinite_and_the_callers_x_back(dot_order, jacobi):
     s = sigma_zero2()                                       # diagonal (1, 1): the Jacobi form takes the same steps
     ref = oracle(s, jacobi, _lib.RULE_CSHARP, 1e-12)
     assert ref["status"] == _lib.NONFINITE and ref["iteration"] == 1 and np.array_equal(ref["x"], s.x)
-    assert_equal_runs(solve(s, jacobi, _lib.RULE_CSHARP, 1e-12), ref)
+    got = solve(s, jacobi, _lib.RULE_CSHARP, 1e-12)
+    assert_equal_runs(got, ref)
+    assert got["messages"] == [nonfinite_message(WHO[jacobi], got, NONFINITE)]
     started = with_b(s, s.b, "sigma_zero2-x0")
     started.x[:] = [0.0, 1.0]
     ok = oracle(started, jacobi, _lib.RULE_CSHARP, 1e-12)

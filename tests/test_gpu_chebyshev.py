@@ -15,7 +15,7 @@ from conjugategradient_amd.chebyshev import ConjugateGradientChebyshevGpu, gersh
 from conjugategradient_amd.jacobi import ConjugateGradientJacobiGpu
 from conjugategradient_amd.parallel import ConjugateGradientRankGpu
 from conjugategradient_amd.solver import ApplicationException, ConjugateGradientSingleGpu
-from tests.gpu_util import ivec
+from tests.gpu_util import ivec, library_messages, maxit_message, nonfinite_message
 from tests.test_chebyshev_host import chebyshev_cg_oracle, default_bounds, gershgorin_oracle
 from tests.test_gpu_jacobi import run_ranks
 from tests.test_sreduce_host import diagonal_of, randn_b, tridiagonal, with_b
@@ -25,6 +25,8 @@ pytestmark = pytest.mark.gpu
 VARIANTS = [False, True]
 DEGREES = [1, 2, 3, 8]               # odd and even degrees end in different z buffers
 MAX_IT = 3000
+# what MGCG_NONFINITE means in this loop, as the library words it (csrc/solver.hip: cg_solve_chebyshev)
+NONFINITE = "p.Ap or r.z is not finite and > 0 (an upper bound below the spectrum makes the polynomial indefinite), or the residual is not finite"
 
 SYSTEMS = {
     "tridiagonal300": lambda: tridiagonal(300)[0],
@@ -77,15 +79,16 @@ def solve(s, degree, bounds, rule, tol, jacobi, min_it=0, max_it=MAX_IT, compres
     cg.Initialize()
     if prepare is not None:
         prepare(cg)
-    try:
-        cg.Solve(trace=True, traceCapacity=trace_capacity)
-    except ApplicationException:
-        assert cg.status == _lib.MAXIT_EXCEEDED
-    except _lib.MgcgError:
-        assert cg.status == _lib.NONFINITE
+    with library_messages() as said:
+        try:
+            cg.Solve(trace=True, traceCapacity=trace_capacity)
+        except ApplicationException:
+            assert cg.status == _lib.MAXIT_EXCEEDED
+        except _lib.MgcgError:
+            assert cg.status == _lib.NONFINITE
     cg.Read()
     out = dict(x=cg.x.copy(), r=cg.ReadResidual(), iteration=cg.Iteration, residual=cg.Residual, status=cg.status, trace=cg.trace,
-               bounds=(cg.lambdaMin, cg.lambdaMax))
+               bounds=(cg.lambdaMin, cg.lambdaMax), messages=list(said))
     cg.Dispose()
     return out
 
@@ -219,7 +222,9 @@ def test_iteration_cap_equals_the_oracle(dot_order, degree):
     ref = reference("poisson16", degree, _lib.RULE_CSHARP, 0.0, False, max_it=3)
     assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 4
     s, _, bounds = system("poisson16")
-    assert_equal_runs(solve(s, degree, bounds[False], _lib.RULE_CSHARP, 0.0, False, max_it=3), ref)
+    got = solve(s, degree, bounds[False], _lib.RULE_CSHARP, 0.0, False, max_it=3)
+    assert_equal_runs(got, ref)
+    assert got["messages"] == [maxit_message("SolveChebyshev", got, 3)]      # "SolveChebyshev: did not converge: iteration 4 exceeded maxIteration 3 (residual ...)"
 
 
 def test_a_trace_shorter_than_the_run(dot_order):
@@ -254,7 +259,9 @@ def test_an_upper_bound_below_the_spectrum_gives_nonfinite_and_the_callers_x_bac
     for which in (s, start):
         ref = chebyshev_cg_oracle(which, 2, (lmax / 30.0, lmax), _lib.RULE_CSHARP, 1e-8)
         assert ref["first_rz"] < 0.0 and ref["status"] == _lib.NONFINITE and ref["iteration"] == 0 and np.array_equal(ref["x"], which.x)
-        assert_equal_runs(solve(which, 2, (lmax / 30.0, lmax), _lib.RULE_CSHARP, 1e-8, False), ref)
+        got = solve(which, 2, (lmax / 30.0, lmax), _lib.RULE_CSHARP, 1e-8, False)
+        assert_equal_runs(got, ref)
+        assert got["messages"] == [nonfinite_message("SolveChebyshev", got, NONFINITE)]
 
 
 def test_a_zero_right_hand_side_gives_nonfinite(dot_order):

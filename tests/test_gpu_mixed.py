@@ -346,7 +346,8 @@ def test_iteration_cap_reports_a_true_residual(h, dot_order, max_it):
     assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 11       # the first update slot behind the cap
     got = d.solve(_lib.RULE_CSHARP, 0.0, max_it=max_it)
     assert_equal_runs(got, ref)
-    assert "maxIteration %d" % max_it in got["message"]
+    # "SolveMixed: did not converge: iteration 11 exceeded maxIteration 9 (true residual ...)"
+    assert got["message"] == "SolveMixed: did not converge: iteration %d exceeded maxIteration %d (true residual %g)" % (got["iteration"], max_it, got["residual"])
     true_r = s.b - O.spmv(s.Elements[: s.nnz], s.ColumnIndeces[: s.nnz], s.RowOffsets, got["x"])
     assert np.array_equal(got["r"], true_r) and got["residual"] == math.sqrt(O.dot(true_r, true_r))
 
@@ -367,7 +368,8 @@ def test_an_indefinite_matrix_breaks_down_with_a_finite_x(h):
     assert d.setup() == 0
     got = d.solve(_lib.RULE_CSHARP, 1e-10 * float(np.linalg.norm(bad.b)), max_it=300)
     assert got["status"] == _lib.NONFINITE, (got["status"], got["iteration"])
-    assert "SolveMixed" in got["message"] and np.isfinite(got["x"]).all()
+    assert got["message"] == ("SolveMixed: stopped at iteration %d: p.Ap is not finite and > 0, or the residual is not finite or beyond the fp32 range"
+                              % got["iteration"]) and np.isfinite(got["x"]).all()
 
 
 @pytest.mark.parametrize("first_ok", [0, 5])

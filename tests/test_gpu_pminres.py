@@ -17,16 +17,21 @@ from conjugategradient_amd.minres import MinimalResidualJacobiGpu
 from conjugategradient_amd.multigrid import ConjugateGradientMgGpu
 from conjugategradient_amd.parallel import ConjugateGradientMgRankGpu, ConjugateGradientRankGpu
 from conjugategradient_amd.solver import ApplicationException, _ptr
-from tests.gpu_util import dvec
+from tests.gpu_util import dvec, library_messages, maxit_message, nonfinite_message
 from tests.test_amg_host import Hierarchy, box_maps, csr_of
 from tests.test_gpu_jacobi import run_ranks
 from tests.test_pminres_host import jacobi_of, m_norm, numpy_residual_vector, pminres_oracle, preconditioner, psystem
-from tests.test_sreduce_host import tridiagonal, with_b
+from tests.test_sreduce_host import serial_sum, tridiagonal, with_b
 
 pytestmark = pytest.mark.gpu
 
 RULES = [_lib.RULE_NATIVE, _lib.RULE_CSHARP, _lib.RULE_SIMPLE, _lib.RULE_VIENNACL]
 MAX_IT = 3000
+# what MGCG_NONFINITE means in this loop, as the library words it (csrc/solver.hip: cg_solve_pminres), in general and at iteration 0 with
+# r . M^-1 r < 0
+NONFINITE = ("the first residual is zero or not finite, r . M^-1 r is negative or not finite (a preconditioner that is not positive definite), or the "
+             "rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)")
+NOT_POSITIVE_DEFINITE = "%s: stopped at iteration 0: the preconditioner is not positive definite (r . M^-1 r = %g for the first residual)"
 JACOBI_CASES = [("viennacl4000", 0.0), ("viennacl4000", 60.0), ("random_spd5000", 0.0), ("random_spd5000", 1.5), ("graph12", 0.0), ("graph12", 20.0)]
 RULE_CASES = [(n, sh, r) for n, sh in JACOBI_CASES for r in RULES]      # every (system, shift) under the four 2-norm rules
 _cache = {}
@@ -74,16 +79,18 @@ def dot_order(mgcg_env):
 
 def _finish(cg, solve):
     """Run solve(); an iteration cap that was hit or a breakdown is a result here, not an exception."""
-    try:
-        solve()
-    except ApplicationException:
-        assert cg.status == _lib.MAXIT_EXCEEDED
-    except _lib.MgcgError:
-        assert cg.status == _lib.NONFINITE
+    with library_messages() as said:
+        try:
+            solve()
+        except ApplicationException:
+            assert cg.status == _lib.MAXIT_EXCEEDED
+        except _lib.MgcgError:
+            assert cg.status == _lib.NONFINITE
     cg.Read()
     r = np.empty(cg.Count)
     cg.vectorR.CopyTo(r, cg.Count, 0)
-    out = dict(x=cg.x.copy(), r=r, iteration=cg.Iteration, residual=cg.Residual, true_residual=cg.TrueResidual, status=cg.status, trace=cg.trace)
+    out = dict(x=cg.x.copy(), r=r, iteration=cg.Iteration, residual=cg.Residual, true_residual=cg.TrueResidual, status=cg.status, trace=cg.trace,
+               messages=list(said))
     cg.Dispose()
     return out
 
@@ -195,7 +202,10 @@ def test_iteration_cap_equals_the_oracle_and_raises(dot_order):
     s = psystem("random_spd5000")
     ref = reference("random_spd5000", 1.5, "jacobi", _lib.RULE_CSHARP, 0.0, max_it=3)
     assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 4
-    assert_equal_runs(solve(s, 1.5, _lib.RULE_CSHARP, 0.0, max_it=3), ref)
+    got = solve(s, 1.5, _lib.RULE_CSHARP, 0.0, max_it=3)
+    assert_equal_runs(got, ref)
+    # "SolveMinresJacobi: did not converge: iteration 4 exceeded maxIteration 3 (residual ... in the M^-1 norm)"
+    assert got["messages"] == [maxit_message("SolveMinresJacobi", got, 3, norm=" in the M^-1 norm")]
     cg = MinimalResidualJacobiGpu(s.Count, maxnz(s), 0, 3, 0.0, rule=_lib.RULE_CSHARP, shift=1.5).load(s)
     cg.Initialize()
     with pytest.raises(ApplicationException, match="MaxIteration=3"):
@@ -251,7 +261,9 @@ def test_corner_cases_equal_the_oracle(dot_order):
     s = singular2()
     ref = pminres_oracle(s, 1.0, jacobi_of(s), _lib.RULE_CSHARP, 1e-12)
     assert ref["status"] == _lib.NONFINITE and ref["iteration"] == 1 and np.array_equal(ref["x"], s.x)
-    assert_equal_runs(solve(s, 1.0, _lib.RULE_CSHARP, 1e-12), ref)
+    got = solve(s, 1.0, _lib.RULE_CSHARP, 1e-12)
+    assert_equal_runs(got, ref)
+    assert got["messages"] == [nonfinite_message("SolveMinresJacobi", got, NONFINITE)]
 
 
 def test_a_preconditioner_that_is_not_positive_definite_is_named(dot_order):
@@ -264,8 +276,10 @@ def test_a_preconditioner_that_is_not_positive_definite_is_named(dot_order):
     cg = MinimalResidualJacobiGpu(s.Count, maxnz(s), 0, 100, 1e-8, rule=_lib.RULE_CSHARP, shift=1.5).load(start)
     cg.Initialize()
     cg.vectorDinv.CopyFrom(np.full(s.Count, -1.0), s.Count)
-    with pytest.raises(_lib.MgcgError, match="not positive definite"):
+    with pytest.raises(_lib.MgcgError, match="not positive definite") as raised:
         cg.Solve(trace=True)
+    bz = -serial_sum(ref["r"] * ref["r"])                   # r . M^-1 r with M^-1 = -I; x is untouched, so the closing residual is the first
+    assert str(raised.value) == "SolveMinresJacobi: " + NOT_POSITIVE_DEFINITE % ("SolveMinresJacobi", bz)
     assert_equal_runs(_finish(cg, lambda: None), ref)
 
 

@@ -13,7 +13,7 @@ from conjugategradient_amd import _lib, problems
 from conjugategradient_amd.parallel import ConjugateGradientRankGpu
 from conjugategradient_amd.singlereduce import ConjugateGradientSingleReduceGpu
 from conjugategradient_amd.solver import ApplicationException
-from tests.gpu_util import dvec
+from tests.gpu_util import dvec, library_messages, maxit_message, nonfinite_message
 from tests.test_gpu_jacobi import run_ranks
 from tests.test_sreduce_host import diagonal_of, randn_b, sreduce_cg_oracle, tridiagonal, with_b
 
@@ -30,6 +30,8 @@ SYSTEMS = {
     "random_spd5000": lambda: randn_b(problems.random_spd(5000), "random_spd5000"),
 }
 _systems, _oracles = {}, {}
+# what MGCG_NONFINITE means in this loop, as the library words it (csrc/solver.hip: cg_solve_sreduce)
+NONFINITE = "w.u or its corrected form is not finite and > 0, or alpha or the residual is not finite"
 
 
 def system(name):
@@ -70,14 +72,15 @@ def solve(s, rule, tol, jacobi, min_it=0, max_it=MAX_IT, compression=None, trace
     cg.Initialize()
     if prepare is not None:
         prepare(cg)
-    try:
-        cg.Solve(trace=True, traceCapacity=trace_capacity)
-    except ApplicationException:
-        assert cg.status == _lib.MAXIT_EXCEEDED
-    except _lib.MgcgError:
-        assert cg.status == _lib.NONFINITE
+    with library_messages() as said:
+        try:
+            cg.Solve(trace=True, traceCapacity=trace_capacity)
+        except ApplicationException:
+            assert cg.status == _lib.MAXIT_EXCEEDED
+        except _lib.MgcgError:
+            assert cg.status == _lib.NONFINITE
     cg.Read()
-    out = dict(x=cg.x.copy(), r=cg.ReadResidual(), iteration=cg.Iteration, residual=cg.Residual, status=cg.status, trace=cg.trace)
+    out = dict(x=cg.x.copy(), r=cg.ReadResidual(), iteration=cg.Iteration, residual=cg.Residual, status=cg.status, trace=cg.trace, messages=list(said))
     cg.Dispose()
     return out
 
@@ -142,7 +145,9 @@ def test_min_iteration_beyond_convergence(dot_order):
 def test_iteration_cap_equals_the_oracle(dot_order, jacobi):
     ref = reference("poisson16", _lib.RULE_CSHARP, 0.0, jacobi, max_it=3)
     assert ref["status"] == _lib.MAXIT_EXCEEDED and ref["iteration"] == 4
-    assert_equal_runs(solve(system("poisson16")[0], _lib.RULE_CSHARP, 0.0, jacobi, max_it=3), ref)
+    got = solve(system("poisson16")[0], _lib.RULE_CSHARP, 0.0, jacobi, max_it=3)
+    assert_equal_runs(got, ref)
+    assert got["messages"] == [maxit_message("SolveSingleReduce", got, 3)]   # "SolveSingleReduce: did not converge: iteration 4 exceeded maxIteration 3 (residual ...)"
 
 
 def test_a_trace_shorter_than_the_run(dot_order):
@@ -207,7 +212,9 @@ def test_an_indefinite_matrix_gives_nonfinite_and_the_callers_x_back(dot_order, 
     s = problems.LinearSystem(np.array([1.0, 2.0, 2.0, 1.0]), c, ro, np.array([0.25, -0.5]), np.array([1.0, -1.0]), "indefinite2")
     ref = sreduce_cg_oracle(s, _lib.RULE_CSHARP, 1e-12, jacobi=jacobi)
     assert ref["status"] == _lib.NONFINITE and np.array_equal(ref["x"], s.x)
-    assert_equal_runs(solve(s, _lib.RULE_CSHARP, 1e-12, jacobi), ref)
+    got = solve(s, _lib.RULE_CSHARP, 1e-12, jacobi)
+    assert_equal_runs(got, ref)
+    assert got["messages"] == [nonfinite_message("SolveSingleReduce", got, NONFINITE)]
 
 
 def test_a_zero_right_hand_side_gives_nonfinite(dot_order):
