@@ -8,7 +8,10 @@ the residual it carries is that of the system itself and every stop rule judges 
 ``BiConjugateGradientStabGpu`` has ``MinimalResidualGpu``'s class surface.  ``Iteration``, ``Residual`` and the trace show the
 recurrence's residual, which can drift from b - A x on a badly conditioned nonsymmetric matrix; ``TrueResidual`` is || b - A x ||_2 from
 one closing product, and ``ReadResidual()`` returns that vector.  ``BiConjugateGradientStabJacobiGpu`` is the same class with M = diag(A).
-Several ranks: ``ConjugateGradientRankGpu.SolveBicgstab`` / ``.SolveBicgstabJacobi``.  The max-norm stop rule is not supported.  No
+Several ranks: ``ConjugateGradientRankGpu.SolveBicgstab`` / ``.SolveBicgstabJacobi``.  The V-cycle as right preconditioner
+(``SolveBicgstabMg``) is the method ``SolveBicgstab(trace=False, hierarchy=None)`` of ``multigrid.ConjugateGradientMgGpu`` and
+``amg.ConjugateGradientAmgGpu``: the hierarchy is the object's own, built from the nonsymmetric matrix itself, or with ``hierarchy`` that
+of another multigrid object -- one built from ``problems.symmetric_part(system)``, say.  The max-norm stop rule is not supported.  No
 arithmetic happens in this module.
 """
 from __future__ import annotations

@@ -695,16 +695,18 @@ int pminres_enqueue_update(const PminresRun& R, const FinalizeArgs& f, int k, in
 // BiCGStab (SolveBicgstab*; kernels_bicgstab.hip has the loop, include/MgcgGpu.h the method).  All pointers are this rank's rows.  phat, shat:
 // the rows' slices of the two full-length buffers the products gather from; without dinv they ARE p and s (phat == p, shat == s) and nothing
 // is stored twice.  With dinv s is written over r (s == r: the two are never alive together) and p lives in a buffer of its own.  v = A phat,
-// t = A shat.  given: several ranks -- the sums arrive all-reduced in ws->bicgstabScalars->red.
+// t = A shat.  given: several ranks -- the sums arrive all-reduced in ws->bicgstabScalars->red.  stored (SolveBicgstabMg, dinv null): the
+// vectors are placed as with dinv, but the caller of the passes writes phat and shat itself between them (the V-cycle) -- the start and the
+// passes S and P write no hatted copy, pass X reads shat.
 struct BicgstabRun {
     Workspace* ws;
     double *x, *r, *p, *s, *phat, *shat, *v, *t, *rhat; const double* dinv;
-    long long n; bool given;
+    long long n; bool given; bool stored;
 };
 double* bicgstab_tau_partials(Workspace* ws);
 double* bicgstab_rr_partials(Workspace* ws);
 double* bicgstab_rho_partials(Workspace* ws);
-// the start behind r = b - A x: rhat = r, p = r, phat = dinv * r (with dinv) and the partial sums of r.r in bicgstab_rr_partials(ws); returns
+// the start behind r = b - A x: rhat = r, p = r, phat = dinv * r (with dinv; stored: left to the caller) and the partial sums of r.r in bicgstab_rr_partials(ws); returns
 // their number (1 under dot_order = 1)
 int bicgstab_enqueue_start(const BicgstabRun& R);
 // the scalars in front of body 0 from those sums (reduceFirst) or from the all-reduced red[3]; r.r not finite or zero stops the loop here

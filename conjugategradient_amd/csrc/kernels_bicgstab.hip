@@ -1,7 +1,8 @@
-// BiCGStab for gfx950 (SolveBicgstab* / SolveBicgstabJacobi*): van der Vorst's method for A x = b with A any CSR matrix, symmetric or not,
-// right-preconditioned with M = I or M = diag(A), so that r stays the residual of the system itself.  include/MgcgGpu.h has the method and its
-// rounding contract; solver.hip's cg_solve_bicgstab the host's side.  Out of scope: the V-cycle as preconditioner (SolveBicgstabMg), BiCGStab(l),
-// GMRES, residual replacement, the block and mixed combinations, the C++ twin under host/.
+// BiCGStab for gfx950 (SolveBicgstab* / SolveBicgstabJacobi* / SolveBicgstabMg): van der Vorst's method for A x = b with A any CSR matrix,
+// symmetric or not, right-preconditioned with M = I, M = diag(A) or the V-cycle of a hierarchy, so that r stays the residual of the system
+// itself.  include/MgcgGpu.h has the method and its rounding contract; solver.hip's cg_solve_bicgstab the host's side.  Out of scope: the
+// V-cycle on several ranks (SolveBicgstabMgParallel), BiCGStab(l), GMRES, residual replacement, the block and mixed combinations, the C++ twin
+// under host/.
 //
 // Per body k two products (launch_spmv_auto with the EPI_DOT epilogue: v = A phat with the partial sums of sigma = rhat.v, t = A shat with those of
 // theta = s.t) and four passes -- bytes per row without / with the diagonal:
@@ -14,6 +15,9 @@
 // 120 bytes per row without the diagonal, 160 with it.  Without the diagonal phat IS p and shat IS s: nothing is multiplied and no hatted copy is
 // stored (pass X then reads one vector fewer than the six its general form names).  With it s is written over r -- the two are never alive
 // together -- and p lives in a buffer of its own, so that both forms take the same seven work vectors.
+// The V-cycle form (HAT_STORED) takes the diagonal form's vectors, but the hatted copies are written between the passes by the hierarchy's cycle
+// (p -> phat in front of the first product, s -> shat in front of the second), so pass S and pass P write no hatted copy and read no dinv, and
+// pass X takes its general six-vector form: 24 + 8 + 64 + 32 = 128 bytes per row.
 // A body is six launches with three reduction points: sigma, {theta, tau}, {rr, rhon}.  The scalars stay on the device (BicgstabScalars): every
 // workgroup of a pass adds the partial sums in front of it in one fixed order (reduce_partials_block), so all of them compute the same alpha,
 // omega, beta, breakdown tests and stop decision, and the first alone persists them, the trace entry and the host mirror.
@@ -55,6 +59,19 @@ struct BicgstabPass {
     long long n;
 };
 
+// Who forms the hatted copies phat = M^-1 p and shat = M^-1 s: nobody (M = I: phat IS p, shat IS s), the passes themselves (dinv * value per
+// element), or somebody else between the passes (the V-cycle: the copies are stored, the passes only read them).  One template parameter of
+// every pass and of the start.
+enum : int { HAT_NONE = 0, HAT_DINV = 1, HAT_STORED = 2 };
+
+// go(HAT) for the form this call takes
+template <typename Go> static void bicgstab_with_hat(const BicgstabRun& R, Go go)
+{
+    if (R.dinv) go(std::integral_constant<int, HAT_DINV>{});
+    else if (R.stored) go(std::integral_constant<int, HAT_STORED>{});
+    else go(std::integral_constant<int, HAT_NONE>{});
+}
+
 __device__ __forceinline__ bool bicgstab_finite(double v) { return fabs(v) <= 1.79e308; }
 
 // A breakdown in front of a body's updates (pass P, one thread): the last judged residual once more, for iteration k + 1
@@ -66,9 +83,10 @@ __device__ __forceinline__ void bicgstab_breakdown(const BicgstabPass& a)
     publish_iteration<0>(a.f, d, a.k + 1, rrOld, 0.0, 0, [] {});
 }
 
-template <bool V2, bool NTV, bool GIVEN, bool DINV>
+template <bool V2, bool NTV, bool GIVEN, int HAT>
 __global__ __launch_bounds__(kBlock) void bicgstab_s_kernel(BicgstabPass a)
 {
+    constexpr bool DINV = HAT == HAT_DINV;             // the hatted copy is formed here; HAT_STORED: the cycle writes it behind this pass
     __shared__ double s_red[4];
     const int done = a.f.sc->done;                     // nobody writes it while this pass runs
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
@@ -128,9 +146,10 @@ __global__ __launch_bounds__(kBlock) void bicgstab_tau_kernel(const double* __re
     if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
-template <bool V2, bool NTV, bool GIVEN, bool DINV>
+template <bool V2, bool NTV, bool GIVEN, int HAT>
 __global__ __launch_bounds__(kBlock) void bicgstab_x_kernel(BicgstabPass a)
 {
+    constexpr bool HATTED = HAT != HAT_NONE;           // shat is a vector of its own, whoever wrote it: the general six-vector form
     __shared__ double s_red[4], s_red2[4];
     if (a.bs->fDone != 0 || a.bs->brokeS != 0) return; // both as pass S left them
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
@@ -147,7 +166,7 @@ __global__ __launch_bounds__(kBlock) void bicgstab_x_kernel(BicgstabPass a)
     __syncthreads();                                   // s_red, s_red2 are used again below
     double accR = 0.0, accH = 0.0;
     struct Elem { double x, r; };
-    // one element, every product into a double of its own; without the diagonal ph is p and sh is s
+    // one element, every product into a double of its own; without a hatted copy ph is p and sh is s
     auto step = [&](double x, double ph, double sh, double s, double t, double rh) {
         Elem o;
         double ap = alpha * ph; double x1 = x + ap; double os = omega * sh; o.x = x1 + os;
@@ -158,7 +177,7 @@ __global__ __launch_bounds__(kBlock) void bicgstab_x_kernel(BicgstabPass a)
     };
     auto one = [&](long long i) {
         const double s = a.s[i];
-        const Elem o = step(a.x[i], a.phat[i], DINV ? a.shat[i] : s, s, a.t[i], a.rhat[i]);
+        const Elem o = step(a.x[i], a.phat[i], HATTED ? a.shat[i] : s, s, a.t[i], a.rhat[i]);
         a.x[i] = o.x; a.r[i] = o.r;
     };
     if constexpr (V2) {
@@ -168,7 +187,7 @@ __global__ __launch_bounds__(kBlock) void bicgstab_x_kernel(BicgstabPass a)
         struct Pair { d2 x, ph, sh, s, t, rh; };
         auto load = [&](Pair& e, long long i) {
             e.x = ldv<NTV>(x2 + i); e.ph = ldv<NTV>(p2 + i); e.s = ldv<NTV>(s2 + i); e.t = ldv<NTV>(t2 + i); e.rh = ldv<NTV>(g2 + i);
-            if constexpr (DINV) e.sh = ldv<NTV>(h2 + i); else e.sh = e.s;
+            if constexpr (HATTED) e.sh = ldv<NTV>(h2 + i); else e.sh = e.s;
         };
         auto finish = [&](const Pair& e, long long i) {
             const Elem o0 = step(e.x.x, e.ph.x, e.sh.x, e.s.x, e.t.x, e.rh.x), o1 = step(e.x.y, e.ph.y, e.sh.y, e.s.y, e.t.y, e.rh.y);
@@ -192,9 +211,10 @@ __global__ __launch_bounds__(kBlock) void bicgstab_x_kernel(BicgstabPass a)
     if (threadIdx.x == 0) { a.outA[blockIdx.x] = sr; a.outB[blockIdx.x] = sh; }
 }
 
-template <bool V2, bool NTV, bool GIVEN, bool DINV>
+template <bool V2, bool NTV, bool GIVEN, int HAT>
 __global__ __launch_bounds__(kBlock) void bicgstab_p_kernel(BicgstabPass a)
 {
+    constexpr bool DINV = HAT == HAT_DINV;             // as in pass S
     __shared__ double s_red[4], s_red2[4];
     if (a.bs->fDone != 0) return;                      // the flag as pass S found it: this pass raises the live one itself
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
@@ -242,10 +262,12 @@ __global__ __launch_bounds__(kBlock) void bicgstab_p_kernel(BicgstabPass a)
     }
 }
 
-// The start behind r = b - A x: rhat = r, p = r, phat = dinv * r and the partial sums of r.r.  Once per call, so the plain element-wise form.
-template <bool DINV>
+// The start behind r = b - A x: rhat = r, p = r, phat = dinv * r (HAT_STORED: phat is left to the cycle) and the partial sums of r.r.  Once
+// per call, so the plain element-wise form.
+template <int HAT>
 __global__ __launch_bounds__(kBlock) void bicgstab_start_kernel(const double* r, double* rhat, double* p, double* phat, const double* dinv, long long n, double* partials)
 {
+    constexpr bool DINV = HAT == HAT_DINV;
     __shared__ double s_red[4];
     double acc = 0.0;
     grid_stride<false>(n, [&](long long) {}, [&](long long i) {
@@ -288,8 +310,9 @@ int bicgstab_enqueue_start(const BicgstabRun& R)
     double* partials = bicgstab_rr_partials(R.ws);
     const int grid = grid_for(R.n, 2);
     const long long n = R.n < 0 ? 0 : R.n;
-    if (R.dinv) hipLaunchKernelGGL((bicgstab_start_kernel<true>), dim3(grid), dim3(kBlock), 0, s, (const double*)R.r, R.rhat, R.p, R.phat, R.dinv, n, partials);
-    else hipLaunchKernelGGL((bicgstab_start_kernel<false>), dim3(grid), dim3(kBlock), 0, s, (const double*)R.r, R.rhat, R.p, R.phat, R.dinv, n, partials);
+    bicgstab_with_hat(R, [&](auto HAT) {
+        hipLaunchKernelGGL((bicgstab_start_kernel<HAT.value>), dim3(grid), dim3(kBlock), 0, s, (const double*)R.r, R.rhat, R.p, R.phat, R.dinv, n, partials);
+    });
     if (dot_reference_order()) { launch_dot_serial(s, R.r, R.r, n, partials, nullptr); return 1; }   // the sum in the reference's order replaces the partial sums
     return grid;
 }
@@ -307,11 +330,11 @@ static BicgstabPass bicgstab_pass_args(const BicgstabRun& R, const FinalizeArgs&
     return a;
 }
 
-// go(V2, NTV, GIVEN, DINV) for the form this call takes
+// go(V2, NTV, GIVEN, HAT) for the form this call takes
 template <typename Go> static void bicgstab_with_form(const BicgstabRun& R, bool v2, Go go)
 {
     with_v2_nt(v2, vec_nt(R.n), [&](auto V2, auto NTV) {
-        with_flags([&](auto GIVEN, auto DINV) { go(V2, NTV, GIVEN, DINV); }, R.given, R.dinv != nullptr);
+        with_flags([&](auto GIVEN) { bicgstab_with_hat(R, [&](auto HAT) { go(V2, NTV, GIVEN, HAT); }); }, R.given);
     });
 }
 
@@ -322,8 +345,8 @@ void bicgstab_enqueue_s(const BicgstabRun& R, const FinalizeArgs& f, int k, int 
     const bool v2 = al16(a.r) && al16(a.v) && al16(a.s) && al16(a.shat) && al16(a.dinv);
     // the grid of update_xp_final_kernel; a rank without rows: one workgroup, for the scalar step
     const int grid = grid_for(R.n, v2 ? 2 : 1);
-    bicgstab_with_form(R, v2, [&](auto V2, auto NTV, auto GIVEN, auto DINV) {
-        hipLaunchKernelGGL((bicgstab_s_kernel<V2.value, NTV.value, GIVEN.value, DINV.value>), dim3(grid), dim3(kBlock), 0, R.ws->stream, a);
+    bicgstab_with_form(R, v2, [&](auto V2, auto NTV, auto GIVEN, auto HAT) {
+        hipLaunchKernelGGL((bicgstab_s_kernel<V2.value, NTV.value, GIVEN.value, HAT.value>), dim3(grid), dim3(kBlock), 0, R.ws->stream, a);
     });
 }
 
@@ -351,8 +374,8 @@ int bicgstab_enqueue_x(const BicgstabRun& R, const FinalizeArgs& f, int k, int n
     a.outA = bicgstab_rr_partials(ws); a.outB = bicgstab_rho_partials(ws);
     const bool v2 = al16(a.x) && al16(a.r) && al16(a.phat) && al16(a.shat) && al16(a.s) && al16(a.t) && al16(a.rhat);
     const int grid = grid_for(R.n, v2 ? 2 : 1);
-    bicgstab_with_form(R, v2, [&](auto V2, auto NTV, auto GIVEN, auto DINV) {
-        hipLaunchKernelGGL((bicgstab_x_kernel<V2.value, NTV.value, GIVEN.value, DINV.value>), dim3(grid), dim3(kBlock), 0, s, a);
+    bicgstab_with_form(R, v2, [&](auto V2, auto NTV, auto GIVEN, auto HAT) {
+        hipLaunchKernelGGL((bicgstab_x_kernel<V2.value, NTV.value, GIVEN.value, HAT.value>), dim3(grid), dim3(kBlock), 0, s, a);
     });
     if (dot_reference_order()) {                       // r.r and rhat.r in the reference's order
         const int* done = &ws->scalars->done;
@@ -371,8 +394,8 @@ void bicgstab_enqueue_p(const BicgstabRun& R, const FinalizeArgs& f, int k, int 
     a.inA = bicgstab_rr_partials(ws); a.nA = nRr; a.inB = bicgstab_rho_partials(ws); a.nB = nRr;
     const bool v2 = al16(a.r) && al16(a.p) && al16(a.v) && al16(a.phat) && al16(a.dinv);
     const int grid = grid_for(R.n, v2 ? 2 : 1);
-    bicgstab_with_form(R, v2, [&](auto V2, auto NTV, auto GIVEN, auto DINV) {
-        hipLaunchKernelGGL((bicgstab_p_kernel<V2.value, NTV.value, GIVEN.value, DINV.value>), dim3(grid), dim3(kBlock), 0, ws->stream, a);
+    bicgstab_with_form(R, v2, [&](auto V2, auto NTV, auto GIVEN, auto HAT) {
+        hipLaunchKernelGGL((bicgstab_p_kernel<V2.value, NTV.value, GIVEN.value, HAT.value>), dim3(grid), dim3(kBlock), 0, ws->stream, a);
     });
 }
 

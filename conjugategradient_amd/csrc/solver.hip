@@ -1420,9 +1420,14 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
     BicgstabRun P{};
     P.ws = ws; P.x = R.x; P.r = R.r; P.v = vVec; P.t = tVec; P.rhat = rhatVec; P.dinv = R.dinv; P.n = n; P.given = R.multi;
     P.phat = bufP + R.offset; P.shat = bufS + R.offset;
-    P.p = R.dinv ? work : P.phat; P.s = R.dinv ? R.r : P.shat;
+    const bool hatted = R.dinv || R.mg;                                                  // phat and shat are vectors of their own
+    P.p = hatted ? work : P.phat; P.s = hatted ? R.r : P.shat; P.stored = R.mg != nullptr;
+    // The V-cycle form: zhat = M^-1 z into the buffer the next product gathers from, gated on the live stop flag as in cg_solve_pminres.  A
+    // cycle writes nothing but its output and the hierarchy's own iterates, so one enqueued behind the stop is skipped whole, and one behind a
+    // breakdown of pass S writes shat only, which nothing reads afterwards.
+    auto cycle = [&](const double* z, double* zhat) { return !R.mg || mg_apply(R.mg, z, zhat, done); };
 
-    // start: r = b - A x through bufP ; rhat = r ; p = r ; phat = dinv r ; rho = rr0 = r.r
+    // start: r = b - A x through bufP ; rhat = r ; p = r ; phat = dinv r (the V-cycle form: body 0's first cycle) ; rho = rr0 = r.r
     bool ok = cg_enqueue_residual(R, bufP, R.r);
     if (ok) {
         const int nRr = bicgstab_enqueue_start(P);
@@ -1435,10 +1440,12 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
     ok = ok && cg_drive(R, who, [&] {
         int nSigma = 0, nTheta = 0;
         R.p = bufP; R.Ap = P.v;
+        if (!cycle(P.p, P.phat)) return false;                                           // the V-cycle form: phat = M^-1 p
         if (!cg_enqueue_product(R, bufP, &nSigma, P.rhat)) return false;                 // v = A phat ; sigma = rhat.v
         if (R.multi && !cg_share_sums(R, ws->partials, nSigma, nullptr, 0, &bs->red[0], done)) return false;
         bicgstab_enqueue_s(P, f, k, nSigma);                                             // alpha ; s ; shat
         R.p = bufS; R.Ap = P.t;
+        if (!cycle(P.s, P.shat)) return false;                                           // the V-cycle form: shat = M^-1 s
         if (!cg_enqueue_product(R, bufS, &nTheta, P.s)) return false;                    // t = A shat ; theta = s.t
         const int nTau = bicgstab_enqueue_tau(P);                                        // tau = t.t
         if (R.multi && !cg_share_sums(R, ws->partials, nTheta, bicgstab_tau_partials(ws), nTau, &bs->red[1], done)) return false;
@@ -2881,8 +2888,19 @@ int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
-// BiCGStab (cg_solve_bicgstab above; refusals: cg_variant_call).  With `jacobi` dinvVector is a handle the export requires.
-static int bicgstab_entry(const char* who, bool jacobi, MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
+// The hierarchy of a V-cycle form (SolveMinresMg, SolveBicgstabMg): one rank, `count` rows on level 0 -- whatever matrix it was built from.
+// True: refused.
+static bool cg_hierarchy_refused(const char* who, const MgcgMg* mg, int count)
+{
+    if (mg->nranks != 1 || mg->multi) set_error("%s: the hierarchy was built for %d rank(s)%s; the V-cycle form runs on one rank", who, mg->nranks, mg->multi ? " on the several-ranks path" : "");
+    else if (mg->levels < 1 || mg->lv[0].n != count) set_error("%s: the hierarchy has %lld rows on level 0, the matrix has %d", who, mg->levels < 1 ? 0LL : (long long)mg->lv[0].n, count);
+    else return false;
+    return true;
+}
+
+// BiCGStab (cg_solve_bicgstab above; refusals: cg_variant_call).  With `jacobi` dinvVector is a handle the export requires, with `vcycle`
+// the hierarchy (one rank: the export passes no communicator and the whole matrix).
+static int bicgstab_entry(const char* who, bool jacobi, bool vcycle, MgcgMg* mg, MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
                           Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                           Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
                           Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector, Vector* dinvVector,
@@ -2896,10 +2914,12 @@ static int bicgstab_entry(const char* who, bool jacobi, MgcgComm* comm, MgcgBlas
         return !cg_rule_refused(who, rule, "the loop carries no max|r|") && !cg_vector_short(who, "v", vVector, countForDevice, "local rows") &&
                !cg_vector_short(who, "t", tVector, countForDevice, "local rows") && !cg_vector_short(who, "rhat", rhatVector, countForDevice, "local rows") &&
                !cg_vector_short(who, "s", sVector, count, "columns (p and s are full length)") &&
-               !(jacobi && cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows"));
+               !(jacobi && cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows")) && !(vcycle && cg_hierarchy_refused(who, mg, count));
     };
-    return cg_variant_call(c, cublas && cusparse && vVector && sVector && tVector && rhatVector && (!jacobi || dinvVector), checks, [&](CgRun& R) {
+    return cg_variant_call(c, cublas && cusparse && vVector && sVector && tVector && rhatVector && (!jacobi || dinvVector) && (!vcycle || mg), checks, [&](CgRun& R) {
+        if (vcycle && R.multi) { set_error("%s: the V-cycle form runs on one rank", who); return (int)MGCG_ERROR; }
         if (jacobi) R.dinv = cg_dinv_address(R, dinvVector);
+        if (vcycle) R.mg = mg;
         cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
         cg_note_written({ R.x, R.Ap, R.r, vVector->data, tVector->data, rhatVector->data }, countForDevice);
         cg_note_written({ R.p, sVector->data }, count);
@@ -2916,7 +2936,7 @@ int SolveBicgstabParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse
                           int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    return bicgstab_entry("SolveBicgstab", false, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+    return bicgstab_entry("SolveBicgstab", false, false, nullptr, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
                           xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, nullptr,
                           count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ,
                           allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
@@ -2944,7 +2964,7 @@ int SolveBicgstabJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cu
                                 int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    return bicgstab_entry("SolveBicgstabJacobi", true, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+    return bicgstab_entry("SolveBicgstabJacobi", true, false, nullptr, comm, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
                           xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, dinvVector,
                           count, countForDevice, offsetForDevice, elementsCountForDevice, minJ, maxJ,
                           allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
@@ -2961,6 +2981,22 @@ int SolveBicgstabJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* ma
     return SolveBicgstabJacobiParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
                                        xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, dinvVector, count, count, 0, elementsCount, 0, count - 1,
                                        allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+// The V-cycle form (one rank): the Jacobi form's seven work vectors, no z vector.  The hierarchy may come from any matrix.
+int SolveBicgstabMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                    Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                    Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector,
+                    int elementsCount, int count,
+                    double allowableResidual, int minIteration, int maxIteration, int rule,
+                    int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return bicgstab_entry("SolveBicgstabMg", false, true, mg, nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+                          xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, nullptr,
+                          count, count, 0, elementsCount, 0, count - 1,
+                          allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
 // Preconditioned MINRES (cg_solve_pminres above; refusals: cg_variant_call).  dinvVector, the hierarchy and zVector are handles the exports
@@ -3022,9 +3058,7 @@ int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
     const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
     auto checks = [&] {
         if (!pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, count) || cg_vector_short(who, "z", zVector, count, "rows")) return false;
-        if (mg->nranks != 1 || mg->multi) { set_error("%s: the hierarchy was built for %d rank(s)%s; the V-cycle form runs on one rank", who, mg->nranks, mg->multi ? " on the several-ranks path" : ""); return false; }
-        if (mg->levels < 1 || mg->lv[0].n != count) { set_error("%s: the hierarchy has %lld rows on level 0, the matrix has %d", who, mg->levels < 1 ? 0LL : (long long)mg->lv[0].n, count); return false; }
-        return true;
+        return !cg_hierarchy_refused(who, mg, count);
     };
     // one rank always: cg_variant_call refuses in front of the device, and cg_call's second look at checks() finds nothing new
     return cg_variant_call(c, cublas && cusparse && mg && r1Vector && w1Vector && w2Vector && zVector, checks, [&](CgRun& R) {

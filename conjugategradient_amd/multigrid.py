@@ -12,8 +12,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import MgcgError, check, lib
+from .bicgstab import _WORK as _BICGSTAB_WORK          # vectorV, vectorS, vectorT, vectorRhat
 from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
-
 
 class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
     """ConjugateGradientSingleGpu plus a V-cycle preconditioner built from ``grid = (nx, ny, nz)``."""
@@ -39,7 +39,7 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
             self.mg = None
         if getattr(self, "vectorZ", None) is not None:
             self.vectorZ.Dispose()
-        for name in ("vectorW1", "vectorW2", "vectorR1"):         # SolveMinres's work space, if it ran
+        for name in ("vectorW1", "vectorW2", "vectorR1") + _BICGSTAB_WORK:   # SolveMinres's and SolveBicgstab's work space, if they ran
             if getattr(self, name, None) is not None:
                 getattr(self, name).Dispose()
                 setattr(self, name, None)
@@ -153,3 +153,41 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         if st != _lib.OK:
             check("SolveMinresMg")
             raise MgcgError(f"SolveMinresMg failed with status {st}")
+
+    def SolveBicgstab(self, trace: bool = False, hierarchy=None):
+        """Solve A x = b, A any CSR matrix, with BiCGStab right-preconditioned by a hierarchy's V-cycle (SolveBicgstabMg).  The
+        hierarchy is ``self.mg``, built from the matrix itself -- right-preconditioned BiCGStab asks nothing of M but a fixed linear map --
+        or, with ``hierarchy``, the ``mg`` of another multigrid object with as many rows, which stays that object's (the supported way to
+        precondition with the hierarchy of another matrix, ``problems.symmetric_part(system)`` for instance).  ``vectorV``, ``vectorS``,
+        ``vectorT`` and ``vectorRhat`` are allocated at the first call.  ``Iteration``, ``Residual`` and ``trace`` show the recurrence's
+        2-norm residual; ``TrueResidual`` is || b - A x ||_2 of the closing product and ``ReadResidual()`` returns that vector."""
+        for name in _BICGSTAB_WORK:
+            if getattr(self, name, None) is None:
+                setattr(self, name, VectorDouble(self.Count))
+        mg = self.mg if hierarchy is None else hierarchy.mg
+        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
+        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        rule = _lib.RULE_CSHARP if self.rule is None else self.rule
+        st = lib().SolveBicgstabMg(self.cublas, self.cusparse, self.matDescr, mg,
+                                   self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                   self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                   self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr,
+                                   nonzeroCount, self.Count, self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
+                                   C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"V-cycle-preconditioned BiCGStab did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveBicgstabMg")
+            raise MgcgError(f"SolveBicgstabMg failed with status {st}")
+
+    def ReadResidual(self) -> np.ndarray:
+        """The true residual that the closing product of the last SolveMinres() or SolveBicgstab() left in its work vector."""
+        r = np.empty(self.Count)
+        self.vectorR.CopyTo(r, self.Count, 0)
+        return r

@@ -251,6 +251,20 @@ def convection_diffusion(nx: int, ny: int, nz: int = 1, c=(0.0, 0.0, 0.0), upwin
                         f"convdiff{nx}x{ny}x{nz}{'u' if upwind else 'c'}", grid=(nx, ny, nz))
 
 
+def symmetric_part(system: LinearSystem) -> LinearSystem:
+    """(A + A^T) / 2 of a system's matrix, with the same b, x and grid: what a V-cycle hierarchy is built from when the one of the
+    nonsymmetric matrix itself is not wanted.  The pattern is the union of A's and A^T's without the sums that come to zero, columns
+    ascending; every entry is one addition and one halving, so the central convection_diffusion() stencil gives poisson()'s matrix
+    exactly and the diagonal is kept."""
+    A = system.to_scipy().copy()                       # (to_scipy shares the system's arrays)
+    A.sum_duplicates()
+    H = ((A + A.T.tocsr()) * 0.5).tocsr()
+    H.sort_indices()
+    return LinearSystem(np.ascontiguousarray(H.data, dtype=np.float64), np.ascontiguousarray(H.indices, dtype=np.int32),
+                        np.ascontiguousarray(H.indptr, dtype=np.int32), np.array(system.x, dtype=np.float64),
+                        np.array(system.b, dtype=np.float64), f"{system.name}-sym", grid=system.grid)
+
+
 def random_nonsymmetric(n: int, per_row: int = 9, seed: int = 12345) -> LinearSystem:
     """A random matrix with A != A^T and an uneven diagonal: per row per_row - 1 off-diagonal draws with columns uniform over the other
     rows and values N(0,1), duplicates summed; diagonal = sum |off-diagonals| + U(0.5, 50) (strictly row dominant, hence nonsingular).

@@ -776,8 +776,8 @@ int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
  *   rhatVector      the shadow residual, fixed after the start (count entries)
  * Refused with MGCG_ERROR, a message and nothing enqueued: MGCG_RULE_HANDMADECL, an unknown rule, a null handle, a vector that is too small.
  * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer), the placement
- * draw and the overlap schedule do not apply.  Out of scope: the V-cycle as preconditioner (SolveBicgstabMg), BiCGStab(l), GMRES, residual
- * replacement, the block and mixed combinations, the C++ twin under host/. */
+ * draw and the overlap schedule do not apply.  The V-cycle as preconditioner: SolveBicgstabMg below.  Out of scope: BiCGStab(l), GMRES,
+ * residual replacement, the block and mixed combinations, the C++ twin under host/. */
 int SolveBicgstab(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                   Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                   Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
@@ -813,6 +813,49 @@ int SolveBicgstabJacobiParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cu
                                 int count, int countForDevice, int offsetForDevice, int elementsCountForDevice, int minJ, int maxJ,
                                 double allowableResidual, int minIteration, int maxIteration, int rule,
                                 int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
+/* The V-cycle form (one rank): SolveBicgstab's method, line for line, right-preconditioned with the V-cycle of any one-rank hierarchy --
+ * MgSetup, MgSetupAggregation, MgSetupAggregates -- whose level 0 has `count` rows: phat = M^-1 p and shat = M^-1 s are what MgApply enqueues
+ * (p -> pVector, s -> sVector) instead of a product per element.  Right-preconditioned BiCGStab asks nothing of M but that it is one fixed
+ * linear map: M need be neither symmetric nor positive definite, so the hierarchy may be built from the nonsymmetric matrix itself (the
+ * set-up sums whole rows and the cycle multiplies by the level matrices as stored: the box maps of MgSetup and of MgSetupAggregates build
+ * the level matrices of the numpy yardstick from A != A^T, bit for bit, and so does MgSetupAggregation; its matching pairs rows on MUTUAL
+ * picks, so where every row's heaviest coupling points the same way -- an upwinded stencil, central differences at a cell Peclet number
+ * near 1 -- nobody is picked back, no level is built and the cycle is nuCoarse Jacobi sweeps on the matrix: still a fixed linear map, and
+ * the caller's own aggregates are the way to a real hierarchy there), or from any other matrix with `count` rows, (A + A^T)/2 for instance.
+ * Only the row count is checked.
+ * Start, breakdown rules, stop rules, trace, the closing product and *trueResidual are SolveBicgstab's, and so is the rounding contract;
+ * under dot_order = 1 every sum is serial, and the cycle is MgApply's fixed sequence of operations in either mode
+ * (tests/test_bicgstab_mg_host.py restates the loop in numpy).
+ * A body is, in this order: the cycle p -> phat ;  v = A phat with sigma = rhat.v ;  pass S (alpha, s over r; no shat written) ;  the cycle
+ * s -> shat ;  t = A shat with theta = s.t, the sum taken with the UNHATTED s ;  tau = t.t ;  pass X (the general form: reads x, phat, shat,
+ * s, t, rhat) ;  pass P (the stop decision, beta, p; no phat written).  The first cycle of body 0 follows the start, which leaves phat alone.
+ * The passes move 24 + 8 + 64 + 32 = 128 bytes per row, beside 120 and 160.
+ * The vectors are the Jacobi form's seven, in the same roles; there is no z vector:
+ *   ApVector        p, the unhatted direction (count entries), the input of the first cycle
+ *   pVector         phat, the first cycle's output and the buffer the first product gathers from
+ *   rVector         r ;  s is written over it between pass S and pass X, and is the input of the second cycle.  On return: b - A x
+ *   sVector         shat, the second cycle's output and the buffer the second product gathers from
+ *   vVector, tVector, rhatVector   as in SolveBicgstabJacobi
+ * WHY A BODY ENQUEUED BEHIND THE STOP CHANGES NOTHING.  The host enqueues bodies ahead of the device's stop.  Both cycles and both products
+ * take the live stop flag as their gate; pass S copies the flag, as it found it, for pass X and pass P.  (1) Pass P raised the flag: every
+ * kernel of the next body's first cycle returns at the gate, the product is skipped, pass S records the flag and returns, the second cycle,
+ * the second product and the tau pass return at the gate, pass X and pass P return at the recorded flag -- no vector, no scalar and no trace
+ * entry is written.  (2) Pass S met a breakdown of sigma (flag still down): it wrote no vector, so rVector still holds r; the second cycle runs
+ * on that r and writes sVector and the hierarchy's own iterates only, the product and the tau pass write tVector and partial sums only, pass X
+ * returns at pass S's note, and pass P publishes the breakdown and raises the flag.  x and r are this body's predecessors', as in
+ * SolveBicgstab; sVector and tVector are read by nothing afterwards (the closing product goes through pVector into rVector).  (3) A
+ * breakdown of omega in pass X: pass X wrote nothing, pass P publishes it.  A cycle never writes x, r, v, t, rhat or a scalar of the loop.
+ * Refused with MGCG_ERROR, a message and nothing enqueued: everything SolveBicgstab refuses; a null mg; a hierarchy of several ranks; a
+ * hierarchy whose level 0 does not have `count` rows ("... rows on level 0, the matrix has ...", as SolveMinresMg).
+ * Out of scope: several ranks (SolveBicgstabMgParallel), changes inside the cycle's kernels, the C++ twin under host/. */
+int SolveBicgstabMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                    Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector,
+                    Vector* vVector, Vector* sVector, Vector* tVector, Vector* rhatVector,
+                    int elementsCount, int count,
+                    double allowableResidual, int minIteration, int maxIteration, int rule,
+                    int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
