@@ -11,7 +11,8 @@
              plain or preconditioned by the diagonal (the V-cycle form is a method of the ``multigrid`` / ``amg`` classes)
 ``bicgstab`` BiCGStab for NONSYMMETRIC systems A x = b (convection-diffusion, upwinded stencils, any CSR matrix), plain or
              right-preconditioned by the diagonal (the V-cycle form, SolveBicgstabMg, is the ``SolveBicgstab`` method of the
-             ``multigrid`` / ``amg`` classes, with the hierarchy of the matrix itself or of another one)
+             ``multigrid`` / ``amg`` classes, with the hierarchy of the matrix itself or of another one); and BiCGStab(l), l = 1 .. 4
+             (``BiConjugateGradientStabLGpu``, SolveBicgstabL), for the convection-dominated systems on which BiCGStab breaks down
 ``chebyshev`` Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, m products and two global sums per iteration
 ``shifted``   multi-shift CG: (A + s_j I) x_j = b for up to 8 shifts from one CG recurrence on A
 ``blockkrylov`` shared-subspace block CG: up to 8 right-hand sides in one block Krylov space (fewer iterations than ``block``)

@@ -1,4 +1,5 @@
-"""BiCGStab (``SolveBicgstab``, ``SolveBicgstabJacobi``): nonsymmetric systems A x = b.
+"""BiCGStab and BiCGStab(l) (``SolveBicgstab``, ``SolveBicgstabJacobi``, ``SolveBicgstabL``, ``SolveBicgstabLJacobi``): nonsymmetric systems
+A x = b.
 
 Every other loop of this package takes a symmetric matrix: on a convection-diffusion stencil, an upwinded operator or any CSR matrix with
 A != A^T the CG loops break down or return a wrong x, and MINRES is not defined.  BiCGStab (van der Vorst) needs only products with A --
@@ -11,8 +12,15 @@ one closing product, and ``ReadResidual()`` returns that vector.  ``BiConjugateG
 Several ranks: ``ConjugateGradientRankGpu.SolveBicgstab`` / ``.SolveBicgstabJacobi``.  The V-cycle as right preconditioner
 (``SolveBicgstabMg``) is the method ``SolveBicgstab(trace=False, hierarchy=None)`` of ``multigrid.ConjugateGradientMgGpu`` and
 ``amg.ConjugateGradientAmgGpu``: the hierarchy is the object's own, built from the nonsymmetric matrix itself, or with ``hierarchy`` that
-of another multigrid object -- one built from ``problems.symmetric_part(system)``, say.  The max-norm stop rule is not supported.  No
-arithmetic happens in this module.
+of another multigrid object -- one built from ``problems.symmetric_part(system)``, say.
+
+BiCGStab's residual polynomial has real roots only -- one minimal-residual step of degree 1 per body -- and where convection dominates (a
+spectrum near the imaginary axis) it stagnates or breaks down.  ``BiConjugateGradientStabLGpu(..., ell=2)`` is BiCGStab(l) (Sleijpen and
+Fokkema, ``SolveBicgstabL``): a body is ``ell`` BiCG steps and one minimal-residual step of degree ``ell``, 1 <= ell <= 4, so ``Iteration``,
+``MinIteration``, ``MaxIteration`` and the trace count bodies of ``2 * ell`` products.  Same surface as ``BiConjugateGradientStabGpu``;
+``BiConjugateGradientStabLJacobiGpu`` is the same with M = diag(A).  One rank; no V-cycle form yet.
+
+The max-norm stop rule is not supported by any of them.  No arithmetic happens in this module.
 """
 from __future__ import annotations
 
@@ -60,6 +68,10 @@ class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
     def _more_vectors(self):
         return ()
 
+    def _work_arguments(self):
+        """What the export takes between the r vector and the sizes."""
+        return (self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr, *self._more_vectors())
+
     def Solve(self, trace: bool = False, traceCapacity: int | None = None):
         """trace: keep the residual trace in ``self.trace``; traceCapacity: its length when the default (room for every iteration) is not wanted."""
         if not self._ready:
@@ -73,7 +85,7 @@ class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
         st = getattr(L, self._export)(self.cublas, self.cusparse, self.matDescr,
                                       self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
                                       self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                      self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr, *self._more_vectors(),
+                                      *self._work_arguments(),
                                       nonzeroCount, self.Count,
                                       self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
                                       C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
@@ -104,6 +116,69 @@ class BiConjugateGradientStabJacobiGpu(BiConjugateGradientStabGpu):
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None):
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
+        self.vectorDinv = VectorDouble(count)
+
+    def Initialize(self):
+        super().Initialize()
+        self._ready = False
+        jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
+                     int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
+        self._ready = True
+
+    def _more_vectors(self):
+        return (self.vectorDinv.Ptr,)
+
+
+class BiConjugateGradientStabLGpu(BiConjugateGradientStabGpu):
+    """BiConjugateGradientStabGpu on the BiCGStab(l) loop (SolveBicgstabL): same members, ``TrueResidual``, ``ReadResidual()``, trace and
+    exceptions; ``ell`` (1 .. 4) is the degree of a body's minimal-residual step, and iterations count bodies of ``2 * ell`` products.  One
+    work vector of ``2 * ell`` slices (one more with the diagonal) replaces v, s, t and rhat: it is sized for the object's ``ell`` and
+    allocated again, larger, by the first ``Solve()`` after ``ell`` was raised.  The library checks ``ell`` and the vector's size; an
+    ``ell`` it refuses leaves the object usable with another."""
+
+    _export = "SolveBicgstabL"
+    _what = "BiCGStab(l)"
+    _slices_more = 0
+
+    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, ell=2):
+        if rule == _lib.RULE_HANDMADECL:
+            raise ValueError(f"{type(self).__name__}: the max-norm rule (RULE_HANDMADECL) is not supported")
+        ConjugateGradientSingleGpu.__init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
+        self.TrueResidual = float("nan")
+        self.ell = int(ell)
+        self.vectorWork, self._work_size = None, 0
+        self._ensure_work()
+        self._ready = False
+
+    def _ensure_work(self):
+        """Room for this ``ell`` (one the library refuses: as for the nearest it takes, so that the call reaches its refusal)."""
+        need = (2 * min(max(int(self.ell), 1), 4) + self._slices_more) * (self.Count + (self.Count & 1))
+        if need > self._work_size:
+            if self.vectorWork is not None:
+                self.vectorWork.Dispose()
+            self.vectorWork, self._work_size = VectorDouble(need), need
+
+    def Dispose(self):
+        if getattr(self, "vectorWork", None) is not None:
+            self.vectorWork.Dispose()
+            self.vectorWork, self._work_size = None, 0
+        super().Dispose()
+
+    def _work_arguments(self):
+        self._ensure_work()
+        return (self.vectorWork.Ptr, *self._more_vectors(), int(self.ell))
+
+
+class BiConjugateGradientStabLJacobiGpu(BiConjugateGradientStabLGpu):
+    """BiConjugateGradientStabLGpu with M = diag(A) as right preconditioner (SolveBicgstabLJacobi); ``Initialize()`` also extracts and
+    checks the diagonal, as ``BiConjugateGradientStabJacobiGpu`` does."""
+
+    _export = "SolveBicgstabLJacobi"
+    _what = "Jacobi-preconditioned BiCGStab(l)"
+    _slices_more = 1
+
+    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, ell=2):
+        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule, ell=ell)
         self.vectorDinv = VectorDouble(count)
 
     def Initialize(self):

@@ -115,7 +115,7 @@ void preload_ops(); void preload_solver(); void preload_comm(); void preload_ker
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
 void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres(); void preload_kernels_pminres();
-void preload_kernels_bicgstab();
+void preload_kernels_bicgstab(); void preload_kernels_bicgstabl();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -214,6 +214,26 @@ struct BicgstabScalars {
     int fDone, brokeS, brokeX, pad;
 };
 
+// What the BiCGStab(l) loop (SolveBicgstabL, SolveBicgstabLJacobi; kernels_bicgstabl.hip) keeps on the device.  rho: step j of body k reads
+// rho[k & 1][j] in every workgroup of pass R_j, pass U_j (j > 0) reads rho[k & 1][j - 1] while its first workgroup writes rho[k & 1][j], and pass P
+// reads rho[k & 1][l - 1] while its first workgroup writes rho[(k + 1) & 1][0]: no workgroup reads an entry that a workgroup of the same launch
+// writes.  alpha is written by pass R_j and omega by the combine pass, each by its first workgroup, for the launches behind it.  fDone:
+// CgScalars::done as pass R_0 found it; every later pass of the body looks here, since pass P raises `done` itself.  broke[j]: the breakdown of
+// sigma or alpha in pass R_j, cleared by pass R_0 and read by later launches only (pass R_j looks at broke[0 .. j-1]).  early[j]: pass U_j found
+// that r_0 as step j - 1 left it meets the stop test -- the body ends there, with rrEarly as its r_0.r_0; the same discipline.  gamma, pivots: what the combine pass solved, for whoever reads the block back.
+// red: the closing r.r.
+constexpr int kBicgstablMaxL = 4;
+constexpr int kBicgstablGram = kBicgstablMaxL * (kBicgstablMaxL + 3) / 2;   // the entries Z_ab, a = 1 .. l, b = 0 .. a
+struct BicgstablScalars {
+    double red;
+    double alpha, omega;
+    double rho[2][kBicgstablMaxL];
+    double gamma[kBicgstablMaxL];
+    double rrEarly;
+    int fDone, pivots;
+    int broke[kBicgstablMaxL], early[kBicgstablMaxL];
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
@@ -247,6 +267,10 @@ struct Workspace {
     SreduceScalars* sreduceScalars = nullptr;    // single-reduction CG (kernels_sreduce.hip), allocated at its first call and kept; its direction p takes ring[1]
     MinresScalars* minresScalars = nullptr;      // MINRES (kernels_minres.hip), allocated at its first call and kept
     BicgstabScalars* bicgstabScalars = nullptr;  // BiCGStab (kernels_bicgstab.hip), allocated at its first call and kept
+    // BiCGStab(l) (kernels_bicgstabl.hip), allocated at its first call and kept: the loop's scalars, and kBicgstablGram + 2 regions of kMaxGrid
+    // partial sums -- one per entry Z_ab of the Gram pass, then r.r and rtilde.r of the combine pass
+    BicgstablScalars* bicgstablScalars = nullptr;
+    double* bicgstablPartials = nullptr;
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -259,6 +283,7 @@ struct Workspace {
     bool ensure_sreduce();                       // sreduceScalars (kernels_sreduce.hip)
     bool ensure_minres();                        // minresScalars (kernels_minres.hip)
     bool ensure_bicgstab();                      // bicgstabScalars (kernels_bicgstab.hip)
+    bool ensure_bicgstabl();                     // bicgstablScalars / bicgstablPartials (kernels_bicgstabl.hip)
 };
 
 } // namespace mgcg
@@ -721,6 +746,32 @@ int bicgstab_enqueue_tau(const BicgstabRun& R);
 int bicgstab_enqueue_x(const BicgstabRun& R, const FinalizeArgs& f, int k, int nTheta, int nTau);
 // pass P of body k: the stop decision, beta, p, phat
 void bicgstab_enqueue_p(const BicgstabRun& R, const FinalizeArgs& f, int k, int nRr);
+
+// BiCGStab(l) (SolveBicgstabL, SolveBicgstabLJacobi; kernels_bicgstabl.hip has the loop, include/MgcgGpu.h the method), one rank.  r[0 .. l],
+// u[0 .. l], rt (the shadow residual) and x: n entries each, 16-byte aligned or not -- the passes take their element-wise form when one is not.
+// With dinv `gather` is the one buffer that holds hat(u_j) or hat(r_j) for the next product; without it the products gather from u_j and r_j
+// themselves and gather is null.
+struct BicgstablRun {
+    Workspace* ws;
+    int ell;
+    double *x, *r[kBicgstablMaxL + 1], *u[kBicgstablMaxL + 1], *rt, *gather; const double* dinv;
+    long long n;
+};
+// the scalars in front of body 0 from the start's nPartials partial sums of r.r in bicgstab_rr_partials(ws) (the start itself is
+// bicgstab_enqueue_start: rt = r_0, u_0 = r_0, gather = dinv r_0); r.r not finite or zero stops the loop here with MGCG_NONFINITE at iteration 0
+void bicgstabl_enqueue_init(Workspace* ws, const FinalizeArgs& f, int nPartials);
+// pass U_j of body k, j = 1 .. l - 1 (nRho: the partial sums of rt.r_j in ws->partials, left by the product that made r_j; nRr: those of r_0.r_0
+// that pass R_{j-1} left): the stop test on r_0 in front of the step, beta, u_0 .. u_j, gather = hat(u_j)
+void bicgstabl_enqueue_u(const BicgstablRun& R, const FinalizeArgs& f, int k, int j, int nRho, int nRr);
+// pass R_j of body k, j = 0 .. l - 1 (nSigma: the partial sums of rt.u_{j+1} in ws->partials): alpha, the breakdown test, r_0 .. r_j, x, gather = hat(r_j)
+// and the partial sums of the new r_0.r_0; returns their number (1 under dot_order = 1)
+int bicgstabl_enqueue_r(const BicgstablRun& R, const FinalizeArgs& f, int k, int j, int nSigma);
+// the Gram pass: the partial sums of Z_ab = r_a.r_b; returns their number per entry (1 under dot_order = 1)
+int bicgstabl_enqueue_gram(const BicgstablRun& R);
+// the combine pass (nGram: partial sums per entry of Z): gamma, u_0, x, r_0 and the partial sums of r_0.r_0 and rt.r_0; returns their number (1 under dot_order = 1)
+int bicgstabl_enqueue_combine(const BicgstablRun& R, const FinalizeArgs& f, int k, int nGram);
+// pass P of body k: the stop decision, beta, u_0, gather = hat(u_0)
+void bicgstabl_enqueue_p(const BicgstablRun& R, const FinalizeArgs& f, int k, int nRr);
 
 // Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).
 // The start: d = it * (dinv r), z = d, the partial sums of r.r and -- withRz, degree 1 -- of r.z; returns their number (1 under dot_order = 1).

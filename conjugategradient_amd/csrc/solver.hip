@@ -1466,6 +1466,76 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
                          "the first residual is zero or not finite, or the recurrence broke down (rhat.v, omega or rhat.r zero, or a value that is not finite)");
 }
 
+// ---------------------------------------------------------------- BiCGStab(l) (SolveBicgstabL, SolveBicgstabLJacobi)
+// Sleijpen and Fokkema's BiCGStab(l) for A x = b, A any CSR matrix, l = 1 .. 4, right-preconditioned with M = I or M = diag(A) (R.dinv), one
+// rank (include/MgcgGpu.h has the method, kernels_bicgstabl.hip the passes).  The host's side is cg_drive: a body is 2 l products and 2 l + 2
+// passes (4 l + 2 launches); a body that the device ends in front of a step (r_0 converged) is enqueued whole, its later launches return.  Every product is the plain loop's (cg_enqueue_product with w = rt, output and gather vector switched per product),
+// so compression modes and automatic column tiles apply unchanged; the deferred x update and the placement draw do not apply.  The caller's r is
+// r_0, its p u_0 and its Ap u_l; `work` holds r_1 .. r_l, u_1 .. u_{l-1}, rt and -- with a diagonal -- the one gather buffer, `stride` entries
+// apart.  Without a diagonal the products gather from u_j and r_j themselves.  One more product behind the loop leaves the true residual b - A x
+// in the caller's r.
+static long long bicgstabl_stride(long long count) { return (count + 1) & ~1LL; }            // even: every slice stays 16-byte aligned
+static int bicgstabl_slices(int ell, bool jacobi) { return 2 * ell + (jacobi ? 1 : 0); }
+static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, int* iteration, double* residual, double* trueResidual,
+                              double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    // everything the call allocates, before anything is enqueued
+    FinalizeArgs f;
+    if (!ws->ensure_bicgstabl() || !cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
+    double* const bufP = R.p; double* const bufAp = R.Ap;
+    const long long stride = bicgstabl_stride(R.count);
+    BicgstablRun P{};
+    P.ws = ws; P.ell = ell; P.x = R.x; P.dinv = R.dinv; P.n = n;
+    P.r[0] = R.r; P.u[0] = bufP; P.u[ell] = bufAp;
+    for (int j = 1; j <= ell; ++j) P.r[j] = work + (j - 1) * stride;
+    for (int j = 1; j < ell; ++j) P.u[j] = work + (ell + j - 1) * stride;
+    P.rt = work + (2 * ell - 1) * stride;
+    P.gather = R.dinv ? work + 2 * ell * stride : nullptr;
+
+    // start: r_0 = b - A x through bufP ; rt = r_0 ; u_0 = r_0 ; gather = dinv r_0 ; rho = rr0 = r_0.r_0
+    bool ok = cg_enqueue_residual(R, bufP, R.r);
+    if (ok) {
+        BicgstabRun S{};
+        S.ws = ws; S.r = R.r; S.rhat = P.rt; S.p = P.u[0]; S.phat = P.gather; S.dinv = R.dinv; S.n = n;
+        bicgstabl_enqueue_init(ws, f, bicgstab_enqueue_start(S));
+    }
+    ok = ok && MGCG_HIP(hipGetLastError());
+
+    // out = A hat(v) with the partial sums of rt.out
+    auto product = [&](double* v, double* out, int* nSums) {
+        double* from = P.gather ? P.gather : v;
+        R.p = from; R.Ap = out;
+        return cg_enqueue_product(R, from, nSums, P.rt);
+    };
+    int k = 0;
+    ok = ok && cg_drive(R, who, [&] {
+        int nSums = 0, nRrStep = 0;
+        for (int j = 0; j < ell; ++j) {
+            if (j > 0) bicgstabl_enqueue_u(P, f, k, j, nSums, nRrStep);                  // the stop test on r_0 ; beta ; u_0 .. u_j ; hat(u_j)
+            if (!product(P.u[j], P.u[j + 1], &nSums)) return false;                      // u_{j+1} = A hat(u_j) ; sigma = rt.u_{j+1}
+            nRrStep = bicgstabl_enqueue_r(P, f, k, j, nSums);                            // alpha ; r_0 .. r_j ; x ; hat(r_j) ; r_0.r_0
+            if (!product(P.r[j], P.r[j + 1], &nSums)) return false;                      // r_{j+1} = A hat(r_j) ; rt.r_{j+1}
+        }
+        const int nGram = bicgstabl_enqueue_gram(P);                                     // Z
+        const int nRr = bicgstabl_enqueue_combine(P, f, k, nGram);                       // gamma ; u_0 ; x ; r_0 ; rr, rhon
+        bicgstabl_enqueue_p(P, f, k, nRr);                                               // the stop decision ; beta ; u_0 ; hat(u_0)
+        if (k < 0x7fffffff) ++k;
+        return MGCG_HIP(hipGetLastError());
+    });
+    R.p = bufP; R.Ap = bufAp;
+    // the closing product: the true residual into the caller's r
+    double rrTrue = 0.0;
+    ok = ok && cg_enqueue_true_residual(R, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws)); }, bicgstab_rr_partials(ws), &ws->bicgstablScalars->red, &rrTrue);
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
+    return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", "",
+                         "the first residual is zero or not finite, or the recurrence broke down (rt.u_{j+1}, omega or rt.r_0 zero, or a value that is not finite)");
+}
+
 // ---------------------------------------------------------------- preconditioned MINRES (SolveMinresJacobi, SolveMinresJacobiParallel, SolveMinresMg)
 // MINRES with a symmetric positive definite preconditioner M (include/MgcgGpu.h has the method, kernels_pminres.hip the two passes): R.dinv --
 // z = dinv r formed per element inside the passes -- or R.mg with R.z, the V-cycle enqueued between them with one dot launch for r.z (one rank).
@@ -2997,6 +3067,63 @@ int SolveBicgstabMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDes
                           xVector, bVector, ApVector, pVector, rVector, vVector, sVector, tVector, rhatVector, nullptr,
                           count, count, 0, elementsCount, 0, count - 1,
                           allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+// BiCGStab(l) (cg_solve_bicgstabl above; refusals: cg_variant_call), one rank.  With `jacobi` dinvVector is a handle the export requires.
+static int bicgstabl_entry_call(const char* who, bool jacobi, MgcgBlas* cublas, MgcgSparse* cusparse,
+                                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
+                                int ell, int elementsCount, int count,
+                                double allowableResidual, int minIteration, int maxIteration, int rule,
+                                int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
+    auto checks = [&] {
+        if (ell < 1 || ell > kBicgstablMaxL) { set_error("%s: ell = %d, must be 1 .. %d", who, ell, kBicgstablMaxL); return false; }
+        if (cg_rule_refused(who, rule, "the loop carries no max|r|")) return false;
+        // a count below 1 is the shared checks' to refuse (cg_call, behind these): it asks for no room here, never for a negative amount
+        const int slices = bicgstabl_slices(ell, jacobi);
+        const long long need = slices * bicgstabl_stride(count > 0 ? count : 0);
+        if (workVector->size < need) {
+            set_error("%s: the work vector holds %lld entries, ell = %d needs %lld (%d slices of %lld: the matrix has %d rows)", who, workVector->size, ell, need, slices, bicgstabl_stride(count), count);
+            return false;
+        }
+        return !(jacobi && cg_vector_short(who, "dinv", dinvVector, count, "local rows"));
+    };
+    return cg_variant_call(c, cublas && cusparse && workVector && (!jacobi || dinvVector), checks, [&](CgRun& R) {
+        if (R.multi) { set_error("%s: the loop runs on one rank", who); return (int)MGCG_ERROR; }
+        if (jacobi) R.dinv = cg_dinv_address(R, dinvVector);
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        cg_note_written({ R.x, R.Ap, R.r, R.p }, count);
+        cg_note_written({ workVector->data }, bicgstabl_slices(ell, jacobi) * bicgstabl_stride(count));
+        return cg_solve_bicgstabl(R, who, ell, workVector->data, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    });
+}
+
+int SolveBicgstabL(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                   Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                   Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
+                   int ell, int elementsCount, int count,
+                   double allowableResidual, int minIteration, int maxIteration, int rule,
+                   int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return bicgstabl_entry_call("SolveBicgstabL", false, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+                                xVector, bVector, ApVector, pVector, rVector, workVector, nullptr, ell, elementsCount, count,
+                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+int SolveBicgstabLJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                         Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                         Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
+                         int ell, int elementsCount, int count,
+                         double allowableResidual, int minIteration, int maxIteration, int rule,
+                         int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return bicgstabl_entry_call("SolveBicgstabLJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+                                xVector, bVector, ApVector, pVector, rVector, workVector, dinvVector, ell, elementsCount, count,
+                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
 // Preconditioned MINRES (cg_solve_pminres above; refusals: cg_variant_call).  dinvVector, the hierarchy and zVector are handles the exports

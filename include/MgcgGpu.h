@@ -776,7 +776,7 @@ int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
  *   rhatVector      the shadow residual, fixed after the start (count entries)
  * Refused with MGCG_ERROR, a message and nothing enqueued: MGCG_RULE_HANDMADECL, an unknown rule, a null handle, a vector that is too small.
  * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer), the placement
- * draw and the overlap schedule do not apply.  The V-cycle as preconditioner: SolveBicgstabMg below.  Out of scope: BiCGStab(l), GMRES,
+ * draw and the overlap schedule do not apply.  The V-cycle as preconditioner: SolveBicgstabMg below; BiCGStab(l): SolveBicgstabL below.  Out of scope: GMRES,
  * residual replacement, the block and mixed combinations, the C++ twin under host/. */
 int SolveBicgstab(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                   Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
@@ -856,6 +856,82 @@ int SolveBicgstabMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDes
                     int elementsCount, int count,
                     double allowableResidual, int minIteration, int maxIteration, int rule,
                     int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
+/* ---- BiCGStab(l): nonsymmetric systems where BiCGStab's degree-1 steps break down, l = 1 .. 4, plain and Jacobi (one rank) ---- */
+/* Sleijpen and Fokkema's BiCGStab(l).  SolveBicgstab's residual polynomial gains one real root per body (a degree-1 minimal-residual step); when
+ * the spectrum of A lies near the imaginary axis (convection dominates) omega drifts to 0 and that loop stagnates or ends MGCG_NONFINITE.  Here
+ * a body is l BiCG steps and ONE minimal-residual step of degree l over r_0 .. r_l, so the polynomial may have complex roots.  Same needs as
+ * SolveBicgstab: products with A only, fixed storage, right-preconditioned with M = I (SolveBicgstabL) or M = diag(A) (SolveBicgstabLJacobi), so
+ * r_0 stays the residual of the system itself and every stop rule judges its 2-norm.  A body costs 2 l products; one rank: 4 l + 2 launches.
+ * The minimal-residual step is solved from the Gram matrix Z_ab = r_a.r_b (normal equations, Cholesky) and not by modified Gram-Schmidt: one
+ * pass over r_0 .. r_l and one reduction point in place of l (l + 1) / 2 dependent ones.
+ * Method: d_i is dinv_i when a diagonal is given and 1 otherwise; with d = 1 the multiplication is not performed and no hatted copy is stored.
+ * hat(v)_i = d_i*v_i.  The vectors are r_0 .. r_l, u_0 .. u_l, the shadow rt, and x.
+ *   start   (MGCG_RULE_SIMPLE: x := 0)
+ *           r_0 = b - A x ;  rt = r_0 ;  u_0 = r_0 ;  rho = rr0 = r_0.r_0
+ *           rr0 == 0 or not finite  ->  MGCG_NONFINITE at iteration 0, x untouched
+ *   body k  for j = 0 .. l-1:
+ *             j > 0:  rrj = r_0.r_0 ;  when the rule's stop test on (rrj, rr0) for iteration k + 1 says "converged", the body ends here:
+ *                     iteration k + 1 with rrj as its figure, MGCG_OK (a cap that is exceeded or a value that is not finite waits for the
+ *                     body's end)
+ *                     rho1 = rt.r_j (the sum the product that made r_j left) ;  beta = alpha*(rho1/rho) ;  rho = rho1
+ *                     u_i = r_i - beta*u_i,  i = 0 .. j                                                              (pass U_j)
+ *             u_{j+1} = A hat(u_j) ;  sigma = rt.u_{j+1}
+ *             sigma == 0 or not finite, or alpha = rho/sigma not finite  ->  MGCG_NONFINITE for iteration k + 1 ;  x and r_0 are what steps
+ *                     0 .. j-1 of this body made them (a consistent pair)
+ *             r_i = r_i - alpha*u_{i+1},  i = 0 .. j ;  x = x + alpha*hat(u_0)                                         (pass R_j)
+ *             r_{j+1} = A hat(r_j) ;  the sum rt.r_{j+1}
+ *           Z_ab = r_a.r_b,  a = 1 .. l,  b = 0 .. a                                                                   (Gram pass)
+ *           gamma:  G = Z[1..l, 1..l].  Cholesky factor C, row by row: for i = 1 .. l { for j = 1 .. i-1 { s = G_ij ; for q = 1 .. j-1:
+ *                     s = s - C_iq*C_jq ;  C_ij = s/C_jj }  s = G_ii ; for q = 1 .. i-1: s = s - C_iq*C_iq ;  pivot_i = s ;  C_ii = sqrt(s) }
+ *                   m = the number of leading pivots that are > 0 and finite (the factorisation ends at the first that is not)
+ *                   forwards:  for i = 1 .. m { s = Z_i0 ; for q = 1 .. i-1: s = s - C_iq*y_q ;  y_i = s/C_ii }
+ *                   backwards: for i = m .. 1 { s = y_i ; for q = i+1 .. m: s = s - C_qi*gamma_q ;  gamma_i = s/C_ii }
+ *                   gamma_{m+1 .. l} = 0 ;  omega = gamma_l
+ *           u_0 = u_0 - gamma_j*u_j ;  x = x + gamma_j*hat(r_{j-1}) ;  r_0 = r_0 - gamma_j*r_j,  each for j = 1, 2 .. l in that order, one
+ *                   term at a time (all l terms, those with gamma_j = 0 included; the r_0 of x's first term is the one the steps left) ;
+ *                   rr = r_0.r_0 ;  rhon = rt.r_0                                                                      (combine pass)
+ *           rr is judged by the rule's stop test against rr0 as the residual of iteration k + 1
+ *           not stopped and (omega == 0 or rhon == 0 or rhon not finite)  ->  MGCG_NONFINITE for iteration k + 1 (x IS this body's iterate)
+ *           beta = alpha*(rhon/((-omega)*rho)) ;  rho = rhon ;  u_0 = r_0 - beta*u_0                                   (pass P)
+ *   end     one more product: rVector = b - A x ;  *trueResidual = sqrt(r.r)      (whenever the loop ended without MGCG_ERROR)
+ * With l = 1 this is BiCGStab in other words (omega = Z_10 / Z_11 through a square root and two divisions), not bit for bit SolveBicgstab.
+ * Rounding contract, SolveBicgstab's: every product (beta*u_i, alpha*u_{i+1}, d_i*u_0_i, alpha*hat(u_0)_i, C_iq*C_jq, C_iq*y_q, C_qi*gamma_q,
+ * gamma_j*u_j, d_i*r_{j-1}_i, gamma_j*hat(r_{j-1})_i, gamma_j*r_j, and the terms of every sum) goes into a double of its own before the add or
+ * subtraction that follows it, nothing is fused; the scalars are evaluated in exactly the order written (rho1/rho first, then times alpha;
+ * -omega, times rho, rhon over that, times alpha).  Under dot_order = 1 every sum is serial left to right: the whole loop is then a fixed
+ * sequence of IEEE operations (tests/test_bicgstabl_host.py restates it in numpy).
+ * `iteration`, minIteration, maxIteration and the trace count BODIES; a body is 2 l products.  Stop: the four 2-norm rules of SolveEx on
+ * (rr, rr0); MGCG_RULE_HANDMADECL is refused.  *iteration, *residual and the trace show the recurrence's figure as in SolveBicgstab; a
+ * breakdown repeats the last judged figure.  WHY THE TEST IN FRONT OF A STEP.  When the Krylov space is exhausted inside a body (fewer rows
+ * than l, a right-hand side made of few eigenvectors) r_0 is at rounding level and the steps behind it are quotients of rounding errors: on
+ * the 2 x 2 matrix [[2, -.5], [-1.5, 2]] with l = 3, step 2 has rho = 6.7e-16, sigma = 6.9e-31 and alpha = 9.7e14, and moves x by 1e-2 while
+ * the recurrence's r_0 stays at 1e-16 -- MGCG_OK with a true residual of 8e-2.  Judging r_0 in front of steps 1 .. l-1 costs no read (pass
+ * R_j sums the r_0 it writes) and ends such a body where it converged; the last body of a run may so have fewer than 2 l products.  The
+ * truncated factorisation does the same for the minimal-residual step: trailing pivots that are 0, negative or not finite are dropped.
+ *   rVector         r_0 (count entries).  On return its first count entries hold the true residual b - A x
+ *   pVector         u_0 (count entries)
+ *   ApVector        u_l (count entries)
+ *   workVector      slices of `count` entries, count rounded up to even apart (every slice stays 16-byte aligned): r_1 .. r_l, then
+ *                   u_1 .. u_{l-1}, then rt, and in the Jacobi form the one gather buffer that holds hat(u_j) or hat(r_j) for the next
+ *                   product -- 2 l slices, 2 l + 1 with a diagonal.  Without a diagonal the products gather from u_j and r_j themselves.
+ * Refused with MGCG_ERROR, a message and nothing enqueued: ell outside 1 .. 4 ("ell = 5, must be 1 .. 4"), a work vector that is too short
+ * (with both sizes), MGCG_RULE_HANDMADECL, and everything SolveBicgstab refuses.
+ * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update, the placement draw and the
+ * overlap schedule do not apply.  Out of scope, and next: several ranks (SolveBicgstabLParallel), the V-cycle form, l > 4, residual
+ * replacement, GMRES, the C++ twin under host/. */
+int SolveBicgstabL(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                   Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                   Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
+                   int ell, int elementsCount, int count,
+                   double allowableResidual, int minIteration, int maxIteration, int rule,
+                   int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+int SolveBicgstabLJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                         Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                         Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
+                         int ell, int elementsCount, int count,
+                         double allowableResidual, int minIteration, int maxIteration, int rule,
+                         int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
