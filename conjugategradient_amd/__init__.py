@@ -5,6 +5,7 @@
 ``parallel``  one-process-per-GPU driver (RCCL inside the library; torch.distributed bootstrap)
 ``multigrid`` the V-cycle preconditioner the reference named but never wrote
 ``amg``       the same V-cycle for ANY CSR matrix: aggregates from the matrix graph (MgSetupAggregation) or from the caller
+``ssor``      SSOR(omega)-preconditioned CG / MINRES / BiCGStab: the one-level form of ``amg`` with two multicolour Gauss-Seidel sweeps
 ``jacobi``    Jacobi-preconditioned CG for general CSR matrices (the call the ViennaCL front-end left commented out)
 ``singlereduce`` single-reduction (Chronopoulos-Gear) CG: one global sum and two launches per iteration, with or without the diagonal
 ``minres``   MINRES for symmetric indefinite and shifted systems (A - shift I) x = b: the solver for what the CG loops refuse,
@@ -19,4 +20,4 @@
 ``mixed``     mixed-precision CG: an fp32 recurrence corrected by fp64 reliable updates, fp64-accurate x and stop test
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "jacobi", "singlereduce", "minres", "bicgstab", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "ssor", "jacobi", "singlereduce", "minres", "bicgstab", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]

@@ -107,6 +107,10 @@ SIGNATURES = {
     "MgLevelCopyAggregates": (_i, [_vp, _i, _vp]),
     "MgDestroy": (None, [_vp]),
     "MgSetInterpolation": (_i, [_vp, _i]),
+    "MgSetSmoother": (_i, [_vp, _i]),
+    "MgSmoother": (_i, [_vp]),
+    "MgLevelColours": (_i, [_vp, _i]),
+    "MgLevelCopyColours": (_i, [_vp, _i, _vp]),
     "MgLevels": (_i, [_vp]),
     "MgLevelRows": (_ll, [_vp, _i]),
     "MgLevelNnz": (_ll, [_vp, _i]),

@@ -4,8 +4,8 @@ The hierarchy is the one of ``ConjugateGradientMgGpu`` -- piecewise-constant tra
 with the aggregates taken from the matrix graph by a deterministic parallel matching (include/MgcgGpu.h writes the algorithm out;
 tests/test_amg_host.py states it in numpy) instead of 2x2x2 boxes of a grid, so the matrix needs no grid and no row order: a permuted
 stencil, a mesh or particle matrix, a graph Laplacian with jumping weights.  ``aggregates`` hands the library the caller's own maps.
-One GPU; ``omega`` is the caller's (omega * lambda_max(D^-1 A) < 2 keeps the preconditioner positive definite).  No arithmetic on
-vectors happens here.
+One GPU; ``omega`` is the caller's (omega * lambda_max(D^-1 A) < 2 keeps the preconditioner positive definite under the Jacobi smoother;
+``smoother="gs"``, multicolour Gauss-Seidel, is positive definite for every 0 < omega < 2).  No arithmetic on vectors happens here.
 """
 from __future__ import annotations
 
@@ -18,16 +18,27 @@ from .multigrid import ConjugateGradientMgGpu
 from .solver import _ptr
 
 
+SMOOTHERS = {"jacobi": 0, "gs": 1}          # MgSetSmoother's modes
+
+
 class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
     """ConjugateGradientMgGpu without ``grid``: ``Apply``, ``Solve(trace=...)``, ``level_csr`` and ``level_dinv`` are the parent's.
 
     ``aggregates``: None (the library's matching: ``passes`` passes per level at strength threshold ``theta``, at most ``levels`` levels,
     none built from a level of ``minCoarse`` rows or fewer) or a list of per-level maps, ``aggregates[l][i]`` = the aggregate of row i of
-    level l; the hierarchy then has ``len(aggregates) + 1`` levels and the last map's largest id + 1 rows on its last level."""
+    level l; the hierarchy then has ``len(aggregates) + 1`` levels and the last map's largest id + 1 rows on its last level.
+
+    ``smoother``: "jacobi" (weighted Jacobi, the default) or "gs" (multicolour Gauss-Seidel, MgSetSmoother(mg, 1): an even ``nuCoarse``
+    and a structurally symmetric pattern of at most 64 colours a level; symmetric positive definite for every 0 < omega < 2).  It is
+    applied in ``Setup()`` after the hierarchy is built; a refusal raises MgcgError with the library's message and leaves ``self.mg`` a
+    usable Jacobi hierarchy."""
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual,
                  levels: int = 8, passes: int = 3, theta: float = 0.25, minCoarse: int = 64, omega: float = 0.8, nu: int = 1, nuCoarse: int = 4,
-                 sigma: float = 0.5, aggregates=None, rule=_lib.RULE_CSHARP):
+                 sigma: float = 0.5, aggregates=None, rule=_lib.RULE_CSHARP, smoother: str = "jacobi"):
+        if smoother not in SMOOTHERS:
+            raise MgcgError(f"smoother {smoother!r}, must be one of {sorted(SMOOTHERS)}")
+        self.smoother = smoother
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, (count, 1, 1),
                          levels=levels, omega=omega, nu=nu, nuCoarse=nuCoarse, sigma=sigma, rule=rule)
         self.passes, self.theta, self.minCoarse = int(passes), float(theta), int(minCoarse)
@@ -65,6 +76,17 @@ class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
         if not self.mg:
             raise MgcgError(f"{name} returned NULL")
         self.levels = L.MgLevels(self.mg)
+        if SMOOTHERS[self.smoother] and L.MgSetSmoother(self.mg, SMOOTHERS[self.smoother]) != 0:
+            check("MgSetSmoother")
+            raise MgcgError("MgSetSmoother failed")
+
+    def level_colours(self, l: int) -> np.ndarray:
+        """The colour of every row of level ``l`` under ``smoother="gs"`` (MgcgError under "jacobi")."""
+        c = np.empty(lib().MgLevelRows(self.mg, l), dtype=np.int32)
+        if lib().MgLevelCopyColours(self.mg, l, _ptr(c)) != 0:
+            check("MgLevelCopyColours")
+            raise MgcgError("MgLevelCopyColours failed")
+        return c
 
     def level_aggregates(self, l: int) -> np.ndarray:
         """The map of level ``l`` to level ``l + 1`` (MgcgError on the last level)."""

@@ -868,6 +868,19 @@ void launch_amg_galerkin_fill(hipStream_t s, long long nc, const int* aggOffsets
                               const int* columnIndeces, const int* agg, const int* expandOffsets, const int* scratch, const int* rowOffsetsC, double sigma,
                               double* elementsC, int* columnIndecesC);
 
+// ---------------------------------------------------------------- multicolour Gauss-Seidel smoother (kernels_gs.hip; MgSetSmoother)
+// one colouring round: colourIn (-1 = uncoloured) -> colourOut; flags[0] = 1 if a row is left uncoloured; *badRow (pre-set to INT_MAX) = the
+// smallest row whose neighbours hold all 64 colours
+void launch_gs_colour_round(hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long n, const int* colourIn, int* colourOut, int* flags, int* badRow);
+// *badRow (pre-set to INT_MAX) = the smallest row that stores an entry of another row of its own colour
+void launch_gs_check(hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long n, const int* colour, int* badRow);
+void launch_gs_zero(hipStream_t s, long long n, double* x, const int* done);
+// x_i += omega * (dinv_i * (b_i - sum_k a_ik x_col)) in place for the rows of one colour, every sum in stored order; avgRow (the level's
+// entries per row) picks the lanes that share a row's loads
+void launch_gs_sweep(hipStream_t s, const int* rows, int count, const double* elements, const int* rowOffsets, const int* columnIndeces,
+                     const double* b, const double* dinv, double omega, double* x, double avgRow, const int* done);
+void preload_kernels_gs();
+
 // ---------------------------------------------------------------- RCCL (dlopen'ed)
 struct CommImpl;
 bool comm_allreduce_sum(MgcgComm* c, double* devPtr, int count, hipStream_t s);

@@ -51,6 +51,11 @@ struct MgLevel {
     int* agg = nullptr;                    // n: row -> aggregate
     int* aggOffsets = nullptr;             // rows of the next level + 1
     int* aggMembers = nullptr;             // n: the members of aggregate I, ascending, at [aggOffsets[I], aggOffsets[I + 1])
+    // Multicolour Gauss-Seidel smoother (MgSetSmoother(mg, 1); every level of an aggregation hierarchy): the rows of colour c, ascending,
+    // are gsRows[gsOffsets[c] .. gsOffsets[c + 1])
+    int* gsRows = nullptr;                 // n (device)
+    std::vector<int> gsOffsets;            // colours + 1 (host: a sweep is one launch per colour)
+    std::vector<int> gsColourOf;           // n (host): what MgLevelCopyColours hands out
 };
 
 } // namespace mgcg
@@ -59,6 +64,7 @@ struct MgcgMg {
     int levels = 0;
     double omega = 0; int nu = 1, nuCoarse = 4; double sigma = 0.5;
     int interp = 0;                        // 0: piecewise-constant P (slab-local), 1: cell-centred linear P (MgSetInterpolation)
+    int smoother = 0;                      // 0: weighted Jacobi, 1: multicolour Gauss-Seidel (MgSetSmoother; aggregation hierarchies only)
     std::vector<mgcg::MgLevel> lv;
     mgcg::SpmvConfig cfg;
     hipStream_t stream = nullptr;
@@ -240,9 +246,29 @@ static bool mg_jacobi(MgcgMg* mg, MgLevel& L, const double* b, double* xin, doub
 
 // `sweeps` Jacobi sweeps on level L for right-hand side b.  first: the first sweep starts from zero.
 // cur is the buffer holding the iterate (ignored when first); *result receives the buffer holding the result.
+// Under MgSetSmoother(mg, 1) the sweeps are multicolour Gauss-Seidel sweeps in place on cur (other is not touched): one launch per colour on
+// the level's plain CSR.  The last level alternates forward (colours 0, 1, ...) and backward sweeps from a forward one; a level with a map
+// sweeps forward before the coarse correction (first) and backward after it.  A first sweep starts from +0.0 stored by a pass of its own.
+// dotOnLast is not served here: the cycle reports no partial sums and the loop runs its own r.z pass (mg_apply: *nDot = 0).
 static bool mg_smooth(MgcgMg* mg, MgLevel& L, const double* b, double* cur, double* other, int sweeps, bool first, const int* done, double** result,
                       bool dotOnLast = false)
 {
+    if (mg->smoother == 1) {
+        const bool last = &L == &mg->lv[(size_t)mg->levels - 1];
+        const int colours = (int)L.gsOffsets.size() - 1;
+        const double avgRow = L.n > 0 ? (double)L.nnz / (double)L.n : 0.0;
+        if (first) launch_gs_zero(mg->stream, L.n, cur, done);
+        for (int sIdx = 0; sIdx < sweeps; ++sIdx) {
+            const bool forward = last ? (sIdx % 2 == 0) : first;
+            for (int q = 0; q < colours; ++q) {
+                const int c = forward ? q : colours - 1 - q;
+                launch_gs_sweep(mg->stream, L.gsRows + L.gsOffsets[(size_t)c], L.gsOffsets[(size_t)c + 1] - L.gsOffsets[(size_t)c], L.elements, L.rowOffsets,
+                                L.columnIndeces, b, L.dinv, mg->omega, cur, avgRow, done);
+            }
+        }
+        *result = cur;
+        return true;
+    }
     for (int sIdx = 0; sIdx < sweeps; ++sIdx) {
         if (first && sIdx == 0) {
             launch_jacobi_first(mg->stream, L.n, mg->omega, L.dinv, L.dinvUniform ? 1 : 0, L.dinvScalar, b, cur + L.offset, done);
@@ -504,7 +530,7 @@ static bool mg_apply(MgcgMg* mg, const double* r, double* z, const int* done, do
     if (!mg->multi) {
         // swaps on level 0: (nu-1) pre + nu post, or (nuCoarse-1) when there is a single level
         const int swaps = (mg->levels == 1) ? (mg->nuCoarse - 1) : (2 * mg->nu - 1);
-        double* start = (swaps % 2 == 0) ? z : L0.xa;
+        double* start = (swaps % 2 == 0 || mg->smoother == 1) ? z : L0.xa;     // (Gauss-Seidel sweeps work in place: no swaps)
         double* other = (start == z) ? L0.xa : z;
         if (!mg_vcycle(mg, 0, r, start, other, done, &res)) return false;
         if (res != z) launch_copy(mg->stream, z, res, L0.n);       // not reached for the buffer choice above
@@ -2601,6 +2627,63 @@ static bool amg_common_arguments(const char* who, MgcgBlas* cublas, MgcgSparse* 
     return true;
 }
 
+// The colouring of one level for MgSetSmoother(mg, 1) (the algorithm is written out in include/MgcgGpu.h): rounds until every row is
+// coloured, one flag per round read by the host as in the matching; then the device check that no row stores an entry of a row of its own
+// colour.  The per-colour row lists (ascending) are index bookkeeping and built here on the host.  false with the message set on a refusal.
+struct GsColouring { int* rows = nullptr; std::vector<int> offsets, colourOf; };
+static bool gs_colour_level(hipStream_t s, const MgLevel& L, int level, GsColouring* out)
+{
+    const size_t n = (size_t)L.n, nAlloc = n > 0 ? n : 1;
+    int *ca = nullptr, *cb = nullptr, *flags = nullptr;       // flags[0]: a row is left; flags[1]: the bad row
+    bool ok = MGCG_HIP(hipMalloc((void**)&ca, sizeof(int) * nAlloc)) && MGCG_HIP(hipMalloc((void**)&cb, sizeof(int) * nAlloc)) &&
+              MGCG_HIP(hipMalloc((void**)&flags, 2 * sizeof(int))) && MGCG_HIP(hipMemsetAsync(ca, 0xff, sizeof(int) * nAlloc, s));
+    bool refused = false;
+    // the largest uncoloured row of all is coloured in every round: n rounds at the most
+    for (long long round = 0; ok && round < (long long)n; ++round) {
+        int h[2] = { 0, 0x7fffffff };
+        ok = MGCG_HIP(hipMemcpyAsync(flags, h, sizeof(h), hipMemcpyHostToDevice, s));
+        if (ok) launch_gs_colour_round(s, L.rowOffsets, L.columnIndeces, L.n, ca, cb, flags, flags + 1);
+        ok = ok && MGCG_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+        std::swap(ca, cb);
+        if (ok && h[1] != 0x7fffffff) {
+            set_error("MgSetSmoother: level %d, row %d: the row's neighbours hold all 64 colours (the multicolour sweep allows 64 per level)", level, h[1]);
+            refused = true;
+            break;
+        }
+        if (!h[0]) break;
+    }
+    if (ok && !refused) {
+        int bad = 0x7fffffff;
+        ok = MGCG_HIP(hipMemcpyAsync(flags + 1, &bad, sizeof(int), hipMemcpyHostToDevice, s));
+        if (ok) launch_gs_check(s, L.rowOffsets, L.columnIndeces, L.n, ca, flags + 1);
+        ok = ok && MGCG_HIP(hipMemcpyAsync(&bad, flags + 1, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+        if (ok && bad != 0x7fffffff) {
+            set_error("MgSetSmoother: level %d, row %d: the row stores an entry of a row of its own colour: the pattern is not structurally symmetric "
+                      "(some row j stores this row and this row does not store j)", level, bad);
+            refused = true;
+        }
+    }
+    if (ok && !refused) {
+        out->colourOf.assign(n, 0);
+        ok = n == 0 || (MGCG_HIP(hipMemcpyAsync(out->colourOf.data(), ca, sizeof(int) * n, hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s)));
+    }
+    if (ok && !refused) {
+        int colours = 0;
+        for (size_t i = 0; i < n; ++i) colours = std::max(colours, out->colourOf[i] + 1);
+        out->offsets.assign((size_t)colours + 1, 0);
+        for (size_t i = 0; i < n; ++i) out->offsets[(size_t)out->colourOf[i] + 1]++;
+        for (int c = 0; c < colours; ++c) out->offsets[(size_t)c + 1] += out->offsets[(size_t)c];
+        std::vector<int> at(out->offsets.begin(), out->offsets.end() - 1), rows(nAlloc, 0);
+        for (size_t i = 0; i < n; ++i) rows[(size_t)at[(size_t)out->colourOf[i]]++] = (int)i;             // ascending within every colour
+        ok = MGCG_HIP(hipMalloc((void**)&out->rows, sizeof(int) * nAlloc)) &&
+             MGCG_HIP(hipMemcpyAsync(out->rows, rows.data(), sizeof(int) * nAlloc, hipMemcpyHostToDevice, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    }
+    if (ca) (void)hipFree(ca);
+    if (cb) (void)hipFree(cb);
+    if (flags) (void)hipFree(flags);
+    return ok && !refused;
+}
+
 } // namespace mgcg
 
 MgcgMg* MgSetupAggregation(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
@@ -2678,6 +2761,7 @@ void MgDestroy(MgcgMg* mg)
         if (L.agg) (void)hipFree(L.agg);
         if (L.aggOffsets) (void)hipFree(L.aggOffsets);
         if (L.aggMembers) (void)hipFree(L.aggMembers);
+        if (L.gsRows) (void)hipFree(L.gsRows);
         if (L.dinv) (void)hipFree(L.dinv);
         if (L.xa) (void)hipFree(L.xa);
         if (L.xb) (void)hipFree(L.xb);
@@ -2713,6 +2797,57 @@ int MgSetInterpolation(MgcgMg* mg, int mode)
         }
     }
     mg->interp = mode;
+    return 0;
+}
+
+int MgSetSmoother(MgcgMg* mg, int mode)
+{
+    if (!mg) { set_error("MgSetSmoother: null handle"); return -1; }
+    if (mode != 0 && mode != 1) { set_error("MgSetSmoother: mode %d, must be 0 (weighted Jacobi) or 1 (multicolour Gauss-Seidel)", mode); return -1; }
+    if (mode == 1 && !mg->algebraic) {
+        set_error("MgSetSmoother: the Gauss-Seidel smoother needs every level stored; this hierarchy was built from a grid (MgSetupAggregates with 2x2x2 box maps builds the same hierarchy)");
+        return -1;
+    }
+    if (mode == 1 && mg->nuCoarse % 2 != 0) {
+        set_error("MgSetSmoother: nuCoarse %d, must be even: the last level alternates forward and backward sweeps and an odd count is not a symmetric operator", mg->nuCoarse);
+        return -1;
+    }
+    if (!device_state()) return -1;
+    if (mg->stream) (void)hipStreamSynchronize(mg->stream);          // no cycle in flight reads the lists that go
+    std::vector<GsColouring> made;
+    if (mode == 1) {
+        made.resize((size_t)mg->levels);
+        for (int l = 0; l < mg->levels; ++l) {
+            if (gs_colour_level(mg->stream, mg->lv[(size_t)l], l, &made[(size_t)l])) continue;
+            for (GsColouring& g : made) if (g.rows) (void)hipFree(g.rows);      // refused: the hierarchy stays as it was
+            return -1;
+        }
+    }
+    for (int l = 0; l < mg->levels; ++l) {
+        MgLevel& L = mg->lv[(size_t)l];
+        if (L.gsRows) (void)hipFree(L.gsRows);
+        L.gsRows = nullptr; L.gsOffsets.clear(); L.gsColourOf.clear();
+        if (mode == 1) { L.gsRows = made[(size_t)l].rows; L.gsOffsets.swap(made[(size_t)l].offsets); L.gsColourOf.swap(made[(size_t)l].colourOf); }
+    }
+    mg->smoother = mode;
+    return 0;
+}
+
+int MgSmoother(const MgcgMg* mg) { return mg ? mg->smoother : 0; }
+
+int MgLevelColours(const MgcgMg* mg, int level)
+{
+    if (!mg || level < 0 || level >= mg->levels) { set_error("MgLevelColours: bad level"); return -1; }
+    return mg->smoother == 1 ? (int)mg->lv[(size_t)level].gsOffsets.size() - 1 : 0;
+}
+
+int MgLevelCopyColours(const MgcgMg* mg, int level, int colourOf[])
+{
+    if (!mg || !colourOf) { set_error("MgLevelCopyColours: null argument"); return -1; }
+    if (level < 0 || level >= mg->levels) { set_error("MgLevelCopyColours: level %d, the hierarchy has %d levels", level, mg->levels); return -1; }
+    if (mg->smoother != 1) { set_error("MgLevelCopyColours: the hierarchy smooths with weighted Jacobi: it has no colours (MgSetSmoother(mg, 1))"); return -1; }
+    const MgLevel& L = mg->lv[(size_t)level];
+    std::copy(L.gsColourOf.begin(), L.gsColourOf.end(), colourOf);
     return 0;
 }
 

@@ -415,6 +415,43 @@ void    MgDestroy(MgcgMg* mg);
  * operators are the same.  With several ranks the call is collective (it plans one extra plane exchange per level and
  * transfer).  Returns 0, or -1 with MgcgGetLastError(). */
 int     MgSetInterpolation(MgcgMg* mg, int mode);
+/* The smoother of the V-cycle: 0 (default) weighted Jacobi, 1 multicolour Gauss-Seidel.  Mode 1 is for aggregation hierarchies
+ * (MgSetupAggregation / MgSetupAggregates: one rank, every level stored; a geometric hierarchy is refused -- MgSetupAggregates with 2x2x2
+ * box maps builds the same one) with an EVEN nuCoarse.  A Gauss-Seidel sweep on a symmetric positive definite matrix converges for every
+ * 0 < omega < 2, and the cycle below is a symmetric positive definite M for every such omega: no spectral estimate is asked of the caller.
+ * A one-level hierarchy (MgSetupAggregates with levels = 1) with nuCoarse = 2 is SSOR(omega)-preconditioned CG, MINRES or BiCGStab through
+ * SolveMg, SolveMinresMg and SolveBicgstabMg.
+ *
+ * The COLOURING of a level is deterministic and defined by the data alone.  Row i's neighbours are the columns j != i of its stored
+ * entries, whatever their value.
+ *   1. the key of a row, 32-bit unsigned arithmetic:
+ *        h = i*0x9E3779B1; h ^= h >> 15; h *= 0x2C1B3C6D; h ^= h >> 12; h *= 0x297A2D39; h ^= h >> 15
+ *      rows compare by (h, i).
+ *   2. a round: every uncoloured row whose (h, i) is larger than that of each of its uncoloured neighbours takes the smallest colour that
+ *      none of its coloured neighbours holds -- "uncoloured" and "coloured" as they stood at the start of the round.
+ *   3. rounds repeat until every row is coloured.  The host reads one flag per round.
+ *   4. at most 64 colours (one 64-bit mask per row): a row whose neighbours hold all 64 is refused, the message names the level and the row.
+ *   5. one device pass then checks every stored entry (i, j), j != i, for colour[i] != colour[j].  It can fail only when the PATTERN is not
+ *      structurally symmetric (some j stores i and i does not store j): refused, the message names the level and the row.  The values may be
+ *      nonsymmetric.  The check is what makes the in-place sweep free of races, hence deterministic.
+ *   The per-colour row lists (rows ascending within a colour) are index bookkeeping and built on the host; no matrix value travels there.
+ * A SWEEP visits the colours 0, 1, ... (forward) or in reverse (backward), one launch per colour; within a colour every row i updates in
+ * place:  s = the row's sum in stored order from +0.0 of the rounded products a_ik * x[col_k], the diagonal included;  res = b_i - s;
+ * t = dinv_i * res;  step = omega * t;  x_i = x_i + step  -- the operations and roundings of the Jacobi sweep, omega the hierarchy's.  The
+ * sweeps sum every row in stored order in EVERY mode, whatever its length (several lanes share a row's loads, one order adds the products),
+ * and read the level's plain CSR whatever the compression mode; the residual pass and the transfers are those of mode 0 (a residual pass
+ * on a level of more than 20 entries a row on average sums by several lanes and a tree unless dot_order = 1, as everywhere in the library).
+ * The CYCLE: a level with a map runs nu forward sweeps from x = +0.0, r = b - A x, the indexed restriction, the next level, x += P e, nu
+ * backward sweeps; the last level runs nuCoarse sweeps from +0.0, sweep s (0-based) forward when s is even and backward when odd.  The
+ * cycle leaves no partial sums of r . z behind: the PCG loop takes them in a pass of its own (16 bytes per row).
+ * Returns 0; -1 with MgcgGetLastError() on a refusal, which leaves the hierarchy exactly as it was (usable, its mode unchanged).  Mode 0
+ * after mode 1 restores the Jacobi cycle bit for bit; mode 1 twice gives the same colours and the same bits.  Not to be called while a solve
+ * on the hierarchy is running. */
+int     MgSetSmoother(MgcgMg* mg, int mode);
+int     MgSmoother(const MgcgMg* mg);                                     /* the mode in force (0 for NULL) */
+int     MgLevelColours(const MgcgMg* mg, int level);                      /* the colours of the level; 0 under mode 0; -1 on a bad level */
+/* colourOf[0 .. MgLevelRows(level)-1] = the colour of every row.  Returns 0; -1 with MgcgGetLastError() under mode 0 or on a bad level. */
+int     MgLevelCopyColours(const MgcgMg* mg, int level, int colourOf[]);
 int     MgLevels(const MgcgMg* mg);
 /* rows / nnz / grid of level l; copy level l's CSR and D^-1 to host arrays (for tests). */
 long long MgLevelRows(const MgcgMg* mg, int level);
