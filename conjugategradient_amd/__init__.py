@@ -14,10 +14,12 @@
              right-preconditioned by the diagonal (the V-cycle form, SolveBicgstabMg, is the ``SolveBicgstab`` method of the
              ``multigrid`` / ``amg`` classes, with the hierarchy of the matrix itself or of another one); and BiCGStab(l), l = 1 .. 4
              (``BiConjugateGradientStabLGpu``, SolveBicgstabL), for the convection-dominated systems on which BiCGStab breaks down
+``gmres``    restarted GMRES(m) for NONSYMMETRIC systems (``GeneralizedMinimalResidualGpu``, SolveGmres), plain or right-preconditioned by
+             the diagonal: the residual never increases, no breakdown on a nonsingular matrix, no drift -- slower per product than ``bicgstab``
 ``chebyshev`` Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, m products and two global sums per iteration
 ``shifted``   multi-shift CG: (A + s_j I) x_j = b for up to 8 shifts from one CG recurrence on A
 ``blockkrylov`` shared-subspace block CG: up to 8 right-hand sides in one block Krylov space (fewer iterations than ``block``)
 ``mixed``     mixed-precision CG: an fp32 recurrence corrected by fp64 reliable updates, fp64-accurate x and stop test
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "ssor", "jacobi", "singlereduce", "minres", "bicgstab", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "ssor", "jacobi", "singlereduce", "minres", "bicgstab", "gmres", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]

@@ -115,7 +115,7 @@ void preload_ops(); void preload_solver(); void preload_comm(); void preload_ker
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
 void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres(); void preload_kernels_pminres();
-void preload_kernels_bicgstab(); void preload_kernels_bicgstabl();
+void preload_kernels_bicgstab(); void preload_kernels_bicgstabl(); void preload_kernels_gmres();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -234,6 +234,22 @@ struct BicgstablScalars {
     int broke[kBicgstablMaxL], early[kBicgstablMaxL];
 };
 
+// What the GMRES(m) loop (SolveGmres, SolveGmresJacobi; kernels_gmres.hip) keeps on the device.  h: the new column of the Hessenberg matrix as the
+// fold launches left it (hp: the h' of the orthogonalisation pass in flight); R, cs, sn, g: the triangular factor (R[i][j], i <= j), the rotations
+// and the rotated right-hand side of the cycle, written by pass N's first workgroup; gLast: g_j where pass N of step k looks for it
+// (gLast[k & 1]) and writes its successor (gLast[(k + 1) & 1]); cols: the completed columns of the cycle, yCount and y: what the close's first
+// launch solved for its x launches.  fDone: CgScalars::done as the first launch of a step found it; note: a restart found r.r zero (1) or not
+// finite (2), read by later launches only.  red: the closing r.r.
+constexpr int kGmresMaxM = 32;
+struct GmresScalars {
+    double red;
+    double h[kGmresMaxM], hp[kGmresMaxM];
+    double cs[kGmresMaxM], sn[kGmresMaxM], g[kGmresMaxM], y[kGmresMaxM];
+    double gLast[2];
+    double R[kGmresMaxM][kGmresMaxM];
+    int fDone, note, cols, yCount;
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
@@ -271,6 +287,10 @@ struct Workspace {
     // partial sums -- one per entry Z_ab of the Gram pass, then r.r and rtilde.r of the combine pass
     BicgstablScalars* bicgstablScalars = nullptr;
     double* bicgstablPartials = nullptr;
+    // GMRES(m) (kernels_gmres.hip), allocated at its first call and kept: the loop's scalars, and kGmresMaxM + 1 regions of kMaxGrid partial
+    // sums -- one per column of the basis for v_i.w, then w.w (and every r.r of the loop)
+    GmresScalars* gmresScalars = nullptr;
+    double* gmresPartials = nullptr;
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -284,6 +304,7 @@ struct Workspace {
     bool ensure_minres();                        // minresScalars (kernels_minres.hip)
     bool ensure_bicgstab();                      // bicgstabScalars (kernels_bicgstab.hip)
     bool ensure_bicgstabl();                     // bicgstablScalars / bicgstablPartials (kernels_bicgstabl.hip)
+    bool ensure_gmres();                         // gmresScalars / gmresPartials (kernels_gmres.hip)
 };
 
 } // namespace mgcg
@@ -772,6 +793,28 @@ int bicgstabl_enqueue_gram(const BicgstablRun& R);
 int bicgstabl_enqueue_combine(const BicgstablRun& R, const FinalizeArgs& f, int k, int nGram);
 // pass P of body k: the stop decision, beta, u_0, gather = hat(u_0)
 void bicgstabl_enqueue_p(const BicgstablRun& R, const FinalizeArgs& f, int k, int nRr);
+
+// GMRES(m) (SolveGmres, SolveGmresJacobi; kernels_gmres.hip has the loop, include/MgcgGpu.h the method), one rank.  V: the basis, column i at
+// V + i * stride, m + 1 columns; w: the product's output; r: where the start and every restart leave b - A x.  With dinv `gather` is the one
+// buffer that holds hat(v_j) for the next product; without it the products gather from v_j itself and gather is null.
+struct GmresRun {
+    Workspace* ws;
+    int m, orth;
+    double *x, *r, *w, *V, *gather; const double* dinv;
+    long long stride, n;
+};
+// where the start, every restart and the closing product leave the partial sums of r.r
+double* gmres_rr_partials(Workspace* ws);
+// the scalars in front of step 0 from the start's nPartials partial sums of r.r; r.r not finite or zero stops the loop here with MGCG_NONFINITE
+// at iteration 0
+void gmres_enqueue_init(const GmresRun& R, const FinalizeArgs& f, int nPartials);
+// v_0 = r / sqrt(r.r), gather = dinv v_0 and g_0 for step k, from nRr partial sums; first: the start (judged by gmres_enqueue_init), else an r.r
+// that is zero or not finite ends the loop through the next step's pass N
+void gmres_enqueue_restart(const GmresRun& R, const FinalizeArgs& f, int k, int nRr, bool first);
+// everything of step k (j = k mod m) behind its product: the orthogonalisation passes and pass N
+void gmres_enqueue_step(const GmresRun& R, const FinalizeArgs& f, int k, int j);
+// the close: y, and x += hat(sum y_i v_i) over the columns the cycle completed; does nothing when there are none
+void gmres_enqueue_close(const GmresRun& R);
 
 // Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).
 // The start: d = it * (dinv r), z = d, the partial sums of r.r and -- withRz, degree 1 -- of r.z; returns their number (1 under dot_order = 1).

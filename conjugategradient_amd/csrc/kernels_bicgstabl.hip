@@ -2,8 +2,8 @@
 // right-preconditioned with M = I or M = diag(A), one rank.  A body is l BiCG steps, which raise the degree of the residual polynomial by l,
 // and ONE minimal-residual step of degree l over r_0 .. r_l, where BiCGStab takes l steps of degree 1: the polynomial may then have complex
 // roots, which is what a spectrum near the imaginary axis asks for.  include/MgcgGpu.h has the method and its rounding contract; solver.hip's
-// cg_solve_bicgstabl the host's side.  Out of scope: several ranks, the V-cycle form, l > 4, residual replacement, GMRES, the C++ twin under
-// host/.
+// cg_solve_bicgstabl the host's side.  GMRES: kernels_gmres.hip.  Out of scope: several ranks, the V-cycle form, l > 4, residual replacement,
+// the C++ twin under host/.
 //
 // Per body k 2 l products (launch_spmv_auto with the EPI_DOT epilogue and w = rt: u_{j+1} = A hat(u_j) with the partial sums of sigma = rt.u_{j+1},
 // r_{j+1} = A hat(r_j) with those of rt.r_{j+1}) and 2 l + 2 passes; vectors read + written, without / with the diagonal (which adds dinv to

@@ -1161,14 +1161,15 @@ static bool cg_variant_begin(CgRun& R, int preconditioned, const double* residua
     return true;
 }
 
-// out = b - A x through a full-length buffer: x into the rows' slice of `full`, its halo exchanged in line, the product with the residual epilogue
-static bool cg_enqueue_residual(CgRun& R, double* full, double* out)
+// out = b - A x through a full-length buffer: x into the rows' slice of `full`, its halo exchanged in line, the product with the residual epilogue.
+// gate (the restarts of the GMRES loop): a device int, nonzero = the product writes nothing.
+static bool cg_enqueue_residual(CgRun& R, double* full, double* out, const int* gate = nullptr)
 {
     hipStream_t s = R.ws->stream;
     launch_copy(s, full + R.offset, R.x, R.nLocal);
     if (!halo_exchange(R.comm, R.halo, full, s)) return false;
     SpmvArgs a = cg_spmv_args(R, full, out);
-    a.b = R.b;
+    a.b = R.b; a.doneFlag = gate;
     launch_spmv_auto(s, EPI_RESIDUAL, a, R.cfg, R.dcsr);
     return true;
 }
@@ -1560,6 +1561,70 @@ static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, 
     if (trueResidual) *trueResidual = std::sqrt(rrTrue);
     return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", "",
                          "the first residual is zero or not finite, or the recurrence broke down (rt.u_{j+1}, omega or rt.r_0 zero, or a value that is not finite)");
+}
+
+// ---------------------------------------------------------------- GMRES(m) (SolveGmres, SolveGmresJacobi)
+// Restarted GMRES for A x = b, A any CSR matrix, 1 <= m <= kGmresMaxM, right-preconditioned with M = I or M = diag(A) (R.dinv), one rank
+// (include/MgcgGpu.h has the method, kernels_gmres.hip the passes).  The host's side is cg_drive: an iteration is one Arnoldi step -- the
+// product and the passes of gmres_enqueue_step -- and in front of every m-th the close and the restart.  Every product is the plain loop's
+// (cg_enqueue_product, gather vector switched per step), so compression modes and automatic column tiles apply unchanged; the deferred x
+// update and the placement draw do not apply.  The caller's r holds b - A x at the start and at every restart, its Ap is w, its p the
+// full-length buffer the residual products gather x from; `work` holds v_0 .. v_m and -- with a diagonal -- the one gather buffer, `stride`
+// entries apart.  The close is enqueued once more behind the loop: it applies the columns of the cycle that the stop, the cap or a breakdown
+// cut short, and does nothing when a close in front of a restart that was enqueued behind the stop has done so already.  One more product
+// leaves the true residual b - A x in the caller's r.
+static int gmres_slices(int m, bool jacobi) { return m + 1 + (jacobi ? 1 : 0); }
+static int cg_solve_gmres(CgRun& R, const char* who, int m, int orth, double* work, int* iteration, double* residual, double* trueResidual,
+                          double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const long long n = R.nLocal;
+    // everything the call allocates, before anything is enqueued
+    FinalizeArgs f;
+    if (!ws->ensure_gmres() || !cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
+    const int* done = &ws->scalars->done;
+    double* const bufP = R.p; double* const bufAp = R.Ap;
+    const long long stride = bicgstabl_stride(R.count);
+    GmresRun P{};
+    P.ws = ws; P.m = m; P.orth = orth; P.x = R.x; P.r = R.r; P.w = bufAp; P.V = work; P.dinv = R.dinv; P.stride = stride; P.n = n;
+    P.gather = R.dinv ? work + (m + 1) * stride : nullptr;
+
+    // r = b - A x through bufP ; beta^2 = r.r ; v_0 = r / beta ; gather = dinv v_0 ; g_0 = beta for step k.  The start also sets the scalars.
+    auto restart = [&](int k, bool first) {
+        if (!cg_enqueue_residual(R, bufP, R.r, first ? nullptr : done)) return false;
+        const int nRr = launch_dot_partials(s, R.r, R.r, n, gmres_rr_partials(ws));
+        if (first) gmres_enqueue_init(P, f, nRr);
+        gmres_enqueue_restart(P, f, k, nRr, first);
+        return true;
+    };
+    bool ok = restart(0, true) && MGCG_HIP(hipGetLastError());
+
+    int k = 0;
+    ok = ok && cg_drive(R, who, [&] {
+        const int j = k % m;
+        if (j == 0 && k > 0) {                                                           // y ; x += hat(V y) ; the next cycle's r, v_0
+            gmres_enqueue_close(P);
+            if (!restart(k, false)) return false;
+        }
+        double* from = P.gather ? P.gather : P.V + j * stride;
+        int nSums = 0;
+        R.p = from; R.Ap = P.w;
+        if (!cg_enqueue_product(R, from, &nSums)) return false;                          // w = A hat(v_j)
+        gmres_enqueue_step(P, f, k, j);                                                  // h ; w ; the rotations ; the stop decision ; v_{j+1}
+        if (k < 0x7fffffff) ++k;
+        return MGCG_HIP(hipGetLastError());
+    });
+    R.p = bufP; R.Ap = bufAp;
+    if (ok) gmres_enqueue_close(P);                                                      // the columns of the cycle that was cut short
+    // the closing product: the true residual into the caller's r
+    double rrTrue = 0.0;
+    ok = ok && cg_enqueue_true_residual(R, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, gmres_rr_partials(ws)); }, gmres_rr_partials(ws), &ws->gmresScalars->red, &rrTrue);
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
+    return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", "",
+                         "the first residual is zero or not finite, or an Arnoldi step left no next direction and no column (A singular on the Krylov space, or a value that is not finite)");
 }
 
 // ---------------------------------------------------------------- preconditioned MINRES (SolveMinresJacobi, SolveMinresJacobiParallel, SolveMinresMg)
@@ -3259,6 +3324,64 @@ int SolveBicgstabLJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* m
     return bicgstabl_entry_call("SolveBicgstabLJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
                                 xVector, bVector, ApVector, pVector, rVector, workVector, dinvVector, ell, elementsCount, count,
                                 allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+// GMRES(m) (cg_solve_gmres above; refusals: cg_variant_call), one rank.  With `jacobi` dinvVector is a handle the export requires.
+static int gmres_entry_call(const char* who, bool jacobi, MgcgBlas* cublas, MgcgSparse* cusparse,
+                            Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                            Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
+                            int m, int orth, int elementsCount, int count,
+                            double allowableResidual, int minIteration, int maxIteration, int rule,
+                            int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
+    auto checks = [&] {
+        if (m < 1 || m > kGmresMaxM) { set_error("%s: m = %d, must be 1 .. %d", who, m, kGmresMaxM); return false; }
+        if (orth < 1 || orth > 2) { set_error("%s: orth = %d, must be 1 or 2", who, orth); return false; }
+        if (cg_rule_refused(who, rule, "the loop carries no max|r|")) return false;
+        // a count below 1 is the shared checks' to refuse (cg_call, behind these): it asks for no room here, never for a negative amount
+        const int slices = gmres_slices(m, jacobi);
+        const long long need = slices * bicgstabl_stride(count > 0 ? count : 0);
+        if (workVector->size < need) {
+            set_error("%s: the work vector holds %lld entries, m = %d needs %lld (%d slices of %lld: the matrix has %d rows)", who, workVector->size, m, need, slices, bicgstabl_stride(count), count);
+            return false;
+        }
+        return !(jacobi && cg_vector_short(who, "dinv", dinvVector, count, "local rows"));
+    };
+    return cg_variant_call(c, cublas && cusparse && workVector && (!jacobi || dinvVector), checks, [&](CgRun& R) {
+        if (R.multi) { set_error("%s: the loop runs on one rank", who); return (int)MGCG_ERROR; }
+        if (jacobi) R.dinv = cg_dinv_address(R, dinvVector);
+        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+        cg_note_written({ R.x, R.Ap, R.r, R.p }, count);
+        cg_note_written({ workVector->data }, gmres_slices(m, jacobi) * bicgstabl_stride(count));
+        return cg_solve_gmres(R, who, m, orth, workVector->data, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    });
+}
+
+int SolveGmres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+               Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+               Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
+               int m, int orth, int elementsCount, int count,
+               double allowableResidual, int minIteration, int maxIteration, int rule,
+               int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return gmres_entry_call("SolveGmres", false, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+                            xVector, bVector, ApVector, pVector, rVector, workVector, nullptr, m, orth, elementsCount, count,
+                            allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+int SolveGmresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                     Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                     Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
+                     int m, int orth, int elementsCount, int count,
+                     double allowableResidual, int minIteration, int maxIteration, int rule,
+                     int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return gmres_entry_call("SolveGmresJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
+                            xVector, bVector, ApVector, pVector, rVector, workVector, dinvVector, m, orth, elementsCount, count,
+                            allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
 // Preconditioned MINRES (cg_solve_pminres above; refusals: cg_variant_call).  dinvVector, the hierarchy and zVector are handles the exports

@@ -813,7 +813,7 @@ int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
  *   rhatVector      the shadow residual, fixed after the start (count entries)
  * Refused with MGCG_ERROR, a message and nothing enqueued: MGCG_RULE_HANDMADECL, an unknown rule, a null handle, a vector that is too small.
  * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update (x_defer), the placement
- * draw and the overlap schedule do not apply.  The V-cycle as preconditioner: SolveBicgstabMg below; BiCGStab(l): SolveBicgstabL below.  Out of scope: GMRES,
+ * draw and the overlap schedule do not apply.  The V-cycle as preconditioner: SolveBicgstabMg below; BiCGStab(l): SolveBicgstabL below; GMRES(m): SolveGmres below.  Out of scope:
  * residual replacement, the block and mixed combinations, the C++ twin under host/. */
 int SolveBicgstab(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                   Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
@@ -955,8 +955,8 @@ int SolveBicgstabMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDes
  * Refused with MGCG_ERROR, a message and nothing enqueued: ell outside 1 .. 4 ("ell = 5, must be 1 .. 4"), a work vector that is too short
  * (with both sizes), MGCG_RULE_HANDMADECL, and everything SolveBicgstab refuses.
  * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update, the placement draw and the
- * overlap schedule do not apply.  Out of scope, and next: several ranks (SolveBicgstabLParallel), the V-cycle form, l > 4, residual
- * replacement, GMRES, the C++ twin under host/. */
+ * overlap schedule do not apply.  GMRES: SolveGmres below.  Out of scope, and next: several ranks (SolveBicgstabLParallel), the V-cycle
+ * form, l > 4, residual replacement, the C++ twin under host/. */
 int SolveBicgstabL(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                    Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                    Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
@@ -969,6 +969,69 @@ int SolveBicgstabLJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* m
                          int ell, int elementsCount, int count,
                          double allowableResidual, int minIteration, int maxIteration, int rule,
                          int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
+/* ---- Restarted GMRES(m): the nonsymmetric solver whose residual never increases, 1 <= m <= 32, plain and Jacobi (one rank) ---- */
+/* Saad and Schultz's GMRES, restarted every m steps.  Against SolveBicgstab and SolveBicgstabL it has three properties: the judged residual
+ * never increases (theirs can peak many orders above || b ||), it cannot break down on a nonsingular matrix (they end MGCG_NONFINITE where
+ * convection dominates), and it does not drift -- every restart recomputes r = b - A x by a product.  It pays with storage (m + 1 vectors)
+ * and traffic (a step touches every column of the cycle): slower per product than both, see DESIGN.md.  Same needs otherwise: products with
+ * A only, right-preconditioned with M = I (SolveGmres) or M = diag(A) (SolveGmresJacobi), so the judged residual is that of A x = b in the
+ * 2-norm.  The orthogonalisation is CLASSICAL Gram-Schmidt applied `orth` times (1 or 2; 2 is "twice is enough"), not modified Gram-Schmidt:
+ * the j + 1 sums of a pass are independent and share one reduction point, where the modified form needs j + 1 dependent ones.
+ * Method: d_i is dinv_i when a diagonal is given and 1 otherwise; with d = 1 the multiplication is not performed and no hatted copy is stored.
+ * hat(v)_i = d_i*v_i.  An ITERATION is one Arnoldi step, which is one product; k counts them from 0, j = k mod m is the step's place in its cycle.
+ *   start   (MGCG_RULE_SIMPLE: x := 0)
+ *           r = b - A x ;  beta2 = rr0 = r.r ;  rr0 == 0 or not finite  ->  MGCG_NONFINITE at iteration 0, x untouched
+ *           beta = sqrt(beta2) ;  v_0 = r/beta ;  g_0 = beta
+ *   step k  w = A hat(v_j)
+ *           `orth` times:  h'_i = v_i.w,  i = 0 .. j ;  w = w - h'_i*v_i  for i = 0, 1 .. j in that order, one term at a time ;
+ *                          the first time h_i = h'_i, the second time h_i = h_i + h'_i
+ *           hn2 = w.w ;  hn = sqrt(hn2)                                                                                (pass N)
+ *           for i = 0 .. j-1:  t1 = c_i*h_i ; t2 = s_i*h_{i+1} ; t3 = s_i*h_i ; t4 = c_i*h_{i+1} ;  h_i = t1 + t2 ;  h_{i+1} = t4 - t3
+ *           d = sqrt(h_j*h_j + hn*hn)     (two products, an add, a square root: no hypot)
+ *           hn2 not finite, or d == 0 or not finite  ->  MGCG_NONFINITE for iteration k + 1 with the last judged figure once more; this
+ *                   step adds no column (A is singular on the Krylov space, or a value is not finite)
+ *           c_j = h_j/d ;  s_j = hn/d ;  g_{j+1} = (-s_j)*g_j ;  g_j = c_j*g_j ;  R_ij = h_i (i < j) ;  R_jj = d ;  the cycle has j + 1 columns
+ *           g_{j+1}*g_{j+1} is judged by the rule's stop test against rr0 as the squared residual of iteration k + 1
+ *           hn2 == 0  ->  the Krylov space is exhausted: MGCG_OK at iteration k + 1 with residual 0, whatever minIteration says
+ *           not stopped:  v_{j+1} = w/hn
+ *   close   once per cycle -- behind step j = m - 1, and for the cycle cut short by a stop, the cap or a breakdown -- over its `cols` columns:
+ *           for i = cols-1 .. 0 { s = g_i ; for q = i+1 .. cols-1: s = s - R_iq*y_q ;  y_i = s/R_ii }
+ *           in groups of 8 columns, c0 = 0, 8 ..:  t = 0 ; for i = c0 .. min(c0 + 8, cols) - 1: t = t + y_i*v_i ;  x = x + hat(t)
+ *   restart r = b - A x ;  beta2 = r.r ;  judges nothing, but beta2 == 0  ->  MGCG_OK at iteration k with residual 0 (no trace entry), and
+ *           beta2 not finite  ->  MGCG_NONFINITE at iteration k with the last judged figure ;  else beta, v_0, g_0 as at the start
+ *   end     one more product: rVector = b - A x ;  *trueResidual = sqrt(r.r)      (whenever the loop ended without MGCG_ERROR)
+ * Rounding contract, SolveBicgstab's: every product (h'_i*v_i, the t's of a rotation, h_j*h_j, hn*hn, (-s_j)*g_j, c_j*g_j, R_iq*y_q,
+ * y_i*v_i, d_i*t_i, and the terms of every sum) goes into a double of its own before the add or subtraction that follows it, nothing is
+ * fused; v_0 and v_{j+1} are formed by division.  Under dot_order = 1 every sum is serial left to right: the whole loop is then a fixed
+ * sequence of IEEE operations (tests/test_gmres_host.py restates it in numpy).
+ * `iteration`, minIteration, maxIteration and the trace count STEPS: trace[0] is the first residual, trace[k] the figure after step k.  Stop:
+ * the four 2-norm rules of SolveEx on (g_{j+1}^2, rr0); MGCG_RULE_HANDMADECL is refused.  *iteration, *residual and the trace show the rotated
+ * estimate |g_{j+1}|, which a restart replaces by the explicit || b - A x ||.
+ *   rVector         b - A x of the start and of every restart (count entries).  On return its first count entries hold the true residual
+ *   pVector         the buffer the residual products gather x from (count entries)
+ *   ApVector        w (count entries)
+ *   workVector      slices of `count` entries, count rounded up to even apart (every slice stays 16-byte aligned): v_0 .. v_m, and in the
+ *                   Jacobi form the one gather buffer that holds hat(v_j) for the next product -- m + 1 slices, m + 2 with a diagonal.
+ *                   Whatever it holds on entry does not reach the result.
+ * Refused with MGCG_ERROR, a message and nothing enqueued: m outside 1 .. 32 ("m = 33, must be 1 .. 32"), orth outside {1, 2}, a work vector
+ * that is too short (with both sizes), MGCG_RULE_HANDMADECL, and everything SolveBicgstab refuses; a communicator of several ranks ("the loop
+ * runs on one rank").
+ * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update, the placement draw and the
+ * overlap schedule do not apply.  Out of scope, and next: several ranks, the V-cycle form, flexible GMRES, m > 32, the C++ twin under host/,
+ * the front-ends. */
+int SolveGmres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+               Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+               Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
+               int m, int orth, int elementsCount, int count,
+               double allowableResidual, int minIteration, int maxIteration, int rule,
+               int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+int SolveGmresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                     Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                     Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
+                     int m, int orth, int elementsCount, int count,
+                     double allowableResidual, int minIteration, int maxIteration, int rule,
+                     int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
