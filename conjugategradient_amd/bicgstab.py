@@ -42,18 +42,20 @@ class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
 
     _export = "SolveBicgstab"
     _what = "BiCGStab"
+    _work_names = _WORK                # the work vectors of `count` entries that the constructor allocates
+    _jacobi = False                    # with M = diag(A): ``vectorDinv``, filled and checked by Initialize(), follows the work vectors
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None):
         if rule == _lib.RULE_HANDMADECL:
             raise ValueError(f"{type(self).__name__}: the max-norm rule (RULE_HANDMADECL) is not supported")
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
         self.TrueResidual = float("nan")
-        for name in _WORK:
+        for name in self._work_names + (("vectorDinv",) if self._jacobi else ()):
             setattr(self, name, VectorDouble(count))
         self._ready = False
 
     def Dispose(self):
-        for name in _WORK + ("vectorDinv",):
+        for name in _WORK + ("vectorDinv", "vectorWork"):
             if getattr(self, name, None) is not None:
                 getattr(self, name).Dispose()
                 setattr(self, name, None)
@@ -63,10 +65,13 @@ class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
         self._ready = False
         check_system_shapes(self.A, self.x, self.b, self.Count)
         super().Initialize()
+        if self._jacobi:
+            jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
+                         int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
         self._ready = True
 
     def _more_vectors(self):
-        return ()
+        return (self.vectorDinv.Ptr,) if self._jacobi else ()
 
     def _work_arguments(self):
         """What the export takes between the r vector and the sizes."""
@@ -113,23 +118,36 @@ class BiConjugateGradientStabJacobiGpu(BiConjugateGradientStabGpu):
 
     _export = "SolveBicgstabJacobi"
     _what = "Jacobi-preconditioned BiCGStab"
-
-    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None):
-        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
-        self.vectorDinv = VectorDouble(count)
-
-    def Initialize(self):
-        super().Initialize()
-        self._ready = False
-        jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
-                     int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
-        self._ready = True
-
-    def _more_vectors(self):
-        return (self.vectorDinv.Ptr,)
+    _jacobi = True
 
 
-class BiConjugateGradientStabLGpu(BiConjugateGradientStabGpu):
+class OneWorkVectorGpu(BiConjugateGradientStabGpu):
+    """BiConjugateGradientStabGpu for the loops that keep their vectors in one work vector (BiCGStab(l), GMRES(m)): ``vectorWork`` of
+    ``_slices()`` slices replaces v, s, t and rhat.  It is sized by the constructor and allocated again, larger, by the first ``Solve()``
+    after the object's sizes were raised."""
+
+    _work_names = ()
+    vectorWork, _work_size = None, 0
+    _slices_more = property(lambda self: 1 if self._jacobi else 0)     # the diagonal's form keeps one slice more
+
+    def _slices(self):
+        """How many slices the loop needs now (for a size the library refuses: as for the nearest it takes, so that the call reaches
+        its refusal)."""
+        raise NotImplementedError
+
+    def _ensure_work(self):
+        need = self._slices() * (self.Count + (self.Count & 1))
+        if need > self._work_size:
+            if self.vectorWork is not None:
+                self.vectorWork.Dispose()
+            self.vectorWork, self._work_size = VectorDouble(need), need
+
+    def Dispose(self):
+        self._work_size = 0
+        super().Dispose()
+
+
+class BiConjugateGradientStabLGpu(OneWorkVectorGpu):
     """BiConjugateGradientStabGpu on the BiCGStab(l) loop (SolveBicgstabL): same members, ``TrueResidual``, ``ReadResidual()``, trace and
     exceptions; ``ell`` (1 .. 4) is the degree of a body's minimal-residual step, and iterations count bodies of ``2 * ell`` products.  One
     work vector of ``2 * ell`` slices (one more with the diagonal) replaces v, s, t and rhat: it is sized for the object's ``ell`` and
@@ -138,31 +156,14 @@ class BiConjugateGradientStabLGpu(BiConjugateGradientStabGpu):
 
     _export = "SolveBicgstabL"
     _what = "BiCGStab(l)"
-    _slices_more = 0
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, ell=2):
-        if rule == _lib.RULE_HANDMADECL:
-            raise ValueError(f"{type(self).__name__}: the max-norm rule (RULE_HANDMADECL) is not supported")
-        ConjugateGradientSingleGpu.__init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
-        self.TrueResidual = float("nan")
+        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
         self.ell = int(ell)
-        self.vectorWork, self._work_size = None, 0
         self._ensure_work()
-        self._ready = False
 
-    def _ensure_work(self):
-        """Room for this ``ell`` (one the library refuses: as for the nearest it takes, so that the call reaches its refusal)."""
-        need = (2 * min(max(int(self.ell), 1), 4) + self._slices_more) * (self.Count + (self.Count & 1))
-        if need > self._work_size:
-            if self.vectorWork is not None:
-                self.vectorWork.Dispose()
-            self.vectorWork, self._work_size = VectorDouble(need), need
-
-    def Dispose(self):
-        if getattr(self, "vectorWork", None) is not None:
-            self.vectorWork.Dispose()
-            self.vectorWork, self._work_size = None, 0
-        super().Dispose()
+    def _slices(self):
+        return 2 * min(max(int(self.ell), 1), 4) + self._slices_more
 
     def _work_arguments(self):
         self._ensure_work()
@@ -175,18 +176,4 @@ class BiConjugateGradientStabLJacobiGpu(BiConjugateGradientStabLGpu):
 
     _export = "SolveBicgstabLJacobi"
     _what = "Jacobi-preconditioned BiCGStab(l)"
-    _slices_more = 1
-
-    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, ell=2):
-        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule, ell=ell)
-        self.vectorDinv = VectorDouble(count)
-
-    def Initialize(self):
-        super().Initialize()
-        self._ready = False
-        jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
-                     int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
-        self._ready = True
-
-    def _more_vectors(self):
-        return (self.vectorDinv.Ptr,)
+    _jacobi = True

@@ -59,29 +59,8 @@ struct BicgstabPass {
     long long n;
 };
 
-// Who forms the hatted copies phat = M^-1 p and shat = M^-1 s: nobody (M = I: phat IS p, shat IS s), the passes themselves (dinv * value per
-// element), or somebody else between the passes (the V-cycle: the copies are stored, the passes only read them).  One template parameter of
-// every pass and of the start.
-enum : int { HAT_NONE = 0, HAT_DINV = 1, HAT_STORED = 2 };
-
-// go(HAT) for the form this call takes
-template <typename Go> static void bicgstab_with_hat(const BicgstabRun& R, Go go)
-{
-    if (R.dinv) go(std::integral_constant<int, HAT_DINV>{});
-    else if (R.stored) go(std::integral_constant<int, HAT_STORED>{});
-    else go(std::integral_constant<int, HAT_NONE>{});
-}
-
-__device__ __forceinline__ bool bicgstab_finite(double v) { return fabs(v) <= 1.79e308; }
-
-// A breakdown in front of a body's updates (pass P, one thread): the last judged residual once more, for iteration k + 1
-__device__ __forceinline__ void bicgstab_breakdown(const BicgstabPass& a)
-{
-    StopDecision d;
-    const double rrOld = a.f.sc->rrNew, rr0 = a.f.sc->rr0;
-    d.res = sqrt(rrOld); d.shown = a.f.rule == MGCG_RULE_VIENNACL ? sqrt(rrOld / rr0) : d.res; d.stop = true; d.status = MGCG_NONFINITE;
-    publish_iteration<0>(a.f, d, a.k + 1, rrOld, 0.0, 0, [] {});
-}
+// HAT (vec_passes.hpp), one template parameter of every pass and of the start: who forms the hatted copies phat = M^-1 p and shat = M^-1 s --
+// nobody (phat IS p, shat IS s), the passes themselves, or the V-cycle between the passes.
 
 template <bool V2, bool NTV, bool GIVEN, int HAT>
 __global__ __launch_bounds__(kBlock) void bicgstab_s_kernel(BicgstabPass a)
@@ -97,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void bicgstab_s_kernel(BicgstabPass a)
     else sigma = reduce_partials_block(a.inA, a.nA, s_red, 0);
     const double rho = a.bs->rho[a.k & 1];
     const double alpha = rho / sigma;
-    if (sigma == 0.0 || !bicgstab_finite(sigma) || !bicgstab_finite(alpha)) {
+    if (sigma == 0.0 || !finite_value(sigma) || !finite_value(alpha)) {
         if (publisher) a.bs->brokeS = 1;
         return;
     }
@@ -109,27 +88,16 @@ __global__ __launch_bounds__(kBlock) void bicgstab_s_kernel(BicgstabPass a)
         a.s[i] = s;
         if constexpr (DINV) a.shat[i] = a.dinv[i] * s;
     };
-    if constexpr (V2) {
-        const d2* r2 = (const d2*)a.r; const d2* v2 = (const d2*)a.v; const d2* d2p = (const d2*)a.dinv;
-        d2* s2 = (d2*)a.s; d2* h2 = (d2*)a.shat;
-        struct Pair { d2 r, v, d; };
-        auto load = [&](Pair& e, long long i) { e.d = {}; e.r = ldv<NTV>(r2 + i); e.v = ldv<NTV>(v2 + i); if constexpr (DINV) e.d = ldv<NTV>(d2p + i); };
-        auto finish = [&](const Pair& e, long long i) {
-            d2 o; o.x = step(e.r.x, e.v.x); o.y = step(e.r.y, e.v.y);
-            stv<NTV>(o, s2 + i);
-            if constexpr (DINV) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, h2 + i); }
-        };
-        chunk_pairs(a.n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair e0, e1;
-            load(e0, i); load(e1, j);
-            finish(e0, i);
-            if (two) finish(e1, j);
-        });
-        if ((a.n & 1) && publisher) one(a.n - 1);
-    } else {
-        grid_stride<false>(a.n, [&](long long) {}, one);
-    }
+    const d2* r2 = (const d2*)a.r; const d2* v2 = (const d2*)a.v; const d2* d2p = (const d2*)a.dinv;
+    d2* s2 = (d2*)a.s; d2* h2 = (d2*)a.shat;
+    struct Pair { d2 r, v, d; };
+    auto load = [&](Pair& e, long long i) { e.d = {}; e.r = ldv<NTV>(r2 + i); e.v = ldv<NTV>(v2 + i); if constexpr (DINV) e.d = ldv<NTV>(d2p + i); };
+    auto finish = [&](const Pair& e, long long i) {
+        d2 o; o.x = step(e.r.x, e.v.x); o.y = step(e.r.y, e.v.y);
+        stv<NTV>(o, s2 + i);
+        if constexpr (DINV) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, h2 + i); }
+    };
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 // the partial sums of t.t: one read per element
@@ -157,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void bicgstab_x_kernel(BicgstabPass a)
     if constexpr (GIVEN) { theta = a.bs->red[1]; tau = a.bs->red[2]; }
     else { theta = reduce_partials_block(a.inA, a.nA, s_red, 0); tau = reduce_partials_block(a.inB, a.nB, s_red2, 0); }
     const double omega = tau == 0.0 ? 0.0 : theta / tau;
-    if (!bicgstab_finite(omega)) {
+    if (!finite_value(omega)) {
         if (publisher) a.bs->brokeX = 1;
         return;
     }
@@ -180,32 +148,21 @@ __global__ __launch_bounds__(kBlock) void bicgstab_x_kernel(BicgstabPass a)
         const Elem o = step(a.x[i], a.phat[i], HATTED ? a.shat[i] : s, s, a.t[i], a.rhat[i]);
         a.x[i] = o.x; a.r[i] = o.r;
     };
-    if constexpr (V2) {
-        d2* x2 = (d2*)a.x; d2* r2 = (d2*)a.r;
-        const d2* p2 = (const d2*)a.phat; const d2* h2 = (const d2*)a.shat; const d2* s2 = (const d2*)a.s;
-        const d2* t2 = (const d2*)a.t; const d2* g2 = (const d2*)a.rhat;
-        struct Pair { d2 x, ph, sh, s, t, rh; };
-        auto load = [&](Pair& e, long long i) {
-            e.x = ldv<NTV>(x2 + i); e.ph = ldv<NTV>(p2 + i); e.s = ldv<NTV>(s2 + i); e.t = ldv<NTV>(t2 + i); e.rh = ldv<NTV>(g2 + i);
-            if constexpr (HATTED) e.sh = ldv<NTV>(h2 + i); else e.sh = e.s;
-        };
-        auto finish = [&](const Pair& e, long long i) {
-            const Elem o0 = step(e.x.x, e.ph.x, e.sh.x, e.s.x, e.t.x, e.rh.x), o1 = step(e.x.y, e.ph.y, e.sh.y, e.s.y, e.t.y, e.rh.y);
-            d2 o;
-            o.x = o0.x; o.y = o1.x; stv<NTV>(o, x2 + i);
-            o.x = o0.r; o.y = o1.r; stv<NTV>(o, r2 + i);
-        };
-        chunk_pairs(a.n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair e0, e1;
-            load(e0, i); load(e1, j);
-            finish(e0, i);
-            if (two) finish(e1, j);
-        });
-        if ((a.n & 1) && publisher) one(a.n - 1);
-    } else {
-        grid_stride<false>(a.n, [&](long long) {}, one);
-    }
+    d2* x2 = (d2*)a.x; d2* r2 = (d2*)a.r;
+    const d2* p2 = (const d2*)a.phat; const d2* h2 = (const d2*)a.shat; const d2* s2 = (const d2*)a.s;
+    const d2* t2 = (const d2*)a.t; const d2* g2 = (const d2*)a.rhat;
+    struct Pair { d2 x, ph, sh, s, t, rh; };
+    auto load = [&](Pair& e, long long i) {
+        e.x = ldv<NTV>(x2 + i); e.ph = ldv<NTV>(p2 + i); e.s = ldv<NTV>(s2 + i); e.t = ldv<NTV>(t2 + i); e.rh = ldv<NTV>(g2 + i);
+        if constexpr (HATTED) e.sh = ldv<NTV>(h2 + i); else e.sh = e.s;
+    };
+    auto finish = [&](const Pair& e, long long i) {
+        const Elem o0 = step(e.x.x, e.ph.x, e.sh.x, e.s.x, e.t.x, e.rh.x), o1 = step(e.x.y, e.ph.y, e.sh.y, e.s.y, e.t.y, e.rh.y);
+        d2 o;
+        o.x = o0.x; o.y = o1.x; stv<NTV>(o, x2 + i);
+        o.x = o0.r; o.y = o1.r; stv<NTV>(o, r2 + i);
+    };
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
     const double sr = block_sum(accR, s_red);
     const double sh = block_sum(accH, s_red2);
     if (threadIdx.x == 0) { a.outA[blockIdx.x] = sr; a.outB[blockIdx.x] = sh; }
@@ -219,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void bicgstab_p_kernel(BicgstabPass a)
     if (a.bs->fDone != 0) return;                      // the flag as pass S found it: this pass raises the live one itself
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
     if (a.bs->brokeS != 0 || a.bs->brokeX != 0) {      // sigma or omega broke down: x is the iterate of the body before
-        if (publisher) bicgstab_breakdown(a);
+        if (publisher) publish_breakdown(a.f, a.k + 1);
         return;
     }
     double rr, rhon;
@@ -228,7 +185,7 @@ __global__ __launch_bounds__(kBlock) void bicgstab_p_kernel(BicgstabPass a)
     const int k = a.k;
     const double omega = a.bs->omega, alpha = a.bs->alpha, rho = a.bs->rho[k & 1];
     StopDecision d = decide_stop(a.f, rr, 0.0, a.f.sc->rr0, k + 1);
-    if (!d.stop && (omega == 0.0 || rhon == 0.0 || !bicgstab_finite(rhon))) { d.stop = true; d.status = MGCG_NONFINITE; }   // x IS this body's iterate
+    if (!d.stop && (omega == 0.0 || rhon == 0.0 || !finite_value(rhon))) { d.stop = true; d.status = MGCG_NONFINITE; }   // x IS this body's iterate
     const double q1 = rhon / rho, q2 = alpha / omega;
     const double beta = q1 * q2;
     if (publisher) publish_iteration<0>(a.f, d, k + 1, rr, 0.0, 0, [&] { a.bs->rho[(k + 1) & 1] = rhon; a.f.sc->beta = beta; });
@@ -239,27 +196,16 @@ __global__ __launch_bounds__(kBlock) void bicgstab_p_kernel(BicgstabPass a)
         a.p[i] = p;
         if constexpr (DINV) a.phat[i] = a.dinv[i] * p;
     };
-    if constexpr (V2) {
-        const d2* r2 = (const d2*)a.r; const d2* v2 = (const d2*)a.v; const d2* d2p = (const d2*)a.dinv;
-        d2* p2 = (d2*)a.p; d2* h2 = (d2*)a.phat;
-        struct Pair { d2 r, p, v, d; };
-        auto load = [&](Pair& e, long long i) { e.d = {}; e.r = ldv<NTV>(r2 + i); e.p = ldv<NTV>(p2 + i); e.v = ldv<NTV>(v2 + i); if constexpr (DINV) e.d = ldv<NTV>(d2p + i); };
-        auto finish = [&](const Pair& e, long long i) {
-            d2 o; o.x = step(e.r.x, e.p.x, e.v.x); o.y = step(e.r.y, e.p.y, e.v.y);
-            stv<NTV>(o, p2 + i);
-            if constexpr (DINV) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, h2 + i); }
-        };
-        chunk_pairs(a.n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair e0, e1;
-            load(e0, i); load(e1, j);
-            finish(e0, i);
-            if (two) finish(e1, j);
-        });
-        if ((a.n & 1) && publisher) one(a.n - 1);
-    } else {
-        grid_stride<false>(a.n, [&](long long) {}, one);
-    }
+    const d2* r2 = (const d2*)a.r; const d2* v2 = (const d2*)a.v; const d2* d2p = (const d2*)a.dinv;
+    d2* p2 = (d2*)a.p; d2* h2 = (d2*)a.phat;
+    struct Pair { d2 r, p, v, d; };
+    auto load = [&](Pair& e, long long i) { e.d = {}; e.r = ldv<NTV>(r2 + i); e.p = ldv<NTV>(p2 + i); e.v = ldv<NTV>(v2 + i); if constexpr (DINV) e.d = ldv<NTV>(d2p + i); };
+    auto finish = [&](const Pair& e, long long i) {
+        d2 o; o.x = step(e.r.x, e.p.x, e.v.x); o.y = step(e.r.y, e.p.y, e.v.y);
+        stv<NTV>(o, p2 + i);
+        if constexpr (DINV) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, h2 + i); }
+    };
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 // The start behind r = b - A x: rhat = r, p = r, phat = dinv * r (HAT_STORED: phat is left to the cycle) and the partial sums of r.r.  Once
@@ -288,20 +234,9 @@ __global__ __launch_bounds__(kBlock) void bicgstab_init_kernel(const double* __r
     if (reduceFirst) rr0 = reduce_partials_block(partials, n, s_red, 0);
     if (threadIdx.x != 0) return;
     if (!reduceFirst) rr0 = bs->red[3];
-    const double res0 = sqrt(rr0);
-    CgScalars* sc = f.sc;
-    sc->rr = rr0; sc->rr0 = rr0; sc->pAp = 0; sc->rrNew = rr0; sc->rzNew = 0; sc->residual = res0; sc->nrmInf = 0;
-    sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = MGCG_OK; sc->pad = 0;
-    sc->fRr = rr0; sc->fRr0 = rr0; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
-    f.mirror->residual = res0; f.mirror->iteration = 0; f.mirror->status = MGCG_OK; f.mirror->done = 0;
-    if (f.trace != nullptr && f.traceCap > 0) f.trace[0] = f.rule == MGCG_RULE_VIENNACL ? sqrt(rr0 / rr0) : res0;
+    publish_start(f, rr0, sqrt(rr0));
     bs->fDone = 0; bs->brokeS = 0; bs->brokeX = 0; bs->alpha = 0.0; bs->omega = 0.0; bs->rho[0] = rr0; bs->rho[1] = 0.0;
-    if (!(rr0 > 0.0 && rr0 <= 1.79e308)) {             // b - A x is zero or not finite
-        sc->done = 1; sc->status = MGCG_NONFINITE;
-        f.mirror->status = MGCG_NONFINITE;
-        __threadfence_system();
-        f.mirror->done = 1;
-    }
+    if (!positive_finite(rr0)) refuse_start(f);        // b - A x is zero or not finite
 }
 
 int bicgstab_enqueue_start(const BicgstabRun& R)
@@ -310,7 +245,7 @@ int bicgstab_enqueue_start(const BicgstabRun& R)
     double* partials = bicgstab_rr_partials(R.ws);
     const int grid = grid_for(R.n, 2);
     const long long n = R.n < 0 ? 0 : R.n;
-    bicgstab_with_hat(R, [&](auto HAT) {
+    with_hat(R.dinv, R.stored, [&](auto HAT) {
         hipLaunchKernelGGL((bicgstab_start_kernel<HAT.value>), dim3(grid), dim3(kBlock), 0, s, (const double*)R.r, R.rhat, R.p, R.phat, R.dinv, n, partials);
     });
     if (dot_reference_order()) { launch_dot_serial(s, R.r, R.r, n, partials, nullptr); return 1; }   // the sum in the reference's order replaces the partial sums
@@ -334,7 +269,7 @@ static BicgstabPass bicgstab_pass_args(const BicgstabRun& R, const FinalizeArgs&
 template <typename Go> static void bicgstab_with_form(const BicgstabRun& R, bool v2, Go go)
 {
     with_v2_nt(v2, vec_nt(R.n), [&](auto V2, auto NTV) {
-        with_flags([&](auto GIVEN) { bicgstab_with_hat(R, [&](auto HAT) { go(V2, NTV, GIVEN, HAT); }); }, R.given);
+        with_flags([&](auto GIVEN) { with_hat(R.dinv, R.stored, [&](auto HAT) { go(V2, NTV, GIVEN, HAT); }); }, R.given);
     });
 }
 

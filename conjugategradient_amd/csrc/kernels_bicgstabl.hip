@@ -76,11 +76,8 @@ struct BicgstablPass {
     long long n;
 };
 
-// Who forms hat(v) = M^-1 v: nobody (M = I: the products gather from u_j and r_j themselves) or the passes (dinv * value per element, stored
-// in the gather buffer for the next product).  One template parameter of every pass.
-enum : int { HAT_NONE = 0, HAT_DINV = 1 };
-
-__device__ __forceinline__ bool bicgstabl_finite(double v) { return fabs(v) <= 1.79e308; }
+// HAT (vec_passes.hpp), one template parameter of every pass: who forms hat(v) = M^-1 v -- nobody (M = I: the products gather from u_j and r_j
+// themselves) or the passes (dinv * value per element, stored in the gather buffer for the next product).  HAT_STORED has no form here.
 // a pass R_j in front of step `upto` of this body met a breakdown (upto = kBicgstablMaxL: any)
 template <int UPTO = kBicgstablMaxL>
 __device__ __forceinline__ bool bicgstabl_broke(const BicgstablScalars* bs)
@@ -98,25 +95,6 @@ __device__ __forceinline__ bool bicgstabl_early(const BicgstablScalars* bs)
 #pragma unroll
     for (int j = 0; j < UPTO; ++j) any |= bs->early[j];
     return any != 0;
-}
-
-// The chunked 16-byte driver of every pass here: load(e, i) fills a Pair for pair index i, finish(e, i) computes and stores it, one(i) is the
-// element-wise form.  Two pairs per array in flight per lane; the odd tail goes to the first thread.
-template <bool V2, typename Pair, typename Load, typename Finish, typename One>
-__device__ __forceinline__ void bicgstabl_stream(long long n, bool publisher, Load load, Finish finish, One one)
-{
-    if constexpr (V2) {
-        chunk_pairs(n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair e0, e1;
-            load(e0, i); load(e1, j);
-            finish(e0, i);
-            if (two) finish(e1, j);
-        });
-        if ((n & 1) && publisher) one(n - 1);
-    } else {
-        grid_stride<false>(n, [&](long long) {}, one);
-    }
 }
 
 template <bool V2, bool NTV, int HAT, int J>
@@ -164,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_u_kernel(BicgstablPass a)
             if constexpr (DINV) if (q == J) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, (d2*)a.gather + i); }
         }
     };
-    bicgstabl_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 template <bool V2, bool NTV, int HAT, int J>
@@ -183,7 +161,7 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_r_kernel(BicgstablPass a)
     const double sigma = reduce_partials_block(a.in, a.nIn, s_red, 0);
     const double rho = a.bs->rho[a.k & 1][J];
     const double alpha = rho / sigma;
-    if (sigma == 0.0 || !bicgstabl_finite(sigma) || !bicgstabl_finite(alpha)) {
+    if (sigma == 0.0 || !finite_value(sigma) || !finite_value(alpha)) {
         if (publisher) a.bs->broke[J] = 1;
         return;
     }
@@ -225,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_r_kernel(BicgstablPass a)
             if constexpr (DINV) if (q == J) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, (d2*)a.gather + i); }
         }
     };
-    bicgstabl_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
     const double sr = block_sum(accR, s_red);
     if (threadIdx.x == 0) a.outA[blockIdx.x] = sr;
 }
@@ -287,7 +265,7 @@ __device__ __forceinline__ int bicgstabl_gamma(const double* Z, double* g)
         double s = Z[bicgstabl_entry(i + 1, i + 1)];
 #pragma unroll
         for (int q = 0; q < i; ++q) { double t = C[i][q] * C[i][q]; s = s - t; }
-        live = live && s > 0.0 && bicgstabl_finite(s);
+        live = live && s > 0.0 && finite_value(s);
         if (live) m = i + 1;
         C[i][i] = sqrt(s);
     }
@@ -367,19 +345,10 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_combine_kernel(BicgstablPass
         o.x = o0.x; o.y = o1.x; stv<NTV>(o, (d2*)a.x + i);
         o.x = o0.r; o.y = o1.r; stv<NTV>(o, (d2*)a.r[0] + i);
     };
-    bicgstabl_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
     const double sr = block_sum(accR, s_red[NE]);
     const double sh = block_sum(accH, s_red[NE + 1]);
     if (threadIdx.x == 0) { a.outA[blockIdx.x] = sr; a.outB[blockIdx.x] = sh; }
-}
-
-// A breakdown in front of a step's updates (pass P, one thread): the last judged residual once more, for iteration k + 1
-__device__ __forceinline__ void bicgstabl_breakdown(const BicgstablPass& a)
-{
-    StopDecision d;
-    const double rrOld = a.f.sc->rrNew, rr0 = a.f.sc->rr0;
-    d.res = sqrt(rrOld); d.shown = a.f.rule == MGCG_RULE_VIENNACL ? sqrt(rrOld / rr0) : d.res; d.stop = true; d.status = MGCG_NONFINITE;
-    publish_iteration<0>(a.f, d, a.k + 1, rrOld, 0.0, 0, [] {});
 }
 
 template <bool V2, bool NTV, int HAT>
@@ -390,7 +359,7 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_p_kernel(BicgstablPass a)
     if (a.bs->fDone != 0) return;                      // the flag as pass R_0 found it: this pass raises the live one itself
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
     if (bicgstabl_broke(a.bs)) {                       // sigma or alpha broke down in step j: x and r_0 are what steps 0 .. j-1 made them
-        if (publisher) bicgstabl_breakdown(a);
+        if (publisher) publish_breakdown(a.f, a.k + 1);
         return;
     }
     if (bicgstabl_early(a.bs)) {                       // r_0 met the stop test in front of a step: the body ended there
@@ -406,7 +375,7 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_p_kernel(BicgstablPass a)
     const int k = a.k;
     const double omega = a.bs->omega, alpha = a.bs->alpha, rho = a.bs->rho[k & 1][a.ell - 1];
     StopDecision d = decide_stop(a.f, rr, 0.0, a.f.sc->rr0, k + 1);
-    if (!d.stop && (omega == 0.0 || rhon == 0.0 || !bicgstabl_finite(rhon))) { d.stop = true; d.status = MGCG_NONFINITE; }   // x IS this body's iterate
+    if (!d.stop && (omega == 0.0 || rhon == 0.0 || !finite_value(rhon))) { d.stop = true; d.status = MGCG_NONFINITE; }   // x IS this body's iterate
     const double mo = -omega;
     const double den = mo * rho;
     const double q = rhon / den;
@@ -429,7 +398,7 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_p_kernel(BicgstablPass a)
         stv<NTV>(o, (d2*)a.u[0] + i);
         if constexpr (DINV) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, (d2*)a.gather + i); }
     };
-    bicgstabl_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 // The scalars in front of body 0 (one workgroup)
@@ -438,23 +407,12 @@ __global__ __launch_bounds__(kBlock) void bicgstabl_init_kernel(const double* __
     __shared__ double s_red[4];
     const double rr0 = reduce_partials_block(partials, n, s_red, 0);
     if (threadIdx.x != 0) return;
-    const double res0 = sqrt(rr0);
-    CgScalars* sc = f.sc;
-    sc->rr = rr0; sc->rr0 = rr0; sc->pAp = 0; sc->rrNew = rr0; sc->rzNew = 0; sc->residual = res0; sc->nrmInf = 0;
-    sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = MGCG_OK; sc->pad = 0;
-    sc->fRr = rr0; sc->fRr0 = rr0; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
-    f.mirror->residual = res0; f.mirror->iteration = 0; f.mirror->status = MGCG_OK; f.mirror->done = 0;
-    if (f.trace != nullptr && f.traceCap > 0) f.trace[0] = f.rule == MGCG_RULE_VIENNACL ? sqrt(rr0 / rr0) : res0;
+    publish_start(f, rr0, sqrt(rr0));
     bs->red = 0.0; bs->alpha = 0.0; bs->omega = 0.0; bs->fDone = 0; bs->pivots = 0;
     for (int j = 0; j < kBicgstablMaxL; ++j) { bs->rho[0][j] = 0.0; bs->rho[1][j] = 0.0; bs->gamma[j] = 0.0; bs->broke[j] = 0; bs->early[j] = 0; }
     bs->rrEarly = 0.0;
     bs->rho[0][0] = rr0;
-    if (!(rr0 > 0.0 && rr0 <= 1.79e308)) {             // b - A x is zero or not finite
-        sc->done = 1; sc->status = MGCG_NONFINITE;
-        f.mirror->status = MGCG_NONFINITE;
-        __threadfence_system();
-        f.mirror->done = 1;
-    }
+    if (!positive_finite(rr0)) refuse_start(f);        // b - A x is zero or not finite
 }
 
 void bicgstabl_enqueue_init(Workspace* ws, const FinalizeArgs& f, int nPartials)
@@ -492,8 +450,7 @@ template <int LO, int HI, typename Go> static void bicgstabl_with_int(int v, Go 
 template <typename Go> static void bicgstabl_with_form(const BicgstablRun& R, bool v2, Go go)
 {
     with_v2_nt(v2, vec_nt(R.n), [&](auto V2, auto NTV) {
-        if (R.dinv) go(V2, NTV, std::integral_constant<int, HAT_DINV>{});
-        else go(V2, NTV, std::integral_constant<int, HAT_NONE>{});
+        with_hat(R.dinv, [&](auto HAT) { go(V2, NTV, HAT); });
     });
 }
 

@@ -86,7 +86,6 @@ __device__ __forceinline__ void cheb_publish_breakdown(const FinalizeArgs& f, in
     __threadfence_system();
     f.mirror->done = 1;
 }
-__device__ __forceinline__ bool cheb_positive(double v) { return v > 0.0 && v <= 1.79e308; }
 
 // ------------------------------------------------------------------ the scalars in front of iteration 0 (one workgroup)
 __global__ __launch_bounds__(kBlock) void cheb_init_scalars_kernel(const double* __restrict__ partials, int n, const double* __restrict__ partialsZ, int nZ,
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void cheb_init_scalars_kernel(const double*
     sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = 0; sc->pad = 0;
     sc->fRr = rz; sc->fRr0 = rr; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
     f.mirror->residual = 0; f.mirror->iteration = 0; f.mirror->status = 0; f.mirror->done = 0;
-    if (!cheb_positive(rz)) cheb_publish_breakdown(f, 0, rr, rr);     // an indefinite polynomial (upper bound below the spectrum), or r = 0
+    if (!positive_finite(rz)) cheb_publish_breakdown(f, 0, rr, rr);     // an indefinite polynomial (upper bound below the spectrum), or r = 0
 }
 void launch_cheb_init_scalars(hipStream_t s, const double* partials, int n, const double* partialsZ, int nZ, bool reduceFirst, const FinalizeArgs& f)
 {
@@ -137,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void cheb_first_kernel(FinalizeArgs f, doub
     } else {
         pAp = sc->pAp;
     }
-    if (!cheb_positive(pAp)) {
+    if (!positive_finite(pAp)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) { sc->pAp = pAp; cheb_publish_breakdown(f, sc->iteration, sc->rrNew, sc->rr0); }
         return;
     }
@@ -224,7 +223,7 @@ __global__ __launch_bounds__(kBlock) void cheb_finalize_kernel(const double* __r
     if (!reduceFirst) { rrNew = sc->rrNew; rzNew = sc->rzNew; }
     const int it = sc->iteration;
     const StopDecision d = decide_stop(f, rrNew, 0.0, sc->rr0, it);
-    if (!d.stop && !cheb_positive(rzNew)) {
+    if (!d.stop && !positive_finite(rzNew)) {
         if (f.trace != nullptr && it < f.traceCap) f.trace[it] = d.shown;
         sc->rrNew = rrNew; sc->rzNew = rzNew; sc->nrmInf = 0; sc->pad = 1;
         cheb_publish_breakdown(f, it + 1, rrNew, sc->rr0);

@@ -78,27 +78,6 @@ struct GmresPass {
     long long stride, n;
 };
 
-__device__ __forceinline__ bool gmres_finite(double v) { return fabs(v) <= 1.79e308; }
-
-// The chunked 16-byte driver of the passes here, as in kernels_bicgstabl.hip: load(e, i) fills a Pair for pair index i, finish(e, i) computes
-// and stores it, one(i) is the element-wise form.  Two pairs per array in flight per lane; the odd tail goes to the first thread.
-template <bool V2, typename Pair, typename Load, typename Finish, typename One>
-__device__ __forceinline__ void gmres_stream(long long n, bool publisher, Load load, Finish finish, One one)
-{
-    if constexpr (V2) {
-        chunk_pairs(n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair e0, e1;
-            load(e0, i); load(e1, j);
-            finish(e0, i);
-            if (two) finish(e1, j);
-        });
-        if ((n & 1) && publisher) one(n - 1);
-    } else {
-        grid_stride<false>(n, [&](long long) {}, one);
-    }
-}
-
 // dot_order = 1: the first launch of a step, in place of the first dots launch
 __global__ void gmres_freeze_kernel(const CgScalars* sc, GmresScalars* gs) { gs->fDone = sc->done; }
 
@@ -195,7 +174,7 @@ __global__ __launch_bounds__(kBlock) void gmres_update_kernel(GmresPass a)
         stv<NTV>(o, (d2*)a.w + i);
         if constexpr (SUMS) { double s0 = o.x * o.x; double s1 = o.y * o.y; accW += s0; accW += s1; }
     };
-    gmres_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
     if constexpr (SUMS) {
         const double sw = block_sum(accW, s_red);
         if (threadIdx.x == 0) a.out[blockIdx.x] = sw;
@@ -246,13 +225,8 @@ __global__ __launch_bounds__(kBlock) void gmres_n_kernel(GmresPass a)
         double p1 = hjj * hjj, p2 = hn * hn;
         const double dd = p1 + p2;
         const double d = sqrt(dd);
-        if (!gmres_finite(hn2) || d == 0.0 || !gmres_finite(d)) {   // no next direction and no column: the last judged figure once more, for iteration k + 1
-            if (publisher) {
-                StopDecision e;
-                const double rrOld = a.f.sc->rrNew, rr0 = a.f.sc->rr0;
-                e.res = sqrt(rrOld); e.shown = a.f.rule == MGCG_RULE_VIENNACL ? sqrt(rrOld / rr0) : e.res; e.stop = true; e.status = MGCG_NONFINITE;
-                publish_iteration<0>(a.f, e, k + 1, rrOld, 0.0, 0, [] {});
-            }
+        if (!finite_value(hn2) || d == 0.0 || !finite_value(d)) {   // no next direction and no column: the last judged figure once more, for iteration k + 1
+            if (publisher) publish_breakdown(a.f, k + 1);
             s_end = 1;
         } else {
             const double c = hjj / d, s = hn / d;
@@ -291,7 +265,7 @@ __global__ __launch_bounds__(kBlock) void gmres_n_kernel(GmresPass a)
         stv<NTV>(o, (d2*)vn + i);
         if constexpr (DINV) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, (d2*)a.gather + i); }
     };
-    gmres_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 // The scalars in front of step 0 (one workgroup), from the partial sums of the first r.r
@@ -300,20 +274,9 @@ __global__ __launch_bounds__(kBlock) void gmres_init_kernel(const double* __rest
     __shared__ double s_red[4];
     const double rr0 = reduce_partials_block(partials, n, s_red, 0);
     if (threadIdx.x != 0) return;
-    const double res0 = sqrt(rr0);
-    CgScalars* sc = f.sc;
-    sc->rr = rr0; sc->rr0 = rr0; sc->pAp = 0; sc->rrNew = rr0; sc->rzNew = 0; sc->residual = res0; sc->nrmInf = 0;
-    sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = MGCG_OK; sc->pad = 0;
-    sc->fRr = rr0; sc->fRr0 = rr0; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
-    f.mirror->residual = res0; f.mirror->iteration = 0; f.mirror->status = MGCG_OK; f.mirror->done = 0;
-    if (f.trace != nullptr && f.traceCap > 0) f.trace[0] = f.rule == MGCG_RULE_VIENNACL ? sqrt(rr0 / rr0) : res0;
+    publish_start(f, rr0, sqrt(rr0));
     gs->red = 0.0; gs->gLast[0] = 0.0; gs->gLast[1] = 0.0; gs->fDone = 0; gs->note = 0; gs->cols = 0; gs->yCount = 0;
-    if (!(rr0 > 0.0 && rr0 <= 1.79e308)) {             // b - A x is zero or not finite
-        sc->done = 1; sc->status = MGCG_NONFINITE;
-        f.mirror->status = MGCG_NONFINITE;
-        __threadfence_system();
-        f.mirror->done = 1;
-    }
+    if (!positive_finite(rr0)) refuse_start(f);        // b - A x is zero or not finite
 }
 
 // beta = sqrt(r.r) ; v_0 = r / beta ; gather = dinv v_0 ; g_0 = beta, where step k will look for it.  Gated on the live flag.
@@ -324,7 +287,7 @@ __global__ __launch_bounds__(kBlock) void gmres_restart_kernel(GmresPass a)
     if (a.f.sc->done != 0) return;                     // nobody writes it while this launch runs
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
     const double beta2 = reduce_partials_block(a.in, a.nIn, s_red, 0);
-    if (!a.first && (beta2 == 0.0 || !gmres_finite(beta2))) {   // (the start's own r.r was judged by gmres_init_kernel)
+    if (!a.first && (beta2 == 0.0 || !finite_value(beta2))) {   // (the start's own r.r was judged by gmres_init_kernel)
         if (publisher) a.gs->note = beta2 == 0.0 ? 1 : 2;
         return;
     }
@@ -345,7 +308,7 @@ __global__ __launch_bounds__(kBlock) void gmres_restart_kernel(GmresPass a)
         stv<NTV>(o, (d2*)a.V + i);
         if constexpr (DINV) { d2 h; h.x = e.d.x * o.x; h.y = e.d.y * o.y; stv<NTV>(h, (d2*)a.gather + i); }
     };
-    gmres_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 // The close's first launch (one workgroup, not gated): y = R^-1 g over the completed columns, backwards; yCount = cols ; cols = 0
@@ -415,7 +378,7 @@ __global__ __launch_bounds__(kBlock) void gmres_x_kernel(GmresPass a)
         d2 o; o.x = e.x.x + h.x; o.y = e.x.y + h.y;
         stv<NTV>(o, (d2*)a.x + i);
     };
-    gmres_stream<V2, Pair>(a.n, publisher, load, finish, one);
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 static GmresPass gmres_pass_args(const GmresRun& R, const FinalizeArgs& f, int k, int j)

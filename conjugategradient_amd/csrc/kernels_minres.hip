@@ -72,22 +72,11 @@ __global__ __launch_bounds__(kBlock) void minres_lanczos_kernel(MinresPass a)
         return y;
     };
     auto one = [&](long long i) { a.y[i] = step(a.q[i], a.v[i], first ? 0.0 : a.y[i]); };
-    if constexpr (V2) {
-        const d2* q2 = (const d2*)a.q; const d2* v2 = (const d2*)a.v; d2* y2 = (d2*)a.y;
-        struct Pair { d2 q, v, p; };
-        auto load = [&](Pair& e, long long i) { e.p = {}; e.q = ldv<NTV>(q2 + i); e.v = ldv<NTV>(v2 + i); if (!first) e.p = ldv<NTV>(y2 + i); };
-        auto finish = [&](const Pair& e, long long i) { d2 o; o.x = step(e.q.x, e.v.x, e.p.x); o.y = step(e.q.y, e.v.y, e.p.y); stv<NTV>(o, y2 + i); };
-        chunk_pairs(a.n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair e0, e1;
-            load(e0, i); load(e1, j);
-            finish(e0, i);
-            if (two) finish(e1, j);
-        });
-        if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(a.n - 1);
-    } else {
-        grid_stride<false>(a.n, [&](long long) {}, one);
-    }
+    const d2* q2 = (const d2*)a.q; const d2* v2 = (const d2*)a.v; d2* y2 = (d2*)a.y;
+    struct Pair { d2 q, v, p; };
+    auto load = [&](Pair& e, long long i) { e.p = {}; e.q = ldv<NTV>(q2 + i); e.v = ldv<NTV>(v2 + i); if (!first) e.p = ldv<NTV>(y2 + i); };
+    auto finish = [&](const Pair& e, long long i) { d2 o; o.x = step(e.q.x, e.v.x, e.p.x); o.y = step(e.q.y, e.v.y, e.p.y); stv<NTV>(o, y2 + i); };
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
     const double t = block_sum(acc, s_red2);
     if (threadIdx.x == 0) a.outPartials[blockIdx.x] = t;
 }
@@ -117,8 +106,7 @@ __global__ __launch_bounds__(kBlock) void minres_update_kernel(MinresPass a)
     const double ig = 1.0 / gamma;
     const double cs = gbar * ig, sn = betan * ig;
     const double phi = cs * st.phibar, phibar = sn * st.phibar;
-    auto finite = [](double v) { return fabs(v) <= 1.79e308; };
-    if (!finite(gamma) || !finite(ig) || !finite(phi) || gamma == 0.0) {      // breakdown: before this body's updates
+    if (!finite_value(gamma) || !finite_value(ig) || !finite_value(phi) || gamma == 0.0) {      // breakdown: before this body's updates
         if (publisher) {
             StopDecision d;
             const double rrOld = st.phibar * st.phibar;
@@ -156,35 +144,24 @@ __global__ __launch_bounds__(kBlock) void minres_update_kernel(MinresPass a)
         step(e);
         a.y[i] = e.y; a.w1[i] = e.w1; a.x[i] = e.x;
     };
-    if constexpr (V2) {
-        d2* y2 = (d2*)a.y; d2* w12 = (d2*)a.w1; d2* x2 = (d2*)a.x;
-        const d2* v2 = (const d2*)a.v; const d2* w22 = (const d2*)a.w2;
-        struct Pair { d2 y, v, w1, w2, x; };
-        auto load = [&](Pair& p, long long i) {
-            p.w1 = {}; p.w2 = {};
-            p.y = ldv<NTV>(y2 + i); p.v = ldv<NTV>(v2 + i); p.x = ldv<NTV>(x2 + i);
-            if (hasW1) p.w1 = ldv<NTV>(w12 + i);
-            if (hasW2) p.w2 = ldv<NTV>(w22 + i);
-        };
-        auto finish = [&](const Pair& p, long long i) {
-            Elem e0 = { p.y.x, p.v.x, p.w1.x, p.w2.x, p.x.x }, e1 = { p.y.y, p.v.y, p.w1.y, p.w2.y, p.x.y };
-            step(e0); step(e1);
-            d2 o;
-            o.x = e0.y; o.y = e1.y; stv<NTV>(o, y2 + i);
-            o.x = e0.w1; o.y = e1.w1; stv<NTV>(o, w12 + i);
-            o.x = e0.x; o.y = e1.x; stv<NTV>(o, x2 + i);
-        };
-        chunk_pairs(a.n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair p0, p1;
-            load(p0, i); load(p1, j);
-            finish(p0, i);
-            if (two) finish(p1, j);
-        });
-        if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(a.n - 1);
-    } else {
-        grid_stride<false>(a.n, [&](long long) {}, one);
-    }
+    d2* y2 = (d2*)a.y; d2* w12 = (d2*)a.w1; d2* x2 = (d2*)a.x;
+    const d2* v2 = (const d2*)a.v; const d2* w22 = (const d2*)a.w2;
+    struct Pair { d2 y, v, w1, w2, x; };
+    auto load = [&](Pair& p, long long i) {
+        p.w1 = {}; p.w2 = {};
+        p.y = ldv<NTV>(y2 + i); p.v = ldv<NTV>(v2 + i); p.x = ldv<NTV>(x2 + i);
+        if (hasW1) p.w1 = ldv<NTV>(w12 + i);
+        if (hasW2) p.w2 = ldv<NTV>(w22 + i);
+    };
+    auto finish = [&](const Pair& p, long long i) {
+        Elem e0 = { p.y.x, p.v.x, p.w1.x, p.w2.x, p.x.x }, e1 = { p.y.y, p.v.y, p.w1.y, p.w2.y, p.x.y };
+        step(e0); step(e1);
+        d2 o;
+        o.x = e0.y; o.y = e1.y; stv<NTV>(o, y2 + i);
+        o.x = e0.w1; o.y = e1.w1; stv<NTV>(o, w12 + i);
+        o.x = e0.x; o.y = e1.x; stv<NTV>(o, x2 + i);
+    };
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
 }
 
 // The start and the closing pass: r = t + shift x (t = b - A x from the product's EPI_RESIDUAL epilogue), the product rounded first, and the
@@ -208,21 +185,11 @@ __global__ __launch_bounds__(kBlock) void minres_init_kernel(const double* __res
     if (threadIdx.x != 0) return;
     if (!reduceFirst) rr0 = ms->red[1];
     const double beta1 = sqrt(rr0);
-    CgScalars* sc = f.sc;
-    sc->rr = rr0; sc->rr0 = rr0; sc->pAp = 0; sc->rrNew = rr0; sc->rzNew = 0; sc->residual = beta1; sc->nrmInf = 0;
-    sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = MGCG_OK; sc->pad = 0;
-    sc->fRr = rr0; sc->fRr0 = rr0; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
-    f.mirror->residual = beta1; f.mirror->iteration = 0; f.mirror->status = MGCG_OK; f.mirror->done = 0;
-    if (f.trace != nullptr && f.traceCap > 0) f.trace[0] = f.rule == MGCG_RULE_VIENNACL ? sqrt(rr0 / rr0) : beta1;
+    publish_start(f, rr0, beta1);
     ms->fDone = 0;
     MinresScalars::State& o = ms->st[0];
     o.beta = 0.0; o.cs = -1.0; o.sn = 0.0; o.dbar = 0.0; o.eps = 0.0; o.phibar = beta1;
-    if (!(rr0 > 0.0 && rr0 <= 1.79e308)) {             // nothing to normalise: b - (A - shift I) x is zero or not finite
-        sc->done = 1; sc->status = MGCG_NONFINITE;
-        f.mirror->status = MGCG_NONFINITE;
-        __threadfence_system();
-        f.mirror->done = 1;
-    }
+    if (!positive_finite(rr0)) refuse_start(f);        // nothing to normalise: b - (A - shift I) x is zero or not finite
 }
 
 // v = r * (1 / beta1), in place

@@ -72,31 +72,20 @@ __global__ __launch_bounds__(kBlock) void pminres_lanczos_kernel(PminresPass a)
     auto one = [&](long long i) {
         a.r1[i] = step(a.q[i], SHIFTED ? a.v[i] : 0.0, first ? 0.0 : a.r1[i], a.r2[i], JACOBI ? a.dinv[i] : 0.0);
     };
-    if constexpr (V2) {
-        const d2* q2 = (const d2*)a.q; const d2* v2 = (const d2*)a.v; d2* p2 = (d2*)a.r1; const d2* c2v = (const d2*)a.r2; const d2* d2v = (const d2*)a.dinv;
-        struct Pair { d2 q, v, p, c, d; };
-        auto load = [&](Pair& e, long long i) {
-            e.v = {}; e.p = {}; e.d = {};
-            e.q = ldv<NTV>(q2 + i); e.c = ldv<NTV>(c2v + i);
-            if constexpr (SHIFTED) e.v = ldv<NTV>(v2 + i);
-            if (!first) e.p = ldv<NTV>(p2 + i);
-            if constexpr (JACOBI) e.d = ldv<NTV>(d2v + i);
-        };
-        auto finish = [&](const Pair& e, long long i) {
-            d2 o; o.x = step(e.q.x, e.v.x, e.p.x, e.c.x, e.d.x); o.y = step(e.q.y, e.v.y, e.p.y, e.c.y, e.d.y);
-            stv<NTV>(o, p2 + i);
-        };
-        chunk_pairs(a.n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair e0, e1;
-            load(e0, i); load(e1, j);
-            finish(e0, i);
-            if (two) finish(e1, j);
-        });
-        if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(a.n - 1);
-    } else {
-        grid_stride<false>(a.n, [&](long long) {}, one);
-    }
+    const d2* q2 = (const d2*)a.q; const d2* v2 = (const d2*)a.v; d2* p2 = (d2*)a.r1; const d2* c2v = (const d2*)a.r2; const d2* d2v = (const d2*)a.dinv;
+    struct Pair { d2 q, v, p, c, d; };
+    auto load = [&](Pair& e, long long i) {
+        e.v = {}; e.p = {}; e.d = {};
+        e.q = ldv<NTV>(q2 + i); e.c = ldv<NTV>(c2v + i);
+        if constexpr (SHIFTED) e.v = ldv<NTV>(v2 + i);
+        if (!first) e.p = ldv<NTV>(p2 + i);
+        if constexpr (JACOBI) e.d = ldv<NTV>(d2v + i);
+    };
+    auto finish = [&](const Pair& e, long long i) {
+        d2 o; o.x = step(e.q.x, e.v.x, e.p.x, e.c.x, e.d.x); o.y = step(e.q.y, e.v.y, e.p.y, e.c.y, e.d.y);
+        stv<NTV>(o, p2 + i);
+    };
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
     if constexpr (JACOBI) {
         const double t = block_sum(acc, s_red3);
         if (threadIdx.x == 0) a.outPartials[blockIdx.x] = t;
@@ -116,7 +105,6 @@ __global__ __launch_bounds__(kBlock) void pminres_update_kernel(PminresPass a)
     const bool publisher = blockIdx.x == 0 && threadIdx.x == 0;
     const MinresScalars::State st = a.ms->st[k & 1];
     const double rr0 = a.f.sc->rr0;
-    auto finite = [](double v) { return fabs(v) <= 1.79e308; };
     // the loop ends before this body's updates, repeating the last judged residual
     auto refuse = [&] {
         if (publisher) {
@@ -126,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void pminres_update_kernel(PminresPass a)
             publish_iteration<0>(a.f, d, k + 1, rrOld, 0.0, 0, [] {});
         }
     };
-    if (!(rz >= 0.0 && rz <= 1.79e308)) { refuse(); return; }                   // M is not positive definite on this residual, or a value that is not finite
+    if (!(rz >= 0.0 && rz <= kFiniteMax)) { refuse(); return; }                   // M is not positive definite on this residual, or a value that is not finite
     // the rotation, every product rounded before the add or subtraction that follows it, in the header's order
     const double sv = a.shift * vv; const double alpha = vq - sv;
     const double betan = sqrt(rz);
@@ -139,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void pminres_update_kernel(PminresPass a)
     const double ig = 1.0 / gamma;
     const double cs = gbar * ig, sn = betan * ig;
     const double phi = cs * st.phibar, phibar = sn * st.phibar;
-    if (!finite(gamma) || !finite(ig) || !finite(phi) || gamma == 0.0) { refuse(); return; }      // breakdown
+    if (!finite_value(gamma) || !finite_value(ig) || !finite_value(phi) || gamma == 0.0) { refuse(); return; }      // breakdown
     const double rr = phibar * phibar;
     StopDecision d = decide_stop(a.f, rr, 0.0, rr0, k + 1);
     const bool exhausted = betan == 0.0;                // the Krylov space is exhausted: the loop ends with this body
@@ -176,36 +164,25 @@ __global__ __launch_bounds__(kBlock) void pminres_update_kernel(PminresPass a)
         step(e);
         a.v[i] = e.v; a.w1[i] = e.w1; a.x[i] = e.x;
     };
-    if constexpr (V2) {
-        d2* v2 = (d2*)a.v; d2* w12 = (d2*)a.w1; d2* x2 = (d2*)a.x;
-        const d2* w22 = (const d2*)a.w2; const d2* z2 = (const d2*)zin; const d2* d2v = (const d2*)a.dinv;
-        struct Pair { d2 v, w1, w2, x, z, d; };
-        auto load = [&](Pair& p, long long i) {
-            p.w1 = {}; p.w2 = {}; p.d = {};
-            p.v = ldv<NTV>(v2 + i); p.x = ldv<NTV>(x2 + i); p.z = ldv<NTV>(z2 + i);
-            if constexpr (JACOBI) p.d = ldv<NTV>(d2v + i);
-            if (hasW1) p.w1 = ldv<NTV>(w12 + i);
-            if (hasW2) p.w2 = ldv<NTV>(w22 + i);
-        };
-        auto finish = [&](const Pair& p, long long i) {
-            Elem e0 = { p.v.x, p.w1.x, p.w2.x, p.x.x, p.z.x, p.d.x }, e1 = { p.v.y, p.w1.y, p.w2.y, p.x.y, p.z.y, p.d.y };
-            step(e0); step(e1);
-            d2 o;
-            o.x = e0.v; o.y = e1.v; stv<NTV>(o, v2 + i);
-            o.x = e0.w1; o.y = e1.w1; stv<NTV>(o, w12 + i);
-            o.x = e0.x; o.y = e1.x; stv<NTV>(o, x2 + i);
-        };
-        chunk_pairs(a.n >> 1, [&](long long i, bool two) {
-            const long long j = two ? i + kBlock : i;
-            Pair p0, p1;
-            load(p0, i); load(p1, j);
-            finish(p0, i);
-            if (two) finish(p1, j);
-        });
-        if ((a.n & 1) && blockIdx.x == 0 && threadIdx.x == 0) one(a.n - 1);
-    } else {
-        grid_stride<false>(a.n, [&](long long) {}, one);
-    }
+    d2* v2 = (d2*)a.v; d2* w12 = (d2*)a.w1; d2* x2 = (d2*)a.x;
+    const d2* w22 = (const d2*)a.w2; const d2* z2 = (const d2*)zin; const d2* d2v = (const d2*)a.dinv;
+    struct Pair { d2 v, w1, w2, x, z, d; };
+    auto load = [&](Pair& p, long long i) {
+        p.w1 = {}; p.w2 = {}; p.d = {};
+        p.v = ldv<NTV>(v2 + i); p.x = ldv<NTV>(x2 + i); p.z = ldv<NTV>(z2 + i);
+        if constexpr (JACOBI) p.d = ldv<NTV>(d2v + i);
+        if (hasW1) p.w1 = ldv<NTV>(w12 + i);
+        if (hasW2) p.w2 = ldv<NTV>(w22 + i);
+    };
+    auto finish = [&](const Pair& p, long long i) {
+        Elem e0 = { p.v.x, p.w1.x, p.w2.x, p.x.x, p.z.x, p.d.x }, e1 = { p.v.y, p.w1.y, p.w2.y, p.x.y, p.z.y, p.d.y };
+        step(e0); step(e1);
+        d2 o;
+        o.x = e0.v; o.y = e1.v; stv<NTV>(o, v2 + i);
+        o.x = e0.w1; o.y = e1.w1; stv<NTV>(o, w12 + i);
+        o.x = e0.x; o.y = e1.x; stv<NTV>(o, x2 + i);
+    };
+    stream_pairs<V2, Pair>(a.n, publisher, load, finish, one);
     const double t = block_sum(acc, s_red2);
     if (threadIdx.x == 0) a.outPartials[blockIdx.x] = t;
 }
@@ -237,22 +214,12 @@ __global__ __launch_bounds__(kBlock) void pminres_init_kernel(const double* __re
     if (threadIdx.x != 0) return;
     if (!reduceFirst) bz = ms->red[3];
     const double beta1 = sqrt(bz);
-    CgScalars* sc = f.sc;
-    sc->rr = bz; sc->rr0 = bz; sc->pAp = 0; sc->rrNew = bz; sc->rzNew = 0; sc->residual = beta1; sc->nrmInf = 0;
-    sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = MGCG_OK; sc->pad = 0;
-    sc->fRr = bz; sc->fRr0 = bz; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
-    f.mirror->residual = beta1; f.mirror->iteration = 0; f.mirror->status = MGCG_OK; f.mirror->done = 0;
-    if (f.trace != nullptr && f.traceCap > 0) f.trace[0] = f.rule == MGCG_RULE_VIENNACL ? sqrt(bz / bz) : beta1;
+    publish_start(f, bz, beta1);
     ms->fDone = 0;
     ms->red[4] = bz;                                    // for the host's message: a negative figure says that M is not positive definite
     MinresScalars::State& o = ms->st[0];
     o.beta = beta1; o.oldb = 0.0; o.cs = -1.0; o.sn = 0.0; o.dbar = 0.0; o.eps = 0.0; o.phibar = beta1;
-    if (!(bz > 0.0 && bz <= 1.79e308)) {               // nothing to normalise: the residual is zero, M is not positive definite, or a value is not finite
-        sc->done = 1; sc->status = MGCG_NONFINITE;
-        f.mirror->status = MGCG_NONFINITE;
-        __threadfence_system();
-        f.mirror->done = 1;
-    }
+    if (!positive_finite(bz)) refuse_start(f);         // nothing to normalise: the residual is zero, M is not positive definite, or a value is not finite
 }
 
 // v = z * (1 / beta1), z = dinv r (JACOBI) or the given vector, and the partial sums of v.v

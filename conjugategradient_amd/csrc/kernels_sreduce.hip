@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void sreduce_pass_kernel(SreducePass a)
     double beta = 0.0, den = delta;
     if (k > 0) { beta = gamma / gammaOld; const double t = beta * gamma; const double q = t / alphaOld; den = delta - q; }
     const double alpha = gamma / den;
-    if (!(den > 0.0 && den <= 1.79e308) || !(fabs(alpha) <= 1.79e308)) {       // breakdown: before this body's updates
+    if (!(den > 0.0 && den <= kFiniteMax) || !(fabs(alpha) <= kFiniteMax)) {   // breakdown: before this body's updates
         if (publisher) { d.stop = true; d.status = MGCG_NONFINITE; publish_iteration<0>(a.f, d, k, rr, 0.0, 0, [] {}); }
         return;
     }

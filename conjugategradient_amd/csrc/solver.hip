@@ -1049,6 +1049,19 @@ static bool cg_drive(CgRun& R, const char* who, Enqueue enqueueIteration, long l
     }, enqueuedOut);
 }
 
+// cg_drive for the variants' loops: body(k) enqueues body k and returns false when it could not; k is the host's count, which saturates at INT_MAX,
+// and the launches' errors are looked at behind every body.
+template <typename Body>
+static bool cg_drive_bodies(CgRun& R, const char* who, Body body)
+{
+    int k = 0;
+    return cg_drive(R, who, [&] {
+        if (!body(k)) return false;
+        if (k < 0x7fffffff) ++k;
+        return MGCG_HIP(hipGetLastError());
+    });
+}
+
 static int cg_solve(CgRun& R, int* iteration, double* residual, double* residualTrace, int traceCapacity)
 {
     hipStream_t s = R.ws->stream;
@@ -1184,18 +1197,28 @@ static bool cg_share_sums(CgRun& R, const double* pA, int nA, const double* pB, 
     return comm_allreduce_sum(R.comm, dst, pB ? 2 : 1, s);
 }
 
-// The closing step of MINRES, preconditioned MINRES and BiCGStab, behind the loop: t = b - A x through `full` into `out`; form() makes the
-// true residual of t and leaves the partial sums of its r.r in `partials`, returning their count; the sum into *dst -- folded on one rank
-// too: no pass follows that would -- and all-reduced on several; *rrTrue is read back behind it and holds once the stream has drained.
+// The close of MINRES, preconditioned MINRES, BiCGStab, BiCGStab(l) and GMRES, behind the loop (ok: all of it was enqueued): t = b - A x
+// through `full` into `out`; form() makes the true residual of t and leaves the partial sums of its r.r in `partials`, returning their count;
+// the sum into *dst -- folded on one rank too: no pass follows that would -- all-reduced on several, and read back behind it; also(), what
+// else the caller reads back; then the stream drained, *trueResidual (may be null) = the root of that sum, and cg_return_one's report.
 template <typename Form>
-static bool cg_enqueue_true_residual(CgRun& R, double* full, double* out, Form form, const double* partials, double* dst, double* rrTrue)
+static int cg_close_true_residual(CgRun& R, bool ok, const char* who, double* full, double* out, Form form, const double* partials, double* dst,
+                                  int devTraceCap, int* iteration, double* residual, double* trueResidual, double* residualTrace,
+                                  const char* inNorm, const char* nonfinite, const std::function<bool()>& also = nullptr)
 {
     hipStream_t s = R.ws->stream;
-    if (!cg_enqueue_residual(R, full, out)) return false;
-    const int nOut = form();
-    launch_reduce_to(s, partials, nOut, dst, nullptr);
-    if (R.multi && !comm_allreduce_sum(R.comm, dst, 1, s)) return false;
-    return MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(rrTrue, dst, sizeof(double), hipMemcpyDeviceToHost, s));
+    double rrTrue = 0.0;
+    ok = ok && cg_enqueue_residual(R, full, out);
+    if (ok) {
+        const int nOut = form();
+        launch_reduce_to(s, partials, nOut, dst, nullptr);
+        ok = (!R.multi || comm_allreduce_sum(R.comm, dst, 1, s)) && MGCG_HIP(hipGetLastError()) &&
+             MGCG_HIP(hipMemcpyAsync(&rrTrue, dst, sizeof(double), hipMemcpyDeviceToHost, s)) && (!also || also());
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
+    return cg_return_one(R, who, devTraceCap, iteration, residual, residualTrace, "residual", inNorm, nonfinite);
 }
 
 // The refusals and rules that the exports of the variants word alike.  A stop rule that is unknown or, with maxNormWhy (why this loop cannot
@@ -1207,6 +1230,8 @@ static bool cg_rule_refused(const char* who, int rule, const char* maxNormWhy)
     else return false;
     return true;
 }
+// The slices of a work vector (BiCGStab(l), GMRES(m)) lie this many entries apart: even, so that every slice stays 16-byte aligned
+static long long cg_work_stride(long long count) { return (count + 1) & ~1LL; }
 // A vector of fewer than `need` entries: true, refused.  of: what `need` counts ("local rows", "columns", "rows"), with a remark if there is one.
 static bool cg_vector_short(const char* who, const char* name, const Vector* v, int need, const char* of)
 {
@@ -1346,8 +1371,7 @@ static int cg_solve_sreduce(CgRun& R, double* sVec, int* iteration, double* resi
     if (ok) launch_init_scalars(s, rrPartials, gPartials, nIn, !R.multi, sc, ws->mirror);
     ok = ok && MGCG_HIP(hipGetLastError());
 
-    int k = 0;
-    ok = ok && cg_drive(R, "SolveSingleReduce", [&] {
+    ok = ok && cg_drive_bodies(R, "SolveSingleReduce", [&](int k) {
         int nDelta = 0;
         if (!cg_enqueue_product(R, R.p, &nDelta)) return false;                          // w = A u ; w.u
         if (R.multi) {
@@ -1355,8 +1379,7 @@ static int cg_solve_sreduce(CgRun& R, double* sVec, int* iteration, double* resi
             if (!comm_allreduce_sum(R.comm, ws->sreduceScalars->red, R.dinv ? 3 : 2, s)) return false;
         }
         nIn = sreduce_enqueue_pass(P, f, k, nDelta, nIn);
-        if (k < 0x7fffffff) ++k;
-        return MGCG_HIP(hipGetLastError());
+        return true;
     });
     if (ok && !R.dinv) launch_copy(s, R.r, uLoc, n);                                     // the residual into the caller's r
     ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
@@ -1377,7 +1400,6 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
                            double* residualTrace, int traceCapacity)
 {
     Workspace* ws = R.ws;
-    hipStream_t s = ws->stream;
     const long long n = R.nLocal;
     // everything the call allocates, before anything is enqueued
     FinalizeArgs f;
@@ -1398,8 +1420,7 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
     ok = ok && MGCG_HIP(hipGetLastError());
 
     double *v = bufR, *vprev = bufP, *w1 = w1Vec, *w2 = w2Vec;
-    int k = 0;
-    ok = ok && cg_drive(R, "SolveMinres", [&] {
+    ok = ok && cg_drive_bodies(R, "SolveMinres", [&](int k) {
         int nDelta = 0;
         R.p = v;                                                                         // the buffer whose halo the product exchanges
         if (!cg_enqueue_product(R, v, &nDelta)) return false;                            // q = A v ; v.q
@@ -1409,18 +1430,13 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
         if (R.multi && !cg_share_sums(R, yyPartials, nYY, nullptr, 0, &ms->red[1], done)) return false;
         minres_enqueue_update(P, f, k, nYY);                                             // w over w1 ; x ; vnext over y
         std::swap(v, vprev); std::swap(w1, w2);                                          // (vprev, v) := (v, vnext) ; (w1, w2) := (w2, w)
-        if (k < 0x7fffffff) ++k;
-        return MGCG_HIP(hipGetLastError());
+        return true;
     });
     R.p = bufP;
     // the closing product: the true residual t + shift x into the caller's r, whatever the parity of the rotation
-    double rrTrue = 0.0;
-    ok = ok && cg_enqueue_true_residual(R, bufP, R.Ap, [&] { return minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift); }, yyPartials, &ms->red[2], &rrTrue);
-    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    if (!ok) return MGCG_ERROR;
-    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    return cg_return_one(R, "SolveMinres", f.traceCap, iteration, residual, residualTrace, "residual", "",
-                         "the first residual is zero or not finite, or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)");
+    return cg_close_true_residual(R, ok, "SolveMinres", bufP, R.Ap, [&] { return minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift); }, yyPartials, &ms->red[2],
+                                  f.traceCap, iteration, residual, trueResidual, residualTrace, "",
+                                  "the first residual is zero or not finite, or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)");
 }
 
 // ---------------------------------------------------------------- BiCGStab (SolveBicgstab*, SolveBicgstabJacobi*)
@@ -1463,8 +1479,7 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
     }
     ok = ok && MGCG_HIP(hipGetLastError());
 
-    int k = 0;
-    ok = ok && cg_drive(R, who, [&] {
+    ok = ok && cg_drive_bodies(R, who, [&](int k) {
         int nSigma = 0, nTheta = 0;
         R.p = bufP; R.Ap = P.v;
         if (!cycle(P.p, P.phat)) return false;                                           // the V-cycle form: phat = M^-1 p
@@ -1479,18 +1494,13 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
         const int nRr = bicgstab_enqueue_x(P, f, k, nTheta, nTau);                       // omega ; x ; r ; rr, rhon
         if (R.multi && !cg_share_sums(R, bicgstab_rr_partials(ws), nRr, bicgstab_rho_partials(ws), nRr, &bs->red[3], done)) return false;
         bicgstab_enqueue_p(P, f, k, nRr);                                                // the stop decision ; beta ; p ; phat
-        if (k < 0x7fffffff) ++k;
-        return MGCG_HIP(hipGetLastError());
+        return true;
     });
     R.p = bufP; R.Ap = work;
     // the closing product: the true residual into the caller's r
-    double rrTrue = 0.0;
-    ok = ok && cg_enqueue_true_residual(R, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws)); }, bicgstab_rr_partials(ws), &bs->red[5], &rrTrue);
-    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    if (!ok) return MGCG_ERROR;
-    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", "",
-                         "the first residual is zero or not finite, or the recurrence broke down (rhat.v, omega or rhat.r zero, or a value that is not finite)");
+    return cg_close_true_residual(R, ok, who, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws)); }, bicgstab_rr_partials(ws), &bs->red[5],
+                                  f.traceCap, iteration, residual, trueResidual, residualTrace, "",
+                                  "the first residual is zero or not finite, or the recurrence broke down (rhat.v, omega or rhat.r zero, or a value that is not finite)");
 }
 
 // ---------------------------------------------------------------- BiCGStab(l) (SolveBicgstabL, SolveBicgstabLJacobi)
@@ -1501,7 +1511,6 @@ static int cg_solve_bicgstab(CgRun& R, const char* who, double* vVec, double* sV
 // r_0, its p u_0 and its Ap u_l; `work` holds r_1 .. r_l, u_1 .. u_{l-1}, rt and -- with a diagonal -- the one gather buffer, `stride` entries
 // apart.  Without a diagonal the products gather from u_j and r_j themselves.  One more product behind the loop leaves the true residual b - A x
 // in the caller's r.
-static long long bicgstabl_stride(long long count) { return (count + 1) & ~1LL; }            // even: every slice stays 16-byte aligned
 static int bicgstabl_slices(int ell, bool jacobi) { return 2 * ell + (jacobi ? 1 : 0); }
 static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, int* iteration, double* residual, double* trueResidual,
                               double* residualTrace, int traceCapacity)
@@ -1513,7 +1522,7 @@ static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, 
     FinalizeArgs f;
     if (!ws->ensure_bicgstabl() || !cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
     double* const bufP = R.p; double* const bufAp = R.Ap;
-    const long long stride = bicgstabl_stride(R.count);
+    const long long stride = cg_work_stride(R.count);
     BicgstablRun P{};
     P.ws = ws; P.ell = ell; P.x = R.x; P.dinv = R.dinv; P.n = n;
     P.r[0] = R.r; P.u[0] = bufP; P.u[ell] = bufAp;
@@ -1537,8 +1546,7 @@ static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, 
         R.p = from; R.Ap = out;
         return cg_enqueue_product(R, from, nSums, P.rt);
     };
-    int k = 0;
-    ok = ok && cg_drive(R, who, [&] {
+    ok = ok && cg_drive_bodies(R, who, [&](int k) {
         int nSums = 0, nRrStep = 0;
         for (int j = 0; j < ell; ++j) {
             if (j > 0) bicgstabl_enqueue_u(P, f, k, j, nSums, nRrStep);                  // the stop test on r_0 ; beta ; u_0 .. u_j ; hat(u_j)
@@ -1549,18 +1557,13 @@ static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, 
         const int nGram = bicgstabl_enqueue_gram(P);                                     // Z
         const int nRr = bicgstabl_enqueue_combine(P, f, k, nGram);                       // gamma ; u_0 ; x ; r_0 ; rr, rhon
         bicgstabl_enqueue_p(P, f, k, nRr);                                               // the stop decision ; beta ; u_0 ; hat(u_0)
-        if (k < 0x7fffffff) ++k;
-        return MGCG_HIP(hipGetLastError());
+        return true;
     });
     R.p = bufP; R.Ap = bufAp;
     // the closing product: the true residual into the caller's r
-    double rrTrue = 0.0;
-    ok = ok && cg_enqueue_true_residual(R, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws)); }, bicgstab_rr_partials(ws), &ws->bicgstablScalars->red, &rrTrue);
-    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    if (!ok) return MGCG_ERROR;
-    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", "",
-                         "the first residual is zero or not finite, or the recurrence broke down (rt.u_{j+1}, omega or rt.r_0 zero, or a value that is not finite)");
+    return cg_close_true_residual(R, ok, who, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, bicgstab_rr_partials(ws)); }, bicgstab_rr_partials(ws), &ws->bicgstablScalars->red,
+                                  f.traceCap, iteration, residual, trueResidual, residualTrace, "",
+                                  "the first residual is zero or not finite, or the recurrence broke down (rt.u_{j+1}, omega or rt.r_0 zero, or a value that is not finite)");
 }
 
 // ---------------------------------------------------------------- GMRES(m) (SolveGmres, SolveGmresJacobi)
@@ -1585,7 +1588,7 @@ static int cg_solve_gmres(CgRun& R, const char* who, int m, int orth, double* wo
     if (!ws->ensure_gmres() || !cg_variant_begin(R, 0, residualTrace, traceCapacity, &f)) return MGCG_ERROR;
     const int* done = &ws->scalars->done;
     double* const bufP = R.p; double* const bufAp = R.Ap;
-    const long long stride = bicgstabl_stride(R.count);
+    const long long stride = cg_work_stride(R.count);
     GmresRun P{};
     P.ws = ws; P.m = m; P.orth = orth; P.x = R.x; P.r = R.r; P.w = bufAp; P.V = work; P.dinv = R.dinv; P.stride = stride; P.n = n;
     P.gather = R.dinv ? work + (m + 1) * stride : nullptr;
@@ -1600,8 +1603,7 @@ static int cg_solve_gmres(CgRun& R, const char* who, int m, int orth, double* wo
     };
     bool ok = restart(0, true) && MGCG_HIP(hipGetLastError());
 
-    int k = 0;
-    ok = ok && cg_drive(R, who, [&] {
+    ok = ok && cg_drive_bodies(R, who, [&](int k) {
         const int j = k % m;
         if (j == 0 && k > 0) {                                                           // y ; x += hat(V y) ; the next cycle's r, v_0
             gmres_enqueue_close(P);
@@ -1612,19 +1614,14 @@ static int cg_solve_gmres(CgRun& R, const char* who, int m, int orth, double* wo
         R.p = from; R.Ap = P.w;
         if (!cg_enqueue_product(R, from, &nSums)) return false;                          // w = A hat(v_j)
         gmres_enqueue_step(P, f, k, j);                                                  // h ; w ; the rotations ; the stop decision ; v_{j+1}
-        if (k < 0x7fffffff) ++k;
-        return MGCG_HIP(hipGetLastError());
+        return true;
     });
     R.p = bufP; R.Ap = bufAp;
     if (ok) gmres_enqueue_close(P);                                                      // the columns of the cycle that was cut short
     // the closing product: the true residual into the caller's r
-    double rrTrue = 0.0;
-    ok = ok && cg_enqueue_true_residual(R, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, gmres_rr_partials(ws)); }, gmres_rr_partials(ws), &ws->gmresScalars->red, &rrTrue);
-    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    if (!ok) return MGCG_ERROR;
-    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", "",
-                         "the first residual is zero or not finite, or an Arnoldi step left no next direction and no column (A singular on the Krylov space, or a value that is not finite)");
+    return cg_close_true_residual(R, ok, who, bufP, R.r, [&] { return launch_dot_partials(s, R.r, R.r, n, gmres_rr_partials(ws)); }, gmres_rr_partials(ws), &ws->gmresScalars->red,
+                                  f.traceCap, iteration, residual, trueResidual, residualTrace, "",
+                                  "the first residual is zero or not finite, or an Arnoldi step left no next direction and no column (A singular on the Krylov space, or a value that is not finite)");
 }
 
 // ---------------------------------------------------------------- preconditioned MINRES (SolveMinresJacobi, SolveMinresJacobiParallel, SolveMinresMg)
@@ -1667,8 +1664,7 @@ static int cg_solve_pminres(CgRun& R, const char* who, double* r1Vec, double* w1
     ok = ok && MGCG_HIP(hipGetLastError());
 
     double *r2 = bufR, *r1 = r1Vec, *w1 = w1Vec, *w2 = w2Vec;
-    int k = 0;
-    ok = ok && cg_drive(R, who, [&] {
+    ok = ok && cg_drive_bodies(R, who, [&](int k) {
         int nVq = 0;
         if (!cg_enqueue_product(R, R.p, &nVq)) return false;                             // q = A v ; v.q
         const PminresRun P = { ws, R.x, vLoc, r1, w1, r2, w2, R.Ap, R.dinv, R.z, n, shift, R.multi };
@@ -1678,19 +1674,15 @@ static int cg_solve_pminres(CgRun& R, const char* who, double* r1Vec, double* w1
         if (R.multi && !cg_share_sums(R, rzPartials, nZ, nullptr, 0, &ms->red[3], done)) return false;
         nVv = pminres_enqueue_update(P, f, k, nZ);                                       // w over w1 ; x ; the next v in place ; v.v
         std::swap(r1, r2); std::swap(w1, w2);                                            // (r1, r2) := (r2, rn) ; (w1, w2) := (w2, w)
-        if (k < 0x7fffffff) ++k;
-        return MGCG_HIP(hipGetLastError());
+        return true;
     });
     // the closing product: the true residual into the caller's r
-    double rrTrue = 0.0, bz = 0.0;
-    ok = ok && cg_enqueue_true_residual(R, R.p, R.Ap, [&] { return minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift); }, minres_yy_partials(ws), &ms->red[2], &rrTrue);
-    ok = ok && MGCG_HIP(hipMemcpyAsync(&bz, &ms->red[4], sizeof(double), hipMemcpyDeviceToHost, s));
-    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
-    if (!ok) return MGCG_ERROR;
-    if (trueResidual) *trueResidual = std::sqrt(rrTrue);
-    const int status = cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "residual", " in the M^-1 norm",
-                                     "the first residual is zero or not finite, r . M^-1 r is negative or not finite (a preconditioner that is not positive definite), or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)");
-    if (ws->mirror->status == MGCG_NONFINITE && ws->mirror->iteration == 0 && bz < 0.0)
+    double bz = 0.0;
+    const int status = cg_close_true_residual(R, ok, who, R.p, R.Ap, [&] { return minres_enqueue_residual(ws, R.Ap, R.x, bufR, n, shift); }, minres_yy_partials(ws), &ms->red[2],
+                                              f.traceCap, iteration, residual, trueResidual, residualTrace, " in the M^-1 norm",
+                                              "the first residual is zero or not finite, r . M^-1 r is negative or not finite (a preconditioner that is not positive definite), or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)",
+                                              [&] { return MGCG_HIP(hipMemcpyAsync(&bz, &ms->red[4], sizeof(double), hipMemcpyDeviceToHost, s)); });
+    if (status != MGCG_ERROR && ws->mirror->status == MGCG_NONFINITE && ws->mirror->iteration == 0 && bz < 0.0)
         set_error("%s: stopped at iteration 0: the preconditioner is not positive definite (r . M^-1 r = %g for the first residual)", who, bz);
     return status;
 }
@@ -1943,6 +1935,72 @@ static int cg_variant_call(const CgCall& c, bool handles, Checks checks, Body bo
     int st = MGCG_ERROR;
     cg_call(c, handles, checks, [&](CgRun& R) { st = body(R); });
     return st;
+}
+
+// The one-rank exports whose loop keeps its vectors in one work vector (BiCGStab(l), GMRES(m)): what they all take.  jacobi: dinv is a
+// handle the export requires.
+struct CgWorkCall {
+    const char* who; bool jacobi;
+    MgcgBlas* cublas; MgcgSparse* cusparse;
+    Vector* elements; VectorInt* rowOffsets; VectorInt* columnIndeces;
+    Vector *x, *b, *Ap, *p, *r, *work, *dinv;
+    int elementsCount, count;
+    double allowableResidual; int minIteration, maxIteration, rule;
+    int* iteration; double* residual; double* trueResidual; double* residualTrace; int traceCapacity;
+};
+
+// Their entry (refusals: cg_variant_call).  params(): the export's refusals of its own sizes, in front of the rule's; slices: how many
+// vectors the work vector holds, cg_work_stride(count) apart; noun, value: the size that the short work vector's message names; loop(R): the solve.
+template <typename Params, typename Loop>
+static int cg_work_vector_call(const CgWorkCall& w, Params params, int slices, const char* noun, int value, Loop loop)
+{
+    const char* who = w.who;
+    const CgCall c = cg_call_one_rank(who, w.cublas, w.cusparse, w.elements, w.rowOffsets, w.columnIndeces, w.x, w.b, w.Ap, w.p, w.r, w.elementsCount, w.count);
+    auto checks = [&] {
+        if (!params() || cg_rule_refused(who, w.rule, "the loop carries no max|r|")) return false;
+        // a count below 1 is the shared checks' to refuse (cg_call, behind these): it asks for no room here, never for a negative amount
+        const long long need = slices * cg_work_stride(w.count > 0 ? w.count : 0);
+        if (w.work->size < need) {
+            set_error("%s: the work vector holds %lld entries, %s = %d needs %lld (%d slices of %lld: the matrix has %d rows)", who, w.work->size, noun, value, need, slices, cg_work_stride(w.count), w.count);
+            return false;
+        }
+        return !(w.jacobi && cg_vector_short(who, "dinv", w.dinv, w.count, "local rows"));
+    };
+    return cg_variant_call(c, w.cublas && w.cusparse && w.work && (!w.jacobi || w.dinv), checks, [&](CgRun& R) {
+        if (R.multi) { set_error("%s: the loop runs on one rank", who); return (int)MGCG_ERROR; }
+        if (w.jacobi) R.dinv = cg_dinv_address(R, w.dinv);
+        cg_set_stop(R, w.allowableResidual, w.minIteration, w.maxIteration, w.rule);
+        cg_note_written({ R.x, R.Ap, R.r, R.p }, w.count);
+        cg_note_written({ w.work->data }, slices * cg_work_stride(w.count));
+        return loop(R);
+    });
+}
+
+// BiCGStab(l) (cg_solve_bicgstabl above)
+static int bicgstabl_call(const CgWorkCall& w, int ell)
+{
+    auto params = [&] {
+        if (ell >= 1 && ell <= kBicgstablMaxL) return true;
+        set_error("%s: ell = %d, must be 1 .. %d", w.who, ell, kBicgstablMaxL);
+        return false;
+    };
+    return cg_work_vector_call(w, params, bicgstabl_slices(ell, w.jacobi), "ell", ell, [&](CgRun& R) {
+        return cg_solve_bicgstabl(R, w.who, ell, w.work->data, w.iteration, w.residual, w.trueResidual, w.residualTrace, w.traceCapacity);
+    });
+}
+
+// GMRES(m) (cg_solve_gmres above)
+static int gmres_call(const CgWorkCall& w, int m, int orth)
+{
+    auto params = [&] {
+        if (m < 1 || m > kGmresMaxM) set_error("%s: m = %d, must be 1 .. %d", w.who, m, kGmresMaxM);
+        else if (orth < 1 || orth > 2) set_error("%s: orth = %d, must be 1 or 2", w.who, orth);
+        else return true;
+        return false;
+    };
+    return cg_work_vector_call(w, params, gmres_slices(m, w.jacobi), "m", m, [&](CgRun& R) {
+        return cg_solve_gmres(R, w.who, m, orth, w.work->data, w.iteration, w.residual, w.trueResidual, w.residualTrace, w.traceCapacity);
+    });
 }
 
 // SolveEx and SolveParallel
@@ -3269,37 +3327,6 @@ int SolveBicgstabMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDes
                           allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
-// BiCGStab(l) (cg_solve_bicgstabl above; refusals: cg_variant_call), one rank.  With `jacobi` dinvVector is a handle the export requires.
-static int bicgstabl_entry_call(const char* who, bool jacobi, MgcgBlas* cublas, MgcgSparse* cusparse,
-                                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
-                                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
-                                int ell, int elementsCount, int count,
-                                double allowableResidual, int minIteration, int maxIteration, int rule,
-                                int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
-{
-    const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
-    auto checks = [&] {
-        if (ell < 1 || ell > kBicgstablMaxL) { set_error("%s: ell = %d, must be 1 .. %d", who, ell, kBicgstablMaxL); return false; }
-        if (cg_rule_refused(who, rule, "the loop carries no max|r|")) return false;
-        // a count below 1 is the shared checks' to refuse (cg_call, behind these): it asks for no room here, never for a negative amount
-        const int slices = bicgstabl_slices(ell, jacobi);
-        const long long need = slices * bicgstabl_stride(count > 0 ? count : 0);
-        if (workVector->size < need) {
-            set_error("%s: the work vector holds %lld entries, ell = %d needs %lld (%d slices of %lld: the matrix has %d rows)", who, workVector->size, ell, need, slices, bicgstabl_stride(count), count);
-            return false;
-        }
-        return !(jacobi && cg_vector_short(who, "dinv", dinvVector, count, "local rows"));
-    };
-    return cg_variant_call(c, cublas && cusparse && workVector && (!jacobi || dinvVector), checks, [&](CgRun& R) {
-        if (R.multi) { set_error("%s: the loop runs on one rank", who); return (int)MGCG_ERROR; }
-        if (jacobi) R.dinv = cg_dinv_address(R, dinvVector);
-        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        cg_note_written({ R.x, R.Ap, R.r, R.p }, count);
-        cg_note_written({ workVector->data }, bicgstabl_slices(ell, jacobi) * bicgstabl_stride(count));
-        return cg_solve_bicgstabl(R, who, ell, workVector->data, iteration, residual, trueResidual, residualTrace, traceCapacity);
-    });
-}
-
 int SolveBicgstabL(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                    Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                    Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
@@ -3308,9 +3335,8 @@ int SolveBicgstabL(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDesc
                    int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    return bicgstabl_entry_call("SolveBicgstabL", false, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
-                                xVector, bVector, ApVector, pVector, rVector, workVector, nullptr, ell, elementsCount, count,
-                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    return bicgstabl_call({ "SolveBicgstabL", false, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                            workVector, nullptr, elementsCount, count, allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity }, ell);
 }
 
 int SolveBicgstabLJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -3321,41 +3347,8 @@ int SolveBicgstabLJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* m
                          int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    return bicgstabl_entry_call("SolveBicgstabLJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
-                                xVector, bVector, ApVector, pVector, rVector, workVector, dinvVector, ell, elementsCount, count,
-                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
-}
-
-// GMRES(m) (cg_solve_gmres above; refusals: cg_variant_call), one rank.  With `jacobi` dinvVector is a handle the export requires.
-static int gmres_entry_call(const char* who, bool jacobi, MgcgBlas* cublas, MgcgSparse* cusparse,
-                            Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
-                            Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector, Vector* dinvVector,
-                            int m, int orth, int elementsCount, int count,
-                            double allowableResidual, int minIteration, int maxIteration, int rule,
-                            int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
-{
-    const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
-    auto checks = [&] {
-        if (m < 1 || m > kGmresMaxM) { set_error("%s: m = %d, must be 1 .. %d", who, m, kGmresMaxM); return false; }
-        if (orth < 1 || orth > 2) { set_error("%s: orth = %d, must be 1 or 2", who, orth); return false; }
-        if (cg_rule_refused(who, rule, "the loop carries no max|r|")) return false;
-        // a count below 1 is the shared checks' to refuse (cg_call, behind these): it asks for no room here, never for a negative amount
-        const int slices = gmres_slices(m, jacobi);
-        const long long need = slices * bicgstabl_stride(count > 0 ? count : 0);
-        if (workVector->size < need) {
-            set_error("%s: the work vector holds %lld entries, m = %d needs %lld (%d slices of %lld: the matrix has %d rows)", who, workVector->size, m, need, slices, bicgstabl_stride(count), count);
-            return false;
-        }
-        return !(jacobi && cg_vector_short(who, "dinv", dinvVector, count, "local rows"));
-    };
-    return cg_variant_call(c, cublas && cusparse && workVector && (!jacobi || dinvVector), checks, [&](CgRun& R) {
-        if (R.multi) { set_error("%s: the loop runs on one rank", who); return (int)MGCG_ERROR; }
-        if (jacobi) R.dinv = cg_dinv_address(R, dinvVector);
-        cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
-        cg_note_written({ R.x, R.Ap, R.r, R.p }, count);
-        cg_note_written({ workVector->data }, gmres_slices(m, jacobi) * bicgstabl_stride(count));
-        return cg_solve_gmres(R, who, m, orth, workVector->data, iteration, residual, trueResidual, residualTrace, traceCapacity);
-    });
+    return bicgstabl_call({ "SolveBicgstabLJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                            workVector, dinvVector, elementsCount, count, allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity }, ell);
 }
 
 int SolveGmres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -3366,9 +3359,8 @@ int SolveGmres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    return gmres_entry_call("SolveGmres", false, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
-                            xVector, bVector, ApVector, pVector, rVector, workVector, nullptr, m, orth, elementsCount, count,
-                            allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    return gmres_call({ "SolveGmres", false, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                        workVector, nullptr, elementsCount, count, allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity }, m, orth);
 }
 
 int SolveGmresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
@@ -3379,9 +3371,8 @@ int SolveGmresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDe
                      int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
 {
     (void)matDescr;
-    return gmres_entry_call("SolveGmresJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector,
-                            xVector, bVector, ApVector, pVector, rVector, workVector, dinvVector, m, orth, elementsCount, count,
-                            allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+    return gmres_call({ "SolveGmresJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                        workVector, dinvVector, elementsCount, count, allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity }, m, orth);
 }
 
 // Preconditioned MINRES (cg_solve_pminres above; refusals: cg_variant_call).  dinvVector, the hierarchy and zVector are handles the exports

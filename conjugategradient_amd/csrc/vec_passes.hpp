@@ -1,7 +1,8 @@
-// Device and launch helpers shared by the translation units that hold the CG loop's vector passes (kernels_blas1.hip, kernels_shift.hip):
-// the wavefront / workgroup reductions, the grid and alignment rules, the streaming-hint loads and stores, the two element drivers, the
-// fixed-order sum of per-workgroup partial sums, and what a finished iteration publishes.  One definition, so that every pass adds in the
-// same order and takes the same forms at the same sizes.
+// Device and launch helpers shared by the translation units that hold the vector passes of the CG loop (kernels_blas1.hip, kernels_shift.hip)
+// and of the Krylov variants (kernels_sreduce, _minres, _pminres, _bicgstab, _bicgstabl, _gmres, _cheb .hip): the wavefront / workgroup
+// reductions, the grid and alignment rules, the streaming-hint loads and stores, the element drivers, the fixed-order sum of per-workgroup
+// partial sums, the finite tests, and what a loop's start, a finished iteration and a breakdown publish.  One definition, so that every pass
+// adds in the same order, takes the same forms at the same sizes and words a stop the same way.
 #pragma once
 #include "common.hpp"
 
@@ -72,6 +73,22 @@ template <typename Go> static void with_v2_nt(bool v2, bool nt, Go go)
     else go(std::false_type{}, std::false_type{});
 }
 
+// Who forms the hatted copy hat(v) = M^-1 v of a BiCGStab or BiCGStab(l) pass: nobody (M = I: the vector itself is read), the pass (dinv *
+// value per element), or somebody else between the passes (the V-cycle: the copy is stored, the passes only read it).  go(HAT); a loop
+// without a stored form passes no `stored` and instantiates none.
+enum : int { HAT_NONE = 0, HAT_DINV = 1, HAT_STORED = 2 };
+template <typename Go> static void with_hat(const double* dinv, Go go)
+{
+    if (dinv) go(std::integral_constant<int, HAT_DINV>{});
+    else go(std::integral_constant<int, HAT_NONE>{});
+}
+template <typename Go> static void with_hat(const double* dinv, bool stored, Go go)
+{
+    if (dinv) go(std::integral_constant<int, HAT_DINV>{});
+    else if (stored) go(std::integral_constant<int, HAT_STORED>{});
+    else go(std::integral_constant<int, HAT_NONE>{});
+}
+
 template <bool V2, typename F2, typename F1>
 __device__ __forceinline__ void grid_stride(long long n, F2 f2, F1 f1)
 {
@@ -97,6 +114,31 @@ __device__ __forceinline__ void chunk_pairs(long long n2, F2 f2x2)
     end = end < n2 ? end : n2;
     for (; i < end; i += 2 * kBlock) f2x2(i, i + kBlock < end);    // pairs i and i + kBlock
 }
+
+// The chunked 16-byte driver of the Krylov variants' passes: load(e, i) fills a Pair for pair index i, finish(e, i) computes and stores it,
+// one(i) is the element-wise form.  Two pairs per array in flight per lane; the odd tail goes to the first thread (publisher).
+template <bool V2, typename Pair, typename Load, typename Finish, typename One>
+__device__ __forceinline__ void stream_pairs(long long n, bool publisher, Load load, Finish finish, One one)
+{
+    if constexpr (V2) {
+        chunk_pairs(n >> 1, [&](long long i, bool two) {
+            const long long j = two ? i + kBlock : i;
+            Pair e0, e1;
+            load(e0, i); load(e1, j);
+            finish(e0, i);
+            if (two) finish(e1, j);
+        });
+        if ((n & 1) && publisher) one(n - 1);
+    } else {
+        grid_stride<false>(n, [&](long long) {}, one);
+    }
+}
+
+// The tests of a scalar that a loop divides by or judges: neither infinite nor NaN; and that, above zero.  kFiniteMax: the bound of both,
+// for the one test that is neither (a sum that may be zero but not negative).
+constexpr double kFiniteMax = 1.79e308;
+__device__ __forceinline__ bool finite_value(double v) { return fabs(v) <= kFiniteMax; }
+__device__ __forceinline__ bool positive_finite(double v) { return v > 0.0 && v <= kFiniteMax; }
 
 // Fixed-order sum (or max) of n partials by the whole workgroup.  The result is valid in EVERY thread: block_sum / block_max read s_red in
 // all threads behind their barrier (update_shifted_kernel relies on it in lanes 0 .. K-1; the other callers use thread 0's copy).
@@ -129,6 +171,35 @@ __device__ __forceinline__ void publish_iteration(const FinalizeArgs& f, const S
         sc->iteration = it + 1;
         f.mirror->residual = d.res; f.mirror->iteration = it + 1;
     }
+}
+
+// The start of a variant's loop, by one thread: every field of CgScalars, the host mirror and trace[0] for the first judged figure rr0 (r.r,
+// or r.z of a preconditioned recurrence) and the residual res0 that goes with it.  The loop's own scalars follow it, and then, where rr0 is
+// zero or not finite (b - A x is), refuse_start: the loop ends MGCG_NONFINITE at iteration 0.
+__device__ __forceinline__ void publish_start(const FinalizeArgs& f, double rr0, double res0)
+{
+    CgScalars* sc = f.sc;
+    sc->rr = rr0; sc->rr0 = rr0; sc->pAp = 0; sc->rrNew = rr0; sc->rzNew = 0; sc->residual = res0; sc->nrmInf = 0;
+    sc->beta = 0; sc->alpha = 0; sc->iteration = 0; sc->done = 0; sc->status = MGCG_OK; sc->pad = 0;
+    sc->fRr = rr0; sc->fRr0 = rr0; sc->fAlpha = 0; sc->fIteration = 0; sc->fDone = 0; sc->pSlot = 0;
+    f.mirror->residual = res0; f.mirror->iteration = 0; f.mirror->status = MGCG_OK; f.mirror->done = 0;
+    if (f.trace != nullptr && f.traceCap > 0) f.trace[0] = f.rule == MGCG_RULE_VIENNACL ? sqrt(rr0 / rr0) : res0;
+}
+__device__ __forceinline__ void refuse_start(const FinalizeArgs& f)
+{
+    f.sc->done = 1; f.sc->status = MGCG_NONFINITE;
+    f.mirror->status = MGCG_NONFINITE;
+    __threadfence_system();
+    f.mirror->done = 1;
+}
+
+// A breakdown in front of an iteration's updates, by one thread: the last judged residual once more, for iteration `it`
+__device__ __forceinline__ void publish_breakdown(const FinalizeArgs& f, int it)
+{
+    StopDecision d;
+    const double rrOld = f.sc->rrNew, rr0 = f.sc->rr0;
+    d.res = sqrt(rrOld); d.shown = f.rule == MGCG_RULE_VIENNACL ? sqrt(rrOld / rr0) : d.res; d.stop = true; d.status = MGCG_NONFINITE;
+    publish_iteration<0>(f, d, it, rrOld, 0.0, 0, [] {});
 }
 
 } // namespace mgcg

@@ -18,15 +18,12 @@ The max-norm stop rule is not supported.  No arithmetic happens in this module.
 """
 from __future__ import annotations
 
-from . import _lib
-from .bicgstab import BiConjugateGradientStabGpu
-from .jacobi import jacobi_setup
-from .solver import ConjugateGradientSingleGpu, VectorDouble
+from .bicgstab import OneWorkVectorGpu
 
 MAX_M = 32
 
 
-class GeneralizedMinimalResidualGpu(BiConjugateGradientStabGpu):
+class GeneralizedMinimalResidualGpu(OneWorkVectorGpu):
     """BiConjugateGradientStabGpu on the GMRES(m) loop (SolveGmres): same members, ``TrueResidual``, ``ReadResidual()``, trace and exceptions;
     iterations count Arnoldi steps.  One work vector of ``m + 1`` slices (one more with the diagonal) holds the basis: it is sized for the
     object's ``m`` and allocated again, larger, by the first ``Solve()`` after ``m`` was raised.  The library checks ``m``, ``orth`` and the
@@ -34,31 +31,14 @@ class GeneralizedMinimalResidualGpu(BiConjugateGradientStabGpu):
 
     _export = "SolveGmres"
     _what = "GMRES(m)"
-    _slices_more = 0
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, m=20, orth=2):
-        if rule == _lib.RULE_HANDMADECL:
-            raise ValueError(f"{type(self).__name__}: the max-norm rule (RULE_HANDMADECL) is not supported")
-        ConjugateGradientSingleGpu.__init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
-        self.TrueResidual = float("nan")
+        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
         self.m, self.orth = int(m), int(orth)
-        self.vectorWork, self._work_size = None, 0
         self._ensure_work()
-        self._ready = False
 
-    def _ensure_work(self):
-        """Room for this ``m`` (one the library refuses: as for the nearest it takes, so that the call reaches its refusal)."""
-        need = (min(max(int(self.m), 1), MAX_M) + 1 + self._slices_more) * (self.Count + (self.Count & 1))
-        if need > self._work_size:
-            if self.vectorWork is not None:
-                self.vectorWork.Dispose()
-            self.vectorWork, self._work_size = VectorDouble(need), need
-
-    def Dispose(self):
-        if getattr(self, "vectorWork", None) is not None:
-            self.vectorWork.Dispose()
-            self.vectorWork, self._work_size = None, 0
-        super().Dispose()
+    def _slices(self):
+        return min(max(int(self.m), 1), MAX_M) + 1 + self._slices_more
 
     def _work_arguments(self):
         self._ensure_work()
@@ -71,18 +51,4 @@ class GeneralizedMinimalResidualJacobiGpu(GeneralizedMinimalResidualGpu):
 
     _export = "SolveGmresJacobi"
     _what = "Jacobi-preconditioned GMRES(m)"
-    _slices_more = 1
-
-    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, m=20, orth=2):
-        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule, m=m, orth=orth)
-        self.vectorDinv = VectorDouble(count)
-
-    def Initialize(self):
-        super().Initialize()
-        self._ready = False
-        jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
-                     int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
-        self._ready = True
-
-    def _more_vectors(self):
-        return (self.vectorDinv.Ptr,)
+    _jacobi = True

@@ -8,8 +8,9 @@
 ``run``: 64^3 SolveEx with x_defer 8 and 1, CgSteps(20), a 64^3 MGCG solve and a 64^3 Jacobi-preconditioned solve, two loopback ranks
 plain, MGCG and Jacobi, four loopback ranks of which three hold no rows, plain and Jacobi; then one 64^3 solve of each one-column variant
 (mixed precision, single reduction, MINRES with a shift that makes the system indefinite, BiCGStab, Jacobi-preconditioned MINRES, Chebyshev
-CG of degree 4) and, on two loopback ranks at 32 x 32 x 16, the five of them that have a several-ranks form, with and without the diagonal
-where both exist.  The placement draw is off (its timing loops launch SpMVs by the free memory of the moment).
+CG of degree 4, BiCGStab(2), GMRES(8) with two orthogonalisation passes), one 32^3 BiCGStab solve with an aggregation hierarchy and, on two
+loopback ranks at 32 x 32 x 16, the five of them that have a several-ranks form, with and without the diagonal where both exist.  The
+placement draw is off (its timing loops launch SpMVs by the free memory of the moment).
 ``table``: per-kernel call counts of the run's *kernel_stats.csv, as one JSON object sorted by name."""
 import csv
 import glob
@@ -151,8 +152,11 @@ BOUNDS = (0.4, 12.0)    # of the 7-point matrix; with the diagonal the same inte
 def variants(done):
     """One solve of each one-column variant on one rank, and of each several-ranks form on two loopback ranks."""
     from conjugategradient_amd import _lib, problems
-    from conjugategradient_amd.bicgstab import BiConjugateGradientStabGpu, BiConjugateGradientStabJacobiGpu
+    from conjugategradient_amd.amg import ConjugateGradientAmgGpu
+    from conjugategradient_amd.bicgstab import (BiConjugateGradientStabGpu, BiConjugateGradientStabJacobiGpu, BiConjugateGradientStabLGpu,
+                                                BiConjugateGradientStabLJacobiGpu)
     from conjugategradient_amd.chebyshev import ConjugateGradientChebyshevGpu
+    from conjugategradient_amd.gmres import GeneralizedMinimalResidualGpu, GeneralizedMinimalResidualJacobiGpu
     from conjugategradient_amd.minres import MinimalResidualGpu, MinimalResidualJacobiGpu
     from conjugategradient_amd.mixed import ConjugateGradientMixedGpu
     from conjugategradient_amd.parallel import ConjugateGradientRankGpu
@@ -177,6 +181,10 @@ def variants(done):
         ("BiCGStab Jacobi", lambda: BiConjugateGradientStabJacobiGpu(*args, rule=_lib.RULE_CSHARP)),
         ("Chebyshev degree 4", lambda: ConjugateGradientChebyshevGpu(*args, rule=_lib.RULE_CSHARP, degree=4, bounds=BOUNDS)),
         ("Chebyshev degree 4 Jacobi", lambda: ConjugateGradientChebyshevGpu(*args, rule=_lib.RULE_CSHARP, degree=4, jacobi=True, bounds=(BOUNDS[0] / 6, BOUNDS[1] / 6))),
+        ("BiCGStab(2)", lambda: BiConjugateGradientStabLGpu(*args, rule=_lib.RULE_CSHARP, ell=2)),
+        ("BiCGStab(2) Jacobi", lambda: BiConjugateGradientStabLJacobiGpu(*args, rule=_lib.RULE_CSHARP, ell=2)),
+        ("GMRES(8) orth 2", lambda: GeneralizedMinimalResidualGpu(*args, rule=_lib.RULE_CSHARP, m=8, orth=2)),
+        ("GMRES(8) orth 2 Jacobi", lambda: GeneralizedMinimalResidualJacobiGpu(*args, rule=_lib.RULE_CSHARP, m=8, orth=2)),
     ]
     for name, make in one_rank:
         cg = make().load(s)
@@ -184,6 +192,13 @@ def variants(done):
         counted(cg.Solve)
         done.append((name, cg.Iteration))
         cg.Dispose()
+
+    c = problems.poisson(32, 32, 32)                            # the V-cycle of an aggregation hierarchy as BiCGStab's preconditioner
+    amg = ConjugateGradientAmgGpu(c.Count, 7, 0, 500, 1e-8, rule=_lib.RULE_CSHARP).load(c)
+    amg.Initialize()
+    counted(amg.SolveBicgstab)
+    done.append(("BiCGStab aggregation 32^3", amg.Iteration))
+    amg.Dispose()
 
     t = problems.poisson(32, 32, 16)
     two_ranks = [

@@ -2,9 +2,10 @@
 messages with tests/golden/variant_refusals.json.  The substring assertions of tests/test_*_host.py say what a message must mention; this
 file pins the text, so that a change of the shared entry path or of a message helper in csrc/solver.hip cannot alter one unnoticed.
 
-The golden file is a recorded result: ``python -m tests.test_variant_refusals_host --record`` writes what the library of the working
-tree says.  It was recorded from the commit before the exports were moved onto one entry path and must not be recorded again to make a
-failing case pass."""
+The golden file is a recorded result: ``python -m tests.test_variant_refusals_host --record`` adds what the library in use (MGCG_LIB_PATH)
+says for the cases the file does not hold yet and keeps every entry it holds.  Each entry was recorded from the commit before its export's
+entry path was reshaped -- the older variants before they moved onto one entry path, SolveBicgstabMg and the work-vector forms before
+theirs were folded -- and must not be recorded again to make a failing case pass."""
 import ctypes as C
 import json
 import os
@@ -26,6 +27,8 @@ _handle = C.create_string_buffer(4096)                     # stands for every ha
 H = C.addressof(_handle)
 _big, _small, _tiny = _VectorHead(None, 10, -1, b""), _VectorHead(None, 9, -1, b""), _VectorHead(None, 3, -1, b"")
 VEC, SHORT, TINY = C.addressof(_big), C.addressof(_small), C.addressof(_tiny)
+_sized = {n: _VectorHead(None, n, -1, b"") for n in (1000, 39, 49, 89, 99, -1)}     # work vectors: roomy, one entry short of each form, and short of nothing
+ROOMY, WORK = C.addressof(_sized[1000]), {n: C.addressof(v) for n, v in _sized.items()}
 IT, RES, TRUE, UP = C.c_int(0), C.c_double(0.0), C.c_double(0.0), C.c_int(0)
 OUT2, OUT3 = (C.byref(IT), C.byref(RES)), (C.byref(IT), C.byref(RES), C.byref(TRUE))
 EIGHT = (VEC,) * 8                                         # elements, rowOffsets, columnIndeces, x, b, Ap, p, r
@@ -85,7 +88,20 @@ def _exports(L):
     def bkrylov(blas=H, k=2, rule=_lib.RULE_CSHARP):
         return L.SolveBlockKrylov(blas, H, None, *EIGHT, *ONE, k, *STOP, rule, None, None, None, None, 0)
 
+    def bicgstab_mg(blas=H, sparse=H, mg=H, v=VEC, s=VEC, t=VEC, rhat=VEC, count=10, rule=_lib.RULE_CSHARP):
+        return L.SolveBicgstabMg(blas, sparse, None, mg, *EIGHT, v, s, t, rhat, 28, count, *STOP, rule, *OUT3, None, 0)
+
+    def work_vector(name, jacobi):
+        """SolveBicgstabL* (ell) and SolveGmres* (m, orth): one work vector, with `jacobi` the diagonal behind it"""
+        def call(blas=H, sparse=H, work=ROOMY, dinv=VEC, ell=2, m=8, orth=2, count=10, rule=_lib.RULE_CSHARP):
+            sizes = (ell,) if "Bicgstab" in name else (m, orth)
+            return getattr(L, name)(blas, sparse, None, *EIGHT, work, *((dinv,) if jacobi else ()), *sizes, 28, count, *STOP, rule, *OUT3, None, 0)
+        return call
+
     return {
+        "SolveBicgstabMg": bicgstab_mg,
+        "SolveBicgstabL": work_vector("SolveBicgstabL", False), "SolveBicgstabLJacobi": work_vector("SolveBicgstabLJacobi", True),
+        "SolveGmres": work_vector("SolveGmres", False), "SolveGmresJacobi": work_vector("SolveGmresJacobi", True),
         "SolveShifted": shifted, "SolveBlockKrylov": bkrylov,
         "SolveSingleReduce": sreduce(False), "SolveSingleReduceParallel": sreduce(True),
         "SolveMinres": minres(False), "SolveMinresParallel": minres(True),
@@ -135,7 +151,28 @@ _MIXED = (_nulls("blas", "sparse", "e32") + _rules() + [("no_rows", dict(count=0
 # the exports of the older variants that refuse through cg_variant_args before they ask for a device (SolveBlockEx asks for it first)
 _SHIFTED = _nulls("blas", "work") + _rules()[1:] + [("k_0", dict(k=0)), ("k_9", dict(k=9)), ("k_before_rule", dict(k=0, rule=5))]
 _BKRYLOV = _nulls("blas") + _rules() + [("k_0", dict(k=0)), ("k_9", dict(k=9)), ("k_before_rule", dict(k=0, rule=5))]
+# the V-cycle form of BiCGStab: _handle is a zeroed hierarchy, so the call with every other argument in order is refused for it
+_BICGSTAB_MG = _BICGSTAB + _nulls("mg") + [("hierarchy_of_no_ranks", dict()), ("count_0", dict(count=0))]
+
+
+def _work_vector(sizes, first, short, jacobi):
+    """The one-rank work-vector forms.  sizes: the refused ell, or m and orth; short: a work vector one entry short of this form (ell = 2:
+    4 or 5 slices of 10; m = 8: 9 or 10).  No rows ask for no room, so count 0 alone is refused only with a device in hand: here
+    it meets a work vector that holds less than nothing."""
+    cases = (_nulls("blas", "sparse", "work") + sizes + _rules()
+             + [("work_one_short", dict(work=WORK[short])), ("count_0_work_of_minus_1", dict(count=0, work=WORK[-1])),
+                ("sizes_before_rule_before_work", dict(rule=5, work=WORK[short], **first))])
+    if jacobi:
+        cases += _nulls("dinv") + _shorts("dinv") + [("work_before_dinv", dict(work=WORK[short], dinv=TINY))]
+    return cases
+
+
+_ELL = [("ell_0", dict(ell=0)), ("ell_5", dict(ell=5))]
+_M_ORTH = [("m_0", dict(m=0)), ("m_33", dict(m=33)), ("orth_0", dict(orth=0)), ("orth_3", dict(orth=3)), ("m_before_orth", dict(m=0, orth=0))]
 CASES = {
+    "SolveBicgstabMg": _BICGSTAB_MG,
+    "SolveBicgstabL": _work_vector(_ELL, dict(ell=0), 39, False), "SolveBicgstabLJacobi": _work_vector(_ELL, dict(ell=0), 49, True),
+    "SolveGmres": _work_vector(_M_ORTH, dict(orth=3), 89, False), "SolveGmresJacobi": _work_vector(_M_ORTH, dict(orth=3), 99, True),
     "SolveShifted": _SHIFTED, "SolveBlockKrylov": _BKRYLOV,
     "SolveSingleReduce": _SREDUCE, "SolveSingleReduceParallel": _SREDUCE,
     "SolveMinres": _MINRES, "SolveMinresParallel": _MINRES,
@@ -199,9 +236,13 @@ if __name__ == "__main__":
     if sys.argv[1:] != ["--record"]:
         sys.exit(__doc__)
     lib = _lib.lib()
-    table = {case: refusal(lib, *case.split("-", 1)) for case in IDS}
-    table.update(_other_exports(lib))
+    with open(GOLDEN) as fh:
+        table = json.load(fh)
+    kept = len(table)
+    fresh = {case: refusal(lib, *case.split("-", 1)) for case in IDS}
+    fresh.update(_other_exports(lib))
+    table.update({key: value for key, value in fresh.items() if key not in table})
     with open(GOLDEN, "w") as fh:
         json.dump(table, fh, indent=1, sort_keys=True)
         fh.write("\n")
-    print(f"{len(table)} refusals recorded in {GOLDEN}")
+    print(f"{len(table) - kept} refusals recorded in {GOLDEN}, {kept} kept as they were")
