@@ -16,6 +16,8 @@
              (``BiConjugateGradientStabLGpu``, SolveBicgstabL), for the convection-dominated systems on which BiCGStab breaks down
 ``gmres``    restarted GMRES(m) for NONSYMMETRIC systems (``GeneralizedMinimalResidualGpu``, SolveGmres), plain or right-preconditioned by
              the diagonal: the residual never increases, no breakdown on a nonsingular matrix, no drift -- slower per product than ``bicgstab``
+             (the V-cycle form, SolveGmresMg -- flexible GMRES -- is the ``SolveGmres`` method of the ``multigrid`` / ``amg`` / ``ssor``
+             classes: it converges where SolveBicgstabMg breaks down)
 ``chebyshev`` Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, m products and two global sums per iteration
 ``shifted``   multi-shift CG: (A + s_j I) x_j = b for up to 8 shifts from one CG recurrence on A
 ``blockkrylov`` shared-subspace block CG: up to 8 right-hand sides in one block Krylov space (fewer iterations than ``block``)

@@ -796,12 +796,15 @@ void bicgstabl_enqueue_p(const BicgstablRun& R, const FinalizeArgs& f, int k, in
 
 // GMRES(m) (SolveGmres, SolveGmresJacobi; kernels_gmres.hip has the loop, include/MgcgGpu.h the method), one rank.  V: the basis, column i at
 // V + i * stride, m + 1 columns; w: the product's output; r: where the start and every restart leave b - A x.  With dinv `gather` is the one
-// buffer that holds hat(v_j) for the next product; without it the products gather from v_j itself and gather is null.
+// buffer that holds hat(v_j) for the next product; without it the products gather from v_j itself and gather is null.  The flexible form
+// (SolveGmresMg): Z holds z_j = M^-1 v_j, column j at Z + j * stride, m columns, written by the caller's cycles; the products gather from z_j
+// and the close adds sum y_i z_i.  Null in the other two forms.
 struct GmresRun {
     Workspace* ws;
     int m, orth;
     double *x, *r, *w, *V, *gather; const double* dinv;
     long long stride, n;
+    double* Z;
 };
 // where the start, every restart and the closing product leave the partial sums of r.r
 double* gmres_rr_partials(Workspace* ws);
@@ -813,7 +816,7 @@ void gmres_enqueue_init(const GmresRun& R, const FinalizeArgs& f, int nPartials)
 void gmres_enqueue_restart(const GmresRun& R, const FinalizeArgs& f, int k, int nRr, bool first);
 // everything of step k (j = k mod m) behind its product: the orthogonalisation passes and pass N
 void gmres_enqueue_step(const GmresRun& R, const FinalizeArgs& f, int k, int j);
-// the close: y, and x += hat(sum y_i v_i) over the columns the cycle completed; does nothing when there are none
+// the close: y, and x += hat(sum y_i v_i) -- with Z: x += sum y_i z_i -- over the columns the cycle completed; does nothing when there are none
 void gmres_enqueue_close(const GmresRun& R);
 
 // Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).

@@ -2,7 +2,16 @@
 // right-preconditioned with M = I or M = diag(A), one rank.  An iteration is one Arnoldi step -- one product -- and a cycle is m of them; the
 // residual never increases, the method cannot break down on a nonsingular matrix, and every restart recomputes r = b - A x by a product, so
 // the judged figure cannot drift from the true one for longer than a cycle.  include/MgcgGpu.h has the method and its rounding contract;
-// solver.hip's cg_solve_gmres the host's side.  Out of scope: several ranks, the V-cycle form, flexible GMRES, m > 32, the C++ twin under host/.
+// solver.hip's cg_solve_gmres the host's side.  Out of scope: several ranks, a non-flexible V-cycle form, m > 32, the C++ twin under host/.
+//
+// The V-cycle form (SolveGmresMg) is flexible GMRES on these kernels, none of them changed: the host enqueues a cycle z_j = M^-1 v_j in front
+// of step j's product, straight into column j of a second block Z behind the basis (GmresRun::Z), the product gathers from that column, and
+// the close hands Z to gmres_x_kernel as its column base: x += sum y_i z_i in the same groups, term order and rounding.  Everything between
+// the product and the close works on V as before.  Its flag argument: the cycle and the product take the LIVE stop flag as their gate, which
+// pass N alone raises and nobody writes while they run; a cycle enqueued behind a stop returns at the gate in every kernel and leaves z_{j+1}
+// unwritten; the close reads columns below cols only, and column cols - 1 = j was written by the cycle in front of step j, with the flag
+// down.  A cycle writes its column and the hierarchy's own iterates, never x, V, w or a scalar of the loop, so a work vector full of NaN on
+// entry does not reach the result.  The close launches stay ungated and keyed on cols / yCount.
 //
 // The basis v_0 .. v_m lives in ONE work vector, column i at V + i * stride (and the gather buffer of the Jacobi form behind them); w is the
 // caller's Ap vector.  The orthogonalisation is classical Gram-Schmidt applied `orth` times -- the j + 1 sums of a pass are independent, so
@@ -390,7 +399,7 @@ static GmresPass gmres_pass_args(const GmresRun& R, const FinalizeArgs& f, int k
 }
 
 // every vector a pass may touch is 16-byte aligned (the columns lie an even number of entries apart)
-static bool gmres_v2(const GmresRun& R) { return al16(R.x) && al16(R.w) && al16(R.V) && al16(R.gather) && al16(R.r) && al16(R.dinv) && (R.stride & 1) == 0; }
+static bool gmres_v2(const GmresRun& R) { return al16(R.x) && al16(R.w) && al16(R.V) && al16(R.Z) && al16(R.gather) && al16(R.r) && al16(R.dinv) && (R.stride & 1) == 0; }
 
 // go(V2, NTV, DINV) for the form this call takes
 template <typename Go> static void gmres_with_form(const GmresRun& R, bool v2, Go go)
@@ -471,6 +480,7 @@ void gmres_enqueue_close(const GmresRun& R)
     hipLaunchKernelGGL(gmres_solve_kernel, dim3(1), dim3(kBlock), 0, s, R.ws->gmresScalars);
     FinalizeArgs none{};
     GmresPass a = gmres_pass_args(R, none, 0, 0);
+    if (R.Z) a.V = R.Z;                                // the flexible form: the same pass over the stored z_i, x += sum y_i z_i
     const bool v2 = gmres_v2(R);
     const int grid = grid_for(R.n, v2 ? 2 : 1);
     for (int c0 = 0; c0 < R.m; c0 += kGmresGroup) {

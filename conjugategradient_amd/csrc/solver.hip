@@ -1566,8 +1566,8 @@ static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, 
                                   "the first residual is zero or not finite, or the recurrence broke down (rt.u_{j+1}, omega or rt.r_0 zero, or a value that is not finite)");
 }
 
-// ---------------------------------------------------------------- GMRES(m) (SolveGmres, SolveGmresJacobi)
-// Restarted GMRES for A x = b, A any CSR matrix, 1 <= m <= kGmresMaxM, right-preconditioned with M = I or M = diag(A) (R.dinv), one rank
+// ---------------------------------------------------------------- GMRES(m) (SolveGmres, SolveGmresJacobi, SolveGmresMg)
+// Restarted GMRES for A x = b, A any CSR matrix, 1 <= m <= kGmresMaxM, right-preconditioned with M = I, M = diag(A) (R.dinv) or a V-cycle (R.mg), one rank
 // (include/MgcgGpu.h has the method, kernels_gmres.hip the passes).  The host's side is cg_drive: an iteration is one Arnoldi step -- the
 // product and the passes of gmres_enqueue_step -- and in front of every m-th the close and the restart.  Every product is the plain loop's
 // (cg_enqueue_product, gather vector switched per step), so compression modes and automatic column tiles apply unchanged; the deferred x
@@ -1576,7 +1576,13 @@ static int cg_solve_bicgstabl(CgRun& R, const char* who, int ell, double* work, 
 // entries apart.  The close is enqueued once more behind the loop: it applies the columns of the cycle that the stop, the cap or a breakdown
 // cut short, and does nothing when a close in front of a restart that was enqueued behind the stop has done so already.  One more product
 // leaves the true residual b - A x in the caller's r.
-static int gmres_slices(int m, bool jacobi) { return m + 1 + (jacobi ? 1 : 0); }
+// The flexible form (SolveGmresMg, R.mg): behind v_0 .. v_m `work` holds z_0 .. z_{m-1}.  In front of step k's product a cycle writes
+// z_j = M^-1 v_j straight into its slice, the product gathers from that slice, and the close adds sum y_i z_i (gmres_enqueue_close with
+// P.Z).  The cycle and the product are gated on the live stop flag, which pass N alone raises and nobody writes while they run; a cycle
+// enqueued behind a stop returns at the gate and leaves its slice unwritten, and the close -- not gated, keyed on cols -- reads columns
+// below cols only, each of which a cycle that ran in front of the stop has written.  A cycle writes its slice and the hierarchy's own
+// iterates, never x, V, w or a scalar of the loop.
+static int gmres_slices(int m, bool jacobi, bool flexible) { return flexible ? 2 * m + 1 : m + 1 + (jacobi ? 1 : 0); }
 static int cg_solve_gmres(CgRun& R, const char* who, int m, int orth, double* work, int* iteration, double* residual, double* trueResidual,
                           double* residualTrace, int traceCapacity)
 {
@@ -1592,6 +1598,7 @@ static int cg_solve_gmres(CgRun& R, const char* who, int m, int orth, double* wo
     GmresRun P{};
     P.ws = ws; P.m = m; P.orth = orth; P.x = R.x; P.r = R.r; P.w = bufAp; P.V = work; P.dinv = R.dinv; P.stride = stride; P.n = n;
     P.gather = R.dinv ? work + (m + 1) * stride : nullptr;
+    P.Z = R.mg ? work + (m + 1) * stride : nullptr;
 
     // r = b - A x through bufP ; beta^2 = r.r ; v_0 = r / beta ; gather = dinv v_0 ; g_0 = beta for step k.  The start also sets the scalars.
     auto restart = [&](int k, bool first) {
@@ -1609,10 +1616,11 @@ static int cg_solve_gmres(CgRun& R, const char* who, int m, int orth, double* wo
             gmres_enqueue_close(P);
             if (!restart(k, false)) return false;
         }
-        double* from = P.gather ? P.gather : P.V + j * stride;
+        double* from = P.Z ? P.Z + j * stride : P.gather ? P.gather : P.V + j * stride;
         int nSums = 0;
+        if (P.Z && !mg_apply(R.mg, P.V + j * stride, from, done)) return false;          // the flexible form: z_j = M^-1 v_j
         R.p = from; R.Ap = P.w;
-        if (!cg_enqueue_product(R, from, &nSums)) return false;                          // w = A hat(v_j)
+        if (!cg_enqueue_product(R, from, &nSums)) return false;                          // w = A hat(v_j) (the flexible form: w = A z_j)
         gmres_enqueue_step(P, f, k, j);                                                  // h ; w ; the rotations ; the stop decision ; v_{j+1}
         return true;
     });
@@ -1938,7 +1946,7 @@ static int cg_variant_call(const CgCall& c, bool handles, Checks checks, Body bo
 }
 
 // The one-rank exports whose loop keeps its vectors in one work vector (BiCGStab(l), GMRES(m)): what they all take.  jacobi: dinv is a
-// handle the export requires.
+// handle the export requires; vcycle: the hierarchy is.
 struct CgWorkCall {
     const char* who; bool jacobi;
     MgcgBlas* cublas; MgcgSparse* cusparse;
@@ -1947,7 +1955,18 @@ struct CgWorkCall {
     int elementsCount, count;
     double allowableResidual; int minIteration, maxIteration, rule;
     int* iteration; double* residual; double* trueResidual; double* residualTrace; int traceCapacity;
+    bool vcycle = false; MgcgMg* mg = nullptr;     // the V-cycle form (SolveGmresMg): the hierarchy is a handle the export requires
 };
+
+// The hierarchy of a V-cycle form (SolveMinresMg, SolveBicgstabMg, SolveGmresMg): one rank, `count` rows on level 0 -- whatever matrix it
+// was built from.  True: refused.
+static bool cg_hierarchy_refused(const char* who, const MgcgMg* mg, int count)
+{
+    if (mg->nranks != 1 || mg->multi) set_error("%s: the hierarchy was built for %d rank(s)%s; the V-cycle form runs on one rank", who, mg->nranks, mg->multi ? " on the several-ranks path" : "");
+    else if (mg->levels < 1 || mg->lv[0].n != count) set_error("%s: the hierarchy has %lld rows on level 0, the matrix has %d", who, mg->levels < 1 ? 0LL : (long long)mg->lv[0].n, count);
+    else return false;
+    return true;
+}
 
 // Their entry (refusals: cg_variant_call).  params(): the export's refusals of its own sizes, in front of the rule's; slices: how many
 // vectors the work vector holds, cg_work_stride(count) apart; noun, value: the size that the short work vector's message names; loop(R): the solve.
@@ -1964,11 +1983,12 @@ static int cg_work_vector_call(const CgWorkCall& w, Params params, int slices, c
             set_error("%s: the work vector holds %lld entries, %s = %d needs %lld (%d slices of %lld: the matrix has %d rows)", who, w.work->size, noun, value, need, slices, cg_work_stride(w.count), w.count);
             return false;
         }
-        return !(w.jacobi && cg_vector_short(who, "dinv", w.dinv, w.count, "local rows"));
+        return !(w.jacobi && cg_vector_short(who, "dinv", w.dinv, w.count, "local rows")) && !(w.vcycle && cg_hierarchy_refused(who, w.mg, w.count));
     };
-    return cg_variant_call(c, w.cublas && w.cusparse && w.work && (!w.jacobi || w.dinv), checks, [&](CgRun& R) {
+    return cg_variant_call(c, w.cublas && w.cusparse && w.work && (!w.jacobi || w.dinv) && (!w.vcycle || w.mg), checks, [&](CgRun& R) {
         if (R.multi) { set_error("%s: the loop runs on one rank", who); return (int)MGCG_ERROR; }
         if (w.jacobi) R.dinv = cg_dinv_address(R, w.dinv);
+        if (w.vcycle) R.mg = w.mg;
         cg_set_stop(R, w.allowableResidual, w.minIteration, w.maxIteration, w.rule);
         cg_note_written({ R.x, R.Ap, R.r, R.p }, w.count);
         cg_note_written({ w.work->data }, slices * cg_work_stride(w.count));
@@ -1989,7 +2009,7 @@ static int bicgstabl_call(const CgWorkCall& w, int ell)
     });
 }
 
-// GMRES(m) (cg_solve_gmres above)
+// GMRES(m) (cg_solve_gmres above); w.vcycle: the flexible form, 2 m + 1 slices
 static int gmres_call(const CgWorkCall& w, int m, int orth)
 {
     auto params = [&] {
@@ -1998,7 +2018,7 @@ static int gmres_call(const CgWorkCall& w, int m, int orth)
         else return true;
         return false;
     };
-    return cg_work_vector_call(w, params, gmres_slices(m, w.jacobi), "m", m, [&](CgRun& R) {
+    return cg_work_vector_call(w, params, gmres_slices(m, w.jacobi, w.vcycle), "m", m, [&](CgRun& R) {
         return cg_solve_gmres(R, w.who, m, orth, w.work->data, w.iteration, w.residual, w.trueResidual, w.residualTrace, w.traceCapacity);
     });
 }
@@ -3216,16 +3236,6 @@ int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
 }
 
-// The hierarchy of a V-cycle form (SolveMinresMg, SolveBicgstabMg): one rank, `count` rows on level 0 -- whatever matrix it was built from.
-// True: refused.
-static bool cg_hierarchy_refused(const char* who, const MgcgMg* mg, int count)
-{
-    if (mg->nranks != 1 || mg->multi) set_error("%s: the hierarchy was built for %d rank(s)%s; the V-cycle form runs on one rank", who, mg->nranks, mg->multi ? " on the several-ranks path" : "");
-    else if (mg->levels < 1 || mg->lv[0].n != count) set_error("%s: the hierarchy has %lld rows on level 0, the matrix has %d", who, mg->levels < 1 ? 0LL : (long long)mg->lv[0].n, count);
-    else return false;
-    return true;
-}
-
 // BiCGStab (cg_solve_bicgstab above; refusals: cg_variant_call).  With `jacobi` dinvVector is a handle the export requires, with `vcycle`
 // the hierarchy (one rank: the export passes no communicator and the whole matrix).
 static int bicgstab_entry(const char* who, bool jacobi, bool vcycle, MgcgMg* mg, MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse,
@@ -3373,6 +3383,20 @@ int SolveGmresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDe
     (void)matDescr;
     return gmres_call({ "SolveGmresJacobi", true, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
                         workVector, dinvVector, elementsCount, count, allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity }, m, orth);
+}
+
+// The V-cycle form (one rank): flexible GMRES, z_j = M^-1 v_j stored behind the basis.  The hierarchy may come from any matrix.
+int SolveGmresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
+                 int m, int orth, int elementsCount, int count,
+                 double allowableResidual, int minIteration, int maxIteration, int rule,
+                 int* iteration, double* residual, double* trueResidual, double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    return gmres_call({ "SolveGmresMg", false, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector,
+                        workVector, nullptr, elementsCount, count, allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity,
+                        true, mg }, m, orth);
 }
 
 // Preconditioned MINRES (cg_solve_pminres above; refusals: cg_variant_call).  dinvVector, the hierarchy and zVector are handles the exports

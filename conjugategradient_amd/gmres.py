@@ -11,8 +11,9 @@ drift.
 ``BiConjugateGradientStabLGpu``'s class surface: ``Iteration``, ``MinIteration``, ``MaxIteration`` and the trace count Arnoldi steps (one
 product each), ``Residual`` is the rotated estimate of || b - A x ||_2, ``TrueResidual`` that norm itself from one closing product, and
 ``ReadResidual()`` returns that vector.  ``m`` (1 .. 32) is the restart length, ``orth`` (1 or 2) the number of classical Gram-Schmidt
-passes per step.  ``GeneralizedMinimalResidualJacobiGpu`` is the same with M = diag(A) as right preconditioner.  One rank; no V-cycle form
-yet.
+passes per step.  ``GeneralizedMinimalResidualJacobiGpu`` is the same with M = diag(A) as right preconditioner.  One rank.  The V-cycle as right
+preconditioner, in Saad's flexible form (``SolveGmresMg``), is the method ``SolveGmres(trace=False, hierarchy=None, m=20, orth=2)`` of
+``multigrid.ConjugateGradientMgGpu``, ``amg.ConjugateGradientAmgGpu`` and ``ssor.ConjugateGradientSsorGpu``.
 
 The max-norm stop rule is not supported.  No arithmetic happens in this module.
 """

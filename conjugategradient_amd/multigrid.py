@@ -13,6 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import MgcgError, check, lib
 from .bicgstab import _WORK as _BICGSTAB_WORK          # vectorV, vectorS, vectorT, vectorRhat
+from .gmres import MAX_M as _GMRES_MAX_M
 from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
 
 class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
@@ -39,10 +40,11 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
             self.mg = None
         if getattr(self, "vectorZ", None) is not None:
             self.vectorZ.Dispose()
-        for name in ("vectorW1", "vectorW2", "vectorR1") + _BICGSTAB_WORK:   # SolveMinres's and SolveBicgstab's work space, if they ran
+        for name in ("vectorW1", "vectorW2", "vectorR1", "vectorWork") + _BICGSTAB_WORK:   # SolveMinres's, SolveGmres's and SolveBicgstab's work space, if they ran
             if getattr(self, name, None) is not None:
                 getattr(self, name).Dispose()
                 setattr(self, name, None)
+        self._work_size = 0
         super().Dispose()
 
     def Initialize(self):
@@ -186,8 +188,44 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
             check("SolveBicgstabMg")
             raise MgcgError(f"SolveBicgstabMg failed with status {st}")
 
+    def SolveGmres(self, trace: bool = False, hierarchy=None, m: int = 20, orth: int = 2):
+        """Solve A x = b, A any CSR matrix, with restarted GMRES(m) right-preconditioned by a hierarchy's V-cycle in the flexible form
+        (SolveGmresMg): the loop for the systems on which ``SolveBicgstab`` ends MGCG_NONFINITE -- where it converges, ``SolveBicgstab``
+        is the faster one.  The hierarchy is ``self.mg`` or, with ``hierarchy``, the ``mg`` of another multigrid object with as many
+        rows, as in ``SolveBicgstab``.  ``m`` (1 .. 32) is the restart length, ``orth`` (1 or 2) the number of classical Gram-Schmidt
+        passes per step; the library checks both.  ``vectorWork`` holds the ``2 m + 1`` slices v_0 .. v_m, z_0 .. z_{m-1}: it is
+        allocated at the first call and again, larger, when ``m`` has grown.  ``Iteration``, ``Residual`` and ``trace`` count Arnoldi
+        steps (one cycle and one product each) and show the rotated estimate of || b - A x ||_2; ``TrueResidual`` is that norm itself
+        from the closing product and ``ReadResidual()`` returns that vector."""
+        need = (2 * min(max(int(m), 1), _GMRES_MAX_M) + 1) * (self.Count + (self.Count & 1))
+        if need > getattr(self, "_work_size", 0):
+            if getattr(self, "vectorWork", None) is not None:
+                self.vectorWork.Dispose()
+            self.vectorWork, self._work_size = VectorDouble(need), need
+        mg = self.mg if hierarchy is None else hierarchy.mg
+        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
+        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
+        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        rule = _lib.RULE_CSHARP if self.rule is None else self.rule
+        st = lib().SolveGmresMg(self.cublas, self.cusparse, self.matDescr, mg,
+                                self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                self.vectorWork.Ptr, int(m), int(orth),
+                                nonzeroCount, self.Count, self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
+                                C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
+        if trace:
+            self.trace = tr[: self.Iteration + 1].copy()
+        if st == _lib.MAXIT_EXCEEDED:
+            lib().MgcgClearLastError()
+            raise ApplicationException(f"V-cycle-preconditioned GMRES(m) did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check("SolveGmresMg")
+            raise MgcgError(f"SolveGmresMg failed with status {st}")
+
     def ReadResidual(self) -> np.ndarray:
-        """The true residual that the closing product of the last SolveMinres() or SolveBicgstab() left in its work vector."""
+        """The true residual that the closing product of the last SolveMinres(), SolveBicgstab() or SolveGmres() left in its work vector."""
         r = np.empty(self.Count)
         self.vectorR.CopyTo(r, self.Count, 0)
         return r

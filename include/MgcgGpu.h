@@ -1018,8 +1018,8 @@ int SolveBicgstabLJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* m
  * that is too short (with both sizes), MGCG_RULE_HANDMADECL, and everything SolveBicgstab refuses; a communicator of several ranks ("the loop
  * runs on one rank").
  * The matrix product is SolveEx's (compression modes and the automatic column tiles apply); the deferred x update, the placement draw and the
- * overlap schedule do not apply.  Out of scope, and next: several ranks, the V-cycle form, flexible GMRES, m > 32, the C++ twin under host/,
- * the front-ends. */
+ * overlap schedule do not apply.  The V-cycle as preconditioner, in the flexible form: SolveGmresMg below.  Out of scope, and next: several
+ * ranks, a non-flexible V-cycle form, m > 32, the C++ twin under host/, the front-ends. */
 int SolveGmres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
@@ -1032,6 +1032,49 @@ int SolveGmresJacobi(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDe
                      int m, int orth, int elementsCount, int count,
                      double allowableResidual, int minIteration, int maxIteration, int rule,
                      int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
+/* ---- V-cycle-preconditioned flexible GMRES(m): the robust nonsymmetric solver with this library's strongest preconditioner (one rank) ---- */
+/* SolveGmres right-preconditioned with the V-cycle of a hierarchy (MgSetup, MgSetupAggregation, MgSetupAggregates; either smoother), in Saad's
+ * FLEXIBLE form: z_j = M^-1 v_j is stored beside the basis and the close adds sum y_i z_i.  SolveBicgstabMg is the faster loop where it
+ * converges; where convection dominates (a central stencil at cell Peclet number >= 2) it ends MGCG_NONFINITE and this loop still converges --
+ * slowly: there the Jacobi-smoothed cycle is a poor map, and what is bought is robustness, not speed.  As in
+ * SolveBicgstabMg the hierarchy may come from ANY matrix with `count` rows, the matrix itself or its symmetric part, for instance; only its
+ * row count is checked.  The flexible form asks nothing of M, not even that it be a fixed linear map.
+ * Method: SolveGmres's with d = 1, line by line, and these changes only.
+ *   start   as SolveGmres
+ *   step k  z_j = M^-1 v_j            MgApply's fixed sequence of operations on the caller's hierarchy, written straight into slice z_j
+ *           w = A z_j                 the product gathers from that slice
+ *           the `orth` Gram-Schmidt passes over v_0 .. v_j, pass N, the rotations, both no-next-direction branches, the stop decision,
+ *           the trace, the iteration count and v_{j+1} = w/hn: SolveGmres's, unchanged, on V
+ *   close   y as in SolveGmres ;  in groups of 8 columns, c0 = 0, 8 ..:  t = 0 ; for i = c0 .. min(c0 + 8, cols) - 1: t = t + y_i*z_i ;
+ *           x = x + t                 (SolveGmres's close with Z in place of V: same groups, term order and rounding contract)
+ *   restart, end   as SolveGmres
+ * A cycle runs after the start, after every restart and after every pass N that did not stop: in front of every product, m per cycle of m
+ * steps and none in the close (x = x + M^-1 (V y) would need one there).  The judged figure is the 2-norm of the system's own residual (right
+ * preconditioning); minIteration, maxIteration, the trace and *iteration count steps of one cycle and one product each.  Under dot_order = 1
+ * the whole loop is a fixed sequence of IEEE operations (tests/test_gmres_mg_host.py restates it in numpy with Hierarchy.apply).
+ * FLAG DISCIPLINE.  The cycle and the product take the LIVE stop flag as their gate: pass N alone raises it, and no workgroup of pass N runs
+ * beside them (one stream).  A cycle enqueued behind a stop therefore returns at the gate in every one of its kernels and leaves z_{j+1}
+ * unwritten; the close reads columns i < cols only, and column cols - 1 = j was written by the cycle in front of step j, which ran with the
+ * flag down -- so an unwritten slice is never read, and a work vector full of NaN on entry does not reach the result.  A cycle writes its z
+ * slice and the hierarchy's own iterates, never x, V, w or a scalar of the loop.  The close launches stay ungated and keyed on cols / yCount,
+ * as in SolveGmres: x is updated exactly once per cycle whatever was enqueued behind the stop.  A restart that found r.r zero or not finite
+ * wrote no v_0; the cycle and the product behind it run on the previous cycle's v_0 and write z_0 and w only, which nothing reads: the next
+ * pass N publishes the end and cols is 0.
+ *   workVector      slices of `count` entries, count rounded up to even apart: v_0 .. v_m, then z_0 .. z_{m-1} -- 2 m + 1 slices (41 vectors
+ *                   at m = 20).  Whatever it holds on entry does not reach the result.
+ *   rVector, pVector, ApVector   as SolveGmres
+ * Refused with MGCG_ERROR, a message and nothing enqueued: everything SolveGmres refuses (m outside 1 .. 32, orth outside {1, 2}, the rule,
+ * a communicator of several ranks); a work vector shorter than 2 m + 1 slices (with both sizes); a null mg; a hierarchy of several ranks; a
+ * hierarchy whose level 0 does not have `count` rows ("... rows on level 0, the matrix has ...", as SolveMinresMg).
+ * Out of scope, and next: several ranks, a non-flexible form (x = x + M^-1 (V y): m fewer slices, one more cycle per restart, and a gated
+ * cycle inside the ungated close), m > 32, changes inside the cycle's kernels, the C++ twin under host/. */
+int SolveGmresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                 Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                 Vector* xVector, Vector* bVector, Vector* ApVector, Vector* pVector, Vector* rVector, Vector* workVector,
+                 int m, int orth, int elementsCount, int count,
+                 double allowableResidual, int minIteration, int maxIteration, int rule,
+                 int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
