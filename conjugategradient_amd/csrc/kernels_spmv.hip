@@ -358,7 +358,9 @@ __global__ __launch_bounds__(BLOCK) void spmv_stream_kernel(SpmvArgs a, int nRow
     }
 }
 
-// LANES lanes per row (power of two, 2..64).  VNT: the values are read with the non-temporal hint and the column ids without it -- for a matrix
+// LANES lanes per row (power of two, 1..64; 1: no tree, the stored-order sum).  Lane l adds the rounded products of entries l, l + LANES, ...
+// in stored order from +0.0, then acc += shfl_down(acc, off) for off = LANES/2 .. 1: a fixed order, pinned bit for bit by
+// tests/test_gpu_products.py against tests/product_cases.py: lanes_per_row_sum.  VNT: the values are read with the non-temporal hint and the column ids without it -- for a matrix
 // whose 12 bytes per nonzero exceed the 256 MB Infinity Cache while its column ids alone fit (the reference drivers' 200-350 k rows x 159:
 // 130-220 MB of column ids): the ids then stay cache-resident from one product of a solve to the next and only the values come from HBM.
 template <int EPI, int LANES, bool VNT = false>
@@ -545,12 +547,13 @@ static int launch_spmv_epi(hipStream_t s, const SpmvArgs& a, const SpmvConfig& c
     }
     switch (kernel) {
     case 1: return launch_stream<EPI>(s, a, cfg);
+    case 2: return launch_vector_l<EPI, 1>(s, a, cfg);      // one lane per row: the shuffle tree is empty, the sum runs in stored order
     case 3: return launch_vector_l<EPI, 2>(s, a, cfg);
     case 4: return launch_vector_l<EPI, 4>(s, a, cfg);
     case 5: return launch_vector_l<EPI, 8>(s, a, cfg);
     case 6: return launch_vector_l<EPI, 16>(s, a, cfg);
     case 7: return launch_vector_l<EPI, 32>(s, a, cfg);
-    default: return launch_vector_l<EPI, 64>(s, a, cfg);
+    default: return launch_vector_l<EPI, 64>(s, a, cfg);     // 8, and every id the header does not list
     }
 }
 

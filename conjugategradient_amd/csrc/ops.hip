@@ -80,6 +80,7 @@ double CsrMVDot(MgcgBlas* cublas, MgcgSparse* cusparse, double* y,
     a.elementsCount = elementsCount; a.rowCount = rowCount; a.columnCount = columnCount; a.w = w; a.partials = cublas->ws.partials;
     const SpmvConfig cfg = cfg_for(cusparse, a, 0);
     const DcsrMatrix* dc = dcsr_lookup_op(cusparse, a, 0);
+    analysis_note_write(y, sizeof(double) * (size_t)rowCount);
     int n = launch_spmv_auto(cublas->ws.stream, EPI_DOT, a, cfg, dc);
     if (dot_reference_order()) { launch_dot_serial(cublas->ws.stream, w, y, rowCount, cublas->ws.partials, nullptr); n = 1; }
     return finish_reduction(cublas->ws, n, 0);

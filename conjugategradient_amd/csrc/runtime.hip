@@ -331,7 +331,10 @@ const DcsrMatrix* dcsr_lookup(MgcgSparse* h, const double* elements, const int* 
     // 3. for matrices whose gathers have no locality (sorted rows, entries far from the diagonal): mode 3 first the propagation-blocking
     //    form (x from LDS, kernels_pb.hip), then -- modes 1 and 3 -- the column-tiled copy
     const bool best = h->compression == 1 || h->compression == 3;
-    if (best && avg <= 32.0 && pattern_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, rowBase, m) && m->patternId != nullptr) {
+    // (the row-pattern kernel lets a masked slot of an empty row gather x[global row]: only where x is known to reach that far -- not for a
+    // matrix with more rows than columns, CsrMV's columnCount < rowCount)
+    const bool xCoversRows = columns <= 0 || columns >= rowBase + rows;
+    if (best && xCoversRows && avg <= 32.0 && pattern_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, rowBase, m) && m->patternId != nullptr) {
         m->usable = true;
     } else if ((((uintptr_t)elements) & 15) == 0 && avg <= 7.75) {
         if (!dcsr_build(h->ws.stream, elements, rowOffsets, columnIndeces, rows, nnz, rowBase, m)) { std::lock_guard<std::mutex> lock(g_analysedMutex); m->release(); identify(); }

@@ -236,7 +236,12 @@ double CsrMVDot(MgcgBlas* cublas, MgcgSparse* cusparse,
                 const double* x, const double* w,
                 int elementsCount, int rowCount, int columnCount);
 /* SpMV kernel selection for CsrMV-family calls on this handle:
- * 0 auto, 1 row-block LDS stream kernel, 2..8 = 2^(k-2) lanes per row (k=8: one wavefront per row). */
+ * 0 auto, 1 row-block LDS stream kernel, 2..8 = 2^(k-2) lanes per row (k=2: one lane per row, the stored-order sum; k=8: one
+ * wavefront per row), 9 row-block "stage raw, multiply by row" kernel, 10 row-tile kernel (256 rows per tile; the auto choice for
+ * short rows).  9 and 10 need elementsCount >= 8 and 16-byte aligned elements, 10 also 16-byte and 9 8-byte aligned
+ * columnIndeces; products that do not qualify fall back 10 -> 9 -> 1.  Kernels 1, 2, 9 and 10 add a row's rounded products in stored order; 3..8 let lane l add entries l, l + L, ... in
+ * stored order and join the L sums in the tree acc_l += acc_(l + off), off = L/2 .. 1.  Every other value (negative, 11, ...) is
+ * not an error: it runs what 8 runs.  A usable form of MgcgSetMatrixCompression takes precedence over this choice. */
 void   MgcgSetSpmvKernel(MgcgSparse* cusparse, int kernel);
 /* Tuning knobs of the stream kernel: rowsPerBlock in {64,128,256}, flags bit0 = non-temporal matrix
  * loads, bit1 = XCD-contiguous row-block mapping, bit2 = banded schedule; gridBlocks (0 = chip-filling default). */
