@@ -103,6 +103,9 @@ SIGNATURES = {
     "MgSetup": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _d, _i, _i, _d]),
     "MgSetupParallel": (_vp, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _i, _i, _d]),
     "MgSetupAggregation": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _i, _d, _i, _i, _d]),
+    "MgSetupAggregationEx": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _i, _d, _i, _i, _d, _i]),
+    "MgStrength": (_i, [_vp]),
+    "MgcgSymmetricPart": (_ll, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i]),
     "MgSetupAggregates": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _i, _i, _d]),
     "MgLevelCopyAggregates": (_i, [_vp, _i, _vp]),
     "MgDestroy": (None, [_vp]),

@@ -15,10 +15,44 @@ import numpy as np
 from . import _lib
 from ._lib import MgcgError, check, lib
 from .multigrid import ConjugateGradientMgGpu
-from .solver import _ptr
+from .problems import LinearSystem
+from .solver import ConjugateGradientGpu, VectorDouble, VectorInt, _ptr
 
 
 SMOOTHERS = {"jacobi": 0, "gs": 1}          # MgSetSmoother's modes
+STRENGTHS = {"own": 0, "symmetric": 1}      # MgSetupAggregationEx's: what the matching reads
+
+
+def symmetric_part_gpu(system: LinearSystem) -> LinearSystem:
+    """(A + A^T) / 2 of a system's matrix formed on the device (``MgcgSymmetricPart``), with the same b, x and grid: the device counterpart
+    of ``problems.symmetric_part``.  Columns ascend and appear once a row; unlike the host routine it KEEPS the sums that come to zero, as
+    stored 0.0 entries (an entry >= 0 never couples in the matching, so they change no map).  Rows of A may be unsorted and hold
+    duplicates."""
+    _lib.require_gpu()
+    L = lib()
+    n, nnz = system.Count, system.nnz
+    if 2 * nnz > 2 ** 31 - 1:
+        raise MgcgError(f"symmetric_part_gpu: 2 x {nnz} entries exceed INT_MAX")
+    blas, sparse = ConjugateGradientGpu.CreateBlas(), ConjugateGradientGpu.CreateSparse()
+    vectors = []
+    try:
+        for kind, size in ((VectorDouble, nnz), (VectorInt, n + 1), (VectorInt, nnz), (VectorDouble, 2 * nnz), (VectorInt, n + 1), (VectorInt, 2 * nnz)):
+            vectors.append(kind(max(size, 1)))
+        a, ro, ci, sa, sro, sci = vectors
+        a.CopyFrom(np.ascontiguousarray(system.Elements[:nnz], dtype=np.float64), nnz)
+        ro.CopyFrom(np.ascontiguousarray(system.RowOffsets, dtype=np.int32), n + 1)
+        ci.CopyFrom(np.ascontiguousarray(system.ColumnIndeces[:nnz], dtype=np.int32), nnz)
+        count = L.MgcgSymmetricPart(blas, sparse, a.Ptr, ro.Ptr, ci.Ptr, nnz, n, sa.Ptr, sro.Ptr, sci.Ptr, 2 * nnz)
+        check("MgcgSymmetricPart")
+        if count < 0:
+            raise MgcgError("MgcgSymmetricPart failed")
+        return LinearSystem(sa.to_numpy(count), sci.to_numpy(count), sro.to_numpy(n + 1), np.array(system.x, dtype=np.float64),
+                            np.array(system.b, dtype=np.float64), f"{system.name}-sym", grid=system.grid)
+    finally:
+        for v in vectors:
+            v.Dispose()
+        L.DestroyBlas(blas)
+        L.DestroySparse(sparse)
 
 
 class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
@@ -31,14 +65,21 @@ class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
     ``smoother``: "jacobi" (weighted Jacobi, the default) or "gs" (multicolour Gauss-Seidel, MgSetSmoother(mg, 1): an even ``nuCoarse``
     and a structurally symmetric pattern of at most 64 colours a level; symmetric positive definite for every 0 < omega < 2).  It is
     applied in ``Setup()`` after the hierarchy is built; a refusal raises MgcgError with the library's message and leaves ``self.mg`` a
-    usable Jacobi hierarchy."""
+    usable Jacobi hierarchy.
+
+    ``strength``: what the library's matching reads -- "own" (the level's own matrix, the default: MgSetupAggregation) or "symmetric" (the
+    symmetric part of every level's own matrix, formed on the device: MgSetupAggregationEx with strength = 1; the level matrices stay
+    sigma * P^T A P of A itself).  For A != A^T, where "own" may not coarsen at all.  Ignored with ``aggregates``."""
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual,
                  levels: int = 8, passes: int = 3, theta: float = 0.25, minCoarse: int = 64, omega: float = 0.8, nu: int = 1, nuCoarse: int = 4,
-                 sigma: float = 0.5, aggregates=None, rule=_lib.RULE_CSHARP, smoother: str = "jacobi"):
+                 sigma: float = 0.5, aggregates=None, rule=_lib.RULE_CSHARP, smoother: str = "jacobi",
+                 strength: str = "own"):
         if smoother not in SMOOTHERS:
             raise MgcgError(f"smoother {smoother!r}, must be one of {sorted(SMOOTHERS)}")
-        self.smoother = smoother
+        if strength not in STRENGTHS:
+            raise MgcgError(f"strength {strength!r}, must be one of {sorted(STRENGTHS)}")
+        self.smoother, self.strength = smoother, strength
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, (count, 1, 1),
                          levels=levels, omega=omega, nu=nu, nuCoarse=nuCoarse, sigma=sigma, rule=rule)
         self.passes, self.theta, self.minCoarse = int(passes), float(theta), int(minCoarse)
@@ -55,11 +96,17 @@ class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
     def Setup(self):
         nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
         L = lib()
+        if self.aggregates is None and self.strength not in STRENGTHS:      # (changed after construction: refused before any call)
+            raise MgcgError(f"strength {self.strength!r}, must be one of {sorted(STRENGTHS)}")
         if self.mg:
             L.MgDestroy(self.mg)
             self.mg = None
         matrix = (self.cublas, self.cusparse, self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr, nonzeroCount, self.Count)
-        if self.aggregates is None:
+        if self.aggregates is None and STRENGTHS[self.strength]:
+            name = "MgSetupAggregationEx"
+            self.mg = L.MgSetupAggregationEx(*matrix, int(self.levels_requested), self.passes, self.theta, self.minCoarse,
+                                             self.omega, self.nu, self.nuCoarse, self.sigma, STRENGTHS[self.strength])
+        elif self.aggregates is None:
             name = "MgSetupAggregation"
             self.mg = L.MgSetupAggregation(*matrix, int(self.levels_requested), self.passes, self.theta, self.minCoarse,
                                            self.omega, self.nu, self.nuCoarse, self.sigma)

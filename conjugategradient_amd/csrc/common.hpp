@@ -913,6 +913,8 @@ void launch_amg_galerkin_count(hipStream_t s, long long nc, const int* aggOffset
 void launch_amg_galerkin_fill(hipStream_t s, long long nc, const int* aggOffsets, const int* members, const double* elements, const int* rowOffsets,
                               const int* columnIndeces, const int* agg, const int* expandOffsets, const int* scratch, const int* rowOffsetsC, double sigma,
                               double* elementsC, int* columnIndecesC);
+// out[k] = elements[source[k]], k < m: the values of the merged matrix [A | A^T] of MgcgSymmetricPart through the host-built entry list
+void launch_amg_gather_values(hipStream_t s, long long m, const int* source, const double* elements, double* out);
 
 // ---------------------------------------------------------------- multicolour Gauss-Seidel smoother (kernels_gs.hip; MgSetSmoother)
 // one colouring round: colourIn (-1 = uncoloured) -> colourOut; flags[0] = 1 if a row is left uncoloured; *badRow (pre-set to INT_MAX) = the

@@ -2,7 +2,8 @@
 // The algorithm is written out in include/MgcgGpu.h; tests/test_amg_host.py states it in numpy and the kernels here must EQUAL it:
 // every sum below is a serial sum in a fixed order from +0.0 (the library is built with -ffp-contract=off).
 //   cycle:   amg_restrict_kernel (bc[I] = sum of r over I's members, ascending), amg_prolong_add_kernel (x[i] += e[agg[i]])
-//   set-up:  the matching pass (row maxima, pick, match), the Galerkin product sigma * P^T A P for an arbitrary map, the diagonal check
+//   set-up:  the matching pass (row maxima, pick, match), the Galerkin product sigma * P^T A P for an arbitrary map, the diagonal check,
+//            the value gather of the merged matrix [A | A^T] from which MgcgSymmetricPart's S = (A + A^T) / 2 is summed by the Galerkin product
 #include "common.hpp"
 
 namespace mgcg {
@@ -236,6 +237,22 @@ void launch_amg_galerkin_fill(hipStream_t s, long long nc, const int* aggOffsets
     if (nc <= 0) return;
     hipLaunchKernelGGL(amg_galerkin_fill_kernel, dim3(amg_grid(nc)), dim3(kBlock), 0, s, nc, aggOffsets, members, elements, rowOffsets, columnIndeces, agg, expandOffsets,
                        scratch, rowOffsetsC, sigma, elementsC, columnIndecesC);
+}
+
+// ---------------------------------------------------------------- the symmetric part: the values of [A | A^T] row by row
+// out[k] = elements[source[k]]: `source` is the host-built list of A's entries in the order of the merged matrix (row i of A in stored order,
+// then the entries of column i by source row and stored order: the transposition permutation).  One lane per merged entry; out streams,
+// the A half of every row reads a contiguous run, the A^T half is the gather a transposition is.
+__global__ __launch_bounds__(kBlock) void amg_gather_values_kernel(long long m, const int* __restrict__ source, const double* __restrict__ elements,
+                                                                   double* __restrict__ out)
+{
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < m; k += stride) out[k] = elements[source[k]];
+}
+void launch_amg_gather_values(hipStream_t s, long long m, const int* source, const double* elements, double* out)
+{
+    if (m <= 0) return;
+    hipLaunchKernelGGL(amg_gather_values_kernel, dim3(amg_grid(m)), dim3(kBlock), 0, s, m, source, elements, out);
 }
 
 void preload_kernels_amg() { preload_code_object(reinterpret_cast<const void*>(&amg_restrict_kernel)); }

@@ -89,6 +89,7 @@ struct MgcgMg {
     bool deepFolds = false;                // levels >= 1 form x_1 and x_1 + P e per gather too (uniform diagonals, power-of-two nx and ny)
     bool skipHalo = false;                 // the next SpMV-shaped pass finds its halo planes already in place (deep-halo cycle: formed locally)
     bool algebraic = false;                // built from aggregates of the matrix graph, not from a grid (also when it has a single level)
+    int strength = 0;                      // what the matching read (MgSetupAggregationEx): 0 the level's own matrix, 1 its symmetric part
 };
 
 namespace mgcg {
@@ -2692,6 +2693,65 @@ static bool amg_level_map(hipStream_t s, const AmgMatrix& A, int passes, double 
     return ok;
 }
 
+// *out = S, the symmetric part of A by the contract of MgcgSymmetricPart (include/MgcgGpu.h), in storage of its own (the caller frees it, also
+// after a failure).  The merged matrix [A | A^T] -- row i = A's row i in stored order, then the stored entries of column i by source row and
+// stored order -- goes through amg_galerkin with the identity map and sigma = 0.5: its contract (entries in stored order, accumulators from
+// +0.0, columns ascending, sigma * acc) is S's.  The offsets and columns come to the host for the counting sort by column (the transposition
+// permutation: index bookkeeping); the values stay on the device and are gathered there.  false with the message set on a refusal.
+static bool amg_symmetric_part(const char* who, hipStream_t s, const AmgMatrix& A, AmgMatrix* out)
+{
+    const size_t n = (size_t)A.n;
+    std::vector<int> ro(n + 1);
+    if (!MGCG_HIP(hipMemcpyAsync(ro.data(), A.rowOffsets, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s)) || !MGCG_HIP(hipStreamSynchronize(s))) return false;
+    if (ro[0] != 0) { set_error("%s: rowOffsets[0] is %d, must be 0", who, ro[0]); return false; }
+    for (size_t i = 0; i < n; ++i)
+        if (ro[i + 1] < ro[i]) { set_error("%s: row %lld: the row offsets descend", who, (long long)i); return false; }
+    const long long nnz = ro[n];
+    if (nnz > A.nnz) { set_error("%s: the row offsets end at %lld, the matrix holds %lld entries", who, nnz, A.nnz); return false; }
+    if (2 * nnz > 0x7fffffffLL) { set_error("%s: 2 x %lld entries exceed int32 offsets", who, nnz); return false; }
+    const size_t nz = (size_t)nnz, mz = 2 * nz, mzAlloc = mz > 0 ? mz : 1;
+    std::vector<int> col(nz), mro(n + 1, 0);
+    if (nz > 0 && (!MGCG_HIP(hipMemcpyAsync(col.data(), A.columnIndeces, sizeof(int) * nz, hipMemcpyDeviceToHost, s)) || !MGCG_HIP(hipStreamSynchronize(s)))) return false;
+    for (size_t i = 0; i < n; ++i)
+        for (int k = ro[i]; k < ro[i + 1]; ++k) {
+            const int c = col[(size_t)k];
+            if (c < 0 || (size_t)c >= n) { set_error("%s: row %lld stores column %d, the matrix has %lld rows", who, (long long)i, c, (long long)n); return false; }
+            mro[(size_t)c + 1]++;                                                       // how often column c is stored: the length of A^T's row c
+        }
+    for (size_t i = 0; i < n; ++i) mro[i + 1] += mro[i] + (ro[i + 1] - ro[i]);
+    std::vector<int> source(mzAlloc, 0), mcol(mzAlloc, 0), at(n);
+    for (size_t i = 0; i < n; ++i) {
+        int p = mro[i];
+        for (int k = ro[i]; k < ro[i + 1]; ++k, ++p) { source[(size_t)p] = k; mcol[(size_t)p] = col[(size_t)k]; }
+        at[i] = p;
+    }
+    for (size_t i = 0; i < n; ++i)                                                      // the stable counting sort by column: source rows ascending, stored order within one
+        for (int k = ro[i]; k < ro[i + 1]; ++k) {
+            const size_t p = (size_t)at[(size_t)col[(size_t)k]]++;
+            source[p] = k; mcol[p] = (int)i;
+        }
+    AmgMatrix M; M.n = A.n; M.nnz = (long long)mz;
+    int* dSource = nullptr;
+    bool ok = MGCG_HIP(hipMalloc((void**)&M.elements, sizeof(double) * mzAlloc)) && MGCG_HIP(hipMalloc((void**)&M.columnIndeces, sizeof(int) * mzAlloc)) &&
+              MGCG_HIP(hipMalloc((void**)&M.rowOffsets, sizeof(int) * (n + 1))) && MGCG_HIP(hipMalloc((void**)&dSource, sizeof(int) * mzAlloc)) &&
+              MGCG_HIP(hipMemcpyAsync(M.columnIndeces, mcol.data(), sizeof(int) * mzAlloc, hipMemcpyHostToDevice, s)) &&
+              MGCG_HIP(hipMemcpyAsync(M.rowOffsets, mro.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, s)) &&
+              MGCG_HIP(hipMemcpyAsync(dSource, source.data(), sizeof(int) * mzAlloc, hipMemcpyHostToDevice, s));
+    if (ok) launch_amg_gather_values(s, (long long)mz, dSource, A.elements, M.elements);
+    if (ok) {
+        std::vector<int> identity(n);
+        for (size_t i = 0; i < n; ++i) identity[i] = (int)i;
+        AmgDeviceMap dm;
+        ok = amg_galerkin(s, M, identity, (int)n, 0.5, out, &dm);                       // (ends with a synchronise: the staging vectors above may go)
+        amg_free(dm);
+    } else {
+        (void)hipStreamSynchronize(s);
+    }
+    if (dSource) (void)hipFree(dSource);
+    amg_free(M);
+    return ok;
+}
+
 // nextMap(l, A_l, map, &nc): 1 = `map` holds level l's aggregates (nc of them), 0 = the hierarchy ends with level l, -1 = error (message set)
 typedef std::function<int(int, const AmgMatrix&, std::vector<int>&, int*)> AmgNextMap;
 static MgcgMg* amg_setup(const char* who, MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
@@ -2829,23 +2889,94 @@ static bool gs_colour_level(hipStream_t s, const MgLevel& L, int level, GsColour
 
 } // namespace mgcg
 
-MgcgMg* MgSetupAggregation(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
-                           int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
-                           double omega, int nu, int nuCoarse, double sigma)
+static MgcgMg* amg_setup_matching(const char* who, MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector,
+                                  VectorInt* columnIndecesVector, int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
+                                  double omega, int nu, int nuCoarse, double sigma, int strength)
 {
-    const char* who = "MgSetupAggregation";
     if (!amg_common_arguments(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, nu, nuCoarse)) return nullptr;
     if (passes < 1 || passes > 4) { set_error("%s: passes %d, must be 1 .. 4", who, passes); return nullptr; }
     if (!(theta > 0.0 && theta <= 1.0)) { set_error("%s: theta %g, must be in (0, 1]", who, theta); return nullptr; }
+    if (strength != 0 && strength != 1) { set_error("%s: strength %d, must be 0 (the matrix's own couplings) or 1 (its symmetric part's)", who, strength); return nullptr; }
     DeviceState* d = device_state();
     if (!d) return nullptr;
     hipStream_t s = d->stream;
     auto nextMap = [&](int, const AmgMatrix& A, std::vector<int>& map, int* nc) -> int {
         if (A.n <= minCoarse) return 0;
-        if (!amg_level_map(s, A, passes, theta, map, nc)) return -1;
+        if (strength == 1) {                              // the matching reads S_l = (A_l + A_l^T) / 2; the Galerkin product stays that of A_l
+            AmgMatrix S;
+            const bool made = amg_symmetric_part(who, s, A, &S) && amg_level_map(s, S, passes, theta, map, nc);
+            amg_free(S);
+            if (!made) return -1;
+        } else if (!amg_level_map(s, A, passes, theta, map, nc)) return -1;
         return (4LL * *nc > 3LL * A.n) ? 0 : 1;           // the next level would keep more than 3/4 of the rows ("nothing matched" included)
     };
-    return amg_setup(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, omega, nu, nuCoarse, sigma, nextMap);
+    MgcgMg* mg = amg_setup(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, omega, nu, nuCoarse, sigma, nextMap);
+    if (mg) mg->strength = strength;
+    return mg;
+}
+
+MgcgMg* MgSetupAggregation(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                           int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
+                           double omega, int nu, int nuCoarse, double sigma)
+{
+    return amg_setup_matching("MgSetupAggregation", cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, passes, theta,
+                              minCoarse, omega, nu, nuCoarse, sigma, 0);
+}
+
+MgcgMg* MgSetupAggregationEx(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                             int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
+                             double omega, int nu, int nuCoarse, double sigma, int strength)
+{
+    return amg_setup_matching("MgSetupAggregationEx", cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, elementsCount, count, levels, passes, theta,
+                              minCoarse, omega, nu, nuCoarse, sigma, strength);
+}
+
+int MgStrength(const MgcgMg* mg) { return mg ? mg->strength : 0; }
+
+long long MgcgSymmetricPart(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                            int elementsCount, int count, Vector* outElements, VectorInt* outRowOffsets, VectorInt* outColumnIndeces, int outCapacity)
+{
+    const char* who = "MgcgSymmetricPart";
+    if (!cublas || !cusparse || !elementsVector || !rowOffsetsVector || !columnIndecesVector) { set_error("%s: null handle", who); return -1; }
+    const bool countOnly = !outElements && !outRowOffsets && !outColumnIndeces;
+    if (!countOnly && (!outElements || !outRowOffsets || !outColumnIndeces)) { set_error("%s: null handle (the three output vectors are given together, or none of them)", who); return -1; }
+    if (count < 1 || elementsCount < 0) { set_error("%s: bad parameters (count %d, elementsCount %d)", who, count, elementsCount); return -1; }
+    if (2LL * elementsCount > 0x7fffffffLL) { set_error("%s: 2 x elementsCount %d exceeds INT_MAX", who, elementsCount); return -1; }
+    if (rowOffsetsVector->size < (long long)count + 1 || elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount) {
+        set_error("%s: matrix vectors too small (%lld values, %lld offsets, %lld columns for %d entries in %d rows)", who, (long long)elementsVector->size,
+                  (long long)rowOffsetsVector->size, (long long)columnIndecesVector->size, elementsCount, count);
+        return -1;
+    }
+    if (!countOnly) {
+        if (outCapacity < 0) { set_error("%s: outCapacity %d, must be >= 0", who, outCapacity); return -1; }
+        if (outRowOffsets->size < (long long)count + 1 || outElements->size < outCapacity || outColumnIndeces->size < outCapacity) {
+            set_error("%s: output vectors too small (%lld values, %lld offsets, %lld columns for a capacity of %d entries in %d rows)", who, (long long)outElements->size,
+                      (long long)outRowOffsets->size, (long long)outColumnIndeces->size, outCapacity, count);
+            return -1;
+        }
+    }
+    DeviceState* d = device_state();
+    if (!d) return -1;
+    hipStream_t s = d->stream;
+    AmgMatrix A; A.elements = elementsVector->data; A.rowOffsets = rowOffsetsVector->data; A.columnIndeces = columnIndecesVector->data; A.n = count; A.nnz = elementsCount;
+    AmgMatrix S;
+    bool ok = amg_symmetric_part(who, s, A, &S);
+    const long long nnzS = S.nnz;
+    if (ok && !countOnly && nnzS > outCapacity) {         // known once the pattern is counted; nothing has been written to the output yet
+        set_error("%s: outCapacity %d is below the %lld entries of the symmetric part (2 x elementsCount always suffices)", who, outCapacity, nnzS);
+        ok = false;
+    }
+    if (ok && !countOnly) {
+        analysis_note_write(outElements->data, sizeof(double) * (size_t)nnzS);
+        analysis_note_write(outColumnIndeces->data, sizeof(int) * (size_t)nnzS);
+        analysis_note_write(outRowOffsets->data, sizeof(int) * ((size_t)count + 1));
+        ok = MGCG_HIP(hipMemcpyAsync(outRowOffsets->data, S.rowOffsets, sizeof(int) * ((size_t)count + 1), hipMemcpyDeviceToDevice, s)) &&
+             (nnzS == 0 || (MGCG_HIP(hipMemcpyAsync(outElements->data, S.elements, sizeof(double) * (size_t)nnzS, hipMemcpyDeviceToDevice, s)) &&
+                            MGCG_HIP(hipMemcpyAsync(outColumnIndeces->data, S.columnIndeces, sizeof(int) * (size_t)nnzS, hipMemcpyDeviceToDevice, s))));
+        ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    }
+    amg_free(S);
+    return ok ? nnzS : -1;
 }
 
 MgcgMg* MgSetupAggregates(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,

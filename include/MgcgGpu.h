@@ -404,6 +404,42 @@ MgcgMg* MgSetupAggregation(MgcgBlas* cublas, MgcgSparse* cusparse,
                            Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                            int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
                            double omega, int nu, int nuCoarse, double sigma);
+/* S = (A + A^T) / 2 of a square count x count CSR matrix, formed on the device into the caller's vectors (device vectors of the library,
+ * as the input).  Returns the number of stored entries of S; with all three output vectors NULL it returns that count and writes nothing.
+ * CONTRACT (one fixed sequence of IEEE operations, the same in every mode, no atomics on values):
+ *   pattern: row i of S stores every column j that row i of A stores or whose own row j stores column i; columns ascend, each appears
+ *            once.  A pair whose sum is zero is KEPT as a stored 0.0 (an entry >= 0 never couples in the matching: zeros change no map).
+ *   value:   acc = +0.0; the stored entries of column j in row i of A are added in stored order; then the stored entries of column i in
+ *            row j of A in stored order; s_ij = 0.5 * acc.
+ * Hence: the diagonal of a row that stores it once comes out exactly (0.5 * (a + a)); S is symmetric bit for bit when no row stores a
+ * column twice (two addends: the sum commutes); a symmetric matrix with ascending unique columns gives itself, pattern and values.  Rows
+ * may be unsorted, hold duplicates and be of any length.  The row offsets and columns are read on the host for the stable counting sort of
+ * the entries by column (the transposition permutation: index bookkeeping, as in the set-up above); no matrix value travels to the host,
+ * the values are gathered and summed on the device.  S is built in storage of the library's own (about 2 x elementsCount values and
+ * 6 x elementsCount ints while it runs) and copied out at the end: on a refusal the output vectors are untouched.
+ * Returns -1 with MgcgGetLastError() on a refusal.  Refused before a device is asked for: a null handle (the three output vectors are
+ * given together or not at all), count < 1, elementsCount < 0, 2 * elementsCount above INT_MAX, input vectors smaller than elementsCount
+ * / count + 1, output vectors smaller than outCapacity / count + 1.  Refused once the arrays have been read: offsets that do not start
+ * at 0, descend or end beyond elementsCount, a column outside [0, count), and an outCapacity below the count of S (the message states
+ * the count; a capacity of 2 * elementsCount always suffices). */
+long long MgcgSymmetricPart(MgcgBlas* cublas, MgcgSparse* cusparse,
+                            Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                            int elementsCount, int count,
+                            Vector* outElements, VectorInt* outRowOffsets, VectorInt* outColumnIndeces, int outCapacity);
+/* MgSetupAggregation with a choice of what the matching reads.  strength = 0: the level's own matrix -- MgSetupAggregation, which is this
+ * call with 0, bit for bit.  strength = 1: the matching of every level l runs on S_l, the symmetric part (MgcgSymmetricPart's contract) of
+ * the level's OWN matrix A_l: pass 1 on S_l, pass p > 1 on the unscaled Galerkin matrix of pass p - 1 built from S_l; S_l is then freed
+ * and the next level is sigma*P^T A_l P of A_l itself with that map.  Nothing else changes: the matching rules, theta, the key, the
+ * numbering, the diagonal checks, the three end rules, the cycle, MgSetSmoother.  Why: on A != A^T the matching reads w = -a_ij from row i
+ * alone and pairs rows on MUTUAL picks; where the strong entry of row i points upstream and row j's entry back is weak or >= 0 (upwind and
+ * strong central convection) nothing pairs and the hierarchy has ONE level.  S_l has the couplings of both rows in both rows.  On a
+ * symmetric matrix with ascending unique columns S_l = A_l and both strengths build the same hierarchy.  M stays a fixed linear operator:
+ * what SolveBicgstabMg, SolveGmresMg (right preconditioning) ask.  Other values of strength are refused before a device is asked for. */
+MgcgMg* MgSetupAggregationEx(MgcgBlas* cublas, MgcgSparse* cusparse,
+                             Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                             int elementsCount, int count, int levels, int passes, double theta, int minCoarse,
+                             double omega, int nu, int nuCoarse, double sigma, int strength);
+int     MgStrength(const MgcgMg* mg);                                     /* the strength the hierarchy was built with (0 for NULL, MgSetup, MgSetupAggregates) */
 /* The same hierarchy from the caller's aggregates (host arrays): levelRows[0 .. levels-1] are the rows of every level (levelRows[0] =
  * count), aggregateOf holds the maps of levels 0 .. levels-2 one after the other (levelRows[l] ids in [0, levelRows[l+1]) each).  Exactly
  * `levels` levels are built.  An id out of range or an empty aggregate is refused (NULL, MgcgGetLastError()). */
