@@ -24,21 +24,18 @@ The max-norm stop rule is not supported by any of them.  No arithmetic happens i
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import numpy as np
-
 from . import _lib
-from ._lib import MgcgError, check, lib
+from ._lib import MgcgError
 from .jacobi import check_system_shapes, jacobi_setup
-from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+from .solver import ConjugateGradientSingleGpu, VectorDouble
 
 _WORK = ("vectorV", "vectorS", "vectorT", "vectorRhat")
 
 
 class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
     """ConjugateGradientSingleGpu on the BiCGStab loop: same constructor, members, ``Iteration`` / ``Residual`` and
-    ``ApplicationException`` behaviour, for any CSR matrix."""
+    ``ApplicationException`` behaviour, for any CSR matrix.  ``ReadResidual()`` returns the true residual b - A x that the last Solve()'s
+    closing product left in its work vector."""
 
     _export = "SolveBicgstab"
     _what = "BiCGStab"
@@ -55,10 +52,8 @@ class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
         self._ready = False
 
     def Dispose(self):
-        for name in _WORK + ("vectorDinv", "vectorWork"):
-            if getattr(self, name, None) is not None:
-                getattr(self, name).Dispose()
-                setattr(self, name, None)
+        self._dispose_vectors(*_WORK, "vectorDinv", "vectorWork")
+        self._work_size = 0
         super().Dispose()
 
     def Initialize(self):
@@ -81,34 +76,8 @@ class BiConjugateGradientStabGpu(ConjugateGradientSingleGpu):
         """trace: keep the residual trace in ``self.trace``; traceCapacity: its length when the default (room for every iteration) is not wanted."""
         if not self._ready:
             raise MgcgError(f"{type(self).__name__}.Solve: Initialize() has not run")
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = (max(self.MaxIteration, self.MinIteration) + 8 if traceCapacity is None else int(traceCapacity)) if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        L = lib()
-        st = getattr(L, self._export)(self.cublas, self.cusparse, self.matDescr,
-                                      self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                      self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                      *self._work_arguments(),
-                                      nonzeroCount, self.Count,
-                                      self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                                      C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: min(self.Iteration + 1, cap)].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"{self._what} did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check(self._export)
-            raise MgcgError(f"{self._export} failed with status {st}")
-
-    def ReadResidual(self) -> np.ndarray:
-        """The true residual b - A x that the last Solve()'s closing product left in its work vector."""
-        r = np.empty(self.Count)
-        self.vectorR.CopyTo(r, self.Count, 0)
-        return r
+        self._native_solve(self._export, self._what, trace, work=self._work_arguments(), third=("TrueResidual", float("nan")),
+                           traceCapacity=traceCapacity)
 
 
 class BiConjugateGradientStabJacobiGpu(BiConjugateGradientStabGpu):
@@ -127,24 +96,12 @@ class OneWorkVectorGpu(BiConjugateGradientStabGpu):
     after the object's sizes were raised."""
 
     _work_names = ()
-    vectorWork, _work_size = None, 0
     _slices_more = property(lambda self: 1 if self._jacobi else 0)     # the diagonal's form keeps one slice more
 
     def _slices(self):
         """How many slices the loop needs now (for a size the library refuses: as for the nearest it takes, so that the call reaches
         its refusal)."""
         raise NotImplementedError
-
-    def _ensure_work(self):
-        need = self._slices() * (self.Count + (self.Count & 1))
-        if need > self._work_size:
-            if self.vectorWork is not None:
-                self.vectorWork.Dispose()
-            self.vectorWork, self._work_size = VectorDouble(need), need
-
-    def Dispose(self):
-        self._work_size = 0
-        super().Dispose()
 
 
 class BiConjugateGradientStabLGpu(OneWorkVectorGpu):
@@ -160,13 +117,13 @@ class BiConjugateGradientStabLGpu(OneWorkVectorGpu):
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, ell=2):
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
         self.ell = int(ell)
-        self._ensure_work()
+        self._ensure_work(self._slices())
 
     def _slices(self):
         return 2 * min(max(int(self.ell), 1), 4) + self._slices_more
 
     def _work_arguments(self):
-        self._ensure_work()
+        self._ensure_work(self._slices())
         return (self.vectorWork.Ptr, *self._more_vectors(), int(self.ell))
 
 

@@ -17,12 +17,10 @@ from __future__ import annotations
 import ctypes as C
 import math
 
-import numpy as np
-
 from . import _lib
 from ._lib import MgcgError, check, lib
 from .jacobi import check_system_shapes, jacobi_setup
-from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+from .solver import ConjugateGradientSingleGpu, VectorDouble
 
 
 def gershgorin_bound(cusparse, vectorElements, vectorRowOffsets, vectorColumnIndeces, elementsCount, countForDevice, offsetForDevice, vectorDinv=None):
@@ -47,7 +45,8 @@ def check_bounds(degree, lambdaMin, lambdaMax):
 
 class ConjugateGradientChebyshevGpu(ConjugateGradientSingleGpu):
     """ConjugateGradientSingleGpu on the Chebyshev-preconditioned loop: same constructor (plus ``degree``, ``jacobi``, ``bounds``,
-    ``eigRatio``), members, ``Iteration`` / ``Residual`` and ``ApplicationException`` behaviour; the stop rules test the true residual."""
+    ``eigRatio``), members, ``Iteration`` / ``Residual`` and ``ApplicationException`` behaviour; the stop rules test the true residual.
+    ``ReadResidual()`` returns the recurrence residual r that the last Solve() left in its work vector."""
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, degree=4, jacobi=False, bounds=None, eigRatio=30.0):
         if rule == _lib.RULE_HANDMADECL:
@@ -66,10 +65,7 @@ class ConjugateGradientChebyshevGpu(ConjugateGradientSingleGpu):
         self._ready = False
 
     def Dispose(self):
-        for name in ("vectorZ", "vectorZ2", "vectorD", "vectorDinv"):
-            if getattr(self, name, None) is not None:
-                getattr(self, name).Dispose()
-                setattr(self, name, None)
+        self._dispose_vectors("vectorZ", "vectorZ2", "vectorD", "vectorDinv")
         super().Dispose()
 
     def Initialize(self):
@@ -91,31 +87,6 @@ class ConjugateGradientChebyshevGpu(ConjugateGradientSingleGpu):
         """trace: keep the residual trace in ``self.trace``; traceCapacity: its length when the default (room for every iteration) is not wanted."""
         if not self._ready:
             raise MgcgError("ConjugateGradientChebyshevGpu.Solve: Initialize() has not run")
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = (max(self.MaxIteration, self.MinIteration) + 8 if traceCapacity is None else int(traceCapacity)) if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        L = lib()
-        st = L.SolveChebyshev(self.cublas, self.cusparse, self.matDescr,
-                              self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                              self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                              self.vectorDinv.Ptr if self.jacobi else None, self.vectorZ.Ptr, self.vectorZ2.Ptr, self.vectorD.Ptr,
-                              nonzeroCount, self.Count, self.degree, self.lambdaMin, self.lambdaMax,
-                              self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                              C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: min(self.Iteration + 1, cap)].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"Chebyshev-preconditioned CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveChebyshev")
-            raise MgcgError(f"SolveChebyshev failed with status {st}")
-
-    def ReadResidual(self) -> np.ndarray:
-        """The recurrence residual r the last Solve() left in its work vector."""
-        r = np.empty(self.Count)
-        self.vectorR.CopyTo(r, self.Count, 0)
-        return r
+        self._native_solve("SolveChebyshev", "Chebyshev-preconditioned CG", trace, traceCapacity=traceCapacity,
+                           work=(self.vectorDinv.Ptr if self.jacobi else None, self.vectorZ.Ptr, self.vectorZ2.Ptr, self.vectorD.Ptr),
+                           more=(self.degree, self.lambdaMin, self.lambdaMax))

@@ -36,13 +36,13 @@ class GeneralizedMinimalResidualGpu(OneWorkVectorGpu):
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, m=20, orth=2):
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
         self.m, self.orth = int(m), int(orth)
-        self._ensure_work()
+        self._ensure_work(self._slices())
 
     def _slices(self):
         return min(max(int(self.m), 1), MAX_M) + 1 + self._slices_more
 
     def _work_arguments(self):
-        self._ensure_work()
+        self._ensure_work(self._slices())
         return (self.vectorWork.Ptr, *self._more_vectors(), int(self.m), int(self.orth))
 
 

@@ -10,13 +10,10 @@ native call.  No arithmetic happens in this module.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
 from ._lib import MgcgError, check, lib
-from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+from .solver import ConjugateGradientSingleGpu, VectorDouble
 
 
 def jacobi_setup(cusparse, vectorElements, vectorRowOffsets, vectorColumnIndeces, elementsCount, countForDevice, offsetForDevice, vectorDinv):
@@ -65,8 +62,7 @@ class ConjugateGradientJacobiGpu(ConjugateGradientSingleGpu):
         self._ready = False
 
     def Dispose(self):
-        if getattr(self, "vectorDinv", None) is not None:
-            self.vectorDinv.Dispose()
+        self._dispose_vectors("vectorDinv")
         super().Dispose()
 
     def Initialize(self):
@@ -80,24 +76,4 @@ class ConjugateGradientJacobiGpu(ConjugateGradientSingleGpu):
     def Solve(self, trace: bool = False):
         if not self._ready:
             raise MgcgError("ConjugateGradientJacobiGpu.Solve: Initialize() has not set the diagonal up")
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        L = lib()
-        st = L.SolveJacobi(self.cublas, self.cusparse, self.matDescr,
-                           self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                           self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorDinv.Ptr,
-                           nonzeroCount, self.Count,
-                           self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                           C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"Jacobi-preconditioned CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveJacobi")
-            raise MgcgError(f"SolveJacobi failed with status {st}")
+        self._native_solve("SolveJacobi", "Jacobi-preconditioned CG", trace, work=(self.vectorDinv.Ptr,))

@@ -18,20 +18,23 @@ remains the plain 2-norm.  No arithmetic happens in this module.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
-import numpy as np
-
 from . import _lib
-from ._lib import MgcgError, check, lib
+from ._lib import MgcgError
 from .jacobi import check_system_shapes, jacobi_setup
-from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+from .solver import ConjugateGradientSingleGpu, VectorDouble
 
 
 class MinimalResidualGpu(ConjugateGradientSingleGpu):
     """ConjugateGradientSingleGpu on the MINRES loop: same constructor (plus ``shift``), members, ``Iteration`` / ``Residual`` and
-    ``ApplicationException`` behaviour, for symmetric matrices of any inertia."""
+    ``ApplicationException`` behaviour, for symmetric matrices of any inertia.  ``ReadResidual()`` returns the true residual
+    b - (A - shift I) x that the last Solve()'s closing product left in its work vector."""
+
+    _export = "SolveMinres"
+    _what = "MINRES"
+    _jacobi = False                    # with M = diag(A): ``vectorDinv``, filled and checked by Initialize(), and ``vectorR1``
+    _unready = "has not run"
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, shift=0.0):
         if rule == _lib.RULE_HANDMADECL:
@@ -41,55 +44,30 @@ class MinimalResidualGpu(ConjugateGradientSingleGpu):
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule)
         self.shift = float(shift)
         self.TrueResidual = float("nan")
-        self.vectorW1 = VectorDouble(count)
-        self.vectorW2 = VectorDouble(count)
+        for name in ("vectorW1", "vectorW2") + (("vectorDinv", "vectorR1") if self._jacobi else ()):
+            setattr(self, name, VectorDouble(count))
         self._ready = False
 
     def Dispose(self):
-        for name in ("vectorW1", "vectorW2"):
-            if getattr(self, name, None) is not None:
-                getattr(self, name).Dispose()
-                setattr(self, name, None)
+        self._dispose_vectors("vectorDinv", "vectorR1", "vectorW1", "vectorW2")
         super().Dispose()
 
     def Initialize(self):
         self._ready = False
         check_system_shapes(self.A, self.x, self.b, self.Count)
         super().Initialize()
+        if self._jacobi:
+            jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
+                         int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
         self._ready = True
 
     def Solve(self, trace: bool = False, traceCapacity: int | None = None):
         """trace: keep the residual trace in ``self.trace``; traceCapacity: its length when the default (room for every iteration) is not wanted."""
         if not self._ready:
-            raise MgcgError("MinimalResidualGpu.Solve: Initialize() has not run")
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = (max(self.MaxIteration, self.MinIteration) + 8 if traceCapacity is None else int(traceCapacity)) if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        L = lib()
-        st = L.SolveMinres(self.cublas, self.cusparse, self.matDescr,
-                           self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                           self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                           self.vectorW1.Ptr, self.vectorW2.Ptr,
-                           nonzeroCount, self.Count, self.shift,
-                           self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                           C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: min(self.Iteration + 1, cap)].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"MINRES did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMinres")
-            raise MgcgError(f"SolveMinres failed with status {st}")
-
-    def ReadResidual(self) -> np.ndarray:
-        """The true residual b - (A - shift I) x that the last Solve()'s closing product left in its work vector."""
-        r = np.empty(self.Count)
-        self.vectorR.CopyTo(r, self.Count, 0)
-        return r
+            raise MgcgError(f"{type(self).__name__}.Solve: Initialize() {self._unready}")
+        work = (self.vectorR1.Ptr, self.vectorW1.Ptr, self.vectorW2.Ptr, self.vectorDinv.Ptr) if self._jacobi else (self.vectorW1.Ptr, self.vectorW2.Ptr)
+        self._native_solve(self._export, self._what, trace, work=work, more=(self.shift,), third=("TrueResidual", float("nan")),
+                           traceCapacity=traceCapacity)
 
 
 class MinimalResidualJacobiGpu(MinimalResidualGpu):
@@ -100,47 +78,7 @@ class MinimalResidualJacobiGpu(MinimalResidualGpu):
     the quantity preconditioned MINRES minimises; ``TrueResidual`` remains the plain 2-norm || b - (A - shift I) x ||_2 of the closing
     product.  A caller who needs the 2-norm below a level looks there."""
 
-    def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, shift=0.0):
-        super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=rule, shift=shift)
-        self.vectorDinv = VectorDouble(count)
-        self.vectorR1 = VectorDouble(count)
-
-    def Dispose(self):
-        for name in ("vectorDinv", "vectorR1"):
-            if getattr(self, name, None) is not None:
-                getattr(self, name).Dispose()
-                setattr(self, name, None)
-        super().Dispose()
-
-    def Initialize(self):
-        super().Initialize()
-        self._ready = False
-        jacobi_setup(self.cusparse, self.vectorA, self.vectorRowOffsets, self.vectorColumnIndeces,
-                     int(self.A.RowOffsets[self.Count]), self.Count, 0, self.vectorDinv)
-        self._ready = True
-
-    def Solve(self, trace: bool = False, traceCapacity: int | None = None):
-        if not self._ready:
-            raise MgcgError("MinimalResidualJacobiGpu.Solve: Initialize() has not set the diagonal up")
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = (max(self.MaxIteration, self.MinIteration) + 8 if traceCapacity is None else int(traceCapacity)) if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        L = lib()
-        st = L.SolveMinresJacobi(self.cublas, self.cusparse, self.matDescr,
-                                 self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                 self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorR1.Ptr,
-                                 self.vectorW1.Ptr, self.vectorW2.Ptr, self.vectorDinv.Ptr,
-                                 nonzeroCount, self.Count, self.shift,
-                                 self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                                 C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: min(self.Iteration + 1, cap)].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"Jacobi-preconditioned MINRES did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMinresJacobi")
-            raise MgcgError(f"SolveMinresJacobi failed with status {st}")
+    _export = "SolveMinresJacobi"
+    _what = "Jacobi-preconditioned MINRES"
+    _jacobi = True
+    _unready = "has not set the diagonal up"

@@ -14,12 +14,9 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
-from . import _lib
 from ._lib import MgcgError, check, lib
 from .jacobi import check_system_shapes
-from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+from .solver import ConjugateGradientSingleGpu, VectorDouble
 
 
 def mixed_setup(cusparse, vectorElements, vectorRowOffsets, vectorColumnIndeces, elementsCount, count, vectorElements32) -> bool:
@@ -56,9 +53,7 @@ class ConjugateGradientMixedGpu(ConjugateGradientSingleGpu):
         self._ready = False
 
     def Dispose(self):
-        if getattr(self, "vectorElements32", None) is not None:
-            self.vectorElements32.Dispose()
-            self.vectorElements32 = None
+        self._dispose_vectors("vectorElements32")
         super().Dispose()
 
     def Initialize(self):
@@ -72,24 +67,4 @@ class ConjugateGradientMixedGpu(ConjugateGradientSingleGpu):
     def Solve(self, trace: bool = False):
         if not self._ready:
             raise MgcgError("ConjugateGradientMixedGpu.Solve: Initialize() has not converted the matrix")
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration, residual, updates = C.c_int(0), C.c_double(0.0), C.c_int(0)
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        L = lib()
-        st = L.SolveMixed(self.cublas, self.cusparse, self.matDescr,
-                          self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                          self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorElements32.Ptr,
-                          nonzeroCount, self.Count,
-                          self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                          C.byref(iteration), C.byref(residual), C.byref(updates), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.ReliableUpdates, self.status = iteration.value, residual.value, updates.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"mixed-precision CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMixed")
-            raise MgcgError(f"SolveMixed failed with status {st}")
+        self._native_solve("SolveMixed", "mixed-precision CG", trace, work=(self.vectorElements32.Ptr,), third=("ReliableUpdates", 0))

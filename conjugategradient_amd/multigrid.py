@@ -6,18 +6,22 @@ piecewise-constant transfer, Galerkin coarse operators scaled by 1/2, weighted-J
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
 from ._lib import MgcgError, check, lib
 from .bicgstab import _WORK as _BICGSTAB_WORK          # vectorV, vectorS, vectorT, vectorRhat
 from .gmres import MAX_M as _GMRES_MAX_M
-from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+from .solver import ConjugateGradientSingleGpu, VectorDouble, _ptr
+
+_TRUE = ("TrueResidual", float("nan"))                 # the third output of SolveMinres, SolveBicgstab and SolveGmres
+
 
 class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
-    """ConjugateGradientSingleGpu plus a V-cycle preconditioner built from ``grid = (nx, ny, nz)``."""
+    """ConjugateGradientSingleGpu plus a V-cycle preconditioner built from ``grid = (nx, ny, nz)``.  ``ReadResidual()`` returns the true
+    residual that the closing product of the last SolveMinres(), SolveBicgstab() or SolveGmres() left in its work vector."""
+
+    _default_rule = _lib.RULE_CSHARP        # what rule=None means here (the one-rank classes without a hierarchy: RULE_NATIVE)
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, grid,
                  levels: int = 3, omega: float | None = None, nu: int = 1, nuCoarse: int = 4, sigma: float = 0.5,
@@ -38,12 +42,8 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         if getattr(self, "mg", None):
             lib().MgDestroy(self.mg)
             self.mg = None
-        if getattr(self, "vectorZ", None) is not None:
-            self.vectorZ.Dispose()
-        for name in ("vectorW1", "vectorW2", "vectorR1", "vectorWork") + _BICGSTAB_WORK:   # SolveMinres's, SolveGmres's and SolveBicgstab's work space, if they ran
-            if getattr(self, name, None) is not None:
-                getattr(self, name).Dispose()
-                setattr(self, name, None)
+        # with SolveMinres's, SolveGmres's and SolveBicgstab's work space, if they ran
+        self._dispose_vectors("vectorZ", "vectorW1", "vectorW2", "vectorR1", "vectorWork", *_BICGSTAB_WORK)
         self._work_size = 0
         super().Dispose()
 
@@ -106,25 +106,7 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         return z
 
     def Solve(self, trace: bool = False):
-        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        rule = _lib.RULE_CSHARP if self.rule is None else self.rule
-        st = lib().SolveMg(self.cublas, self.cusparse, self.matDescr, self.mg,
-                           self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                           self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorZ.Ptr,
-                           nonzeroCount, self.Count, self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                           C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"MGCG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMg")
-            raise MgcgError(f"SolveMg failed with status {st}")
+        self._native_solve("SolveMg", "MGCG", trace, head=(self.mg,), work=(self.vectorZ.Ptr,))
 
     def SolveMinres(self, shift: float = 0.0, trace: bool = False):
         """Solve (A - shift I) x = b with MINRES preconditioned by this hierarchy's V-cycle (SolveMinresMg): A symmetric, definite or not.
@@ -132,29 +114,9 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         allocated at the first call.  ``Iteration``, ``Residual`` and ``trace`` show the residual in the M^-1 norm, sqrt(r . M^-1 r),
         which is what the stop rule judges; ``TrueResidual`` is the plain 2-norm || b - (A - shift I) x ||_2 of the closing product, and
         ``vectorR`` holds that vector."""
-        for name in ("vectorW1", "vectorW2", "vectorR1"):
-            if getattr(self, name, None) is None:
-                setattr(self, name, VectorDouble(self.Count))
-        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        rule = _lib.RULE_CSHARP if self.rule is None else self.rule
-        st = lib().SolveMinresMg(self.cublas, self.cusparse, self.matDescr, self.mg,
-                                 self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                 self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorR1.Ptr,
-                                 self.vectorW1.Ptr, self.vectorW2.Ptr, self.vectorZ.Ptr,
-                                 nonzeroCount, self.Count, float(shift), self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                                 C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"V-cycle-preconditioned MINRES did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMinresMg")
-            raise MgcgError(f"SolveMinresMg failed with status {st}")
+        self._ensure_vectors(self.Count, "vectorW1", "vectorW2", "vectorR1")      # (Count is fixed: one that exists is never too small)
+        self._native_solve("SolveMinresMg", "V-cycle-preconditioned MINRES", trace, head=(self.mg,), more=(float(shift),),
+                           work=(self.vectorR1.Ptr, self.vectorW1.Ptr, self.vectorW2.Ptr, self.vectorZ.Ptr), third=_TRUE)
 
     def SolveBicgstab(self, trace: bool = False, hierarchy=None):
         """Solve A x = b, A any CSR matrix, with BiCGStab right-preconditioned by a hierarchy's V-cycle (SolveBicgstabMg).  The
@@ -163,30 +125,9 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         precondition with the hierarchy of another matrix, ``problems.symmetric_part(system)`` for instance).  ``vectorV``, ``vectorS``,
         ``vectorT`` and ``vectorRhat`` are allocated at the first call.  ``Iteration``, ``Residual`` and ``trace`` show the recurrence's
         2-norm residual; ``TrueResidual`` is || b - A x ||_2 of the closing product and ``ReadResidual()`` returns that vector."""
-        for name in _BICGSTAB_WORK:
-            if getattr(self, name, None) is None:
-                setattr(self, name, VectorDouble(self.Count))
-        mg = self.mg if hierarchy is None else hierarchy.mg
-        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        rule = _lib.RULE_CSHARP if self.rule is None else self.rule
-        st = lib().SolveBicgstabMg(self.cublas, self.cusparse, self.matDescr, mg,
-                                   self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                   self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                   self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr,
-                                   nonzeroCount, self.Count, self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                                   C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"V-cycle-preconditioned BiCGStab did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveBicgstabMg")
-            raise MgcgError(f"SolveBicgstabMg failed with status {st}")
+        self._ensure_vectors(self.Count, *_BICGSTAB_WORK)
+        self._native_solve("SolveBicgstabMg", "V-cycle-preconditioned BiCGStab", trace, head=(self.mg if hierarchy is None else hierarchy.mg,),
+                           work=(self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr), third=_TRUE)
 
     def SolveGmres(self, trace: bool = False, hierarchy=None, m: int = 20, orth: int = 2):
         """Solve A x = b, A any CSR matrix, with restarted GMRES(m) right-preconditioned by a hierarchy's V-cycle in the flexible form
@@ -197,35 +138,6 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         allocated at the first call and again, larger, when ``m`` has grown.  ``Iteration``, ``Residual`` and ``trace`` count Arnoldi
         steps (one cycle and one product each) and show the rotated estimate of || b - A x ||_2; ``TrueResidual`` is that norm itself
         from the closing product and ``ReadResidual()`` returns that vector."""
-        need = (2 * min(max(int(m), 1), _GMRES_MAX_M) + 1) * (self.Count + (self.Count & 1))
-        if need > getattr(self, "_work_size", 0):
-            if getattr(self, "vectorWork", None) is not None:
-                self.vectorWork.Dispose()
-            self.vectorWork, self._work_size = VectorDouble(need), need
-        mg = self.mg if hierarchy is None else hierarchy.mg
-        nonzeroCount = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(float("nan"))
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        rule = _lib.RULE_CSHARP if self.rule is None else self.rule
-        st = lib().SolveGmresMg(self.cublas, self.cusparse, self.matDescr, mg,
-                                self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                self.vectorWork.Ptr, int(m), int(orth),
-                                nonzeroCount, self.Count, self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                                C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"V-cycle-preconditioned GMRES(m) did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveGmresMg")
-            raise MgcgError(f"SolveGmresMg failed with status {st}")
-
-    def ReadResidual(self) -> np.ndarray:
-        """The true residual that the closing product of the last SolveMinres(), SolveBicgstab() or SolveGmres() left in its work vector."""
-        r = np.empty(self.Count)
-        self.vectorR.CopyTo(r, self.Count, 0)
-        return r
+        self._ensure_work(2 * min(max(int(m), 1), _GMRES_MAX_M) + 1)
+        self._native_solve("SolveGmresMg", "V-cycle-preconditioned GMRES(m)", trace, head=(self.mg if hierarchy is None else hierarchy.mg,),
+                           work=(self.vectorWork.Ptr, int(m), int(orth)), third=_TRUE)

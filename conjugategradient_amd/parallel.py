@@ -28,6 +28,8 @@ from ._lib import MgcgError, check, lib
 from .problems import partition_offsets
 from .solver import ApplicationException, ConjugateGradientGpu, VectorDouble, VectorInt, _ptr
 
+_TRUE = ("TrueResidual", 0.0)           # the third output of a rank's MINRES and BiCGStab methods (it starts at NaN on one rank)
+
 
 # --------------------------------------------------------------------------- partition / halo arithmetic
 @dataclass
@@ -198,13 +200,9 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
 
     def Dispose(self):
         if getattr(self, "cublas", None):
-            for v in (self.vectorElements, self.vectorColumnIndeces, self.vectorRowOffsets, self.vectorX, self.vectorB,
-                      self.vectorAp, self.vectorP, self.vectorR, getattr(self, "vectorDinv", None), getattr(self, "vectorS", None),
-                      getattr(self, "vectorZ", None), getattr(self, "vectorZ2", None), getattr(self, "vectorD", None),
-                      getattr(self, "vectorW1", None), getattr(self, "vectorW2", None), getattr(self, "vectorR1", None),
-                      getattr(self, "vectorV", None), getattr(self, "vectorT", None), getattr(self, "vectorRhat", None)):
-                if v is not None:
-                    v.Dispose()
+            self._dispose_vectors("vectorElements", "vectorColumnIndeces", "vectorRowOffsets", "vectorX", "vectorB", "vectorAp", "vectorP",
+                                  "vectorR", "vectorDinv", "vectorS", "vectorZ", "vectorZ2", "vectorD", "vectorW1", "vectorW2", "vectorR1",
+                                  "vectorV", "vectorT", "vectorRhat")
             if self._own_comm and self.comm:
                 lib().MgcgCommDestroy(self.comm)
             lib().DestroyBlas(self.cublas)
@@ -222,6 +220,23 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         if self.comm is None:
             self.comm = create_comm(self.rank, self.world)
             self._own_comm = True
+
+    # what ConjugateGradientGpu._native_solve takes from a rank: the communicator first, the partition for sizes, self.rule as it stands
+    _matrix = "vectorElements"
+
+    def _handles(self):
+        return (self.comm, self.cublas, self.cusparse, self.matDescr)
+
+    def _sizes(self):
+        p = self.part
+        return (self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ)
+
+    def _rule(self):
+        return self.rule
+
+    def _dinv(self):
+        """The Ptr of the dinv vector that SetupJacobi() filled; None where it has not run or has failed."""
+        return self.vectorDinv.Ptr if getattr(self, "vectorDinv", None) is not None and getattr(self, "jacobiError", None) is None else None
 
     def Initialize(self):
         """Upload this rank's partition from the host arrays (A, x, b), as :358-379 does per device."""
@@ -268,25 +283,7 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
 
     def Solve(self, trace: bool = False):
         self._ensure_comm()
-        p = self.part
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = lib().SolveParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
-                                 self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                 self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                 self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
-                                 self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                 C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveParallel")
-            raise MgcgError(f"SolveParallel failed with status {st}")
+        self._native_solve("SolveParallel", "CG", trace)
 
     def SetupJacobi(self):
         """dinv = 1 / diag(A) for this rank's rows (call after Initialize / InitializePoisson; no collective: the diagonal needs no halo).
@@ -295,8 +292,7 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         from .jacobi import jacobi_setup
 
         p = self.part
-        if getattr(self, "vectorDinv", None) is None or self.vectorDinv.size < p.count:
-            self.vectorDinv = VectorDouble(p.count)
+        self._ensure_vectors(p.count, "vectorDinv")
         self.jacobiError = None
         try:
             jacobi_setup(self.cusparse, self.vectorElements, self.vectorRowOffsets, self.vectorColumnIndeces, p.elementCount, p.count, p.offset, self.vectorDinv)
@@ -307,56 +303,16 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
     def SolveJacobi(self, trace: bool = False):
         """Solve() with the Jacobi preconditioner (SolveJacobiParallel); SetupJacobi() first."""
         self._ensure_comm()
-        p = self.part
-        usable = getattr(self, "vectorDinv", None) is not None and getattr(self, "jacobiError", None) is None
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = lib().SolveJacobiParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
-                                       self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                       self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                       self.vectorDinv.Ptr if usable else None,
-                                       self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
-                                       self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                       C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"Jacobi-preconditioned CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveJacobiParallel")
-            raise MgcgError(f"SolveJacobiParallel failed with status {st}")
+        self._native_solve("SolveJacobiParallel", "Jacobi-preconditioned CG", trace, work=(self._dinv(),))
 
     def SolveSingleReduce(self, trace: bool = False, jacobi: bool = False):
         """Solve() on the single-reduction loop (SolveSingleReduceParallel): one all-reduce per iteration.  jacobi: with the diagonal
         preconditioner (SetupJacobi() first).  Every rank passes the same ``jacobi``."""
         self._ensure_comm()
-        p = self.part
-        if jacobi and (getattr(self, "vectorDinv", None) is None or getattr(self, "jacobiError", None) is not None):
+        if jacobi and self._dinv() is None:
             raise MgcgError("SolveSingleReduce(jacobi=True): SetupJacobi() has not set the diagonal up")
-        if getattr(self, "vectorS", None) is None or self.vectorS.size < p.count:
-            self.vectorS = VectorDouble(p.count)
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = lib().SolveSingleReduceParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
-                                             self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                             self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorS.Ptr,
-                                             self.vectorDinv.Ptr if jacobi else None,
-                                             self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
-                                             self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                             C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"single-reduction CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveSingleReduceParallel")
-            raise MgcgError(f"SolveSingleReduceParallel failed with status {st}")
+        self._ensure_vectors(self.part.count, "vectorS")
+        self._native_solve("SolveSingleReduceParallel", "single-reduction CG", trace, work=(self.vectorS.Ptr, self.vectorDinv.Ptr if jacobi else None))
 
     def SolveMinres(self, trace: bool = False, shift: float = 0.0):
         """Solve (A - shift I) x = b with MINRES (SolveMinresParallel): A symmetric, definite or not.  Two all-reduces per iteration, as
@@ -364,32 +320,11 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         ``part.count`` entries hold this rank's rows of the true residual and ``TrueResidual`` its global 2-norm.  Every rank passes the
         same ``shift``."""
         self._ensure_comm()
-        p = self.part
         if self.vectorR.size < self.Count:
             self.vectorR.Dispose()
             self.vectorR = VectorDouble(self.Count)
-        for name in ("vectorW1", "vectorW2"):
-            if getattr(self, name, None) is None or getattr(self, name).size < p.count:
-                setattr(self, name, VectorDouble(p.count))
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = lib().SolveMinresParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
-                                       self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                       self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                       self.vectorW1.Ptr, self.vectorW2.Ptr,
-                                       self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ, float(shift),
-                                       self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                       C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"MINRES did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMinresParallel")
-            raise MgcgError(f"SolveMinresParallel failed with status {st}")
+        self._ensure_vectors(self.part.count, "vectorW1", "vectorW2")
+        self._native_solve("SolveMinresParallel", "MINRES", trace, work=(self.vectorW1.Ptr, self.vectorW2.Ptr), more=(float(shift),), third=_TRUE)
 
     def SolveMinresJacobi(self, trace: bool = False, shift: float = 0.0):
         """SolveMinres() with the Jacobi preconditioner (SolveMinresJacobiParallel); SetupJacobi() first.  Only v (vectorP) is full length.
@@ -397,30 +332,9 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         global 2-norm of b - (A - shift I) x, whose local rows are left in vectorR.  A rank whose SetupJacobi() failed still enters the
         native call, with no dinv vector: every rank gets MGCG_ERROR.  Every rank passes the same ``shift``."""
         self._ensure_comm()
-        p = self.part
-        usable = getattr(self, "vectorDinv", None) is not None and getattr(self, "jacobiError", None) is None
-        for name in ("vectorW1", "vectorW2", "vectorR1"):
-            if getattr(self, name, None) is None or getattr(self, name).size < p.count:
-                setattr(self, name, VectorDouble(p.count))
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = lib().SolveMinresJacobiParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
-                                             self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                             self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorR1.Ptr,
-                                             self.vectorW1.Ptr, self.vectorW2.Ptr, self.vectorDinv.Ptr if usable else None,
-                                             self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ, float(shift),
-                                             self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                             C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"Jacobi-preconditioned MINRES did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMinresJacobiParallel")
-            raise MgcgError(f"SolveMinresJacobiParallel failed with status {st}")
+        self._ensure_vectors(self.part.count, "vectorW1", "vectorW2", "vectorR1")
+        self._native_solve("SolveMinresJacobiParallel", "Jacobi-preconditioned MINRES", trace, more=(float(shift),), third=_TRUE,
+                           work=(self.vectorR1.Ptr, self.vectorW1.Ptr, self.vectorW2.Ptr, self._dinv()))
 
     def SolveBicgstab(self, trace: bool = False, jacobi: bool = False):
         """Solve A x = b with BiCGStab (SolveBicgstabParallel): A any CSR matrix, symmetric or not.  Three all-reduces per iteration (of
@@ -429,34 +343,11 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         (SolveBicgstabJacobiParallel; SetupJacobi() first) -- a rank whose SetupJacobi() failed still enters the native call, with no dinv
         vector: every rank gets MGCG_ERROR.  Every rank passes the same ``jacobi``."""
         self._ensure_comm()
-        p = self.part
-        usable = getattr(self, "vectorDinv", None) is not None and getattr(self, "jacobiError", None) is None
-        if getattr(self, "vectorS", None) is None or self.vectorS.size < self.Count:
-            self.vectorS = VectorDouble(self.Count)
-        for name in ("vectorV", "vectorT", "vectorRhat"):
-            if getattr(self, name, None) is None or getattr(self, name).size < p.count:
-                setattr(self, name, VectorDouble(p.count))
-        iteration, residual, true = C.c_int(0), C.c_double(0.0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        export = "SolveBicgstabJacobiParallel" if jacobi else "SolveBicgstabParallel"
-        more = ((self.vectorDinv.Ptr if usable else None),) if jacobi else ()
-        st = getattr(lib(), export)(self.comm, self.cublas, self.cusparse, self.matDescr,
-                                    self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                    self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                    self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr, *more,
-                                    self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
-                                    self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                    C.byref(iteration), C.byref(residual), C.byref(true), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.TrueResidual, self.status = iteration.value, residual.value, true.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"{'Jacobi-preconditioned ' if jacobi else ''}BiCGStab did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check(export)
-            raise MgcgError(f"{export} failed with status {st}")
+        self._ensure_vectors(self.Count, "vectorS")
+        self._ensure_vectors(self.part.count, "vectorV", "vectorT", "vectorRhat")
+        self._native_solve("SolveBicgstabJacobiParallel" if jacobi else "SolveBicgstabParallel", "Jacobi-preconditioned BiCGStab" if jacobi else "BiCGStab",
+                           trace, third=_TRUE,
+                           work=(self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr, *((self._dinv(),) if jacobi else ())))
 
     def SolveBicgstabJacobi(self, trace: bool = False):
         """SolveBicgstab() right-preconditioned with the diagonal (SolveBicgstabJacobiParallel); SetupJacobi() first."""
@@ -467,35 +358,15 @@ class ConjugateGradientRankGpu(ConjugateGradientGpu):
         jacobi=True (SetupJacobi() first) -- is required here: the bound of a partitioned matrix is the maximum over the ranks, which the
         caller takes.  Every rank passes the same ``jacobi``, ``degree`` and ``bounds``."""
         self._ensure_comm()
-        p = self.part
         if bounds is None:
             raise ValueError("SolveChebyshev: bounds = (lambdaMin, lambdaMax) is required on ranks")
         lmin, lmax = float(bounds[0]), float(bounds[1])
-        if jacobi and (getattr(self, "vectorDinv", None) is None or getattr(self, "jacobiError", None) is not None):
+        if jacobi and self._dinv() is None:
             raise MgcgError("SolveChebyshev(jacobi=True): SetupJacobi() has not set the diagonal up")
-        for name, size in (("vectorZ", self.Count), ("vectorZ2", self.Count), ("vectorD", p.count)):
-            if getattr(self, name, None) is None or getattr(self, name).size < size:
-                setattr(self, name, VectorDouble(size))
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = lib().SolveChebyshevParallel(self.comm, self.cublas, self.cusparse, self.matDescr,
-                                          self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                          self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                                          self.vectorDinv.Ptr if jacobi else None, self.vectorZ.Ptr, self.vectorZ2.Ptr, self.vectorD.Ptr,
-                                          self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
-                                          int(degree), lmin, lmax,
-                                          self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                          C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"Chebyshev-preconditioned CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveChebyshevParallel")
-            raise MgcgError(f"SolveChebyshevParallel failed with status {st}")
+        self._ensure_vectors(self.Count, "vectorZ", "vectorZ2")
+        self._ensure_vectors(self.part.count, "vectorD")
+        self._native_solve("SolveChebyshevParallel", "Chebyshev-preconditioned CG", trace, more=(int(degree), lmin, lmax),
+                           work=(self.vectorDinv.Ptr if jacobi else None, self.vectorZ.Ptr, self.vectorZ2.Ptr, self.vectorD.Ptr))
 
     @staticmethod
     def LastOverlap():
@@ -544,8 +415,6 @@ class ConjugateGradientMgRankGpu(ConjugateGradientRankGpu):
         if getattr(self, "mg", None):
             lib().MgDestroy(self.mg)
             self.mg = None
-        if getattr(self, "vectorZ", None) is not None:
-            self.vectorZ.Dispose()
         super().Dispose()
 
     def Setup(self):
@@ -581,25 +450,7 @@ class ConjugateGradientMgRankGpu(ConjugateGradientRankGpu):
 
     def Solve(self, trace: bool = False):
         self._ensure_comm()
-        p = self.part
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = lib().SolveMgParallel(self.comm, self.cublas, self.cusparse, self.matDescr, self.mg,
-                                   self.vectorElements.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                   self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorZ.Ptr,
-                                   self.Count, p.count, p.offset, p.elementCount, p.minJ, p.maxJ,
-                                   self.AllowableResidual, self.MinIteration, self.MaxIteration, self.rule,
-                                   C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            lib().MgcgClearLastError()
-            raise ApplicationException(f"MGCG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveMgParallel")
-            raise MgcgError(f"SolveMgParallel failed with status {st}")
+        self._native_solve("SolveMgParallel", "MGCG", trace, head=(self.mg,), work=(self.vectorZ.Ptr,))
 
 
 # --------------------------------------------------------------------------- host-driven phases over torch.distributed

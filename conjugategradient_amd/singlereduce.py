@@ -11,19 +11,16 @@ is not supported.  After ``Solve()``, ``ReadResidual()`` returns the recurrence 
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import numpy as np
-
 from . import _lib
-from ._lib import MgcgError, check, lib
+from ._lib import MgcgError
 from .jacobi import check_system_shapes, jacobi_setup
-from .solver import ApplicationException, ConjugateGradientSingleGpu, VectorDouble, _ptr
+from .solver import ConjugateGradientSingleGpu, VectorDouble
 
 
 class ConjugateGradientSingleReduceGpu(ConjugateGradientSingleGpu):
     """ConjugateGradientSingleGpu on the single-reduction loop: same constructor (plus ``jacobi``), members, ``Iteration`` / ``Residual``
-    and ``ApplicationException`` behaviour; the stop rules test the true residual."""
+    and ``ApplicationException`` behaviour; the stop rules test the true residual.  ``ReadResidual()`` returns the recurrence residual r
+    that the last Solve() left in its work vector."""
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, rule=None, jacobi=False):
         if rule == _lib.RULE_HANDMADECL:
@@ -35,10 +32,7 @@ class ConjugateGradientSingleReduceGpu(ConjugateGradientSingleGpu):
         self._ready = False
 
     def Dispose(self):
-        for name in ("vectorS", "vectorDinv"):
-            if getattr(self, name, None) is not None:
-                getattr(self, name).Dispose()
-                setattr(self, name, None)
+        self._dispose_vectors("vectorS", "vectorDinv")
         super().Dispose()
 
     def Initialize(self):
@@ -54,31 +48,5 @@ class ConjugateGradientSingleReduceGpu(ConjugateGradientSingleGpu):
         """trace: keep the residual trace in ``self.trace``; traceCapacity: its length when the default (room for every iteration) is not wanted."""
         if not self._ready:
             raise MgcgError("ConjugateGradientSingleReduceGpu.Solve: Initialize() has not run")
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration, residual = C.c_int(0), C.c_double(0.0)
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = (max(self.MaxIteration, self.MinIteration) + 8 if traceCapacity is None else int(traceCapacity)) if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        L = lib()
-        st = L.SolveSingleReduce(self.cublas, self.cusparse, self.matDescr,
-                                 self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                                 self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr, self.vectorS.Ptr,
-                                 self.vectorDinv.Ptr if self.jacobi else None,
-                                 nonzeroCount, self.Count,
-                                 self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                                 C.byref(iteration), C.byref(residual), _ptr(tr) if trace else None, cap)
-        self.Iteration, self.Residual, self.status = iteration.value, residual.value, st
-        if trace:
-            self.trace = tr[: min(self.Iteration + 1, cap)].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"single-reduction CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveSingleReduce")
-            raise MgcgError(f"SolveSingleReduce failed with status {st}")
-
-    def ReadResidual(self) -> np.ndarray:
-        """The recurrence residual r the last Solve() left in its work vector."""
-        r = np.empty(self.Count)
-        self.vectorR.CopyTo(r, self.Count, 0)
-        return r
+        self._native_solve("SolveSingleReduce", "single-reduction CG", trace, traceCapacity=traceCapacity,
+                           work=(self.vectorS.Ptr, self.vectorDinv.Ptr if self.jacobi else None))

@@ -211,6 +211,62 @@ class ConjugateGradientGpu(ConjugateGradient):
     def Read(self):
         raise NotImplementedError
 
+    # -- the one native-call path of the one-column solvers; the classes say what differs -------------------
+    _matrix = "vectorA"                     # the member that holds the matrix values (a rank: vectorElements)
+    _default_rule = _lib.RULE_NATIVE        # what rule=None means on one rank (ConjugateGradientMgGpu: RULE_CSHARP)
+
+    def _handles(self):
+        """What an export takes in front of the hierarchy and the matrix (a rank: the communicator first)."""
+        return (self.cublas, self.cusparse, self.matDescr)
+
+    def _sizes(self):
+        """What an export takes between the work vectors and the scalars of its loop (a rank: its partition)."""
+        return (int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz, self.Count)
+
+    def _rule(self):
+        return self._default_rule if self.rule is None else self.rule      # (a rank passes self.rule as it stands)
+
+    def _native_solve(self, export, what, trace, head=(), work=(), more=(), third=None, traceCapacity=None):
+        """One solve in one native call: ``export(handles, *head, the eight vectors, *work, sizes, *more, stop rule, outputs, trace)``.
+        ``what`` names the loop in the ApplicationException; ``third`` = (attribute, starting value) is the output behind iteration and
+        residual -- a float goes out as a double, an int as an int -- and ``traceCapacity`` the trace's length where the default, room
+        for every iteration, is not wanted.  Stores Iteration, Residual, the third output, status and the trace, THEN raises
+        ApplicationException past MaxIteration and MgcgError for every other status but MGCG_OK."""
+        cells = [C.c_int(0), C.c_double(0.0)] + ([(C.c_double if isinstance(third[1], float) else C.c_int)(third[1])] if third else [])
+        cap = (max(self.MaxIteration, self.MinIteration) + 8 if traceCapacity is None else int(traceCapacity)) if trace else 0
+        tr = np.zeros(max(cap, 1)) if trace else None
+        L = lib()
+        st = getattr(L, export)(*self._handles(), *head,
+                                getattr(self, self._matrix).Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
+                                self.vectorX.Ptr, self.vectorB.Ptr, self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
+                                *work, *self._sizes(), *more,
+                                self.AllowableResidual, self.MinIteration, self.MaxIteration, self._rule(),
+                                *(C.byref(c) for c in cells), _ptr(tr) if trace else None, cap)
+        self.Iteration, self.Residual, self.status = cells[0].value, cells[1].value, st
+        if third:
+            setattr(self, third[0], cells[2].value)
+        if trace:
+            self.trace = tr[: min(self.Iteration + 1, cap)].copy()      # cap = 0 (a traceCapacity of 0): the empty trace
+        if st == _lib.MAXIT_EXCEEDED:
+            L.MgcgClearLastError()
+            raise ApplicationException(f"{what} did not converge within MaxIteration={self.MaxIteration}")
+        if st != _lib.OK:
+            check(export)
+            raise MgcgError(f"{export} failed with status {st}")
+
+    def _ensure_vectors(self, size, *names):
+        """Every ``self.<name>`` is a VectorDouble of at least ``size`` entries: allocated where it is missing or smaller."""
+        for name in names:
+            if getattr(self, name, None) is None or getattr(self, name).size < size:
+                setattr(self, name, VectorDouble(size))
+
+    def _dispose_vectors(self, *names):
+        """Dispose the named vectors that this object has and set them to None."""
+        for name in names:
+            if getattr(self, name, None) is not None:
+                getattr(self, name).Dispose()
+                setattr(self, name, None)
+
 
 class ConjugateGradientSingleGpu(ConjugateGradientGpu):
     """ConjugateGradientSingleGpu.cs:9-179: whole solve in ONE native call."""
@@ -260,11 +316,10 @@ class ConjugateGradientSingleGpu(ConjugateGradientGpu):
         self.vectorX.CopyFrom(self.x, self.Count)
 
     def Solve(self, trace: bool = False):
-        nonzeroCount = int(self.A.RowOffsets[self.Count])
-        iteration = C.c_int(0)
-        residual = C.c_double(0.0)
-        L = lib()
-        if self.rule is None and not trace:
+        if self.rule is None and not trace:                 # the reference's own export, with its own protocol
+            nonzeroCount = int(self.A.RowOffsets[self.Count])
+            iteration, residual = C.c_int(0), C.c_double(0.0)
+            L = lib()
             L.Solve(self.cublas, self.cusparse, self.matDescr,
                     self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
                     self.vectorX.Ptr, self.vectorB.Ptr,
@@ -281,28 +336,25 @@ class ConjugateGradientSingleGpu(ConjugateGradientGpu):
                     raise ApplicationException(msg)
                 raise MgcgError(msg)
             return
-        rule = _lib.RULE_NATIVE if self.rule is None else self.rule
-        cap = max(self.MaxIteration, self.MinIteration) + 8 if trace else 0
-        tr = np.zeros(max(cap, 1)) if trace else None
-        st = L.SolveEx(self.cublas, self.cusparse, self.matDescr,
-                       self.vectorA.Ptr, self.vectorRowOffsets.Ptr, self.vectorColumnIndeces.Ptr,
-                       self.vectorX.Ptr, self.vectorB.Ptr,
-                       self.vectorAp.Ptr, self.vectorP.Ptr, self.vectorR.Ptr,
-                       nonzeroCount, self.Count,
-                       self.AllowableResidual, self.MinIteration, self.MaxIteration, rule,
-                       C.byref(iteration), C.byref(residual),
-                       _ptr(tr) if trace else None, cap)
-        self.Iteration = iteration.value
-        self.Residual = residual.value
-        self.status = st
-        if trace:
-            self.trace = tr[: self.Iteration + 1].copy()
-        if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
-            raise ApplicationException(f"CG did not converge within MaxIteration={self.MaxIteration}")
-        if st != _lib.OK:
-            check("SolveEx")
-            raise MgcgError(f"SolveEx failed with status {st}")
+        self._native_solve("SolveEx", "CG", trace)
+
+    vectorWork, _work_size = None, 0        # the loops that keep their vectors in one work vector: BiCGStab(l), GMRES(m), SolveGmresMg
+
+    def _ensure_work(self, slices):
+        """``vectorWork`` has room for ``slices`` slices of Count entries, rounded up to even: allocated at the first call and again,
+        larger, when it holds less."""
+        need = slices * (self.Count + (self.Count & 1))
+        if need > self._work_size:
+            if self.vectorWork is not None:
+                self.vectorWork.Dispose()
+            self.vectorWork, self._work_size = VectorDouble(need), need
+
+    def ReadResidual(self) -> np.ndarray:
+        """What the last solve left in ``vectorR``: the recurrence residual of a CG loop; the true residual of the closing product --
+        b - (A - shift I) x -- of MINRES, BiCGStab, BiCGStab(l) and GMRES(m), with or without a preconditioner."""
+        r = np.empty(self.Count)
+        self.vectorR.CopyTo(r, self.Count, 0)
+        return r
 
     def Read(self):
         self.vectorX.CopyTo(self.x, self.Count)
