@@ -6,6 +6,7 @@
 ``multigrid`` the V-cycle preconditioner the reference named but never wrote
 ``amg``       the same V-cycle for ANY CSR matrix: aggregates from the matrix graph (MgSetupAggregation) or from the caller;
               ``strength="symmetric"`` (MgSetupAggregationEx) matches on the symmetric part, for A != A^T that does not coarsen otherwise
+              ``amg.csr_transpose_gpu`` / ``amg.transpose_gpu``: A^T of any CSR matrix formed on the device (MgcgCsrTranspose), values as bit copies
 ``ssor``      SSOR(omega)-preconditioned CG / MINRES / BiCGStab: the one-level form of ``amg`` with two multicolour Gauss-Seidel sweeps
 ``jacobi``    Jacobi-preconditioned CG for general CSR matrices (the call the ViennaCL front-end left commented out)
 ``singlereduce`` single-reduction (Chronopoulos-Gear) CG: one global sum and two launches per iteration, with or without the diagonal

@@ -106,6 +106,8 @@ SIGNATURES = {
     "MgSetupAggregationEx": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _i, _d, _i, _i, _d, _i]),
     "MgStrength": (_i, [_vp]),
     "MgcgSymmetricPart": (_ll, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i]),
+    "MgcgCsrTranspose": (_ll, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "MgcgTransposeClassLimits": (None, [_pi, _pi]),
     "MgSetupAggregates": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _i, _i, _d]),
     "MgLevelCopyAggregates": (_i, [_vp, _i, _vp]),
     "MgDestroy": (None, [_vp]),

@@ -9,6 +9,7 @@ One GPU; ``omega`` is the caller's (omega * lambda_max(D^-1 A) < 2 keeps the pre
 """
 from __future__ import annotations
 
+import ctypes as C
 
 import numpy as np
 
@@ -53,6 +54,67 @@ def symmetric_part_gpu(system: LinearSystem) -> LinearSystem:
             v.Dispose()
         L.DestroyBlas(blas)
         L.DestroySparse(sparse)
+
+
+def transpose_class_limits():
+    """(shortMax, ldsMax) of ``MgcgCsrTranspose``: a column stored shortMax times or less is sorted by one lane in registers, one stored
+    ldsMax times or less by one workgroup in LDS, a longer one by one workgroup in global memory.  Needs no GPU."""
+    short, lds = C.c_int(0), C.c_int(0)
+    lib().MgcgTransposeClassLimits(C.byref(short), C.byref(lds))
+    return short.value, lds.value
+
+
+def csr_transpose_gpu(elements, column_indices, row_offsets, columns, with_source=False):
+    """A^T of a CSR matrix of ``len(row_offsets) - 1`` rows and ``columns`` columns, formed on the device (``MgcgCsrTranspose``): numpy
+    arrays ``(elements, column_indices, row_offsets)`` of A^T, and the source list behind them with ``with_source`` (``source[q]`` = the
+    stored position in A of entry q of A^T).  Row c of A^T holds the stored entries of column c of A by ascending stored position; values
+    are bit copies.  ``elements`` None asks for the pattern alone and gives None back in its place.  Rows may be unsorted, empty and hold
+    duplicates; entries beyond ``row_offsets[-1]`` are ignored."""
+    _lib.require_gpu()
+    L = lib()
+    ro = np.ascontiguousarray(row_offsets, dtype=np.int32)
+    ci = np.ascontiguousarray(column_indices, dtype=np.int32)
+    rows, held, columns = len(ro) - 1, len(ci), int(columns)
+    if elements is not None:
+        elements = np.ascontiguousarray(elements, dtype=np.float64)
+        if len(elements) != held:
+            raise MgcgError(f"csr_transpose_gpu: {len(elements)} values, {held} columns")
+    blas, sparse = ConjugateGradientGpu.CreateBlas(), ConjugateGradientGpu.CreateSparse()
+    vectors = {}
+    try:
+        sizes = dict(ro=(VectorInt, rows + 1), ci=(VectorInt, held), tro=(VectorInt, columns + 1), tci=(VectorInt, held))
+        if elements is not None:
+            sizes.update(a=(VectorDouble, held), ta=(VectorDouble, held))
+        if with_source:
+            sizes.update(src=(VectorInt, held))
+        for key, (kind, size) in sizes.items():
+            vectors[key] = kind(max(size, 1))
+        vectors["ro"].CopyFrom(ro, rows + 1)
+        if held:
+            vectors["ci"].CopyFrom(ci, held)
+            if elements is not None:
+                vectors["a"].CopyFrom(elements, held)
+        ptr = lambda key: vectors[key].Ptr if key in vectors else None
+        count = L.MgcgCsrTranspose(blas, sparse, ptr("a"), ptr("ro"), ptr("ci"), held, rows, columns, ptr("ta"), ptr("tro"), ptr("tci"), ptr("src"))
+        check("MgcgCsrTranspose")
+        if count < 0:
+            raise MgcgError("MgcgCsrTranspose failed")
+        out = (vectors["ta"].to_numpy(max(held, 1))[:count] if elements is not None else None, vectors["tci"].to_numpy(max(held, 1))[:count],
+               vectors["tro"].to_numpy(columns + 1))
+        return out + (vectors["src"].to_numpy(max(held, 1))[:count],) if with_source else out
+    finally:
+        for v in vectors.values():
+            v.Dispose()
+        L.DestroyBlas(blas)
+        L.DestroySparse(sparse)
+
+
+def transpose_gpu(system: LinearSystem) -> LinearSystem:
+    """A^T of a (square) system's matrix formed on the device (``csr_transpose_gpu``), with the same b, x and grid.  Its rows come out with
+    ascending columns whatever the order of A's rows; duplicates stay apart, in stored order."""
+    n, nnz = system.Count, system.nnz
+    e, c, ro = csr_transpose_gpu(system.Elements[:nnz], system.ColumnIndeces[:nnz], system.RowOffsets, n)
+    return LinearSystem(e, c, ro, np.array(system.x, dtype=np.float64), np.array(system.b, dtype=np.float64), f"{system.name}-T", grid=system.grid)
 
 
 class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):

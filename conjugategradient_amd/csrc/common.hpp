@@ -913,8 +913,27 @@ void launch_amg_galerkin_count(hipStream_t s, long long nc, const int* aggOffset
 void launch_amg_galerkin_fill(hipStream_t s, long long nc, const int* aggOffsets, const int* members, const double* elements, const int* rowOffsets,
                               const int* columnIndeces, const int* agg, const int* expandOffsets, const int* scratch, const int* rowOffsetsC, double sigma,
                               double* elementsC, int* columnIndecesC);
-// out[k] = elements[source[k]], k < m: the values of the merged matrix [A | A^T] of MgcgSymmetricPart through the host-built entry list
+// out[k] = elements[source[k]], k < m: the values of the merged matrix [A | A^T] of MgcgSymmetricPart through its source list
 void launch_amg_gather_values(hipStream_t s, long long m, const int* source, const double* elements, double* out);
+
+// ---------------------------------------------------------------- CSR transposition (kernels_transpose.hip; MgcgCsrTranspose, MgcgSymmetricPart)
+constexpr int kTransposeShortMax = 32;     // a column stored this often or less is sorted by one lane in registers
+constexpr int kTransposeLdsMax = 4096;     // ... this often or less by one workgroup in LDS; a longer one by one workgroup in global memory
+// status3[0] (pre-set to INT_MAX) = the smallest row whose offsets descend, status3[1] = rowOffsets[0], status3[2] = rowOffsets[rows]
+void launch_transpose_check_offsets(hipStream_t s, const int* rowOffsets, long long rows, int* status3);
+// counts[c] (zeroed) = how often column c is stored; *badRow (pre-set to INT_MAX) = the smallest row that stores a column outside [0, columns).
+// The offsets must have passed the check above and end at nnz.
+void launch_transpose_count(hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long rows, long long columns, long long nnz, int* counts, int* badRow);
+// keys[offsetsT[c] .. offsetsT[c + 1]) = (k << 32) | row of the stored entries of column c by ascending stored position k; offsetsT = the
+// scanned counts; scratch: cursor (columns ints), work (1 + min(columns, nnz / (kTransposeShortMax + 1)) ints)
+bool launch_transpose_claim_and_sort(hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long rows, long long columns, long long nnz,
+                                     const int* offsetsT, int* cursor, int* work, unsigned long long* keys);
+// A^T's columns (the rows of A), source list and values from the keys; outSource and outElements (with elements) may be null
+void launch_transpose_emit(hipStream_t s, long long nnz, const unsigned long long* keys, const double* elements, int* outColumns, int* outSource, double* outElements);
+// the merged matrix [A | A^T] of a square matrix: offsets (n + 1), columns and source list (2 nnz each)
+void launch_transpose_merged(hipStream_t s, const int* rowOffsets, const int* columnIndeces, const int* offsetsT, const unsigned long long* keys, long long n, long long nnz,
+                             int* mergedOffsets, int* mergedColumns, int* mergedSource);
+void preload_kernels_transpose();
 
 // ---------------------------------------------------------------- multicolour Gauss-Seidel smoother (kernels_gs.hip; MgSetSmoother)
 // one colouring round: colourIn (-1 = uncoloured) -> colourOut; flags[0] = 1 if a row is left uncoloured; *badRow (pre-set to INT_MAX) = the

@@ -2693,61 +2693,102 @@ static bool amg_level_map(hipStream_t s, const AmgMatrix& A, int passes, double 
     return ok;
 }
 
+// What the transposition of a checked matrix leaves on the device: the offsets of A^T and, per entry of A^T, the key (k << 32) | row of A
+// (kernels_transpose.hip).  The caller frees it, also after a failure.
+struct CsrTransposed { int* offsets = nullptr; unsigned long long* keys = nullptr; };
+static void amg_free(CsrTransposed& t)
+{
+    if (t.offsets) (void)hipFree(t.offsets);
+    if (t.keys) (void)hipFree(t.keys);
+    t = CsrTransposed();
+}
+
+// The offsets of a rows-row matrix start at 0, never descend and end at or below `held`; *nnz = where they end.  Three ints come to the
+// host.  false with the message set on a refusal.
+static bool csr_check_offsets(const char* who, hipStream_t s, const int* rowOffsets, long long rows, long long held, long long* nnz)
+{
+    int* dStatus = nullptr;
+    int h[3] = { 0x7fffffff, 0, 0 };
+    bool ok = MGCG_HIP(hipMalloc((void**)&dStatus, sizeof(h))) && MGCG_HIP(hipMemcpyAsync(dStatus, h, sizeof(h), hipMemcpyHostToDevice, s));
+    if (ok) launch_transpose_check_offsets(s, rowOffsets, rows, dStatus);
+    ok = ok && MGCG_HIP(hipMemcpyAsync(h, dStatus, sizeof(h), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    if (dStatus) (void)hipFree(dStatus);
+    if (!ok) return false;
+    if (h[1] != 0) { set_error("%s: rowOffsets[0] is %d, must be 0", who, h[1]); return false; }
+    if (h[0] != 0x7fffffff) { set_error("%s: row %lld: the row offsets descend", who, (long long)h[0]); return false; }
+    if (h[2] > held) { set_error("%s: the row offsets end at %lld, the matrix holds %lld entries", who, (long long)h[2], held); return false; }
+    *nnz = h[2];
+    return true;
+}
+
+// The transposition of a matrix whose offsets passed csr_check_offsets and end at nnz: the column check (the flag comes to the host and, on
+// a refusal, the one offending row, to name its column; `what` is the word for the bound: "rows" of a square matrix or "columns"), the
+// counts, their scan, the claim pass and the sort of every segment.  Complete when it returns.  false with the message set on a refusal.
+static bool csr_transpose_device(const char* who, hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long rows, long long columns, long long nnz,
+                                 const char* what, CsrTransposed* out)
+{
+    const size_t nz = (size_t)nnz, nzAlloc = nz > 0 ? nz : 1, listed = (size_t)std::min<long long>(columns, nnz / (kTransposeShortMax + 1));
+    int *cursor = nullptr, *work = nullptr, *dflag = nullptr;
+    int bad = 0x7fffffff;
+    bool ok = MGCG_HIP(hipMalloc((void**)&out->offsets, sizeof(int) * ((size_t)columns + 1))) && MGCG_HIP(hipMalloc((void**)&dflag, sizeof(int))) &&
+              MGCG_HIP(hipMemsetAsync(out->offsets, 0, sizeof(int) * ((size_t)columns + 1), s)) &&
+              MGCG_HIP(hipMemcpyAsync(dflag, &bad, sizeof(int), hipMemcpyHostToDevice, s));
+    if (ok) launch_transpose_count(s, rowOffsets, columnIndeces, rows, columns, nnz, out->offsets, dflag);
+    ok = ok && MGCG_HIP(hipMemcpyAsync(&bad, dflag, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    if (dflag) (void)hipFree(dflag);
+    if (ok && bad != 0x7fffffff) {
+        int ends[2] = { 0, 0 };
+        ok = MGCG_HIP(hipMemcpy(ends, rowOffsets + bad, sizeof(ends), hipMemcpyDeviceToHost));
+        std::vector<int> row((size_t)(ok ? ends[1] - ends[0] : 0));
+        ok = ok && MGCG_HIP(hipMemcpy(row.data(), columnIndeces + ends[0], sizeof(int) * row.size(), hipMemcpyDeviceToHost));
+        if (!ok) return false;
+        for (int c : row)
+            if (c < 0 || c >= columns) { set_error("%s: row %lld stores column %d, the matrix has %lld %s", who, (long long)bad, c, columns, what); break; }
+        return false;
+    }
+    ok = ok && exclusive_scan(s, out->offsets, columns + 1);
+    ok = ok && MGCG_HIP(hipMalloc((void**)&out->keys, sizeof(unsigned long long) * nzAlloc)) && MGCG_HIP(hipMalloc((void**)&cursor, sizeof(int) * (size_t)columns)) &&
+         MGCG_HIP(hipMalloc((void**)&work, sizeof(int) * (listed + 1))) &&
+         launch_transpose_claim_and_sort(s, rowOffsets, columnIndeces, rows, columns, nnz, out->offsets, cursor, work, out->keys);
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (cursor) (void)hipFree(cursor);
+    if (work) (void)hipFree(work);
+    return ok;
+}
+
 // *out = S, the symmetric part of A by the contract of MgcgSymmetricPart (include/MgcgGpu.h), in storage of its own (the caller frees it, also
 // after a failure).  The merged matrix [A | A^T] -- row i = A's row i in stored order, then the stored entries of column i by source row and
 // stored order -- goes through amg_galerkin with the identity map and sigma = 0.5: its contract (entries in stored order, accumulators from
-// +0.0, columns ascending, sigma * acc) is S's.  The offsets and columns come to the host for the counting sort by column (the transposition
-// permutation: index bookkeeping); the values stay on the device and are gathered there.  false with the message set on a refusal.
+// +0.0, columns ascending, sigma * acc) is S's.  The checks, the transposition (pattern and source list) and the merged matrix are formed on
+// the device (kernels_transpose.hip); the flags, the end of the offsets and, on a refusal, one row come to the host.  false with the
+// message set on a refusal.
 static bool amg_symmetric_part(const char* who, hipStream_t s, const AmgMatrix& A, AmgMatrix* out)
 {
     const size_t n = (size_t)A.n;
-    std::vector<int> ro(n + 1);
-    if (!MGCG_HIP(hipMemcpyAsync(ro.data(), A.rowOffsets, sizeof(int) * (n + 1), hipMemcpyDeviceToHost, s)) || !MGCG_HIP(hipStreamSynchronize(s))) return false;
-    if (ro[0] != 0) { set_error("%s: rowOffsets[0] is %d, must be 0", who, ro[0]); return false; }
-    for (size_t i = 0; i < n; ++i)
-        if (ro[i + 1] < ro[i]) { set_error("%s: row %lld: the row offsets descend", who, (long long)i); return false; }
-    const long long nnz = ro[n];
-    if (nnz > A.nnz) { set_error("%s: the row offsets end at %lld, the matrix holds %lld entries", who, nnz, A.nnz); return false; }
+    long long nnz = 0;
+    if (!csr_check_offsets(who, s, A.rowOffsets, A.n, A.nnz, &nnz)) return false;
     if (2 * nnz > 0x7fffffffLL) { set_error("%s: 2 x %lld entries exceed int32 offsets", who, nnz); return false; }
-    const size_t nz = (size_t)nnz, mz = 2 * nz, mzAlloc = mz > 0 ? mz : 1;
-    std::vector<int> col(nz), mro(n + 1, 0);
-    if (nz > 0 && (!MGCG_HIP(hipMemcpyAsync(col.data(), A.columnIndeces, sizeof(int) * nz, hipMemcpyDeviceToHost, s)) || !MGCG_HIP(hipStreamSynchronize(s)))) return false;
-    for (size_t i = 0; i < n; ++i)
-        for (int k = ro[i]; k < ro[i + 1]; ++k) {
-            const int c = col[(size_t)k];
-            if (c < 0 || (size_t)c >= n) { set_error("%s: row %lld stores column %d, the matrix has %lld rows", who, (long long)i, c, (long long)n); return false; }
-            mro[(size_t)c + 1]++;                                                       // how often column c is stored: the length of A^T's row c
-        }
-    for (size_t i = 0; i < n; ++i) mro[i + 1] += mro[i] + (ro[i + 1] - ro[i]);
-    std::vector<int> source(mzAlloc, 0), mcol(mzAlloc, 0), at(n);
-    for (size_t i = 0; i < n; ++i) {
-        int p = mro[i];
-        for (int k = ro[i]; k < ro[i + 1]; ++k, ++p) { source[(size_t)p] = k; mcol[(size_t)p] = col[(size_t)k]; }
-        at[i] = p;
-    }
-    for (size_t i = 0; i < n; ++i)                                                      // the stable counting sort by column: source rows ascending, stored order within one
-        for (int k = ro[i]; k < ro[i + 1]; ++k) {
-            const size_t p = (size_t)at[(size_t)col[(size_t)k]]++;
-            source[p] = k; mcol[p] = (int)i;
-        }
+    const size_t mz = 2 * (size_t)nnz, mzAlloc = mz > 0 ? mz : 1;
+    CsrTransposed T;
     AmgMatrix M; M.n = A.n; M.nnz = (long long)mz;
     int* dSource = nullptr;
-    bool ok = MGCG_HIP(hipMalloc((void**)&M.elements, sizeof(double) * mzAlloc)) && MGCG_HIP(hipMalloc((void**)&M.columnIndeces, sizeof(int) * mzAlloc)) &&
-              MGCG_HIP(hipMalloc((void**)&M.rowOffsets, sizeof(int) * (n + 1))) && MGCG_HIP(hipMalloc((void**)&dSource, sizeof(int) * mzAlloc)) &&
-              MGCG_HIP(hipMemcpyAsync(M.columnIndeces, mcol.data(), sizeof(int) * mzAlloc, hipMemcpyHostToDevice, s)) &&
-              MGCG_HIP(hipMemcpyAsync(M.rowOffsets, mro.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, s)) &&
-              MGCG_HIP(hipMemcpyAsync(dSource, source.data(), sizeof(int) * mzAlloc, hipMemcpyHostToDevice, s));
-    if (ok) launch_amg_gather_values(s, (long long)mz, dSource, A.elements, M.elements);
+    bool ok = csr_transpose_device(who, s, A.rowOffsets, A.columnIndeces, A.n, A.n, nnz, "rows", &T) &&
+              MGCG_HIP(hipMalloc((void**)&M.elements, sizeof(double) * mzAlloc)) && MGCG_HIP(hipMalloc((void**)&M.columnIndeces, sizeof(int) * mzAlloc)) &&
+              MGCG_HIP(hipMalloc((void**)&M.rowOffsets, sizeof(int) * (n + 1))) && MGCG_HIP(hipMalloc((void**)&dSource, sizeof(int) * mzAlloc));
+    if (ok) {
+        launch_transpose_merged(s, A.rowOffsets, A.columnIndeces, T.offsets, T.keys, A.n, nnz, M.rowOffsets, M.columnIndeces, dSource);
+        launch_amg_gather_values(s, (long long)mz, dSource, A.elements, M.elements);
+        ok = MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipStreamSynchronize(s));
+    }
+    amg_free(T);                                                                        // (before the product asks for its own storage)
+    if (dSource) { (void)hipFree(dSource); dSource = nullptr; }
     if (ok) {
         std::vector<int> identity(n);
         for (size_t i = 0; i < n; ++i) identity[i] = (int)i;
         AmgDeviceMap dm;
-        ok = amg_galerkin(s, M, identity, (int)n, 0.5, out, &dm);                       // (ends with a synchronise: the staging vectors above may go)
+        ok = amg_galerkin(s, M, identity, (int)n, 0.5, out, &dm);
         amg_free(dm);
-    } else {
-        (void)hipStreamSynchronize(s);
     }
-    if (dSource) (void)hipFree(dSource);
     amg_free(M);
     return ok;
 }
@@ -2977,6 +3018,53 @@ long long MgcgSymmetricPart(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elem
     }
     amg_free(S);
     return ok ? nnzS : -1;
+}
+
+void MgcgTransposeClassLimits(int* shortMax, int* ldsMax)
+{
+    if (shortMax) *shortMax = kTransposeShortMax;
+    if (ldsMax) *ldsMax = kTransposeLdsMax;
+}
+
+long long MgcgCsrTranspose(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                           int elementsCount, int rows, int columns, Vector* outElements, VectorInt* outRowOffsets, VectorInt* outColumnIndeces, VectorInt* outSource)
+{
+    const char* who = "MgcgCsrTranspose";
+    if (!cublas || !cusparse || !rowOffsetsVector || !columnIndecesVector || !outRowOffsets || !outColumnIndeces) { set_error("%s: null handle", who); return -1; }
+    if ((elementsVector == nullptr) != (outElements == nullptr)) { set_error("%s: null handle (elements and outElements are given together, or neither of them)", who); return -1; }
+    if (rows < 1 || columns < 1 || elementsCount < 0) { set_error("%s: bad parameters (rows %d, columns %d, elementsCount %d)", who, rows, columns, elementsCount); return -1; }
+    if (rowOffsetsVector->size < (long long)rows + 1 || columnIndecesVector->size < elementsCount || (elementsVector && elementsVector->size < elementsCount)) {
+        set_error("%s: matrix vectors too small (%lld values, %lld offsets, %lld columns for %d entries in %d rows)", who, elementsVector ? (long long)elementsVector->size : -1LL,
+                  (long long)rowOffsetsVector->size, (long long)columnIndecesVector->size, elementsCount, rows);
+        return -1;
+    }
+    if (outRowOffsets->size < (long long)columns + 1 || outColumnIndeces->size < elementsCount || (outElements && outElements->size < elementsCount) ||
+        (outSource && outSource->size < elementsCount)) {
+        set_error("%s: output vectors too small (%lld values, %lld offsets, %lld columns, %lld sources for %d entries in %d rows of the transpose)", who,
+                  outElements ? (long long)outElements->size : -1LL, (long long)outRowOffsets->size, (long long)outColumnIndeces->size,
+                  outSource ? (long long)outSource->size : -1LL, elementsCount, columns);
+        return -1;
+    }
+    DeviceState* d = device_state();
+    if (!d) return -1;
+    hipStream_t s = d->stream;
+    long long nnz = 0;
+    if (!csr_check_offsets(who, s, rowOffsetsVector->data, rows, elementsCount, &nnz)) return -1;
+    CsrTransposed T;
+    bool ok = csr_transpose_device(who, s, rowOffsetsVector->data, columnIndecesVector->data, rows, columns, nnz, "columns", &T);
+    if (ok) {                                             // every refusal is behind: the outputs are written from here on
+        analysis_note_write(outRowOffsets->data, sizeof(int) * ((size_t)columns + 1));
+        analysis_note_write(outColumnIndeces->data, sizeof(int) * (size_t)nnz);
+        if (outSource) analysis_note_write(outSource->data, sizeof(int) * (size_t)nnz);
+        if (outElements) analysis_note_write(outElements->data, sizeof(double) * (size_t)nnz);
+        ok = MGCG_HIP(hipMemcpyAsync(outRowOffsets->data, T.offsets, sizeof(int) * ((size_t)columns + 1), hipMemcpyDeviceToDevice, s));
+        if (ok) launch_transpose_emit(s, nnz, T.keys, elementsVector ? elementsVector->data : nullptr, outColumnIndeces->data, outSource ? outSource->data : nullptr,
+                                      outElements ? outElements->data : nullptr);
+        ok = ok && MGCG_HIP(hipGetLastError());
+        ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    }
+    amg_free(T);
+    return ok ? nnz : -1;
 }
 
 MgcgMg* MgSetupAggregates(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,

@@ -413,10 +413,12 @@ MgcgMg* MgSetupAggregation(MgcgBlas* cublas, MgcgSparse* cusparse,
  *            row j of A in stored order; s_ij = 0.5 * acc.
  * Hence: the diagonal of a row that stores it once comes out exactly (0.5 * (a + a)); S is symmetric bit for bit when no row stores a
  * column twice (two addends: the sum commutes); a symmetric matrix with ascending unique columns gives itself, pattern and values.  Rows
- * may be unsorted, hold duplicates and be of any length.  The row offsets and columns are read on the host for the stable counting sort of
- * the entries by column (the transposition permutation: index bookkeeping, as in the set-up above); no matrix value travels to the host,
- * the values are gathered and summed on the device.  S is built in storage of the library's own (about 2 x elementsCount values and
- * 6 x elementsCount ints while it runs) and copied out at the end: on a refusal the output vectors are untouched.
+ * may be unsorted, hold duplicates and be of any length.  The offsets and columns are checked and the entries are ordered by column on the
+ * device (the transposition of MgcgCsrTranspose below, pattern and source list); no entry-sized array and no matrix value travels to the
+ * host -- two flags, the end of the offsets and, on a refusal, the one offending row do -- and the values are gathered and summed on the
+ * device.  S is built in storage of the library's own (about 2 x elementsCount values and 6 x elementsCount ints while it runs, the
+ * transposition's share of it freed before the sums are formed, and 3 x count ints) and copied out at the end: on a refusal the output
+ * vectors are untouched.
  * Returns -1 with MgcgGetLastError() on a refusal.  Refused before a device is asked for: a null handle (the three output vectors are
  * given together or not at all), count < 1, elementsCount < 0, 2 * elementsCount above INT_MAX, input vectors smaller than elementsCount
  * / count + 1, output vectors smaller than outCapacity / count + 1.  Refused once the arrays have been read: offsets that do not start
@@ -426,6 +428,33 @@ long long MgcgSymmetricPart(MgcgBlas* cublas, MgcgSparse* cusparse,
                             Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                             int elementsCount, int count,
                             Vector* outElements, VectorInt* outRowOffsets, VectorInt* outColumnIndeces, int outCapacity);
+/* A^T of a rows x columns CSR matrix, formed on the device into the caller's vectors (device vectors of the library, as the input).
+ * elementsVector NULL asks for the pattern alone (outElements is then NULL too; the two are given together or not at all).  Returns
+ * rowOffsets[rows], the stored entries of A^T.
+ * CONTRACT (no arithmetic, no atomics on values; two calls give identical arrays):
+ *   row c of A^T holds the stored entries of column c of A by ascending stored position k (k = the index into elementsVector /
+ *   columnIndecesVector: it ascends with the row of A and, inside one row, with the stored order -- so duplicates keep their order);
+ *   outSource[q] = k (outSource may be NULL); outColumnIndeces[q] = the row of A that stores k; outElements[q] = elements[k], a bit copy
+ *   (a NaN's payload and -0.0 survive); outRowOffsets holds columns + 1 offsets from 0.
+ * Rows of A may be unsorted, may be empty and may hold duplicates; the matrix may be rectangular; a column that nobody stores gives an
+ * empty row; entries of the input vectors beyond rowOffsets[rows] are ignored, entries of the output vectors beyond the result are left
+ * alone.  The call is synchronous.  While it runs it holds 2 x elementsCount + 2 x columns ints of device storage of its own, and one
+ * more for every column stored more than 32 times.  How: integer counts per column and their scan give the offsets; every entry claims
+ * a slot of its column's segment, and every segment is then sorted by k -- by one lane in registers up to *shortMax = 32 entries, by one
+ * workgroup in LDS up to *ldsMax = 4096, by one workgroup in global memory beyond that (slow, and correct for a column that every row
+ * stores); MgcgTransposeClassLimits reports the two boundaries.
+ * Returns -1 with MgcgGetLastError() on a refusal.  Refused before a device is asked for: a null handle, elementsVector and outElements
+ * not given together, rows < 1, columns < 1, elementsCount < 0, input vectors smaller than elementsCount / rows + 1, output vectors
+ * smaller than elementsCount / columns + 1.  Refused once the arrays have been read, with the outputs untouched: offsets that do not
+ * start at 0, descend ("row %lld: the row offsets descend": the smallest such row) or end beyond elementsCount, and a column outside
+ * [0, columns) ("row %lld stores column %d, the matrix has %lld columns": the smallest such row, its first such entry; the host reads
+ * that one row to name the column). */
+long long MgcgCsrTranspose(MgcgBlas* cublas, MgcgSparse* cusparse,
+                           Vector* elementsVector /* NULL: pattern only */, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                           int elementsCount, int rows, int columns,
+                           Vector* outElements /* NULL iff elementsVector is NULL */, VectorInt* outRowOffsets, VectorInt* outColumnIndeces,
+                           VectorInt* outSource /* may be NULL */);
+void      MgcgTransposeClassLimits(int* shortMax, int* ldsMax);           /* the longest column of the register class and of the LDS class (either may be NULL) */
 /* MgSetupAggregation with a choice of what the matching reads.  strength = 0: the level's own matrix -- MgSetupAggregation, which is this
  * call with 0, bit for bit.  strength = 1: the matching of every level l runs on S_l, the symmetric part (MgcgSymmetricPart's contract) of
  * the level's OWN matrix A_l: pass 1 on S_l, pass p > 1 on the unscaled Galerkin matrix of pass p - 1 built from S_l; S_l is then freed
