@@ -115,7 +115,7 @@ void preload_ops(); void preload_solver(); void preload_comm(); void preload_ker
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
 void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres(); void preload_kernels_pminres();
-void preload_kernels_bicgstab(); void preload_kernels_bicgstabl(); void preload_kernels_gmres();
+void preload_kernels_bicgstab(); void preload_kernels_bicgstabl(); void preload_kernels_gmres(); void preload_kernels_lsqr();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -250,6 +250,20 @@ struct GmresScalars {
     int fDone, note, cols, yCount;
 };
 
+// What the LSQR loop (MgcgSolveLsqr, kernels_lsqr.hip) keeps on the device.  alpha, beta: the norms of the unnormalised vectors vh and uh that the
+// body about to run finds; phibar, rhobar, psi2 (the damped residual's sum of psi^2), tr (theta / rho of the body before, for the deferred w
+// update): the rotation's state.  Only the start and the scalar launch write them, so no pass reads a field that a workgroup of the same
+// launch writes.  rot: what pass V's first workgroup leaves for the scalar launch.  fDone: CgScalars::done as pass U found it; pass V looks
+// here, since it raises `done` itself on a breakdown.  bb: b.b; note: what the start refused (0 nothing, 1 beta1, 2 alpha1, 3 g0^2); resNorm:
+// the estimate sqrt(phibar^2 + psi2) of the last judged body; red: the closing r.r and t.t.
+struct LsqrScalars {
+    double red[2];
+    double alpha, beta, phibar, rhobar, psi2, tr;
+    double bb, resNorm;
+    struct Rotation { double betan, rho, c, s, phibarn, psi2; } rot;
+    int fDone, note;
+};
+
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
@@ -291,6 +305,7 @@ struct Workspace {
     // sums -- one per column of the basis for v_i.w, then w.w (and every r.r of the loop)
     GmresScalars* gmresScalars = nullptr;
     double* gmresPartials = nullptr;
+    LsqrScalars* lsqrScalars = nullptr;          // LSQR (kernels_lsqr.hip), allocated at its first call and kept
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -305,6 +320,7 @@ struct Workspace {
     bool ensure_bicgstab();                      // bicgstabScalars (kernels_bicgstab.hip)
     bool ensure_bicgstabl();                     // bicgstablScalars / bicgstablPartials (kernels_bicgstabl.hip)
     bool ensure_gmres();                         // gmresScalars / gmresPartials (kernels_gmres.hip)
+    bool ensure_lsqr();                          // lsqrScalars (kernels_lsqr.hip)
 };
 
 } // namespace mgcg
@@ -818,6 +834,29 @@ void gmres_enqueue_restart(const GmresRun& R, const FinalizeArgs& f, int k, int 
 void gmres_enqueue_step(const GmresRun& R, const FinalizeArgs& f, int k, int j);
 // the close: y, and x += hat(sum y_i v_i) -- with Z: x += sum y_i z_i -- over the columns the cycle completed; does nothing when there are none
 void gmres_enqueue_close(const GmresRun& R);
+
+// LSQR (MgcgSolveLsqr; kernels_lsqr.hip has the loop, include/MgcgGpu.h the method), one rank.  uh (rows) and vh (columns): the two unnormalised
+// vectors of the bidiagonalisation; w, x: columns; q = A vh (rows); t = A^T uh (columns); b: rows.
+struct LsqrRun {
+    Workspace* ws;
+    double *x, *uh, *vh, *w, *q, *t; const double* b;
+    long long rows, columns; double damp;
+};
+double* lsqr_uu_partials(Workspace* ws);
+double* lsqr_vv_partials(Workspace* ws);
+// the start in front of t = A^T uh: x = 0, uh = b, beta1 = sqrt(b.b)
+void lsqr_enqueue_start_beta(const LsqrRun& R);
+// ... and behind it: vh = t * (1 / beta1), alpha1 = sqrt(vh.vh), g0 = alpha1 beta1 and the scalars in front of body 0; a beta1 or alpha1 that is
+// zero or not finite stops the loop here with MGCG_NONFINITE at iteration 0
+void lsqr_enqueue_start_alpha(const LsqrRun& R, const FinalizeArgs& f);
+// pass U of body k behind q = A vh; returns the number of partial sums of uh.uh it leaves (1 under dot_order = 1: one more launch)
+int lsqr_enqueue_u(const LsqrRun& R, int k);
+// pass V of body k behind t = A^T uh, and the scalar launch (under dot_order = 1 one more launch between them)
+void lsqr_enqueue_v(const LsqrRun& R, const FinalizeArgs& f, int k, int nUU);
+// the close: the partial sums of r.r of r = b - A x in uh -> lsqr_uu_partials; t = t - damp^2 x and those of t.t -> lsqr_vv_partials; each
+// returns their number (1 under dot_order = 1)
+int lsqr_enqueue_close_residual(const LsqrRun& R);
+int lsqr_enqueue_close_normal(const LsqrRun& R);
 
 // Chebyshev-preconditioned CG (SolveChebyshev*; kernels_cheb.hip has the method, solver.hip's cg_solve_chebyshev the loop).
 // The start: d = it * (dinv r), z = d, the partial sums of r.r and -- withRz, degree 1 -- of r.z; returns their number (1 under dot_order = 1).

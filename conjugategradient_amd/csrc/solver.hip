@@ -1440,6 +1440,84 @@ static int cg_solve_minres(CgRun& R, double* w1Vec, double* w2Vec, double shift,
                                   "the first residual is zero or not finite, or the rotation broke down (A - shift I singular on the Krylov space, or a value that is not finite)");
 }
 
+// ---------------------------------------------------------------- LSQR (MgcgSolveLsqr)
+// Paige and Saunders' LSQR for min || A x - b ||_2 (+ damp^2 || x ||^2), A any CSR matrix of rows x columns, one rank (include/MgcgGpu.h has the
+// method, kernels_lsqr.hip the passes).  The loop multiplies by two matrices of different shapes -- A, and A^T as the caller stored it -- so
+// each has a description of its own (LsqrMatrix: kernel configuration, far band, analysed form), set up as cg_matrix_setup and CsrMV's
+// rectangular path set one up; CgRun, which describes one square matrix, carries only what the host's side of the loop reads: the workspace
+// and the stop rule.  Both products are launch_spmv_auto, so compression modes and the automatic column tiles apply to each matrix.
+struct LsqrMatrix {
+    const double* elements; const int* rowOffsets; const int* columnIndeces;
+    int elementsCount, rows, columns;
+    SpmvConfig cfg; const DcsrMatrix* dcsr = nullptr;
+};
+static void lsqr_matrix_setup(MgcgSparse* h, LsqrMatrix& M)
+{
+    long long meanDistance = 0;
+    M.cfg = cfg_of(h);
+    if (M.elementsCount >= 8) M.cfg.periodRows = spmv_period(h, M.rowOffsets, M.columnIndeces, M.rows, 0, &M.cfg.maxRow, &meanDistance);
+    M.dcsr = dcsr_lookup(h, M.elements, M.rowOffsets, M.columnIndeces, M.rows, M.elementsCount, 0, M.columns, meanDistance);
+    if (meanDistance >= (1LL << 19) && M.columns >= (8LL << 19)) M.cfg.flags |= 16;     // gathers without locality: the stream form among the CSR kernels
+    M.cfg.flags |= 8;                            // as the plain CG loop: the row-tile kernel may read the matrix with the non-temporal hint
+}
+// y = M x (b null) or y = b - M x; gate: a device int, nonzero = the product writes nothing
+static void lsqr_enqueue_product(hipStream_t s, const LsqrMatrix& M, const double* x, double* y, const double* b, const int* gate)
+{
+    SpmvArgs a{};
+    a.elements = M.elements; a.rowOffsets = M.rowOffsets; a.columnIndeces = M.columnIndeces; a.x = x; a.y = y;
+    a.elementsCount = M.elementsCount; a.rowCount = M.rows; a.columnCount = M.columns;
+    a.alpha = 1.0; a.beta = 0.0; a.b = b; a.doneFlag = gate;
+    launch_spmv_auto(s, b ? EPI_RESIDUAL : EPI_AXPBY, a, M.cfg, M.dcsr);
+}
+
+static int lsqr_solve(CgRun& R, LsqrMatrix& A, LsqrMatrix& At, const LsqrRun& P, int* iteration, double* residual, double* residualNorm,
+                      double* trueResidual, double* trueNormalResidual, double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const char* who = "MgcgSolveLsqr";
+    // everything the call allocates, before anything is enqueued
+    FinalizeArgs f = cg_finalize_args(R, true, 0);
+    if (!ws->ensure_lsqr() || !cg_trace_columns(ws, 1, residualTrace, traceCapacity, f)) return MGCG_ERROR;
+    lsqr_matrix_setup(R.cusparse, A);
+    lsqr_matrix_setup(R.cusparse, At);
+    const int* done = &ws->scalars->done;
+
+    // start: x = 0, uh = b, beta1 ; t = A^T uh ; vh = t / beta1, alpha1, g0
+    lsqr_enqueue_start_beta(P);
+    lsqr_enqueue_product(s, At, P.uh, P.t, nullptr, nullptr);
+    lsqr_enqueue_start_alpha(P, f);
+    bool ok = MGCG_HIP(hipGetLastError());
+
+    ok = ok && cg_drive_bodies(R, who, [&](int k) {
+        lsqr_enqueue_product(s, A, P.vh, P.q, nullptr, done);                            // q = A vh
+        const int nUU = lsqr_enqueue_u(P, k);                                            // uh ; uh.uh
+        lsqr_enqueue_product(s, At, P.uh, P.t, nullptr, done);                           // t = A^T uh
+        lsqr_enqueue_v(P, f, k, nUU);                                                    // w ; x ; vh ; vh.vh ; the scalars
+        return true;
+    });
+    // the two closing products: r = b - A x over uh, t = A^T r - damp^2 x over t, and their 2-norms
+    LsqrScalars h{};
+    if (ok) {
+        lsqr_enqueue_product(s, A, P.x, P.uh, P.b, nullptr);
+        const int nR = lsqr_enqueue_close_residual(P);
+        lsqr_enqueue_product(s, At, P.uh, P.t, nullptr, nullptr);
+        const int nT = lsqr_enqueue_close_normal(P);
+        launch_reduce2_to(s, lsqr_uu_partials(ws), nR, &ws->lsqrScalars->red[0], lsqr_vv_partials(ws), nT, &ws->lsqrScalars->red[1], nullptr);
+        ok = MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(&h, ws->lsqrScalars, sizeof(h), hipMemcpyDeviceToHost, s));
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    if (!ok) return MGCG_ERROR;
+    if (residualNorm) *residualNorm = h.resNorm;
+    if (trueResidual) *trueResidual = std::sqrt(h.red[0]);
+    if (trueNormalResidual) *trueNormalResidual = std::sqrt(h.red[1]);
+    const char* nonfinite = h.note == 1 ? "beta_1 = || b || is zero or not finite"
+                          : h.note == 2 ? "alpha_1 = || A^T b || / beta_1 is zero or not finite (a nonzero b is orthogonal to the range of A)"
+                          : h.note == 3 ? "g_0 = alpha_1 beta_1 has a square that is zero or not finite"
+                          : "a scalar of the bidiagonalisation or of the rotation is not finite";
+    return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "normal residual", "", nonfinite);
+}
+
 // ---------------------------------------------------------------- BiCGStab (SolveBicgstab*, SolveBicgstabJacobi*)
 // Van der Vorst's BiCGStab for A x = b, A any CSR matrix, right-preconditioned with M = I or M = diag(A) (R.dinv) (include/MgcgGpu.h has the
 // method, kernels_bicgstab.hip the passes).  The host's side is cg_drive: a body is two products and four passes (six launches), on several ranks
@@ -3453,6 +3531,49 @@ int SolveMinres(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
     return SolveMinresParallel(nullptr, cublas, cusparse, matDescr, elementsVector, rowOffsetsVector, columnIndecesVector,
                                xVector, bVector, ApVector, pVector, rVector, w1Vector, w2Vector, count, count, 0, elementsCount, 0, count - 1, shift,
                                allowableResidual, minIteration, maxIteration, rule, iteration, residual, trueResidual, residualTrace, traceCapacity);
+}
+
+// LSQR (lsqr_solve above), one rank.  The shapes differ from every other export's, so the refusals are worded here: what needs no device is
+// refused before one is asked for, and nothing is enqueued for a call that fails.
+int MgcgSolveLsqr(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+              Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+              Vector* elementsTVector, VectorInt* rowOffsetsTVector, VectorInt* columnIndecesTVector,
+              Vector* xVector, Vector* bVector, Vector* uVector, Vector* vVector, Vector* wVector, Vector* qVector, Vector* tVector,
+              int elementsCount, int rows, int columns, double damp,
+              double allowableResidual, int minIteration, int maxIteration, int rule,
+              int* iteration, double* residual, double* residualNorm, double* trueResidual, double* trueNormalResidual,
+              double* residualTrace, int traceCapacity)
+{
+    (void)matDescr;
+    const char* who = "MgcgSolveLsqr";
+    if (!cublas || !cusparse) { set_error("%s: null handle", who); return MGCG_ERROR; }
+    if (!elementsVector || !rowOffsetsVector || !columnIndecesVector || !elementsTVector || !rowOffsetsTVector || !columnIndecesTVector ||
+        !xVector || !bVector || !uVector || !vVector || !wVector || !qVector || !tVector) { set_error("%s: null vector handle", who); return MGCG_ERROR; }
+    if (rows < 1 || columns < 1 || elementsCount < 0) { set_error("%s: bad sizes (rows %d, columns %d, elementsCount %d)", who, rows, columns, elementsCount); return MGCG_ERROR; }
+    if (!(damp >= 0.0 && damp <= 1.79e308)) { set_error("%s: damp is negative or not finite", who); return MGCG_ERROR; }
+    if (cg_rule_refused(who, rule, "the recurrence carries no max-norm of A^T r")) return MGCG_ERROR;
+    if (residualTrace && traceCapacity > 0x7ffffff0) { set_error("%s: trace capacity too large", who); return MGCG_ERROR; }
+    auto matrix_short = [&](const char* name, const Vector* e, const VectorInt* ro, const VectorInt* ci, int nRows) {
+        if (e->size >= elementsCount && ci->size >= elementsCount && ro->size >= (long long)nRows + 1) return false;
+        set_error("%s: a vector of %s is smaller than the matrix (%d stored entries, %d rows)", who, name, elementsCount, nRows);
+        return true;
+    };
+    if (matrix_short("A", elementsVector, rowOffsetsVector, columnIndecesVector, rows) ||
+        matrix_short("A^T", elementsTVector, rowOffsetsTVector, columnIndecesTVector, columns)) return MGCG_ERROR;
+    if (cg_vector_short(who, "x", xVector, columns, "columns") || cg_vector_short(who, "b", bVector, rows, "rows") ||
+        cg_vector_short(who, "u", uVector, rows, "rows") || cg_vector_short(who, "v", vVector, columns, "columns") ||
+        cg_vector_short(who, "w", wVector, columns, "columns") || cg_vector_short(who, "q", qVector, rows, "rows") ||
+        cg_vector_short(who, "t", tVector, columns, "columns")) return MGCG_ERROR;
+    if (!device_state()) return MGCG_ERROR;
+    CgRun R;
+    R.ws = &cublas->ws; R.cusparse = cusparse; R.nLocal = rows; R.count = columns;
+    cg_set_stop(R, allowableResidual, minIteration, maxIteration, rule);
+    LsqrMatrix A = { elementsVector->data, rowOffsetsVector->data, columnIndecesVector->data, elementsCount, rows, columns };
+    LsqrMatrix At = { elementsTVector->data, rowOffsetsTVector->data, columnIndecesTVector->data, elementsCount, columns, rows };
+    const LsqrRun P = { R.ws, xVector->data, uVector->data, vVector->data, wVector->data, qVector->data, tVector->data, bVector->data, rows, columns, damp };
+    cg_note_written({ P.uh, P.q }, rows);
+    cg_note_written({ P.x, P.vh, P.w, P.t }, columns);
+    return lsqr_solve(R, A, At, P, iteration, residual, residualNorm, trueResidual, trueNormalResidual, residualTrace, traceCapacity);
 }
 
 // BiCGStab (cg_solve_bicgstab above; refusals: cg_variant_call).  With `jacobi` dinvVector is a handle the export requires, with `vcycle`

@@ -290,6 +290,55 @@ def random_nonsymmetric(n: int, per_row: int = 9, seed: int = 12345) -> LinearSy
                         np.zeros(n), b, f"random_nonsymmetric{n}")
 
 
+@dataclass
+class LeastSquaresSystem:
+    """A (Rows x Columns, CSR) and b (Rows entries) of a least-squares problem min || A x - b ||_2 (``lsqr.LeastSquaresGpu.load``)."""
+
+    Elements: np.ndarray        # float64[nnz]
+    ColumnIndeces: np.ndarray   # int32[nnz]
+    RowOffsets: np.ndarray      # int32[Rows+1]
+    b: np.ndarray               # float64[Rows]
+    Columns: int
+    name: str = ""
+
+    @property
+    def Rows(self) -> int:
+        return int(self.RowOffsets.shape[0]) - 1
+
+    @property
+    def nnz(self) -> int:
+        return int(self.RowOffsets[-1])
+
+    def to_scipy(self):
+        import scipy.sparse as sp
+
+        return sp.csr_matrix((self.Elements[: self.nnz], self.ColumnIndeces[: self.nnz], self.RowOffsets), shape=(self.Rows, self.Columns))
+
+
+def least_squares(system, columns: int, b=None, name: str | None = None) -> LeastSquaresSystem:
+    """The CSR arrays of anything that has ``Elements``, ``ColumnIndeces`` and ``RowOffsets`` as a rows x ``columns`` least-squares
+    problem with right-hand side ``b`` (default: the system's own)."""
+    ro = np.ascontiguousarray(system.RowOffsets, dtype=np.int32)
+    nnz = int(ro[-1])
+    rhs = np.array(system.b if b is None else b, dtype=np.float64)
+    if rhs.shape[0] != ro.shape[0] - 1:
+        raise ValueError(f"b holds {rhs.shape[0]} entries, the matrix has {ro.shape[0] - 1} rows")
+    return LeastSquaresSystem(np.ascontiguousarray(system.Elements[:nnz], dtype=np.float64), np.ascontiguousarray(system.ColumnIndeces[:nnz], dtype=np.int32),
+                              ro, rhs, int(columns), getattr(system, "name", "") if name is None else name)
+
+
+def sparse_rectangular(rows: int, columns: int, per_row: int = 8, seed: int = 12345) -> LeastSquaresSystem:
+    """A random sparse rows x columns matrix for least squares: every row stores min(per_row, columns) draws with columns uniform over
+    [0, columns) in ascending order (a column drawn twice in a row is stored twice: the product adds both) and values N(0,1); b = N(0,1),
+    in general not in the range of A.  Vectorised: 4 M x 1 M with 8 per row takes seconds."""
+    rng = np.random.default_rng(seed)
+    k = min(int(per_row), int(columns))
+    c = np.sort(rng.integers(0, columns, size=(rows, k), dtype=np.int32), axis=1)
+    e = rng.standard_normal(rows * k)
+    ro = (np.arange(rows + 1, dtype=np.int64) * k).astype(np.int32)
+    return LeastSquaresSystem(e, np.ascontiguousarray(c.reshape(-1)), ro, rng.standard_normal(rows), int(columns), f"sparse_rect{rows}x{columns}x{k}")
+
+
 def partition_offsets(count: int, device_count: int, row_offsets=None, balance: str = "rows") -> list[int]:
     """Row-range partition of Mgcg/cuBlas/Mgcg/ConjugateGradientParallelGpu.cs:271-277:
     floor(count/device_count) rows each, the last device takes the remainder.

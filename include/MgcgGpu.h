@@ -1146,6 +1146,80 @@ int SolveGmresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
                  double allowableResidual, int minIteration, int maxIteration, int rule,
                  int* iteration, double* residual, double* trueResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
+/* ---- LSQR: least squares min || A x - b ||_2 for a rectangular CSR matrix, optionally damped (one rank) ---- */
+/* Paige and Saunders' LSQR.  A is any CSR matrix of rows x columns -- more rows than columns or fewer, square and nonsymmetric, rank
+ * deficient -- and b any right-hand side, consistent or not.  The call minimises || A x - b ||^2 + damp^2 || x ||^2 (damp >= 0; 0: plain least
+ * squares) and, where the minimiser is not unique, tends to the one of minimum norm.  It is analytically CG on the normal equations
+ * (A^T A + damp^2 I) x = A^T b without ever forming A^T A; it converges on that spectrum, so on a square system that BiCGStab or GMRES solve
+ * it is the slower method, and it is the one that still works where those are undefined.
+ * The caller hands in TWO CSR triples: A, and A^T (columns x rows) exactly as MgcgCsrTranspose writes it.  THE LIBRARY DOES NOT VERIFY THAT
+ * THE SECOND IS THE TRANSPOSE OF THE FIRST.  The transposed product is therefore the ordinary gather product on A^T: deterministic, no
+ * float atomics, row c of A^T summed in ascending stored position of A.  Both products are CsrMV's (rectangular operands; compression modes
+ * and the automatic column tiles apply to each matrix by itself).
+ * Method (the bidiagonalisation u_k, v_k with || u || = || v || = 1; lambda = damp):
+ *   start   x := 0 under EVERY rule (the caller's x is overwritten: callers with a guess x0 pass b - A x0 and add x0 back)
+ *           beta_1 = || b || ; u_1 = b/beta_1 ; alpha_1 = || A^T u_1 || ; v_1 = A^T u_1/alpha_1 ; w_1 = v_1 ; phibar_1 = beta_1 ; rhobar_1 = alpha_1 ;
+ *           g_0 = alpha_1 beta_1 ; Psi = 0
+ *   body k  beta_k+1 u_k+1 = A v_k - alpha_k u_k ;  alpha_k+1 v_k+1 = A^T u_k+1 - beta_k+1 v_k
+ *           damp != 0: rhobar' = sqrt(rhobar^2 + lambda^2) ; psi = (lambda/rhobar') phibar ; phibar = (rhobar/rhobar') phibar ; Psi += psi^2 ; rhobar = rhobar'
+ *           rho = sqrt(rhobar^2 + beta_k+1^2) ; c = rhobar/rho ; s = beta_k+1/rho ; theta = s alpha_k+1 ; rhobar = -c alpha_k+1 ; phi = c phibar ; phibar = s phibar
+ *           x += (phi/rho) w ;  w = v_k+1 - (theta/rho) w
+ *           judged: g = |phibar| alpha_k+1 |c|, the estimate of || A^T (b - A x) - lambda^2 x ||_2 ; kept: sqrt(phibar^2 + Psi), the estimate of
+ *           the (damped) residual norm
+ * As computed -- the vectors stay UNNORMALISED in memory, uh = beta u (rows) and vh = alpha v (columns), and the w update of body k is done
+ * by body k + 1 (its theta needs alpha_k+1, which is known only behind the pass that writes x); k counts from 0 here:
+ *   start   x = 0 ; uh = b ; bb = b.b ; beta = sqrt(bb) ; t = A^T uh ; vh_j = t_j*(1/beta) ; vv = vh.vh ; alpha = sqrt(vv) ; g0 = alpha*beta ;
+ *           gg0 = g0*g0 ; phibar = beta ; rhobar = alpha ; Psi = 0 ; trace[0] = g0 (sqrt(gg0/gg0) under MGCG_RULE_VIENNACL)
+ *           bb zero or not finite  ->  MGCG_NONFINITE at iteration 0 with g0 := beta ; else vv, else gg0 zero or not finite  ->  the same (the
+ *           message says which: "beta_1 = || b ||", "alpha_1 = || A^T b || / beta_1", "g_0")
+ *   body k  q = A vh
+ *   pass U  ia = 1/alpha ; ab = alpha/beta ;  uh_i = q_i*ia - ab*uh_i ;  uu = uh.uh                                            (24 bytes per row)
+ *   t = A^T uh
+ *   pass V  betan = sqrt(uu)
+ *           damp != 0: rd = sqrt(rhobar*rhobar + damp*damp) ; psi = (damp/rd)*phibar ; phibar = (rhobar/rd)*phibar ; Psi = Psi + psi*psi ; rhobar = rd
+ *           rho = sqrt(rhobar*rhobar + betan*betan) ; c = rhobar/rho ; s = betan/rho ; phi = c*phibar ; phibarn = s*phibar ; xs = phi/rho
+ *           betan, rho, xs, phibarn or Psi not finite, or rho == 0  ->  MGCG_NONFINITE reported for iteration k + 1, nothing changed by this body
+ *           vn_j = vh_j*ia ;  w_j = vn_j - tr*w_j  (k = 0: w_j = vn_j, w is not read) ;  x_j = x_j + xs*w_j
+ *           vh_j = t_j*(1/betan) - betan*vn_j ;  vv = vh.vh        (betan == 0: vh is not formed)                         (56 bytes per column)
+ *   scalars alphan = sqrt(vv) (0 when betan == 0) ; theta = s*alphan ; rhobar = -(c*alphan) ; tr = theta/rho ; g = (|phibarn|*alphan)*|c| ;
+ *           gg = g*g ; the estimate sqrt(phibarn*phibarn + Psi) ; gg is judged by the rule's stop test against gg0 as iteration k + 1
+ *           g == 0 (betan or alphan exactly zero): x is the solution -- the loop ends here with MGCG_OK, whatever minIteration says
+ *           alphan or g not finite  ->  MGCG_NONFINITE for iteration k + 1; x is this body's, every scalar of whose update was finite
+ *           alpha = alphan ; beta = betan ; phibar = phibarn
+ *   end     two closing products, whenever the loop ended without MGCG_ERROR: uVector = b - A x ; tVector = A^T uVector, and with damp != 0
+ *           t_j = t_j - (damp*damp)*x_j ;  *trueResidual = sqrt(u.u) ;  *trueNormalResidual = sqrt(t.t)
+ * Rounding contract: every product and every quotient goes into a double of its own before the add or subtraction that follows it, nothing
+ * is fused; 1/alpha, 1/beta, 1/betan, alpha/beta and phi/rho are formed once and multiplied; every square root is sqrt of two separately
+ * rounded squares and their sum, never hypot; a matrix row is summed as CsrMV sums it; the terms of the sums are b_i*b_i, vh_j*vh_j, uh_i*uh_i,
+ * u_i*u_i and t_j*t_j of the rounded values.  Under dot_order = 1 every sum is serial left to right and the whole loop is a fixed sequence of
+ * IEEE operations (tests/test_lsqr_host.py restates it in numpy).
+ * Stop: the four 2-norm rules of SolveEx on (gg, gg0), exactly as SolveMinres applies them to (rr, rr0); MGCG_RULE_HANDMADECL is refused.
+ * g is judged because it tends to zero for consistent and inconsistent systems alike; || b - A x || does not.  *iteration, *residual and the
+ * trace show sqrt(gg) (g itself unless g*g underflows; sqrt(gg/gg0) in the trace under MGCG_RULE_VIENNACL); *residualNorm (may be NULL) the
+ * estimate of the residual norm at the last judged body (beta_1 at iteration 0); *trueResidual and *trueNormalResidual (may be NULL) the
+ * closing products' figures.  A breakdown repeats the last judged figure in *residual and its trace entry.
+ * One body is five launches with two reduction points: the two products, the two passes above and one single-workgroup launch for the
+ * scalars behind pass V.  Vector traffic per body: 24 bytes per row + 56 per column, next to the two products (each reads its matrix once,
+ * gathers one vector and writes the other).
+ *   xVector (columns)  the result; bVector (rows) is only read
+ *   uVector (rows)     uh during the loop; on return b - A x
+ *   tVector (columns)  A^T uh during the loop; on return A^T (b - A x) - damp^2 x
+ *   vVector, wVector (columns), qVector (rows)   work space: vh, w, q.  No work vector and no x is read before the call has written it.
+ * Refused with MGCG_ERROR, a message and nothing enqueued, before a device is asked for: a null handle; rows < 1, columns < 1 or
+ * elementsCount < 0 ("bad sizes"); a vector of A or of A^T smaller than elementsCount / rows + 1 / columns + 1; a vector too small for its role
+ * ("the x vector holds .. entries, the matrix has .. columns": x, v, w, t by columns; b, u, q by rows); damp negative or not finite; an unknown
+ * rule or MGCG_RULE_HANDMADECL.
+ * Out of scope: several ranks (a row partition of A makes A^T u a sum across ranks), preconditioning, LSMR, an initial guess, fusing the
+ * passes into the products' epilogues, the C++ twin under host/. */
+int MgcgSolveLsqr(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+              Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,        /* A: rows x columns */
+              Vector* elementsTVector, VectorInt* rowOffsetsTVector, VectorInt* columnIndecesTVector,     /* A^T: columns x rows (MgcgCsrTranspose) */
+              Vector* xVector, Vector* bVector, Vector* uVector, Vector* vVector, Vector* wVector, Vector* qVector, Vector* tVector,
+              int elementsCount, int rows, int columns, double damp,
+              double allowableResidual, int minIteration, int maxIteration, int rule,
+              int* iteration, double* residual, double* residualNorm /* may be NULL */, double* trueResidual /* may be NULL */,
+              double* trueNormalResidual /* may be NULL */, double* residualTrace, int traceCapacity);
+
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
  * MgcgJacobiSetup wrote) is given: Gershgorin's upper bound of the spectrum of A (of D^-1 A), rigorous, usually within a small factor
