@@ -83,6 +83,7 @@ SIGNATURES = {
     "Xpay": (None, [_vp, _vp, _vp, _i, _d]),
     "NrmInf": (_d, [_vp, _vp, _i]),
     "CsrMVDot": (_d, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i]),
+    "MgcgCsrMVEpilogue": (_d, [_vp, _vp, _vp]),       # (blas, sparse, MgcgEpilogueArgs*)
     "MgcgSetSpmvKernel": (None, [_vp, _i]),
     "MgcgSetSpmvTuning": (None, [_vp, _i, _i, _i]),
     "MgcgSetSpmvPeriod": (None, [_vp, _i]),
@@ -181,6 +182,15 @@ SHIFT_MAX_K = 8      # shifts of one SolveShifted call
 # MgcgSetMatrixCompression modes: off; the best lossless form (row patterns, per-nonzero codes, column tiles); per-nonzero codes only;
 # as the best form, with the propagation-blocking form (class 5) before the column tiles for matrices without locality
 COMPRESSION_OFF, COMPRESSION_BEST, COMPRESSION_CODES, COMPRESSION_PB = range(4)
+# MgcgCsrMVEpilogue: the solver epilogues' ids (MGCG_EPI_*) and its argument block, field for field as include/MgcgGpu.h declares it
+EPI_RESIDUAL, EPI_JACOBI, EPI_RESIDUAL_DOT, EPI_JACOBI_DOT, EPI_CHEBYSHEV, EPI_CHEBYSHEV_DOT = 2, 3, 4, 6, 7, 8
+
+
+class EpilogueArgs(C.Structure):
+    _fields_ = [("epilogue", _i), ("elementsCount", _i), ("rowCount", _i), ("columnCount", _i),
+                ("y", _vp), ("elements", _vp), ("rowOffsets", _vp), ("columnIndeces", _vp), ("x", _vp), ("b", _vp), ("xo", _vp),
+                ("dinv", _vp), ("dinvScalar", _d), ("omega", _d), ("d", _vp), ("c1", _d), ("c2", _d), ("xInner", _d), ("xOuter", _d),
+                ("rowBegin", _i), ("rowEnd", _i), ("gapBegin", _i), ("gapEnd", _i), ("done", _vp)]
 
 _LIB = None
 

@@ -350,6 +350,7 @@ int launch_spmv_pb(hipStream_t s, int epilogue, const SpmvArgs& a, const DcsrVie
     case EPI_JACOBI:       return launch_pb_epi<EPI_JACOBI>(s, a, m);
     case EPI_JACOBI_DOT:   return launch_pb_epi<EPI_JACOBI_DOT>(s, a, m);
     }
+    set_error("propagation-blocking SpMV: epilogue %d is not implemented (the Chebyshev step multiplies through the CSR kernels)", epilogue);   // never a silent no-op
     return 0;
 }
 

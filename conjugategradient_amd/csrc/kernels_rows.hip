@@ -403,6 +403,7 @@ static int launch_spmv_pattern(hipStream_t s, int epilogue, const SpmvArgs& a, c
     case EPI_JACOBI:       return launch_pattern_epi<EPI_JACOBI>(s, a, m, gridReq, periodRows);
     case EPI_JACOBI_DOT:   return launch_pattern_epi<EPI_JACOBI_DOT>(s, a, m, gridReq, periodRows);
     }
+    set_error("row-pattern SpMV: epilogue %d is not implemented (the Chebyshev step multiplies through the CSR kernels)", epilogue);   // never a silent no-op
     return 0;
 }
 

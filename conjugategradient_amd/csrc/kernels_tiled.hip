@@ -326,6 +326,7 @@ int launch_spmv_tiled(hipStream_t s, int epilogue, const SpmvArgs& a, const Dcsr
     case EPI_JACOBI:       return launch_tiled_epi<EPI_JACOBI>(s, a, m);
     case EPI_JACOBI_DOT:   return launch_tiled_epi<EPI_JACOBI_DOT>(s, a, m);
     }
+    set_error("column-tiled SpMV: epilogue %d is not implemented (the Chebyshev step multiplies through the CSR kernels)", epilogue);   // never a silent no-op
     return 0;
 }
 

@@ -86,6 +86,66 @@ double CsrMVDot(MgcgBlas* cublas, MgcgSparse* cusparse, double* y,
     return finish_reduction(cublas->ws, n, 0);
 }
 
+static_assert(MGCG_EPI_RESIDUAL == EPI_RESIDUAL && MGCG_EPI_JACOBI == EPI_JACOBI && MGCG_EPI_RESIDUAL_DOT == EPI_RESIDUAL_DOT && MGCG_EPI_JACOBI_DOT == EPI_JACOBI_DOT &&
+              MGCG_EPI_CHEBYSHEV == EPI_CHEBYSHEV && MGCG_EPI_CHEBYSHEV_DOT == EPI_CHEBYSHEV_DOT, "include/MgcgGpu.h names the epilogues by the library's own ids");
+
+// One solver-only epilogue by the solvers' routes (the header states the contract): whole matrix = launch_spmv_auto on the handle's form,
+// a row range = launch_spmv_range, a gap = launch_spmv_two_ranges, Chebyshev = launch_spmv on plain CSR (cheb_enqueue_steps, solver.hip).
+double MgcgCsrMVEpilogue(MgcgBlas* cublas, MgcgSparse* cusparse, const MgcgEpilogueArgs* p)
+{
+    NEED_DEVICE(NAN);
+    if (!cublas || !cusparse || !p) { set_error("MgcgCsrMVEpilogue: null argument"); return NAN; }
+    const int epi = p->epilogue;
+    const bool residual = epi == EPI_RESIDUAL || epi == EPI_RESIDUAL_DOT, jacobi = epi_is_jacobi(epi), cheb = epi_is_chebyshev(epi);
+    if (!residual && !jacobi && !cheb) { set_error("MgcgCsrMVEpilogue: epilogue %d is none of the six solver epilogues", epi); return NAN; }
+    if (p->rowCount < 0 || p->elementsCount < 0 || p->columnCount < 0) { set_error("MgcgCsrMVEpilogue: negative size"); return NAN; }
+    if (!p->y || !p->rowOffsets || !p->x || !p->b || (p->elementsCount > 0 && (!p->elements || !p->columnIndeces)) || (!residual && !p->xo) || (cheb && !p->d)) {
+        set_error("MgcgCsrMVEpilogue: null operand"); return NAN;
+    }
+    const long long n = p->rowCount;
+    const bool ranged = p->rowEnd != 0 || p->rowBegin != 0, gapped = p->gapEnd != 0 || p->gapBegin != 0;
+    if ((ranged && (p->rowBegin < 0 || p->rowBegin >= p->rowEnd || p->rowEnd > n)) || (gapped && (p->gapBegin < 0 || p->gapBegin >= p->gapEnd || p->gapEnd > n)) || (ranged && gapped)) {
+        set_error("MgcgCsrMVEpilogue: bad row selection (range [%d, %d), gap [%d, %d), %lld rows)", p->rowBegin, p->rowEnd, p->gapBegin, p->gapEnd, n); return NAN;
+    }
+    if (cheb && (ranged || gapped)) { set_error("MgcgCsrMVEpilogue: the Chebyshev epilogues take whole matrices only"); return NAN; }
+    const bool scaled = p->xOuter != 0.0;
+    if (scaled && epi != EPI_RESIDUAL) { set_error("MgcgCsrMVEpilogue: a scaled x (xOuter != 0) goes with MGCG_EPI_RESIDUAL only"); return NAN; }
+    auto overlaps = [&](const double* q, long long len) { return q != nullptr && q < p->y + n && p->y < q + len; };
+    if (overlaps(p->b, n) || overlaps(p->xo, n) || overlaps(p->x, p->columnCount) || overlaps(p->d, n)) { set_error("MgcgCsrMVEpilogue: y overlaps an operand"); return NAN; }
+    if (n == 0) return 0.0;
+    SpmvArgs a{};
+    a.elements = p->elements; a.rowOffsets = p->rowOffsets; a.columnIndeces = p->columnIndeces; a.x = p->x; a.y = p->y;
+    a.elementsCount = p->elementsCount; a.rowCount = p->rowCount; a.columnCount = p->columnCount;
+    a.b = p->b; a.w = p->xo; a.dinv = p->dinv; a.dinvUniform = p->dinv ? 0 : 1; a.dinvScalar = p->dinvScalar; a.omega = p->omega;
+    a.d = p->d; a.c1 = p->c1; a.c2 = p->c2; a.doneFlag = p->done; a.partials = cublas->ws.partials;
+    if (scaled) { a.xScaled = 1; a.xInner = p->xInner; a.xOuter = p->xOuter; }
+    const SpmvConfig cfg = cfg_for(cusparse, a, 0);
+    const DcsrMatrix* dc = cheb ? nullptr : dcsr_lookup_op(cusparse, a, 0);
+    if (scaled) {                                   // (mg_vcycle's canScale: the only kernels that form xOuter * (xInner * x[col]) per gather)
+        const bool form = dc != nullptr && dc->usable && a.elementsCount >= 8;
+        if (form ? dc->patternId == nullptr : !spmv_takes_rowtile(a, cfg)) { set_error("MgcgCsrMVEpilogue: neither the row-tile kernel nor the row-pattern form serves this matrix: x cannot be scaled per gather"); return NAN; }
+    }
+    analysis_note_write(p->y, sizeof(double) * (size_t)n);
+    if (cheb) analysis_note_write(p->d, sizeof(double) * (size_t)n);
+    hipStream_t s = cublas->ws.stream;
+    double* partials = cublas->ws.partials;
+    int nP;
+    if (cheb) nP = launch_spmv(s, epi, a, cfg);
+    else if (ranged) nP = launch_spmv_range(s, epi, a, cfg, dc, p->rowBegin, p->rowEnd, partials, kMaxPartials);
+    else if (gapped) nP = launch_spmv_two_ranges(s, epi, a, cfg, dc, p->gapBegin, p->gapEnd, partials, kMaxPartials);
+    else nP = launch_spmv_auto(s, epi, a, cfg, dc);
+    if (!epi_has_dot(epi)) { (void)MGCG_HIP(hipGetLastError()); return 0.0; }
+    if (dot_reference_order()) {                    // as CsrMVDot: the sum once more, serially, over the rows the pass wrote
+        const double* u = residual ? p->y : p->b;
+        const long long r0 = ranged ? p->rowBegin : 0, r1 = ranged ? p->rowEnd : gapped ? p->gapBegin : n;
+        nP = 0;
+        if (r1 > r0) launch_dot_serial(s, u + r0, p->y + r0, r1 - r0, partials + nP++, p->done);
+        if (gapped && p->gapEnd < n) launch_dot_serial(s, u + p->gapEnd, p->y + p->gapEnd, n - p->gapEnd, partials + nP++, p->done);
+    }
+    if (nP <= 0) return 0.0;
+    return finish_reduction(cublas->ws, nP, 0);
+}
+
 void Axpy(MgcgBlas* cublas, double* y, const double* x, int count, double alpha)
 {
     NEED_DEVICE();

@@ -403,6 +403,7 @@ int launch_spmv_range(hipStream_t s, int epilogue, const SpmvArgs& whole, const 
     if (a.w) a.w += r0;
     if (a.b) a.b += r0;
     if (a.dinv) a.dinv += r0;
+    if (a.d) a.d += r0;                                  // (the Chebyshev step's increment is indexed by row like y)
     const bool compressed = dc != nullptr && dc->usable && whole.elementsCount >= 8;
     SpmvConfig c = cfg;
     c.flags &= ~6;                                       // the XCD / banded maps assume the whole matrix

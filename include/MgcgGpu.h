@@ -235,6 +235,54 @@ double CsrMVDot(MgcgBlas* cublas, MgcgSparse* cusparse,
                 double* y, const double* elements, const int* rowOffsets, const int* columnIndeces,
                 const double* x, const double* w,
                 int elementsCount, int rowCount, int columnCount);
+/* One fused pass of the kind the solvers run: the product A x with one of the six solver-only epilogues, on raw device pointers,
+ * by the route the solvers take -- the handle's kernel id, tuning, period and matrix form (MgcgSetSpmvKernel, MgcgSetSpmvTuning,
+ * MgcgSetSpmvPeriod, MgcgSetMatrixCompression) apply as they do to CsrMV.  acc_i is row i's sum in the order of the kernel or form
+ * that serves the product (MgcgSetSpmvKernel); every product and sum below is rounded on its own, in the order written:
+ *   MGCG_EPI_RESIDUAL       y_i = b_i - acc_i
+ *   MGCG_EPI_RESIDUAL_DOT   the same, and the call returns sum_i y_i * y_i
+ *   MGCG_EPI_JACOBI         y_i = xo_i + omega * (dinv_i * (b_i - acc_i))
+ *   MGCG_EPI_JACOBI_DOT     the same, and the call returns sum_i b_i * y_i
+ *   MGCG_EPI_CHEBYSHEV      d_i = c1 * d_i + c2 * (dinv_i * (b_i - acc_i)) ; y_i = xo_i + d_i   (d is read and rewritten)
+ *   MGCG_EPI_CHEBYSHEV_DOT  the same, and the call returns sum_i b_i * y_i
+ * dinv == NULL: every dinv_i is dinvScalar and no array is read.  xOuter != 0 (MGCG_EPI_RESIDUAL only): the multiplied vector is
+ * xOuter * (xInner * x[col]), formed per gather -- served by the row-tile kernel (10) and by the row-pattern form (class 3) alone.
+ * Rows: rowEnd == 0 and gapEnd == 0, the whole matrix; rowEnd > 0, rows [rowBegin, rowEnd) only; gapEnd > 0, every row but those
+ * of [gapBegin, gapEnd) -- one launch of the row-tile kernel when both cuts are multiples of 256, two launches otherwise.  Rows
+ * outside the selection are not written, and the returned sum runs over the selected rows.  The arrays always describe the whole
+ * matrix: y, b, xo, dinv and d are indexed by row, x by column.  The Chebyshev epilogues multiply through the plain CSR kernels
+ * whatever form the handle holds, and take whole matrices only.
+ * done (may be NULL): a device int; when it is nonzero the pass writes nothing (and the returned value means nothing).
+ * The returned sum (0.0 for the epilogues without one) is added up per workgroup and then over the workgroups, each in a fixed
+ * order; under the knob dot_order = 1 it is formed again as CsrMVDot forms its own: one serial sum, left to right, over the selected
+ * rows -- with a gap, the serial sum of the rows in front of the gap plus the serial sum of those behind it.
+ * Refused (MgcgGetLastError, NaN returned, nothing launched): an epilogue outside the six; a null operand the epilogue reads; a
+ * row range or gap outside the matrix, both at once, or either with a Chebyshev epilogue; xOuter != 0 with another epilogue
+ * than MGCG_EPI_RESIDUAL, or where neither the row-tile kernel nor the row-pattern form serves the matrix; y overlapping b, xo,
+ * x or d (the column-tiled and propagation-blocking forms accumulate in y). */
+#define MGCG_EPI_RESIDUAL      2
+#define MGCG_EPI_JACOBI        3
+#define MGCG_EPI_RESIDUAL_DOT  4
+#define MGCG_EPI_JACOBI_DOT    6
+#define MGCG_EPI_CHEBYSHEV     7
+#define MGCG_EPI_CHEBYSHEV_DOT 8
+typedef struct MgcgEpilogueArgs {
+    int epilogue;                 /* MGCG_EPI_* */
+    int elementsCount, rowCount, columnCount;
+    double* y;
+    const double* elements; const int* rowOffsets; const int* columnIndeces;
+    const double* x;
+    const double* b;
+    const double* xo;
+    const double* dinv; double dinvScalar;
+    double omega;
+    double* d; double c1, c2;
+    double xInner, xOuter;
+    int rowBegin, rowEnd;
+    int gapBegin, gapEnd;
+    const int* done;
+} MgcgEpilogueArgs;
+double MgcgCsrMVEpilogue(MgcgBlas* cublas, MgcgSparse* cusparse, const MgcgEpilogueArgs* args);
 /* SpMV kernel selection for CsrMV-family calls on this handle:
  * 0 auto, 1 row-block LDS stream kernel, 2..8 = 2^(k-2) lanes per row (k=2: one lane per row, the stored-order sum; k=8: one
  * wavefront per row), 9 row-block "stage raw, multiply by row" kernel, 10 row-tile kernel (256 rows per tile; the auto choice for

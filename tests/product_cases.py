@@ -1,5 +1,6 @@
-"""Matrices and host statements of the sparse product's summation orders, shared by tests/test_product_cases_host.py and
-tests/test_gpu_products.py.  No GPU is needed to import this.
+"""Matrices and host statements of the sparse product's summation orders and of its solver epilogues, shared by
+tests/test_product_cases_host.py, tests/test_gpu_products.py and tests/test_gpu_epilogues.py: the cases and their expected row sums are
+built once for all of them.  No GPU is needed to import this.
 
 The lanes-per-row kernels (spmv_vector_kernel, spmv_float_vector_kernel) have a fixed order: every product is rounded on its own, lane l
 of a row's L lanes adds the products of entries l, l + L, ... in stored order from +0.0, and the L sums meet in the tree
@@ -100,10 +101,10 @@ def assert_rows_within_bound(got, row_offsets, exact, size, dtype=np.float64, wh
 
 
 def assert_same_rows(got, want, row_offsets, what=""):
-    """np.array_equal, with the rows that differ and their lengths in the message."""
+    """np.array_equal -- a NaN equal to a NaN, to nothing else -- with the rows that differ and their lengths in the message."""
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    if not np.array_equal(got, want):
+    if not np.array_equal(got, want, equal_nan=True):
         bad = np.nonzero(~((got == want) | (np.isnan(got) & np.isnan(want))))[0]
         length = np.diff(np.asarray(row_offsets, dtype=np.int64))
         raise AssertionError(f"{what}: {bad.size} of {got.size} rows differ, first rows {bad[:8].tolist()} of lengths {length[bad[:8]].tolist()}: "
@@ -146,3 +147,130 @@ def rectangular(rows, cols, per_row, seed):
     s = problems.LinearSystem(np.ascontiguousarray(e[order]), np.ascontiguousarray(c[order]), ro, np.zeros(rows), np.zeros(rows), f"rect{rows}x{cols}x{per_row}")
     assert (np.diff(ro) == 0).sum() >= rows // 11 and int(c.max()) < cols
     return s
+
+
+# --------------------------------------------------------------------------- kernel ids, and the cases of the GPU product tests, computed once
+KERNELS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10)                  # MgcgSetSpmvKernel: 1 stream, 2..8 = 2^(k-2) lanes per row, 9 rows, 10 row-tile
+LANE_KERNELS = (2, 3, 4, 5, 6, 7, 8)
+
+
+def lanes_of(kernel):
+    """Lanes per row of a listed kernel id."""
+    return 2 ** (kernel - 2) if 2 <= kernel <= 8 else 1
+
+
+def _ragged():
+    from tests.block_cases import ragged_spd
+
+    return ragged_spd(1350)
+
+
+MATRICES = {
+    "poisson": (lambda: problems.poisson(20, 17, 13), None),
+    "ragged": (_ragged, None),
+    "mgcg700": (lambda: problems.mgcg_main(700, 24), None),
+    "rect700x1900x8": (lambda: rectangular(700, 1900, 8, 1), 1900),
+    "rect700x1900x40": (lambda: rectangular(700, 1900, 40, 2), 1900),
+    "rect1900x700x8": (lambda: rectangular(1900, 700, 8, 3), 700),
+    "rect1900x700x40": (lambda: rectangular(1900, 700, 40, 4), 700),
+    "wide-bands": (lambda: banded_rectangular(700, 1900), 1900),
+    "tall-bands": (lambda: banded_rectangular(1900, 700), 700),
+}
+MATRICES.update({f"ramp{lanes}": ((lambda lanes=lanes: ramp_for(lanes)), RAMP_COLS) for lanes in LANES})
+_cases, _sums = {}, {}
+
+
+class Case:
+    """A matrix of MATRICES (or any system handed in) with its vectors, every one from a seed of its own: x (columns), and by row w, y0
+    and the epilogue operands b, xo, dinv (positive, 10^U(-3, 3)) and d."""
+
+    def __init__(self, name, system=None, cols=None):
+        if system is None:
+            build, cols = MATRICES[name]
+            system = build()
+        self.name, self.s = name, system
+        self.rows, self.cols = self.s.Count, self.s.Count if cols is None else cols
+        seed = sum(map(ord, name))
+        self.x = np.random.default_rng(seed).standard_normal(self.cols)
+        self.w = np.random.default_rng(seed + 1).standard_normal(self.rows)         # another seed than x: never the same vector
+        self.y0 = np.random.default_rng(seed + 2).standard_normal(self.rows)
+        self.b = np.random.default_rng(seed + 3).standard_normal(self.rows)
+        self.xo = np.random.default_rng(seed + 4).standard_normal(self.rows)
+        self.dinv = 10.0 ** np.random.default_rng(seed + 5).uniform(-3.0, 3.0, self.rows)
+        self.d = np.random.default_rng(seed + 6).standard_normal(self.rows)
+        for v in (self.x, self.w, self.y0, self.b, self.xo, self.dinv, self.d):
+            v.setflags(write=False)
+        self.A = None
+
+    def device(self):
+        if self.A is None:
+            from tests.gpu_util import DeviceCsr
+
+            self.A = DeviceCsr(self.s)
+        return self.A
+
+
+def case(name):
+    if name not in _cases:
+        _cases[name] = Case(name)
+    return _cases[name]
+
+
+def ramp_of(kernel):
+    """The ramp of a kernel id: its lane count's, and the longest one for the stored-order kernels."""
+    return case(f"ramp{lanes_of(kernel)}" if kernel in (3, 4, 5, 6, 7, 8) else "ramp64")
+
+
+def row_sums(c, lanes, oracle):
+    """A x as a kernel of `lanes` lanes per row forms it: the oracle's product for one lane, the emulation otherwise."""
+    key = (c.name, lanes)
+    if key not in _sums:
+        s = c.s
+        _sums[key] = (oracle.spmv(s.Elements, s.ColumnIndeces, s.RowOffsets, c.x) if lanes == 1
+                      else lanes_per_row_sum(s.Elements, s.ColumnIndeces, s.RowOffsets, c.x, lanes))
+        _sums[key].setflags(write=False)
+    return _sums[key]
+
+
+def analysis_class(hh):
+    """MgcgAnalysisInfo's class of the first matrix analysed on the handle."""
+    import ctypes as C
+
+    from conjugategradient_amd import _lib
+
+    d, v, r, n = C.c_int(), C.c_int(), C.c_longlong(), C.c_longlong()
+    return _lib.lib().MgcgAnalysisInfo(hh.sparse, 0, C.byref(d), C.byref(v), C.byref(r), C.byref(n))
+
+
+# --------------------------------------------------------------------------- the solver epilogues (include/MgcgGpu.h: MgcgCsrMVEpilogue)
+EPI_RESIDUAL, EPI_JACOBI, EPI_RESIDUAL_DOT, EPI_JACOBI_DOT, EPI_CHEBYSHEV, EPI_CHEBYSHEV_DOT = 2, 3, 4, 6, 7, 8
+EPILOGUES = (EPI_RESIDUAL, EPI_RESIDUAL_DOT, EPI_JACOBI, EPI_JACOBI_DOT, EPI_CHEBYSHEV, EPI_CHEBYSHEV_DOT)
+EPI_NAMES = {EPI_RESIDUAL: "residual", EPI_RESIDUAL_DOT: "residual-dot", EPI_JACOBI: "jacobi", EPI_JACOBI_DOT: "jacobi-dot",
+             EPI_CHEBYSHEV: "chebyshev", EPI_CHEBYSHEV_DOT: "chebyshev-dot"}
+EPI_OPERATIONS = {EPI_RESIDUAL: 1, EPI_RESIDUAL_DOT: 1, EPI_JACOBI: 4, EPI_JACOBI_DOT: 4, EPI_CHEBYSHEV: 5, EPI_CHEBYSHEV_DOT: 5}   # rounded operations behind acc
+
+
+def epilogue_value(epi, acc, b, xo=None, dinv=None, omega=None, d=None, c1=None, c2=None):
+    """spmv_epilogue_value (csrc/kernels_spmv.hip) on float64 arrays, every product and sum a NumPy operation of its own and therefore
+    rounded on its own (the library is built without contraction).  dinv: an array or one number.  Returns (y, d_new, terms): d_new is the
+    Chebyshev step's new d (None otherwise), terms the rounded terms of the fused sum -- r r, or b y -- (None for an epilogue without one)."""
+    acc, b = np.asarray(acc, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    res = b - acc
+    dn = None
+    if epi in (EPI_RESIDUAL, EPI_RESIDUAL_DOT):
+        y = res
+    elif epi in (EPI_JACOBI, EPI_JACOBI_DOT):
+        t = dinv * res
+        s = omega * t
+        y = xo + s
+    elif epi in (EPI_CHEBYSHEV, EPI_CHEBYSHEV_DOT):
+        t = dinv * res
+        p = c1 * d
+        q = c2 * t
+        dn = p + q
+        y = xo + dn
+    else:
+        raise ValueError(epi)
+    terms = y * y if epi == EPI_RESIDUAL_DOT else b * y if epi in (EPI_JACOBI_DOT, EPI_CHEBYSHEV_DOT) else None
+    assert y.dtype == np.float64 and (dn is None or dn.dtype == np.float64) and (terms is None or terms.dtype == np.float64)
+    return y, dn, terms

@@ -57,6 +57,27 @@ def test_header_compiles_as_plain_c(tmp_path):
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
 
 
+def test_epilogue_argument_block_has_the_header_s_layout(tmp_path):
+    """MgcgCsrMVEpilogue takes one struct: _lib.EpilogueArgs must have the size and the field offsets a C compiler gives MgcgEpilogueArgs,
+    and the epilogue ids of _lib those of the header."""
+    from conjugategradient_amd import _lib
+
+    fields = [name for name, _ in _lib.EpilogueArgs._fields_]
+    ids = ["RESIDUAL", "JACOBI", "RESIDUAL_DOT", "JACOBI_DOT", "CHEBYSHEV", "CHEBYSHEV_DOT"]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "MgcgGpu.h"', "int main(void) {", '    printf("%zu\\n", sizeof(MgcgEpilogueArgs));']
+    lines += ['    printf("%%zu\\n", offsetof(MgcgEpilogueArgs, %s));' % f for f in fields]
+    lines += ['    printf("%%d\\n", MGCG_EPI_%s);' % i for i in ids]
+    lines += ["    return 0;", "}"]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)]).decode().split()]
+    assert got[0] == C.sizeof(_lib.EpilogueArgs)
+    assert got[1: 1 + len(fields)] == [getattr(_lib.EpilogueArgs, f).offset for f in fields]
+    assert got[1 + len(fields):] == [getattr(_lib, "EPI_" + i) for i in ids]
+
+
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="this check is for hosts without a GPU")
 def test_no_device_fails_loudly(hiplib):
     """No HIP device: handles are NULL, value-returning ops return NaN, and the reason is reported --

@@ -4,29 +4,20 @@ Kernel ids (MgcgSetSpmvKernel): 1 stream, 2..8 = 2^(k-2) lanes per row, 9 rows, 
 (1, 2, 9, 10) is the oracle's product; of the lanes-per-row kernels, tests/product_cases.py: lanes_per_row_sum -- their stated order in
 NumPy, itself held to the any-order bound of the correctly rounded row sums (tests/test_product_cases_host.py and, again, here).
 Comparisons are np.array_equal unless a docstring says otherwise.  Every input is a valid product."""
-import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
-from conjugategradient_amd import _lib, problems
+from conjugategradient_amd import _lib
 from conjugategradient_amd.solver import ConjugateGradientSingleGpu
-from tests.block_cases import ragged_spd
 from tests.gpu_util import DeviceCsr, Handles, assert_trace_close, dvec, ivec, tuning
-from tests.product_cases import (RAMP_COLS, assert_rows_within_bound, assert_same_rows, banded_rectangular, exact_rows, lanes_per_row_sum,
-                                 ramp, ramp_for, rectangular)
+from tests.product_cases import (KERNELS, LANE_KERNELS, MATRICES, analysis_class, assert_rows_within_bound, assert_same_rows, case, exact_rows,
+                                 lanes_of, lanes_per_row_sum, ramp, ramp_of, row_sums)
 
 pytestmark = pytest.mark.gpu
 
-KERNELS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10)
-LANE_KERNELS = (2, 3, 4, 5, 6, 7, 8)
 U = 2.0 ** -53
-
-
-def lanes_of(kernel):
-    """Lanes per row of a listed kernel id."""
-    return 2 ** (kernel - 2) if 2 <= kernel <= 8 else 1
 
 
 def auto_kernel(s):
@@ -38,64 +29,14 @@ def auto_kernel(s):
 @pytest.fixture(scope="module")
 def h():
     hh = Handles()
+    _lib.lib().MgcgSetMatrixCompression(hh.sparse, 0)     # a usable form takes precedence over a kernel id: MGCG_COMPRESSION must not decide what these tests run
     yield hh
     hh.close()
 
 
-# --------------------------------------------------------------------------- matrices, vectors and expected row sums, computed once
-MATRICES = {
-    "poisson": (lambda: problems.poisson(20, 17, 13), None),
-    "ragged": (lambda: ragged_spd(1350), None),
-    "mgcg700": (lambda: problems.mgcg_main(700, 24), None),
-    "rect700x1900x8": (lambda: rectangular(700, 1900, 8, 1), 1900),
-    "rect700x1900x40": (lambda: rectangular(700, 1900, 40, 2), 1900),
-    "rect1900x700x8": (lambda: rectangular(1900, 700, 8, 3), 700),
-    "rect1900x700x40": (lambda: rectangular(1900, 700, 40, 4), 700),
-    "wide-bands": (lambda: banded_rectangular(700, 1900), 1900),
-    "tall-bands": (lambda: banded_rectangular(1900, 700), 700),
-}
-MATRICES.update({f"ramp{lanes}": ((lambda lanes=lanes: ramp_for(lanes)), RAMP_COLS) for lanes in (1, 2, 4, 8, 16, 32, 64)})
+# --------------------------------------------------------------------------- the cases and their expected row sums: tests/product_cases.py
 RECTANGULAR = [name for name in MATRICES if name.startswith("rect")] + ["wide-bands", "tall-bands"]
-_cases, _sums, _exact = {}, {}, {}
-
-
-class Case:
-    def __init__(self, name):
-        build, cols = MATRICES[name]
-        self.name, self.s = name, build()
-        self.rows, self.cols = self.s.Count, self.s.Count if cols is None else cols
-        seed = sum(map(ord, name))
-        self.x = np.random.default_rng(seed).standard_normal(self.cols)
-        self.w = np.random.default_rng(seed + 1).standard_normal(self.rows)         # another seed than x: never the same vector
-        self.y0 = np.random.default_rng(seed + 2).standard_normal(self.rows)
-        self.A = None
-
-    def device(self):
-        if self.A is None:
-            self.A = DeviceCsr(self.s)
-        return self.A
-
-
-def case(name):
-    if name not in _cases:
-        _cases[name] = Case(name)
-    return _cases[name]
-
-
-def ramp_of(kernel):
-    """The ramp of a kernel id: its lane count's, and the longest one for the stored-order kernels."""
-    return case(f"ramp{lanes_of(kernel)}" if kernel in (3, 4, 5, 6, 7, 8) else "ramp64")
-
-
-def row_sums(c, lanes, oracle):
-    """A x as a kernel of `lanes` lanes per row forms it: the oracle's product for one lane, the emulation otherwise."""
-    key = (c.name, lanes)
-    if key not in _sums:
-        s = c.s
-        _sums[key] = (oracle.spmv(s.Elements, s.ColumnIndeces, s.RowOffsets, c.x) if lanes == 1
-                      else lanes_per_row_sum(s.Elements, s.ColumnIndeces, s.RowOffsets, c.x, lanes))
-        _sums[key].setflags(write=False)
-    return _sums[key]
+_exact = {}
 
 
 def assert_within_row_bound(c, got, what):
@@ -135,11 +76,6 @@ def assert_dot(c, got, y, what):
     want, size = math.fsum(prod), math.fsum(np.abs(prod))
     print(f"{what}: dot {got!r}, fsum {want!r}, error {abs(got - want):.3e}, bound {1.01 * (c.rows + 3) * U * size:.3e}")
     assert abs(got - want) <= 1.01 * (c.rows + 3) * U * size, (what, got, want)
-
-
-def analysis_class(hh):
-    d, v, r, n = C.c_int(), C.c_int(), C.c_longlong(), C.c_longlong()
-    return _lib.lib().MgcgAnalysisInfo(hh.sparse, 0, C.byref(d), C.byref(v), C.byref(r), C.byref(n))
 
 
 # --------------------------------------------------------------------------- a. row lengths, bit for bit
