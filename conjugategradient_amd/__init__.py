@@ -8,6 +8,8 @@
               ``strength="symmetric"`` (MgSetupAggregationEx) matches on the symmetric part, for A != A^T that does not coarsen otherwise
               ``amg.csr_transpose_gpu`` / ``amg.transpose_gpu``: A^T of any CSR matrix formed on the device (MgcgCsrTranspose), values as bit copies
 ``ssor``      SSOR(omega)-preconditioned CG / MINRES / BiCGStab: the one-level form of ``amg`` with two multicolour Gauss-Seidel sweeps
+``ilu``       multicolour ILU(0)-preconditioned CG / MINRES / BiCGStab / GMRES(m) (MgSetupIlu0): the incomplete factorisation in the colour
+              order of ``ssor``, stored so that every colour is one contiguous stream and M^-1 reads the factor once
 ``jacobi``    Jacobi-preconditioned CG for general CSR matrices (the call the ViennaCL front-end left commented out)
 ``singlereduce`` single-reduction (Chronopoulos-Gear) CG: one global sum and two launches per iteration, with or without the diagonal
 ``minres``   MINRES for symmetric indefinite and shifted systems (A - shift I) x = b: the solver for what the CG loops refuse,
@@ -28,4 +30,4 @@
 ``mixed``     mixed-precision CG: an fp32 recurrence corrected by fp64 reliable updates, fp64-accurate x and stop test
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "ssor", "jacobi", "singlereduce", "minres", "bicgstab", "gmres", "lsqr", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "ssor", "ilu", "jacobi", "singlereduce", "minres", "bicgstab", "gmres", "lsqr", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]

@@ -117,6 +117,12 @@ SIGNATURES = {
     "MgSmoother": (_i, [_vp]),
     "MgLevelColours": (_i, [_vp, _i]),
     "MgLevelCopyColours": (_i, [_vp, _i, _vp]),
+    "MgSetupIlu0": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _d]),
+    "MgIsIlu": (_i, [_vp]),
+    "MgIluColours": (_i, [_vp]),
+    "MgIluPivotRange": (_i, [_vp, _pd, _pd]),
+    "MgIluSetupMs": (_i, [_vp, _vp]),
+    "MgIluCopyFactor": (_ll, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "MgLevels": (_i, [_vp]),
     "MgLevelRows": (_ll, [_vp, _i]),
     "MgLevelNnz": (_ll, [_vp, _i]),

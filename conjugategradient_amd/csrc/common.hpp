@@ -987,6 +987,27 @@ void launch_gs_sweep(hipStream_t s, const int* rows, int count, const double* el
                      const double* b, const double* dinv, double omega, double* x, double avgRow, const int* done);
 void preload_kernels_gs();
 
+// ---------------------------------------------------------------- multicolour ILU(0) (kernels_ilu.hip; MgSetupIlu0)
+// `lanes`: the lanes that share a row (4, 8 or 16, picked from the matrix's entries per row as launch_gs_sweep picks them)
+// flags3[0 .. 2] (pre-set to INT_MAX) = the smallest row that stores a column outside [0, n) / that is empty / that stores no diagonal
+void launch_ilu_check_rows(hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long n, int* flags3);
+// lengths[i] = the length of old row rowOf[i], i < n; lengths[n] = 0 (n + 1 ints: exclusive_scan makes B's offsets of them)
+void launch_ilu_lengths(hipStream_t s, const int* rowOffsets, const int* rowOf, long long n, int* lengths);
+// B = P (A + shift diag(A)) P^T, every row sorted by new column; diagPos[i] = where row i's diagonal stands; *dupRow (pre-set to INT_MAX) =
+// the smallest old row that stores a column twice.  The rows must have passed launch_ilu_check_rows.
+void launch_ilu_build(hipStream_t s, const double* elements, const int* rowOffsets, const int* columnIndeces, const int* rowOf, const int* newOf, long long n,
+                      double shift, const int* offsetsB, double* valuesB, int* columnsB, int* diagPos, int* dupRow, int lanes);
+// the IKJ elimination in place of new rows [row0, row0 + count), one colour, and their pinv; *badRow (pre-set to INT_MAX) = the smallest old
+// row of them whose pivot is zero or not finite
+void launch_ilu_factor(hipStream_t s, int row0, int count, const int* offsetsB, const int* columnsB, const int* diagPos, double* valuesB, double* pinv,
+                       const int* rowOf, int* badRow, int lanes);
+// partials[2 b], partials[2 b + 1] = smallest and largest pivot seen by block b; returns the blocks (kMaxGrid at the most)
+int launch_ilu_pivot_range(hipStream_t s, const double* valuesB, const int* diagPos, long long n, double* partials);
+// one colour of the forward (y_i = r[rowOf[i]] - sum l_ik y_k) or backward (t_i = pinv_i (y_i - sum u_ij t_j), z[rowOf[i]] = t_i) pass
+void launch_ilu_pass(hipStream_t s, bool backward, int row0, int count, const double* valuesB, const int* offsetsB, const int* columnsB, const int* diagPos,
+                     const double* pinv, const int* rowOf, const double* r, double* y, double* t, double* z, int lanes, const int* done);
+void preload_kernels_ilu();
+
 // ---------------------------------------------------------------- RCCL (dlopen'ed)
 struct CommImpl;
 bool comm_allreduce_sum(MgcgComm* c, double* devPtr, int count, hipStream_t s);

@@ -58,6 +58,20 @@ struct MgLevel {
     std::vector<int> gsColourOf;           // n (host): what MgLevelCopyColours hands out
 };
 
+// Multicolour ILU(0) (MgSetupIlu0): the factor of B = P (A + shift diag(A)) P^T in the colour order, rows sorted by new column.  The rows
+// of colour c are the new rows [colourOffsets[c], colourOffsets[c + 1]).  y and t of the two passes are lv[0].xa and lv[0].xb.
+struct MgIlu {
+    double* values = nullptr; int* columns = nullptr; int* offsets = nullptr;   // nnz, nnz, n + 1 (device)
+    int* diag = nullptr;                   // n: where every row's diagonal stands
+    double* pinv = nullptr;                // n: 1 / pivot
+    int* rowOf = nullptr;                  // n: new row -> row of A
+    std::vector<int> colourOffsets;        // colours + 1 (host: a pass is one launch per colour)
+    long long nnz = 0;
+    int lanes = 8;                         // lanes per row of the kernels
+    double pivotMin = 0.0, pivotMax = 0.0;
+    double setupMs[3] = { 0.0, 0.0, 0.0 };  // checks and colouring, building B, factorisation (host clock around the phases' own synchronisations)
+};
+
 } // namespace mgcg
 
 struct MgcgMg {
@@ -90,6 +104,7 @@ struct MgcgMg {
     bool skipHalo = false;                 // the next SpMV-shaped pass finds its halo planes already in place (deep-halo cycle: formed locally)
     bool algebraic = false;                // built from aggregates of the matrix graph, not from a grid (also when it has a single level)
     int strength = 0;                      // what the matching read (MgSetupAggregationEx): 0 the level's own matrix, 1 its symmetric part
+    mgcg::MgIlu* ilu = nullptr;            // MgSetupIlu0: the handle is an ILU(0) factor (one level, one rank), M^-1 = U^-1 L^-1; owned
 };
 
 namespace mgcg {
@@ -527,6 +542,18 @@ static bool mg_apply(MgcgMg* mg, const double* r, double* z, const int* done, do
     t_lastFolds = 0;
     struct Reset { MgcgMg* m; int* n; ~Reset() { if (n) *n = m->fusedDotCount; m->fuseDotPartials = nullptr; } } reset{ mg, nDot };
     MgLevel& L0 = mg->lv[0];
+    if (mg->ilu != nullptr) {
+        // z = U^-1 L^-1 r: forward over the colours ascending, backward descending, one launch each; no r.z is reported (*nDot = 0)
+        const MgIlu& F = *mg->ilu;
+        const int colours = (int)F.colourOffsets.size() - 1;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int q = 0; q < colours; ++q) {
+                const int c = pass == 0 ? q : colours - 1 - q;
+                launch_ilu_pass(mg->stream, pass == 1, F.colourOffsets[(size_t)c], F.colourOffsets[(size_t)c + 1] - F.colourOffsets[(size_t)c], F.values, F.offsets,
+                                F.columns, F.diag, F.pinv, F.rowOf, r, L0.xa, L0.xb, z, F.lanes, done);
+            }
+        return MGCG_HIP(hipGetLastError());
+    }
     double* res = nullptr;
     if (!mg->multi) {
         // swaps on level 0: (nu-1) pre + nu post, or (nuCoarse-1) when there is a single level
@@ -2953,7 +2980,7 @@ static bool amg_common_arguments(const char* who, MgcgBlas* cublas, MgcgSparse* 
 // coloured, one flag per round read by the host as in the matching; then the device check that no row stores an entry of a row of its own
 // colour.  The per-colour row lists (ascending) are index bookkeeping and built here on the host.  false with the message set on a refusal.
 struct GsColouring { int* rows = nullptr; std::vector<int> offsets, colourOf; };
-static bool gs_colour_level(hipStream_t s, const MgLevel& L, int level, GsColouring* out)
+static bool gs_colour_level(hipStream_t s, const MgLevel& L, int level, GsColouring* out, const char* who = "MgSetSmoother")
 {
     const size_t n = (size_t)L.n, nAlloc = n > 0 ? n : 1;
     int *ca = nullptr, *cb = nullptr, *flags = nullptr;       // flags[0]: a row is left; flags[1]: the bad row
@@ -2968,7 +2995,7 @@ static bool gs_colour_level(hipStream_t s, const MgLevel& L, int level, GsColour
         ok = ok && MGCG_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
         std::swap(ca, cb);
         if (ok && h[1] != 0x7fffffff) {
-            set_error("MgSetSmoother: level %d, row %d: the row's neighbours hold all 64 colours (the multicolour sweep allows 64 per level)", level, h[1]);
+            set_error("%s: level %d, row %d: the row's neighbours hold all 64 colours (the multicolour sweep allows 64 per level)", who, level, h[1]);
             refused = true;
             break;
         }
@@ -2980,8 +3007,8 @@ static bool gs_colour_level(hipStream_t s, const MgLevel& L, int level, GsColour
         if (ok) launch_gs_check(s, L.rowOffsets, L.columnIndeces, L.n, ca, flags + 1);
         ok = ok && MGCG_HIP(hipMemcpyAsync(&bad, flags + 1, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
         if (ok && bad != 0x7fffffff) {
-            set_error("MgSetSmoother: level %d, row %d: the row stores an entry of a row of its own colour: the pattern is not structurally symmetric "
-                      "(some row j stores this row and this row does not store j)", level, bad);
+            set_error("%s: level %d, row %d: the row stores an entry of a row of its own colour: the pattern is not structurally symmetric "
+                      "(some row j stores this row and this row does not store j)", who, level, bad);
             refused = true;
         }
     }
@@ -3180,6 +3207,7 @@ MgcgMg* MgSetupAggregates(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elemen
 int MgLevelCopyAggregates(const MgcgMg* mg, int level, int aggregateOf[])
 {
     if (!mg || !aggregateOf) { set_error("MgLevelCopyAggregates: null argument"); return -1; }
+    if (mg->ilu) { set_error("MgLevelCopyAggregates: the handle is an ILU(0) factor (MgSetupIlu0): it has no aggregates"); return -1; }
     if (!mg->algebraic) { set_error("MgLevelCopyAggregates: a geometric hierarchy has no stored aggregates"); return -1; }
     if (level < 0 || level >= mg->levels - 1 || mg->lv[(size_t)level].agg == nullptr) { set_error("MgLevelCopyAggregates: level %d has no map (the hierarchy has %d levels)", level, mg->levels); return -1; }
     const MgLevel& L = mg->lv[(size_t)level];
@@ -3192,6 +3220,11 @@ void MgDestroy(MgcgMg* mg)
     if (!mg) return;
     if (mg->stream) (void)hipStreamSynchronize(mg->stream);
     if (mg->rExt) (void)hipFree(mg->rExt);
+    if (mg->ilu) {
+        for (void* p : { (void*)mg->ilu->values, (void*)mg->ilu->columns, (void*)mg->ilu->offsets, (void*)mg->ilu->diag, (void*)mg->ilu->pinv, (void*)mg->ilu->rowOf })
+            if (p) (void)hipFree(p);
+        delete mg->ilu;
+    }
     for (auto& L : mg->lv) {
         if (L.ownsMatrix) {       // freed addresses may be handed out again: analyses keyed by them are void
             if (L.elements) { analysis_note_write(L.elements, sizeof(double) * (size_t)(L.nnz > 0 ? L.nnz : 1)); (void)hipFree(L.elements); }
@@ -3222,6 +3255,7 @@ void MgDestroy(MgcgMg* mg)
 int MgSetInterpolation(MgcgMg* mg, int mode)
 {
     if (!mg || (mode != 0 && mode != 1)) { set_error("MgSetInterpolation: mode must be 0 (piecewise constant) or 1 (cell-centred linear)"); return -1; }
+    if (mg->ilu) { set_error("MgSetInterpolation: the handle is an ILU(0) factor (MgSetupIlu0): it has no transfer operators"); return -1; }
     if (mode == 1 && mg->algebraic) { set_error("MgSetInterpolation: the linear transfer needs a grid; this hierarchy was built from aggregates"); return -1; }
     if (!device_state()) return -1;
     if (mode == 1 && mg->multi) {
@@ -3244,6 +3278,7 @@ int MgSetSmoother(MgcgMg* mg, int mode)
 {
     if (!mg) { set_error("MgSetSmoother: null handle"); return -1; }
     if (mode != 0 && mode != 1) { set_error("MgSetSmoother: mode %d, must be 0 (weighted Jacobi) or 1 (multicolour Gauss-Seidel)", mode); return -1; }
+    if (mg->ilu) { set_error("MgSetSmoother: the handle is an ILU(0) factor (MgSetupIlu0): it has no smoother"); return -1; }
     if (mode == 1 && !mg->algebraic) {
         set_error("MgSetSmoother: the Gauss-Seidel smoother needs every level stored; this hierarchy was built from a grid (MgSetupAggregates with 2x2x2 box maps builds the same hierarchy)");
         return -1;
@@ -3285,10 +3320,158 @@ int MgLevelCopyColours(const MgcgMg* mg, int level, int colourOf[])
 {
     if (!mg || !colourOf) { set_error("MgLevelCopyColours: null argument"); return -1; }
     if (level < 0 || level >= mg->levels) { set_error("MgLevelCopyColours: level %d, the hierarchy has %d levels", level, mg->levels); return -1; }
+    if (mg->ilu) { set_error("MgLevelCopyColours: the handle is an ILU(0) factor (MgSetupIlu0): MgIluCopyFactor hands out its order (rowOf)"); return -1; }
     if (mg->smoother != 1) { set_error("MgLevelCopyColours: the hierarchy smooths with weighted Jacobi: it has no colours (MgSetSmoother(mg, 1))"); return -1; }
     const MgLevel& L = mg->lv[(size_t)level];
     std::copy(L.gsColourOf.begin(), L.gsColourOf.end(), colourOf);
     return 0;
+}
+
+// Multicolour ILU(0) (the contract is written out in include/MgcgGpu.h; kernels_ilu.hip).  What comes to the host: the flags, the colour
+// of every row (gs_colour_level) and -- on a refused pivot -- one int and one double; what goes to the device from it: the two permutations.
+MgcgMg* MgSetupIlu0(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    int elementsCount, int count, double shift)
+{
+    const char* who = "MgSetupIlu0";
+    if (!cublas || !cusparse || !elementsVector || !rowOffsetsVector || !columnIndecesVector) { set_error("%s: null handle", who); return nullptr; }
+    if (count < 1 || elementsCount < 0) { set_error("%s: bad parameters (count %d, elementsCount %d)", who, count, elementsCount); return nullptr; }
+    if (rowOffsetsVector->size < (long long)count + 1 || elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount) {
+        set_error("%s: matrix vectors too small (%lld values, %lld offsets, %lld columns for %d entries in %d rows)", who, (long long)elementsVector->size,
+                  (long long)rowOffsetsVector->size, (long long)columnIndecesVector->size, elementsCount, count);
+        return nullptr;
+    }
+    if (!(shift >= 0.0) || !(shift <= 1.7976931348623157e308)) { set_error("%s: shift %g, must be finite and >= 0", who, shift); return nullptr; }
+    DeviceState* d = device_state();
+    if (!d) return nullptr;
+    hipStream_t s = d->stream;
+    const double* elements = elementsVector->data;
+    const int *rowOffsets = rowOffsetsVector->data, *columnIndeces = columnIndecesVector->data;
+    const size_t n = (size_t)count;
+    const int kNone = 0x7fffffff;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = now();
+    long long nnz = 0;
+    if (!csr_check_offsets(who, s, rowOffsets, count, elementsCount, &nnz)) return nullptr;
+
+    MgcgMg* mg = new MgcgMg();
+    MgIlu* F = mg->ilu = new MgIlu();                     // from here on MgDestroy frees whatever a failed set-up had allocated
+    mg->omega = 1.0; mg->stream = s; mg->cfg = cfg_of(cusparse); mg->algebraic = true;
+    MgLevel L;
+    L.nx = count; L.ny = 1; L.nz = 1; L.z0 = 0; L.z1 = 1;
+    L.n = count; L.nGlobal = count; L.offset = 0; L.nnz = nnz;
+    L.elements = const_cast<double*>(elements); L.rowOffsets = const_cast<int*>(rowOffsets); L.columnIndeces = const_cast<int*>(columnIndeces); L.ownsMatrix = false;
+    L.cfg = mg->cfg;
+    F->nnz = nnz;
+    F->lanes = (double)nnz <= 4.0 * (double)count ? 4 : ((double)nnz <= 10.0 * (double)count ? 8 : 16);
+    const size_t nzAlloc = nnz > 0 ? (size_t)nnz : 1;
+
+    int *dflags = nullptr, *dNewOf = nullptr;
+    double* dPartials = nullptr;
+    int h[3] = { kNone, kNone, kNone };
+    bool ok = MGCG_HIP(hipMalloc((void**)&dflags, sizeof(h))) && MGCG_HIP(hipMemcpyAsync(dflags, h, sizeof(h), hipMemcpyHostToDevice, s));
+    if (ok) launch_ilu_check_rows(s, rowOffsets, columnIndeces, count, dflags);
+    ok = ok && MGCG_HIP(hipMemcpyAsync(h, dflags, sizeof(h), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    if (ok && h[0] != kNone) { set_error("%s: row %d stores a column outside [0, %d)", who, h[0], count); ok = false; }
+    else if (ok && h[1] != kNone) { set_error("%s: row %d is empty", who, h[1]); ok = false; }
+    else if (ok && h[2] != kNone) { set_error("%s: row %d stores no diagonal entry", who, h[2]); ok = false; }
+
+    // the colours and the order: new row = position in the list sorted by (colour, row)
+    GsColouring colouring;
+    std::vector<int> newOf;
+    ok = ok && gs_colour_level(s, L, 0, &colouring, who);
+    F->rowOf = colouring.rows;
+    const auto t1 = now();
+    if (ok) {
+        F->colourOffsets = colouring.offsets;
+        std::vector<int> at(colouring.offsets.begin(), colouring.offsets.end() - 1);
+        newOf.resize(n);
+        for (size_t i = 0; i < n; ++i) newOf[i] = at[(size_t)colouring.colourOf[i]]++;
+        ok = MGCG_HIP(hipMalloc((void**)&dNewOf, sizeof(int) * n)) && MGCG_HIP(hipMemcpyAsync(dNewOf, newOf.data(), sizeof(int) * n, hipMemcpyHostToDevice, s)) &&
+             MGCG_HIP(hipStreamSynchronize(s));
+    }
+    // B, every row sorted by new column
+    ok = ok && MGCG_HIP(hipMalloc((void**)&F->offsets, sizeof(int) * (n + 1))) && MGCG_HIP(hipMalloc((void**)&F->values, sizeof(double) * nzAlloc)) &&
+         MGCG_HIP(hipMalloc((void**)&F->columns, sizeof(int) * nzAlloc)) && MGCG_HIP(hipMalloc((void**)&F->diag, sizeof(int) * n)) &&
+         MGCG_HIP(hipMalloc((void**)&F->pinv, sizeof(double) * n)) && MGCG_HIP(hipMalloc((void**)&L.xa, sizeof(double) * n)) &&
+         MGCG_HIP(hipMalloc((void**)&L.xb, sizeof(double) * n)) && MGCG_HIP(hipMalloc((void**)&dPartials, sizeof(double) * 2 * (size_t)kMaxGrid));
+    if (ok) launch_ilu_lengths(s, rowOffsets, F->rowOf, count, F->offsets);
+    ok = ok && MGCG_HIP(hipGetLastError()) && exclusive_scan(s, F->offsets, (long long)count + 1);
+    int bad = kNone;
+    ok = ok && MGCG_HIP(hipMemcpyAsync(dflags, &bad, sizeof(int), hipMemcpyHostToDevice, s));
+    if (ok) launch_ilu_build(s, elements, rowOffsets, columnIndeces, F->rowOf, dNewOf, count, shift, F->offsets, F->values, F->columns, F->diag, dflags, F->lanes);
+    ok = ok && MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(&bad, dflags, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    if (ok && bad != kNone) { set_error("%s: row %d stores a column twice", who, bad); ok = false; }
+    const auto t2 = now();
+    // the factor: one launch per colour, the pivot flag read after each
+    const int colours = ok ? (int)F->colourOffsets.size() - 1 : 0;
+    for (int c = 0; ok && c < colours; ++c) {
+        launch_ilu_factor(s, F->colourOffsets[(size_t)c], F->colourOffsets[(size_t)c + 1] - F->colourOffsets[(size_t)c], F->offsets, F->columns, F->diag, F->values,
+                          F->pinv, F->rowOf, dflags, F->lanes);
+        ok = MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(&bad, dflags, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+        if (ok && bad != kNone) {
+            int where = 0;
+            double pivot = 0.0;
+            if (MGCG_HIP(hipMemcpy(&where, F->diag + newOf[(size_t)bad], sizeof(int), hipMemcpyDeviceToHost)) && MGCG_HIP(hipMemcpy(&pivot, F->values + where, sizeof(double), hipMemcpyDeviceToHost)))
+                set_error("%s: row %d: the pivot is %g, zero or not finite: this matrix has no ILU(0) factor in the colour order (shift > 0 factors A + shift * diag(A))", who, bad, pivot);
+            ok = false;
+        }
+    }
+    if (ok) {
+        const int blocks = launch_ilu_pivot_range(s, F->values, F->diag, count, dPartials);
+        std::vector<double> partials(2 * (size_t)blocks);
+        ok = MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(partials.data(), dPartials, sizeof(double) * partials.size(), hipMemcpyDeviceToHost, s)) &&
+             MGCG_HIP(hipStreamSynchronize(s));
+        F->pivotMin = partials[0]; F->pivotMax = partials[1];
+        for (int b = 1; ok && b < blocks; ++b) { F->pivotMin = std::min(F->pivotMin, partials[2 * (size_t)b]); F->pivotMax = std::max(F->pivotMax, partials[2 * (size_t)b + 1]); }
+    }
+    const auto t3 = now();
+    F->setupMs[0] = ms(t0, t1); F->setupMs[1] = ms(t1, t2); F->setupMs[2] = ms(t2, t3);
+    if (dflags) (void)hipFree(dflags);
+    if (dNewOf) (void)hipFree(dNewOf);
+    if (dPartials) (void)hipFree(dPartials);
+    mg->lv.push_back(L);                                  // (also after a failure: MgDestroy frees what it had allocated)
+    mg->levels = 1;
+    if (!ok) { MgDestroy(mg); return nullptr; }
+    return mg;
+}
+
+int MgIsIlu(const MgcgMg* mg) { return (mg && mg->ilu) ? 1 : 0; }
+
+int MgIluColours(const MgcgMg* mg)
+{
+    if (!mg || !mg->ilu) { set_error("MgIluColours: the handle is not an ILU(0) factor (MgSetupIlu0)"); return -1; }
+    return (int)mg->ilu->colourOffsets.size() - 1;
+}
+
+int MgIluPivotRange(const MgcgMg* mg, double* smallest, double* largest)
+{
+    if (!mg || !mg->ilu) { set_error("MgIluPivotRange: the handle is not an ILU(0) factor (MgSetupIlu0)"); return -1; }
+    if (smallest) *smallest = mg->ilu->pivotMin;
+    if (largest) *largest = mg->ilu->pivotMax;
+    return 0;
+}
+
+int MgIluSetupMs(const MgcgMg* mg, double ms[3])
+{
+    if (!mg || !mg->ilu || !ms) { set_error("MgIluSetupMs: the handle is not an ILU(0) factor (MgSetupIlu0), or a null argument"); return -1; }
+    std::copy(mg->ilu->setupMs, mg->ilu->setupMs + 3, ms);
+    return 0;
+}
+
+long long MgIluCopyFactor(const MgcgMg* mg, double elements[], int columnIndeces[], int rowOffsets[], int diagonal[], int rowOf[])
+{
+    if (!mg || !mg->ilu) { set_error("MgIluCopyFactor: the handle is not an ILU(0) factor (MgSetupIlu0)"); return -1; }
+    const MgIlu& F = *mg->ilu;
+    const size_t n = (size_t)mg->lv[0].n, nz = (size_t)F.nnz;
+    if (elements || columnIndeces || rowOffsets || diagonal || rowOf) (void)hipStreamSynchronize(mg->stream);
+    bool ok = true;
+    if (elements) ok = ok && MGCG_HIP(hipMemcpy(elements, F.values, sizeof(double) * nz, hipMemcpyDeviceToHost));
+    if (columnIndeces) ok = ok && MGCG_HIP(hipMemcpy(columnIndeces, F.columns, sizeof(int) * nz, hipMemcpyDeviceToHost));
+    if (rowOffsets) ok = ok && MGCG_HIP(hipMemcpy(rowOffsets, F.offsets, sizeof(int) * (n + 1), hipMemcpyDeviceToHost));
+    if (diagonal) ok = ok && MGCG_HIP(hipMemcpy(diagonal, F.diag, sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (rowOf) ok = ok && MGCG_HIP(hipMemcpy(rowOf, F.rowOf, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return ok ? F.nnz : -1;
 }
 
 int MgLevels(const MgcgMg* mg) { return mg ? mg->levels : 0; }
@@ -3307,6 +3490,7 @@ void MgLevelCopyCsr(const MgcgMg* mg, int l, double elements[], int columnIndece
 void MgLevelCopyDinv(const MgcgMg* mg, int l, double dinv[])
 {
     if (!mg || l < 0 || l >= mg->levels) { set_error("MgLevelCopyDinv: bad level"); return; }
+    if (mg->ilu) { set_error("MgLevelCopyDinv: the handle is an ILU(0) factor (MgSetupIlu0): it keeps no D^-1 (MgIluCopyFactor hands out the factor)"); return; }
     (void)hipStreamSynchronize(mg->stream);
     (void)MGCG_HIP(hipMemcpy(dinv, mg->lv[l].dinv, sizeof(double) * (size_t)mg->lv[l].n, hipMemcpyDeviceToHost));
 }

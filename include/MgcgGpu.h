@@ -570,6 +570,57 @@ int     MgSmoother(const MgcgMg* mg);                                     /* the
 int     MgLevelColours(const MgcgMg* mg, int level);                      /* the colours of the level; 0 under mode 0; -1 on a bad level */
 /* colourOf[0 .. MgLevelRows(level)-1] = the colour of every row.  Returns 0; -1 with MgcgGetLastError() under mode 0 or on a bad level. */
 int     MgLevelCopyColours(const MgcgMg* mg, int level, int colourOf[]);
+/* Multicolour ILU(0): M = L U, the incomplete factorisation without fill of A + shift * diag(A) in the COLOUR ORDER, as one more kind of
+ * MgcgMg handle.  MgApply, SolveMg, SolveMinresMg, SolveBicgstabMg and SolveGmresMg take it wherever they take a hierarchy: z = M^-1 r is
+ * U^-1 L^-1 r.  One rank; any CSR matrix with a stored diagonal in every row, rows in any stored order, no column twice in a row, a
+ * structurally symmetric pattern of at most 64 colours; the values may be nonsymmetric.
+ *
+ * REFUSED before a device is asked for (NULL, MgcgGetLastError()): a null handle; count < 1 or elementsCount < 0; vectors smaller than
+ * elementsCount or count + 1; a shift that is not finite or is negative.
+ * REFUSED once the arrays have been read, in this order, each naming the smallest such row of A: offsets that do not start at 0, that
+ * descend or that end beyond elementsCount; a row that stores a column outside [0, count); an empty row; a row without a stored diagonal;
+ * the two refusals of the colouring below; a row that stores a column twice; a pivot that is zero or not finite.  A refusal commits nothing.
+ *
+ * The COLOURS are those of MgSetSmoother above, by the same code: the same key, the same rounds, at most 64 colours, the same check pass
+ * (an unsymmetric pattern is refused); the messages are MgSetSmoother's under this call's name, with "level 0".
+ * The ORDER: new row index = the row's position in the list of all rows sorted by (colour, row).  rowOf[new] = old.  The rows of a colour
+ * are one contiguous range of new indices and store no entry of each other.
+ * The PERMUTED MATRIX B = P (A + shift diag(A)) P^T is stored as CSR with every row sorted by new column.  Its diagonal entry is
+ * a_ii + shift * a_ii, the product rounded first (shift = 0: a_ii itself, for every finite a_ii); the other entries are bit copies.
+ * The FACTOR is the IKJ ILU(0) of B in place, every product rounded before its subtraction: for new row i ascending, for each stored
+ * entry (i, k) with k < i in stored (ascending) order:
+ *     l = b_ik * pinv_k, stored as b_ik;   for each stored (k, j) with j > k, ascending: if row i stores column j,  b_ij = b_ij - l * b_kj;
+ * and when the row is done pinv_i = 1.0 / b_ii.  "i ascending" is one launch per colour; the bits do not depend on how a colour's rows
+ * are spread over lanes.  The pivot flag is read after every colour: the refusal names the smallest row of A, among the rows of the first
+ * colour that has one, whose pivot b_ii is zero or not finite, and the pivot's value.
+ * The SIGN of the pivots is not judged.  MgIluPivotRange reports the smallest and the largest.  The CG and MINRES forms (SolveMg,
+ * SolveMinresMg) need a symmetric positive definite M: A symmetric and ALL pivots positive; shift > 0 -- ILU(0) of A + shift * D -- is the
+ * usual remedy where they are not.  SolveBicgstabMg and SolveGmresMg ask nothing of M but that it exists.
+ * The APPLICATION z = M^-1 r, r and z in the caller's order, y and t in the new order in the handle's own buffers:
+ *     forward, colours ascending:   s = the sum in stored order from +0.0 of the rounded products l_ik * y_k over the row's entries left of
+ *                                   its diagonal;   y_i = r[rowOf[i]] - s
+ *     backward, colours descending: s = the same sum of u_ij * t_j over the entries right of the diagonal;   t_i = pinv_i * (y_i - s);
+ *                                   z[rowOf[i]] = t_i
+ * One launch per colour per direction over a contiguous range of rows; the sums are serial in every mode (dot_order changes nothing here).
+ * The application leaves no partial sums of r . z behind: the loops take them in a pass of their own, as under MgSetSmoother(mg, 1).
+ *
+ * The handle has one level: MgLevels = 1, MgLevelRows(0) = count, MgLevelNnz(0) = the entries, MgLevelCopyCsr(0) = A as given.  MgDestroy
+ * frees it.  It reads the caller's matrix vectors only during this call.  MgSetSmoother, MgSetInterpolation, MgLevelCopyAggregates,
+ * MgLevelCopyColours and MgLevelCopyDinv refuse it with a message that says what the handle is.  A solve checks its row count and its one
+ * rank as it checks a hierarchy's. */
+MgcgMg* MgSetupIlu0(MgcgBlas* cublas, MgcgSparse* cusparse,
+                    Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    int elementsCount, int count, double shift);
+int     MgIsIlu(const MgcgMg* mg);                                        /* 1 for such a handle, 0 otherwise and for NULL */
+int     MgIluColours(const MgcgMg* mg);                                   /* the colours; -1 with a message on another handle */
+int     MgIluPivotRange(const MgcgMg* mg, double* smallest, double* largest);   /* 0; -1 with a message on another handle */
+/* ms[0 .. 2] = what the set-up took on the host's clock: checks and colouring, building B, factorisation with the pivot range. */
+int     MgIluSetupMs(const MgcgMg* mg, double ms[3]);
+/* The factor as it stands on the device: values, new columns and count + 1 offsets of B's factor (L strictly left of every row's diagonal,
+ * the multipliers; U from the diagonal on, the diagonal entry is the pivot), diagonal[i] = the position of row i's diagonal, rowOf[new] =
+ * old.  Any pointer may be NULL (not copied).  Returns the entry count, so a call with all pointers NULL sizes the arrays; -1 with a
+ * message on another handle. */
+long long MgIluCopyFactor(const MgcgMg* mg, double elements[], int columnIndeces[], int rowOffsets[], int diagonal[], int rowOf[]);
 int     MgLevels(const MgcgMg* mg);
 /* rows / nnz / grid of level l; copy level l's CSR and D^-1 to host arrays (for tests). */
 long long MgLevelRows(const MgcgMg* mg, int level);
