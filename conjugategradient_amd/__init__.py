@@ -24,10 +24,13 @@
              classes: it converges where SolveBicgstabMg breaks down)
 ``lsqr``     LSQR for least squares min || A x - b ||_2 with ANY CSR matrix (``LeastSquaresGpu``, MgcgSolveLsqr): rectangular, rank deficient
              (minimum-norm solution), inconsistent right-hand sides, Tikhonov damping; A^T is formed on the device (MgcgCsrTranspose)
+``eigen``    LOBPCG for the k = 1 .. 8 lowest or highest EIGENPAIRS of a symmetric CSR matrix (``SymmetricEigenGpu``, MgcgSolveLobpcg): values,
+             vectors and residuals, plain or preconditioned by the diagonal (the V-cycle form, MgcgSolveLobpcgMg, is the ``SolveLobpcg``
+             method of the ``multigrid`` / ``amg`` / ``ssor`` / ``ilu`` classes)
 ``chebyshev`` Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, m products and two global sums per iteration
 ``shifted``   multi-shift CG: (A + s_j I) x_j = b for up to 8 shifts from one CG recurrence on A
 ``blockkrylov`` shared-subspace block CG: up to 8 right-hand sides in one block Krylov space (fewer iterations than ``block``)
 ``mixed``     mixed-precision CG: an fp32 recurrence corrected by fp64 reliable updates, fp64-accurate x and stop test
 ``problems``  the linear systems the reference hard-codes + the BASELINE.json stencils
 """
-__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "ssor", "ilu", "jacobi", "singlereduce", "minres", "bicgstab", "gmres", "lsqr", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]
+__all__ = ["_lib", "solver", "parallel", "multigrid", "amg", "ssor", "ilu", "jacobi", "singlereduce", "minres", "bicgstab", "gmres", "lsqr", "eigen", "chebyshev", "shifted", "blockkrylov", "mixed", "problems"]

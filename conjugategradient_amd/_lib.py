@@ -154,6 +154,9 @@ SIGNATURES = {
     "SolveGmresJacobi": (_i, [_vp] * 13 + [_i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
     "SolveGmresMg": (_i, [_vp] * 13 + [_i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
     "MgcgSolveLsqr": (_i, [_vp] * 16 + [_i, _i, _i, _d, _d, _i, _i, _i, _pi, _pd, _pd, _pd, _pd, _vp, _i]),
+    "MgcgLobpcgWorkSize": (_ll, [_i, _i]),
+    "MgcgSolveLobpcg": (_i, [_vp] * 9 + [_i, _i, _i, _i, _d, _i, _i, _i, _pi, _vp, _vp, _vp, _vp, _pi, _vp, _i]),
+    "MgcgSolveLobpcgMg": (_i, [_vp] * 9 + [_i, _i, _i, _i, _d, _i, _i, _i, _pi, _vp, _vp, _vp, _vp, _pi, _vp, _i]),
     "SolveBicgstabParallel": (_i, [_vp] * 16 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
     "SolveBicgstabJacobiParallel": (_i, [_vp] * 17 + [_i, _i, _i, _i, _i, _i, _d, _i, _i, _i, _pi, _pd, _pd, _vp, _i]),
     "MgcgGershgorinBound": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _pd]),

@@ -115,7 +115,7 @@ void preload_ops(); void preload_solver(); void preload_comm(); void preload_ker
 void preload_kernels_rowtile(); void preload_kernels_dcsr(); void preload_kernels_tiled(); void preload_kernels_blas1();
 void preload_kernels_mg(); void preload_kernels_amg(); void preload_spectrum(); void preload_kernels_pb(); void preload_kernels_block(); void preload_kernels_shift();
 void preload_kernels_bkrylov(); void preload_kernels_mixed(); void preload_kernels_sreduce(); void preload_kernels_cheb(); void preload_kernels_minres(); void preload_kernels_pminres();
-void preload_kernels_bicgstab(); void preload_kernels_bicgstabl(); void preload_kernels_gmres(); void preload_kernels_lsqr();
+void preload_kernels_bicgstab(); void preload_kernels_bicgstabl(); void preload_kernels_gmres(); void preload_kernels_lsqr(); void preload_kernels_lobpcg();
 
 // Device scalars of one CG run (lives in the handle's workspace).
 struct CgScalars {
@@ -266,6 +266,7 @@ struct LsqrScalars {
 
 // ---------------------------------------------------------------- handles
 struct BlockScalars;                 // per-column scalars of the block CG loop (kernels_block.hip)
+struct LobScalars;                   // the dense problem and per-column results of the LOBPCG loop (kernels_lobpcg.hip)
 struct BkScalars;                    // k x k matrices and per-column results of the shared-subspace block CG loop (kernels_bkrylov.hip)
 struct Workspace {
     int device = -1;
@@ -306,6 +307,9 @@ struct Workspace {
     GmresScalars* gmresScalars = nullptr;
     double* gmresPartials = nullptr;
     LsqrScalars* lsqrScalars = nullptr;          // LSQR (kernels_lsqr.hip), allocated at its first call and kept
+    // LOBPCG (kernels_lobpcg.hip), allocated at its first call and kept: the loop's scalars and three regions of Gram partial sums
+    LobScalars* lobScalars = nullptr;
+    double* lobPartials = nullptr;
     bool init();
     void destroy();
     bool ensure_trace(int cap);
@@ -321,6 +325,7 @@ struct Workspace {
     bool ensure_bicgstabl();                     // bicgstablScalars / bicgstablPartials (kernels_bicgstabl.hip)
     bool ensure_gmres();                         // gmresScalars / gmresPartials (kernels_gmres.hip)
     bool ensure_lsqr();                          // lsqrScalars (kernels_lsqr.hip)
+    bool ensure_lobpcg();                        // lobScalars / lobPartials (kernels_lobpcg.hip)
 };
 
 } // namespace mgcg
@@ -674,6 +679,33 @@ bool bk_read_results(Workspace* ws, int k, BkResult* out);
 // (kernels_block.hip: spmv_block_kernel's gather with the Gram epilogue); returns the number of partial sums per entry
 int launch_spmv_block_gram(hipStream_t s, int k, const double* elements, const int* rowOffsets, const int* columnIndeces,
                            const double* S, double* T, long long rows, double* gramPartials, const int* done);
+
+// y_j = A x_j for k columns, x and y column-major with the same column stride ld >= rows (CsrMVBlock's path on operands that lie ld apart);
+// done (may be null): a device int, nonzero = the product writes nothing
+void launch_spmv_block_plain(hipStream_t s, int k, const double* elements, const int* rowOffsets, const int* columnIndeces,
+                             const double* x, double* y, long long ld, long long rows, const int* done);
+
+// LOBPCG (MgcgSolveLobpcg / MgcgSolveLobpcgMg; kernels_lobpcg.hip has the passes and the dense step, include/MgcgGpu.h the method), one rank.
+// X: the caller's block, column j at j * n.  AX, W, AW, P, AP, Rv: the six blocks of the work vector, column j of each at j * ld (ld = n
+// rounded up to even).  pre: 0 W = R, 1 W = dinv o R inside the residual pass, 2 somebody else forms W from R between lob_enqueue_residual
+// and lob_enqueue_rest (the V-cycle).  The loop's stop flag is ws->scalars->done: lob_enqueue_start expects it cleared.
+struct LobRun {
+    Workspace* ws;
+    const double* elements; const int* rowOffsets; const int* columnIndeces;
+    long long n, ld; int k, largest, relative, pre;
+    double tol; int minIt, maxIt;
+    double *X, *AX, *W, *AW, *P, *AP, *Rv; const double* dinv;
+    double* trace; int traceCap;
+};
+struct LobResult {
+    int iteration, restarts, failWhich, failPivot;     // failWhich: 0 none, 1 X0^T X0, 2 W^T W (or a zero column of W), 3 the basis [X W], 4 theta, 5 theta of the start block
+    double theta[kBlockMaxK], residual[kBlockMaxK], trueResidual[kBlockMaxK]; int status[kBlockMaxK];
+};
+bool lob_enqueue_start(const LobRun& R);               // AX, the orthonormal start block, its Ritz values
+int lob_enqueue_residual(const LobRun& R);             // body: R, its column sums (and W unless pre = 2); returns the partial sums per column
+bool lob_enqueue_rest(const LobRun& R, int body, int nR);   // body: the judgement (of nR partial sums), the W step, AW, the Gram matrices, the dense step, the combine pass
+bool lob_enqueue_close(const LobRun& R);               // AX = A X once more, R = AX - X theta, the true residuals
+bool lob_read_results(Workspace* ws, int k, LobResult* out);
 
 // Mixed-precision CG (SolveMixed; kernels_mixed.hip has the loop and its rounding contract).  e32: the matrix values as floats (MgcgMixedSetup).
 // y = A32 x in fp32, every row summed in stored order (lane = row form) or, for long rows outside dot_order = 1, per lane and then across the

@@ -541,6 +541,16 @@ static void csrmv_block(hipStream_t s, double* y, const double* elements, const 
     (void)launch_spmv_block<K>(s, BEPI_PLAIN, a, count >= 8000000);
 }
 
+void launch_spmv_block_plain(hipStream_t s, int k, const double* elements, const int* rowOffsets, const int* columnIndeces,
+                             const double* x, double* y, long long ld, long long rows, const int* done)
+{
+    if (rows <= 0) return;
+    BlockSpmvArgs a{};
+    a.elements = elements; a.rowOffsets = rowOffsets; a.columnIndeces = columnIndeces;
+    a.x = x; a.y = y; a.ld = ld; a.rows = (int)rows; a.done = done;
+    dispatch_k(k, [&](auto K) { (void)launch_spmv_block<K.value>(s, BEPI_PLAIN, a, rows >= 8000000); });
+}
+
 void preload_kernels_block() { preload_code_object(reinterpret_cast<const void*>(&block_snapshot_kernel)); }
 
 } // namespace mgcg

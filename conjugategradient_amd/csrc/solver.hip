@@ -1545,6 +1545,52 @@ static int lsqr_solve(CgRun& R, LsqrMatrix& A, LsqrMatrix& At, const LsqrRun& P,
     return cg_return_one(R, who, f.traceCap, iteration, residual, residualTrace, "normal residual", "", nonfinite);
 }
 
+// ---------------------------------------------------------------- LOBPCG (MgcgSolveLobpcg, MgcgSolveLobpcgMg)
+// The k extreme eigenpairs of a symmetric CSR matrix (include/MgcgGpu.h has the method, kernels_lobpcg.hip the passes and the dense step), one
+// rank.  The matrix is read as plain CSR by the block product, so no matrix set-up; the host's side is cg_drive.  A body is the residual pass,
+// with a hierarchy k cycles W_j = M^-1 R_j, and the rest (lob_enqueue_rest); CgRun carries what the host's side of the loop reads.
+static int lob_solve(CgRun& R, LobRun& P, MgcgMg* mg, const char* who, int* iteration, double theta[], double residual[], double trueResidual[],
+                     int status[], int* restarts, double* residualTrace, int traceCapacity)
+{
+    Workspace* ws = R.ws;
+    hipStream_t s = ws->stream;
+    const int k = P.k;
+    const int cap = (residualTrace && traceCapacity > 0) ? traceCapacity : 0;
+    // everything the call allocates, before anything is enqueued
+    if (!ws->ensure_lobpcg() || (cap && !ws->ensure_trace(k * cap))) return MGCG_ERROR;
+    P.trace = cap ? ws->trace : nullptr; P.traceCap = cap;
+    const int* done = &ws->scalars->done;
+    hipLaunchKernelGGL(clear_done_kernel, dim3(1), dim3(1), 0, s, ws->scalars);
+    bool ok = lob_enqueue_start(P);
+    ok = ok && cg_drive_bodies(R, who, [&](int body) {
+        const int nR = lob_enqueue_residual(P);
+        for (int j = 0; mg && j < k; ++j)
+            if (!mg_apply(mg, P.Rv + j * P.ld, P.W + j * P.ld, done)) return false;          // W_j = M^-1 R_j
+        return lob_enqueue_rest(P, body, nR);
+    });
+    ok = ok && lob_enqueue_close(P);
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    LobResult h{};
+    ok = ok && lob_read_results(ws, k, &h);
+    if (!ok) return MGCG_ERROR;
+    const bool startFailed = h.failWhich == 1 || h.failWhich == 5;
+    if (iteration) *iteration = startFailed ? -1 : h.iteration;      // the last body that was judged: none when the start broke down
+    if (restarts) *restarts = h.restarts;
+    int nTrace[kBlockMaxK];
+    for (int j = 0; j < k; ++j) {
+        nTrace[j] = startFailed ? 0 : h.iteration + 1;
+        if (theta) theta[j] = h.theta[j];
+        if (trueResidual) trueResidual[j] = startFailed ? NAN : h.trueResidual[j];
+    }
+    const int worst = cg_return_columns(ws, k, nullptr, h.residual, h.status, nTrace, cap, nullptr, residual, status, residualTrace, traceCapacity, &ok);
+    if (h.failWhich) {
+        static const char* const names[] = { "", "the first factorisation, of X0^T X0 (dependent or zero start columns)", "the factorisation of W^T W (a zero or dependent column of W)",
+                                             "the factorisation of the basis [X W]^T [X W]", "the Ritz values: one is not finite", "the Ritz values of the start block: one is not finite" };
+        set_error("%s: breakdown in %s: pivot %d is not finite and > 0 (body %d); X, AX and theta keep the last completed body", who, names[h.failWhich], h.failPivot, h.iteration);
+    } else cg_columns_message(who, worst, "a residual is not finite", R.maxIt);
+    return ok ? worst : MGCG_ERROR;
+}
+
 // ---------------------------------------------------------------- BiCGStab (SolveBicgstab*, SolveBicgstabJacobi*)
 // Van der Vorst's BiCGStab for A x = b, A any CSR matrix, right-preconditioned with M = I or M = diag(A) (R.dinv) (include/MgcgGpu.h has the
 // method, kernels_bicgstab.hip the passes).  The host's side is cg_drive: a body is two products and four passes (six launches), on several ranks
@@ -2140,6 +2186,49 @@ static int solve_plain(const CgCall& c, double allowableResidual, int minIterati
         st = cg_solve(R, iteration, residual, residualTrace, traceCapacity);
     });
     return st;
+}
+
+// The entry of MgcgSolveLobpcg and MgcgSolveLobpcgMg (lob_solve above): what needs no device is refused before one is asked for, and nothing is enqueued for a call that fails.
+static int lob_entry(const char* who, bool vcycle, MgcgMg* mg, MgcgBlas* cublas, MgcgSparse* cusparse,
+                     Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector, Vector* xVector, Vector* workVector, Vector* dinvVector,
+                     int elementsCount, int count, int k, int largest, double allowableResidual, int relative, int minIteration, int maxIteration,
+                     int* iteration, double theta[], double residual[], double trueResidual[], int status[], int* restarts, double residualTrace[], int traceCapacity)
+{
+    if (!cublas || !cusparse || (vcycle && !mg)) { set_error("%s: null handle", who); return MGCG_ERROR; }
+    if (!elementsVector || !rowOffsetsVector || !columnIndecesVector || !xVector || !workVector) { set_error("%s: null vector handle", who); return MGCG_ERROR; }
+    if (k < 1 || k > kBlockMaxK) { set_error("%s: k = %d eigenpairs, must be 1 .. %d", who, k, kBlockMaxK); return MGCG_ERROR; }
+    if (count < 1 || elementsCount < 0) { set_error("%s: bad sizes (count %d, elementsCount %d)", who, count, elementsCount); return MGCG_ERROR; }
+    if (3LL * k > count) { set_error("%s: k = %d eigenpairs need a basis of %d columns, the matrix has %d rows", who, k, 3 * k, count); return MGCG_ERROR; }
+    if (largest != 0 && largest != 1) { set_error("%s: largest = %d, must be 0 or 1", who, largest); return MGCG_ERROR; }
+    if (relative != 0 && relative != 1) { set_error("%s: relative = %d, must be 0 or 1", who, relative); return MGCG_ERROR; }
+    if (!(allowableResidual >= 0.0 && allowableResidual <= 1.79e308)) { set_error("%s: allowableResidual is negative or not finite", who); return MGCG_ERROR; }
+    if (vcycle && largest) { set_error("%s: largest = 1 is not supported with a hierarchy: its cycle approximates A^-1, which favours the lowest eigenvalues", who); return MGCG_ERROR; }
+    if (residualTrace && traceCapacity > 0 && (long long)k * traceCapacity > 0x7fffffffLL) { set_error("%s: trace capacity too large", who); return MGCG_ERROR; }
+    if (elementsVector->size < elementsCount || columnIndecesVector->size < elementsCount || rowOffsetsVector->size < (long long)count + 1) {
+        set_error("%s: a vector of the matrix is smaller than the matrix (%d stored entries, %d rows)", who, elementsCount, count); return MGCG_ERROR;
+    }
+    const long long kn = (long long)k * count, need = MgcgLobpcgWorkSize(count, k);
+    if (xVector->size < kn) { set_error("%s: the x vector holds %lld entries, k = %d columns of %d rows need %lld", who, xVector->size, k, count, kn); return MGCG_ERROR; }
+    // (need > 0 behind the checks of k and count above; were it not, no size would pass for nothing)
+    if (need <= 0 || workVector->size < need) { set_error("%s: the work vector holds %lld entries, MgcgLobpcgWorkSize(%d, %d) = %lld", who, workVector->size, count, k, need); return MGCG_ERROR; }
+    if (dinvVector && cg_vector_short(who, "dinv", dinvVector, count, "rows")) return MGCG_ERROR;
+    if (vcycle && cg_hierarchy_refused(who, mg, count)) return MGCG_ERROR;
+    if (!device_state()) return MGCG_ERROR;
+    CgRun R;
+    R.ws = &cublas->ws; R.cusparse = cusparse; R.nLocal = count; R.count = count;
+    cg_set_stop(R, allowableResidual, minIteration, maxIteration, MGCG_RULE_CSHARP);
+    if (vcycle && mg->stream != R.ws->stream) { set_error("%s: the hierarchy was set up with another MgcgBlas handle than this call's", who); return MGCG_ERROR; }
+    const long long ld = cg_work_stride(count);
+    double* w = workVector->data;
+    LobRun P{};
+    P.ws = R.ws; P.elements = elementsVector->data; P.rowOffsets = rowOffsetsVector->data; P.columnIndeces = columnIndecesVector->data;
+    P.n = count; P.ld = ld; P.k = k; P.largest = largest; P.relative = relative; P.pre = vcycle ? 2 : dinvVector ? 1 : 0;
+    P.tol = allowableResidual; P.minIt = minIteration; P.maxIt = maxIteration;
+    P.X = xVector->data; P.AX = w; P.W = w + k * ld; P.AW = w + 2 * k * ld; P.P = w + 3 * k * ld; P.AP = w + 4 * k * ld; P.Rv = w + 5 * k * ld;
+    P.dinv = dinvVector ? dinvVector->data : nullptr;
+    cg_note_written({ P.X }, kn);
+    cg_note_written({ w }, need);
+    return lob_solve(R, P, vcycle ? mg : nullptr, who, iteration, theta, residual, trueResidual, status, restarts, residualTrace, traceCapacity);
 }
 
 void preload_solver() { preload_code_object(reinterpret_cast<const void*>(&snapshot_kernel)); }
@@ -3758,6 +3847,41 @@ int MgcgSolveLsqr(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
     cg_note_written({ P.uh, P.q }, rows);
     cg_note_written({ P.x, P.vh, P.w, P.t }, columns);
     return lsqr_solve(R, A, At, P, iteration, residual, residualNorm, trueResidual, trueNormalResidual, residualTrace, traceCapacity);
+}
+
+// LOBPCG (lob_entry above), one rank: no preconditioner or, with dinvVector, the diagonal's; and with a hierarchy, its cycle
+long long MgcgLobpcgWorkSize(int count, int k)
+{
+    if (count < 1 || k < 1 || k > kBlockMaxK) return 0;
+    return 6LL * k * cg_work_stride(count);           // (at most 48 * 2^31: a 64-bit count, as the vectors' sizes are)
+}
+
+int MgcgSolveLobpcg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                    Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    Vector* xVector, Vector* workVector, Vector* dinvVector,
+                    int elementsCount, int count, int k, int largest,
+                    double allowableResidual, int relative, int minIteration, int maxIteration,
+                    int* iteration, double theta[], double residual[], double trueResidual[], int status[], int* restarts,
+                    double residualTrace[], int traceCapacity)
+{
+    (void)matDescr;
+    return lob_entry("MgcgSolveLobpcg", false, nullptr, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, workVector, dinvVector,
+                     elementsCount, count, k, largest, allowableResidual, relative, minIteration, maxIteration,
+                     iteration, theta, residual, trueResidual, status, restarts, residualTrace, traceCapacity);
+}
+
+int MgcgSolveLobpcgMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                      Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                      Vector* xVector, Vector* workVector,
+                      int elementsCount, int count, int k, int largest,
+                      double allowableResidual, int relative, int minIteration, int maxIteration,
+                      int* iteration, double theta[], double residual[], double trueResidual[], int status[], int* restarts,
+                      double residualTrace[], int traceCapacity)
+{
+    (void)matDescr;
+    return lob_entry("MgcgSolveLobpcgMg", true, mg, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, workVector, nullptr,
+                     elementsCount, count, k, largest, allowableResidual, relative, minIteration, maxIteration,
+                     iteration, theta, residual, trueResidual, status, restarts, residualTrace, traceCapacity);
 }
 
 // BiCGStab (cg_solve_bicgstab above; refusals: cg_variant_call).  With `jacobi` dinvVector is a handle the export requires, with `vcycle`

@@ -43,7 +43,7 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
             lib().MgDestroy(self.mg)
             self.mg = None
         # with SolveMinres's, SolveGmres's and SolveBicgstab's work space, if they ran
-        self._dispose_vectors("vectorZ", "vectorW1", "vectorW2", "vectorR1", "vectorWork", *_BICGSTAB_WORK)
+        self._dispose_vectors("vectorZ", "vectorW1", "vectorW2", "vectorR1", "vectorWork", "vectorEigenX", "vectorEigenWork", *_BICGSTAB_WORK)
         self._work_size = 0
         super().Dispose()
 
@@ -128,6 +128,14 @@ class ConjugateGradientMgGpu(ConjugateGradientSingleGpu):
         self._ensure_vectors(self.Count, *_BICGSTAB_WORK)
         self._native_solve("SolveBicgstabMg", "V-cycle-preconditioned BiCGStab", trace, head=(self.mg if hierarchy is None else hierarchy.mg,),
                            work=(self.vectorV.Ptr, self.vectorS.Ptr, self.vectorT.Ptr, self.vectorRhat.Ptr), third=_TRUE)
+
+    def SolveLobpcg(self, k: int, trace: bool = False, hierarchy=None, relative: bool = True, X0=None, seed: int = 1):
+        """The k = 1 .. 8 lowest eigenpairs of the symmetric matrix A by LOBPCG preconditioned with a hierarchy's cycle (MgcgSolveLobpcgMg;
+        ``eigen`` has the results' members: ``Theta``, ``X``, ``Residual``, ``TrueResidual``, ``Iteration``, ``Restarts``, ``status``,
+        ``ColumnStatus``, ``trace``).  The hierarchy is ``self.mg`` or, with ``hierarchy``, the ``mg`` of another object with as many rows;
+        b and x take no part.  ``AllowableResidual`` bounds || A x_j - theta_j x_j ||_2, relative to |theta_j| unless ``relative`` is false."""
+        from .eigen import lobpcg_call
+        lobpcg_call(self, "MgcgSolveLobpcgMg", k, (self.mg if hierarchy is None else hierarchy.mg,), (), False, relative, trace, X0, seed)
 
     def SolveGmres(self, trace: bool = False, hierarchy=None, m: int = 20, orth: int = 2):
         """Solve A x = b, A any CSR matrix, with restarted GMRES(m) right-preconditioned by a hierarchy's V-cycle in the flexible form

@@ -247,8 +247,13 @@ class ConjugateGradientGpu(ConjugateGradient):
             setattr(self, third[0], cells[2].value)
         if trace:
             self.trace = tr[: min(self.Iteration + 1, cap)].copy()      # cap = 0 (a traceCapacity of 0): the empty trace
+        self._raise_for_status(export, what, st)
+
+    def _raise_for_status(self, export, what, st):
+        """What every native solve does with its status once the outputs are stored: ApplicationException past MaxIteration (the
+        library's message is cleared), MgcgError with the library's message for every other status but MGCG_OK."""
         if st == _lib.MAXIT_EXCEEDED:
-            L.MgcgClearLastError()
+            lib().MgcgClearLastError()
             raise ApplicationException(f"{what} did not converge within MaxIteration={self.MaxIteration}")
         if st != _lib.OK:
             check(export)

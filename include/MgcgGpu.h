@@ -1319,6 +1319,83 @@ int MgcgSolveLsqr(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
               int* iteration, double* residual, double* residualNorm /* may be NULL */, double* trueResidual /* may be NULL */,
               double* trueNormalResidual /* may be NULL */, double* residualTrace, int traceCapacity);
 
+/* ---- LOBPCG: the k extreme eigenpairs of a symmetric CSR matrix (one rank) ---- */
+/* MgcgSolveLobpcg: Knyazev's locally optimal block preconditioned CG for the k = 1 .. 8 lowest eigenpairs A x_j = theta_j x_j of a symmetric
+ * count x count CSR matrix (symmetry is not checked), fp64, the matrix read as plain CSR by CsrMVBlock's k-column product whatever
+ * compression mode the handle carries.  "Lowest" means highest when largest = 1.  xVector holds the n x k start block X on entry and the
+ * eigenvectors on return, column j at [j*count, (j+1)*count) as CsrMVBlock takes it.  The preconditioner M^-1 is the identity, the diagonal's
+ * inverse (dinvVector: what MgcgJacobiSetup wrote) or, in MgcgSolveLobpcgMg, the cycle of a one-rank hierarchy whose level 0 has count rows
+ * (MgSetup, MgSetupAggregation(Ex), MgSetupAggregates, the Gauss-Seidel / SSOR and the ILU(0) handles; k calls of MgApply's cycle per body).
+ * The method as computed (m = 3k columns, 2k while P is absent):
+ *   start   AX = A X ;  G = X^T X = U^T U (Cholesky, U upper) ;  X = X U^-1 ; AX = AX U^-1
+ *           H = X^T AX (upper triangle, mirrored) = Z diag(theta) Z^T (cyclic Jacobi, below) ;  X = X Z ; AX = AX Z ;  P absent
+ *   body i  R = AX - X diag(theta) ;  rn_j = || R_j ||_2 ;  the stop decision (below)
+ *           W_j = M^-1 R_j  (identity: W = R; dinv: W = dinv o R inside the same pass; hierarchy: k cycles on the columns)
+ *           T = X^T W (all k x k entries) ;  W_j = W_j - sum_l X_l T[l][j]
+ *           G = W^T W ;  d_a = 1 / sqrt(G_aa) (a G_aa that is not finite and > 0 -- a zero column of W -- : breakdown "W", pivot a) ;
+ *           (d_a G_ab) d_b = U^T U (a failed pivot: breakdown "W") ;  W = W (D U^-1): the columns scaled to 2-norm 1 and orthonormalised,
+ *           both through one k x k coefficient block D U^-1 with (D U^-1)[l][j] = d_l U^-1[l][j]
+ *           AW = A W                                       (the one k-column product of the body)
+ *           S = [X W P], AS = [AX AW AP] ;  G_B = S^T S , G_A = S^T AS   (upper triangles, all entries summed: none is assumed 0 or 1)
+ *           G_B = U^T U ;  with P present a pivot d_i must be finite, > 0 and > 2^-20 (G_B)_ii (computed as d_i > 2^-20 * (G_B)_ii): else P
+ *                          is dropped for this body and the next and the leading 2k problem is formed instead (counted in *restarts);
+ *                          with P absent the test is the raw one, finite and > 0, and a failure is breakdown "basis".  (The error of H
+ *                          is about eps / min d_i: a basis that passes only the raw test lets columns that converged long ago drift
+ *                          until the loop breaks down -- poisson(7,6,5), k = 5, Jacobi: NONFINITE in body 105; it converges with the
+ *                          floor, which keeps that error below 2^-33.)
+ *           H = U^-T (G_A U^-1) (G_A mirrored, both products with full sums; H's upper triangle mirrored) ;  H = Z diag(w) Z^T ;
+ *           C = U^-1 Z[:, lowest k] ;  theta = those w, ascending (descending for largest) ;  a theta that is not finite: breakdown
+ *           Pnew = [W P] C[k:, :] scaled by 1 / sqrt(c_j^T G_B[k:, k:] c_j), its column's 2-norm out of the Gram matrix (c_j = C[k:, j];
+ *           G_B[k:, k:] c_j first, then the sum over its rows; a value that is not finite and > 0 gives the factor 0), APnew by the same
+ *           factor ;  X = S C ;  AX = AS C ;  P = Pnew ; AP = APnew       (one row-local pass, in place)
+ *   close   AX = A X by one more product ;  trueResidual_j = || AX_j - theta_j X_j ||_2 ;  the work vector's R block holds those columns
+ * Nothing is frozen: every column is updated until the loop ends.
+ * The dense symmetric eigenproblem H = Z diag(w) Z^T (order at most 24) is solved by cyclic Jacobi rotations on the device: Z = I; a sweep
+ * visits (p, q) for p = 0 .. m-2, q = p+1 .. m-1 in that order; a pair with |h_pq| <= 2^-53 (|h_pp| + |h_qq|) (or a NaN there) is passed over;
+ * otherwise tau = (h_qq - h_pp) / (2 h_pq), t = 1 / (|tau| + sqrt(1 + tau*tau)) with the sign of tau (+ for 0), c = 1 / sqrt(1 + t*t),
+ * s = t c; for every r but p and q: h_rp = h_pr = c h_rp - s h_rq and h_rq = h_qr = s h_rp + c h_rq (of the old values);
+ * h_pp = h_pp - t h_pq, h_qq = h_qq + t h_pq (old h_pq), h_pq = h_qp = 0; for every r: z_rp = c z_rp - s z_rq, z_rq = s z_rp + c z_rq.
+ * The sweeps end behind the first sweep that rotated nothing, or behind 30.  w is the diagonal; it is sorted ascending (descending for
+ * largest) by a stable sort: equal values keep their index order.
+ * Stop: column j is converged when rn_j <= allowableResidual (relative = 0) or rn_j <= allowableResidual |theta_j| (relative = 1).  The
+ * loop ends in the first body i in which every column is converged and i >= minIteration (MGCG_OK), else in body i >= maxIteration
+ * (MGCG_MAXIT_EXCEEDED; status[j] then says which columns had converged).  The decision is made on the device; the host looks at the flag
+ * every check_every bodies.  *iteration is the index of the last body that was judged; residual[j] = rn_j, theta[j], status[j] and the trace
+ * (rn_j of body i at residualTrace[j*traceCapacity + i], the first min(*iteration + 1, traceCapacity) entries) belong to that body.
+ * Breakdown: a failed first factorisation (dependent or zero start columns, a value that is not finite), a failure in "W" or "basis", or a
+ * theta that is not finite ends the call with MGCG_NONFINITE for every column; X, AX and theta of the last completed body are kept (a valid
+ * orthonormal Ritz block; after a failed start no body was judged: *iteration is -1 and trueResidual NaN; X is the caller's after a failed
+ * first factorisation and X U^-1, orthonormal, where a Ritz value of the start block is not finite); MgcgGetLastError names the factorisation and the pivot.
+ * Rounding contract: every product goes into a double of its own before the add or subtraction that follows it, nothing is fused; a sum over
+ * a block index starts with its first product and adds the others left to right, structural zeros included; the Cholesky factorisation and
+ * the triangular inverse are SolveBlockKrylov's; a Gram entry sum_i a_i b_i is a fixed tree of per-workgroup partial sums, and one serial
+ * left-to-right sum over the rows under dot_order = 1, which makes the whole loop a fixed sequence of IEEE operations
+ * (tests/test_lobpcg_host.py restates it in numpy).
+ *   workVector  MgcgLobpcgWorkSize(count, k) entries: the six blocks AX, W, AW, P, AP, R of k columns each, every column count rounded up
+ *               to even apart: a 64-bit count, as the sizes of the vectors are (512^3 rows with k = 4 need 3.2e9).  0 from
+ *               MgcgLobpcgWorkSize means bad sizes (count < 1 or k outside 1 .. 8); no call is accepted with a work vector of fewer entries.
+ * Refused with MGCG_ERROR, a message and nothing enqueued, before a device is asked for: a null handle; k outside 1 .. 8; count < 1 or
+ * elementsCount < 0; 3k > count; largest or relative outside {0, 1}; allowableResidual negative or not finite; largest = 1 with a hierarchy;
+ * a vector of the matrix, x (k count entries), the work vector or dinv too small, each named; a hierarchy of several ranks or whose level 0
+ * has not count rows.
+ * Out of scope: soft locking of converged columns, generalised problems A x = lambda B x, k > 8, several ranks, interior eigenvalues and
+ * shift-invert, the C++ twin under host/; MgcgEstimateSpectrum stays as it is. */
+long long MgcgLobpcgWorkSize(int count, int k);
+int MgcgSolveLobpcg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr,
+                    Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                    Vector* xVector /* count*k, in: start block, out: eigenvectors */, Vector* workVector, Vector* dinvVector /* may be NULL */,
+                    int elementsCount, int count, int k, int largest,
+                    double allowableResidual, int relative, int minIteration, int maxIteration,
+                    int* iteration, double theta[], double residual[], double trueResidual[] /* may be NULL */, int status[], int* restarts,
+                    double residualTrace[], int traceCapacity);
+int MgcgSolveLobpcgMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr, MgcgMg* mg,
+                      Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
+                      Vector* xVector, Vector* workVector,
+                      int elementsCount, int count, int k, int largest,
+                      double allowableResidual, int relative, int minIteration, int maxIteration,
+                      int* iteration, double theta[], double residual[], double trueResidual[] /* may be NULL */, int status[], int* restarts,
+                      double residualTrace[], int traceCapacity);
+
 /* ---- Chebyshev-preconditioned CG: a polynomial preconditioner for any CSR matrix, no global sum inside it (one rank or several) ---- */
 /* *bound = the maximum, over the local rows [offsetForDevice, +countForDevice), of sum_j |a_ij| -- times dinv_i when dinvVector (what
  * MgcgJacobiSetup wrote) is given: Gershgorin's upper bound of the spectrum of A (of D^-1 A), rigorous, usually within a small factor
