@@ -7,6 +7,7 @@
 ``amg``       the same V-cycle for ANY CSR matrix: aggregates from the matrix graph (MgSetupAggregation) or from the caller;
               ``strength="symmetric"`` (MgSetupAggregationEx) matches on the symmetric part, for A != A^T that does not coarsen otherwise
               ``amg.csr_transpose_gpu`` / ``amg.transpose_gpu``: A^T of any CSR matrix formed on the device (MgcgCsrTranspose), values as bit copies
+              ``amg.csr_multiply_gpu`` / ``amg.multiply_gpu``: C = A B of two CSR matrices formed on the device (MgcgCsrMultiply), every sum in a fixed order
 ``ssor``      SSOR(omega)-preconditioned CG / MINRES / BiCGStab: the one-level form of ``amg`` with two multicolour Gauss-Seidel sweeps
 ``ilu``       multicolour ILU(0)-preconditioned CG / MINRES / BiCGStab / GMRES(m) (MgSetupIlu0): the incomplete factorisation in the colour
               order of ``ssor``, stored so that every colour is one contiguous stream and M^-1 reads the factor once

@@ -109,6 +109,8 @@ SIGNATURES = {
     "MgcgSymmetricPart": (_ll, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i]),
     "MgcgCsrTranspose": (_ll, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "MgcgTransposeClassLimits": (None, [_pi, _pi]),
+    "MgcgCsrMultiply": (_ll, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
+    "MgcgMultiplyClassLimits": (None, [_pi, _pi]),
     "MgSetupAggregates": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _i, _i, _d]),
     "MgLevelCopyAggregates": (_i, [_vp, _i, _vp]),
     "MgDestroy": (None, [_vp]),

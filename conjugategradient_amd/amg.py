@@ -117,6 +117,76 @@ def transpose_gpu(system: LinearSystem) -> LinearSystem:
     return LinearSystem(e, c, ro, np.array(system.x, dtype=np.float64), np.array(system.b, dtype=np.float64), f"{system.name}-T", grid=system.grid)
 
 
+def multiply_class_limits():
+    """(shortMax, ldsMax) of ``MgcgCsrMultiply``: a row of C of shortMax products or fewer is formed by one lane in registers, one of
+    ldsMax products or fewer by one workgroup in LDS, a longer one by one workgroup in global scratch.  Needs no GPU."""
+    short, lds = C.c_int(0), C.c_int(0)
+    lib().MgcgMultiplyClassLimits(C.byref(short), C.byref(lds))
+    return short.value, lds.value
+
+
+def csr_multiply_gpu(a, b, columns):
+    """C = A B of two CSR matrices formed on the device (``MgcgCsrMultiply``).  ``a`` and ``b`` are ``(elements or None, column_indices,
+    row_offsets)``; A has ``len(a[2]) - 1`` rows, B has ``len(b[2]) - 1`` rows -- the columns of A -- and ``columns`` columns.  Returns
+    numpy arrays ``(elements, column_indices, row_offsets)`` of C; ``elements`` None in both asks for the pattern alone and gives None back
+    in its place.  Columns of C ascend and appear once a row; c_ij is the serial sum, from +0.0, of its products a_ik * b_kj in the order
+    row i of A and then row k of B store them (no FMA), and a sum that comes to zero stays as a stored 0.0.  Rows may be unsorted, empty
+    and hold duplicates; entries beyond ``row_offsets[-1]`` are ignored.  Two calls: the count of C, then the arrays."""
+    _lib.require_gpu()
+    L = lib()
+    if (a[0] is None) != (b[0] is None):
+        raise MgcgError("csr_multiply_gpu: the elements of a and b are given together, or neither of them")
+    host = {}
+    for key, (e, c, ro) in (("a", a), ("b", b)):
+        host[key + "ro"] = np.ascontiguousarray(ro, dtype=np.int32)
+        host[key + "ci"] = np.ascontiguousarray(c, dtype=np.int32)
+        if e is not None:
+            host[key + "e"] = np.ascontiguousarray(e, dtype=np.float64)
+            if len(host[key + "e"]) != len(host[key + "ci"]):
+                raise MgcgError(f"csr_multiply_gpu: {key}: {len(host[key + 'e'])} values, {len(host[key + 'ci'])} columns")
+    rows, inner, columns = len(host["aro"]) - 1, len(host["bro"]) - 1, int(columns)
+    heldA, heldB = len(host["aci"]), len(host["bci"])
+    blas, sparse = ConjugateGradientGpu.CreateBlas(), ConjugateGradientGpu.CreateSparse()
+    vectors = {}
+    try:
+        for key, array in host.items():
+            vectors[key] = (VectorDouble if key.endswith("e") else VectorInt)(max(len(array), 1))
+            if len(array):
+                vectors[key].CopyFrom(array, len(array))
+        ptr = lambda key: vectors[key].Ptr if key in vectors else None
+        matrices = (blas, sparse, ptr("ae"), ptr("aro"), ptr("aci"), heldA, ptr("be"), ptr("bro"), ptr("bci"), heldB, rows, inner, columns)
+        count = L.MgcgCsrMultiply(*matrices, None, None, None, 0)
+        check("MgcgCsrMultiply")
+        if count < 0:
+            raise MgcgError("MgcgCsrMultiply failed")
+        room = max(int(count), 1)
+        vectors["cro"], vectors["cci"] = VectorInt(rows + 1), VectorInt(room)
+        if a[0] is not None:
+            vectors["ce"] = VectorDouble(room)
+        if L.MgcgCsrMultiply(*matrices, ptr("ce"), ptr("cro"), ptr("cci"), int(count)) != count:
+            check("MgcgCsrMultiply")
+            raise MgcgError("MgcgCsrMultiply failed")
+        return (vectors["ce"].to_numpy(room)[:count] if a[0] is not None else None, vectors["cci"].to_numpy(room)[:count],
+                vectors["cro"].to_numpy(rows + 1))
+    finally:
+        for v in vectors.values():
+            v.Dispose()
+        L.DestroyBlas(blas)
+        L.DestroySparse(sparse)
+
+
+def multiply_gpu(system_a: LinearSystem, system_b: LinearSystem) -> LinearSystem:
+    """A B of two square systems' matrices of one size formed on the device (``csr_multiply_gpu``), with b, x and grid of the first."""
+    n = system_a.Count
+    if system_b.Count != n:
+        raise MgcgError(f"multiply_gpu: {n} rows times {system_b.Count} rows")
+    na, nb = system_a.nnz, system_b.nnz
+    e, c, ro = csr_multiply_gpu((system_a.Elements[:na], system_a.ColumnIndeces[:na], system_a.RowOffsets),
+                                (system_b.Elements[:nb], system_b.ColumnIndeces[:nb], system_b.RowOffsets), n)
+    return LinearSystem(e, c, ro, np.array(system_a.x, dtype=np.float64), np.array(system_a.b, dtype=np.float64),
+                        f"{system_a.name}*{system_b.name}", grid=system_a.grid)
+
+
 class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
     """ConjugateGradientMgGpu without ``grid``: ``Apply``, ``Solve(trace=...)``, ``level_csr`` and ``level_dinv`` are the parent's.
 

@@ -1006,6 +1006,31 @@ void launch_transpose_merged(hipStream_t s, const int* rowOffsets, const int* co
                              int* mergedOffsets, int* mergedColumns, int* mergedSource);
 void preload_kernels_transpose();
 
+// ---------------------------------------------------------------- CSR matrix product C = A B (kernels_multiply.hip; MgcgCsrMultiply)
+constexpr int kMultiplyShortMax = 32;      // a row of C of this many products or fewer is formed by one lane in registers
+constexpr int kMultiplyLdsMax = 2048;      // ... of this many or fewer by one workgroup in LDS; a longer one by one workgroup in global scratch
+constexpr int kMultiplyLongGrid = 64;      // workgroups that walk the work list for such rows, at the most: each holds scratch for the longest row
+struct MultiplyArgs {
+    const double* elementsA; const int* rowOffsetsA; const int* columnIndecesA;      // elementsA, elementsB null: the pattern alone
+    const double* elementsB; const int* rowOffsetsB; const int* columnIndecesB;
+    long long rows;
+    const int* products;                   // u_i, the products of row i of C (launch_multiply_products)
+    const int* work;                       // work[0] rows above the register class, listed from work[1]
+    int* lengths;                          // count pass: the stored entries of every row of C
+    const int* offsetsC; int* outColumnIndeces; double* outElements;                 // fill pass (outElements null: the pattern alone)
+    unsigned long long* scratchKeys; double* scratchProducts; long long scratchStride;
+};
+// *badRow (pre-set to INT_MAX) = the smallest row that stores a column outside [0, bound).  The offsets have passed their check and end at nnz.
+void launch_multiply_check_columns(hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long rows, long long bound, long long nnz, int* badRow);
+// products[i] = u_i; stat2 (pre-set to {INT_MAX, 0}) = {the smallest row with more than INT_MAX products, the largest u_i above
+// kMultiplyShortMax}; work (work[0] zeroed, rows + 1 ints) lists the rows above the register class
+void launch_multiply_products(hipStream_t s, const int* rowOffsetsA, const int* columnIndecesA, const int* rowOffsetsB, long long rows, int* products, int* work, int* stat2);
+// the count pass (fill false) or the fill pass over every row of C; listed = work[0], longest = stat2[1]
+bool launch_multiply_pass(hipStream_t s, const MultiplyArgs& a, bool fill, int listed, int longest, int longGrid);
+// *total (zeroed) = the sum of lengths[0 .. rows) in 64 bits
+void launch_multiply_total(hipStream_t s, const int* lengths, long long rows, unsigned long long* total);
+void preload_kernels_multiply();
+
 // ---------------------------------------------------------------- multicolour Gauss-Seidel smoother (kernels_gs.hip; MgSetSmoother)
 // one colouring round: colourIn (-1 = uncoloured) -> colourOut; flags[0] = 1 if a row is left uncoloured; *badRow (pre-set to INT_MAX) = the
 // smallest row whose neighbours hold all 64 colours

@@ -3261,6 +3261,126 @@ long long MgcgCsrTranspose(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* eleme
     return ok ? nnz : -1;
 }
 
+void MgcgMultiplyClassLimits(int* shortMax, int* ldsMax)
+{
+    if (shortMax) *shortMax = kMultiplyShortMax;
+    if (ldsMax) *ldsMax = kMultiplyLdsMax;
+}
+
+// Every stored column of a matrix whose offsets passed csr_check_offsets and end at nnz lies in [0, bound): the flag comes to the host and,
+// on a refusal, the one offending row, to name its column (the transposition's message).  false with the message set on a refusal.
+static bool csr_check_columns(const char* who, hipStream_t s, const int* rowOffsets, const int* columnIndeces, long long rows, long long bound, long long nnz)
+{
+    int* dflag = nullptr;
+    int bad = 0x7fffffff;
+    bool ok = MGCG_HIP(hipMalloc((void**)&dflag, sizeof(int))) && MGCG_HIP(hipMemcpyAsync(dflag, &bad, sizeof(int), hipMemcpyHostToDevice, s));
+    if (ok) launch_multiply_check_columns(s, rowOffsets, columnIndeces, rows, bound, nnz, dflag);
+    ok = ok && MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(&bad, dflag, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    if (dflag) (void)hipFree(dflag);
+    if (!ok || bad == 0x7fffffff) return ok;
+    int ends[2] = { 0, 0 };
+    ok = MGCG_HIP(hipMemcpy(ends, rowOffsets + bad, sizeof(ends), hipMemcpyDeviceToHost));
+    std::vector<int> row((size_t)(ok ? ends[1] - ends[0] : 0));
+    ok = ok && MGCG_HIP(hipMemcpy(row.data(), columnIndeces + ends[0], sizeof(int) * row.size(), hipMemcpyDeviceToHost));
+    if (!ok) return false;
+    for (int c : row)
+        if (c < 0 || c >= bound) { set_error("%s: row %lld stores column %d, the matrix has %lld columns", who, (long long)bad, c, bound); break; }
+    return false;
+}
+
+long long MgcgCsrMultiply(MgcgBlas* cublas, MgcgSparse* cusparse,
+                          Vector* elementsA, VectorInt* rowOffsetsA, VectorInt* columnIndecesA, int elementsCountA,
+                          Vector* elementsB, VectorInt* rowOffsetsB, VectorInt* columnIndecesB, int elementsCountB,
+                          int rows, int inner, int columns, Vector* outElements, VectorInt* outRowOffsets, VectorInt* outColumnIndeces, int outCapacity)
+{
+    const char* who = "MgcgCsrMultiply";
+    if (!cublas || !cusparse || !rowOffsetsA || !columnIndecesA || !rowOffsetsB || !columnIndecesB) { set_error("%s: null handle", who); return -1; }
+    const bool countOnly = !outElements && !outRowOffsets && !outColumnIndeces;
+    if ((elementsA == nullptr) != (elementsB == nullptr) || (!countOnly && (elementsA == nullptr) != (outElements == nullptr))) {
+        set_error("%s: null handle (elementsA, elementsB and outElements are given together, or none of them)", who);
+        return -1;
+    }
+    if (!countOnly && (!outRowOffsets || !outColumnIndeces)) { set_error("%s: null handle (the output vectors are given together or not at all)", who); return -1; }
+    if (rows < 1 || inner < 1 || columns < 1 || elementsCountA < 0 || elementsCountB < 0 || (!countOnly && outCapacity < 0)) {
+        set_error("%s: bad parameters (rows %d, inner %d, columns %d, elementsCountA %d, elementsCountB %d, outCapacity %d)", who, rows, inner, columns,
+                  elementsCountA, elementsCountB, outCapacity);
+        return -1;
+    }
+    if (rowOffsetsA->size < (long long)rows + 1 || columnIndecesA->size < elementsCountA || (elementsA && elementsA->size < elementsCountA)) {
+        set_error("%s: vectors of A too small (%lld values, %lld offsets, %lld columns for %d entries in %d rows)", who, elementsA ? (long long)elementsA->size : -1LL,
+                  (long long)rowOffsetsA->size, (long long)columnIndecesA->size, elementsCountA, rows);
+        return -1;
+    }
+    if (rowOffsetsB->size < (long long)inner + 1 || columnIndecesB->size < elementsCountB || (elementsB && elementsB->size < elementsCountB)) {
+        set_error("%s: vectors of B too small (%lld values, %lld offsets, %lld columns for %d entries in %d rows)", who, elementsB ? (long long)elementsB->size : -1LL,
+                  (long long)rowOffsetsB->size, (long long)columnIndecesB->size, elementsCountB, inner);
+        return -1;
+    }
+    if (!countOnly && (outRowOffsets->size < (long long)rows + 1 || outColumnIndeces->size < outCapacity || (outElements && outElements->size < outCapacity))) {
+        set_error("%s: output vectors too small (%lld values, %lld offsets, %lld columns for a capacity of %d entries in %d rows)", who,
+                  outElements ? (long long)outElements->size : -1LL, (long long)outRowOffsets->size, (long long)outColumnIndeces->size, outCapacity, rows);
+        return -1;
+    }
+    DeviceState* d = device_state();
+    if (!d) return -1;
+    hipStream_t s = d->stream;
+    long long nnzA = 0, nnzB = 0;
+    if (!csr_check_offsets("MgcgCsrMultiply: A", s, rowOffsetsA->data, rows, elementsCountA, &nnzA) ||
+        !csr_check_offsets("MgcgCsrMultiply: B", s, rowOffsetsB->data, inner, elementsCountB, &nnzB) ||
+        !csr_check_columns("MgcgCsrMultiply: A", s, rowOffsetsA->data, columnIndecesA->data, rows, inner, nnzA) ||
+        !csr_check_columns("MgcgCsrMultiply: B", s, rowOffsetsB->data, columnIndecesB->data, inner, columns, nnzB)) return -1;
+
+    const size_t n = (size_t)rows;
+    int *products = nullptr, *work = nullptr, *stat = nullptr, *offsets = nullptr;
+    unsigned long long *keys = nullptr, *dTotal = nullptr, total = 0;
+    double* scratchProducts = nullptr;
+    int hstat[2] = { 0x7fffffff, 0 }, listed = 0;
+    // the products of every row, the work list of the rows above the register class
+    bool ok = MGCG_HIP(hipMalloc((void**)&products, sizeof(int) * n)) && MGCG_HIP(hipMalloc((void**)&work, sizeof(int) * (n + 1))) &&
+              MGCG_HIP(hipMalloc((void**)&stat, sizeof(hstat))) && MGCG_HIP(hipMalloc((void**)&offsets, sizeof(int) * (n + 1))) &&
+              MGCG_HIP(hipMalloc((void**)&dTotal, sizeof(total))) &&
+              MGCG_HIP(hipMemcpyAsync(stat, hstat, sizeof(hstat), hipMemcpyHostToDevice, s)) && MGCG_HIP(hipMemsetAsync(work, 0, sizeof(int), s)) &&
+              MGCG_HIP(hipMemsetAsync(offsets, 0, sizeof(int) * (n + 1), s)) && MGCG_HIP(hipMemsetAsync(dTotal, 0, sizeof(total), s));
+    if (ok) launch_multiply_products(s, rowOffsetsA->data, columnIndecesA->data, rowOffsetsB->data, rows, products, work, stat);
+    ok = ok && MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(hstat, stat, sizeof(hstat), hipMemcpyDeviceToHost, s)) &&
+         MGCG_HIP(hipMemcpyAsync(&listed, work, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    if (ok && hstat[0] != 0x7fffffff) { set_error("%s: row %lld of the product has more than %d products", who, (long long)hstat[0], 0x7fffffff); ok = false; }
+    // the scratch of the global class: one segment of the longest row's products a workgroup, as many workgroups as 1 GiB of keys allows
+    const int longest = hstat[1];
+    int longGrid = 1;
+    MultiplyArgs a = { elementsA ? elementsA->data : nullptr, rowOffsetsA->data, columnIndecesA->data, elementsB ? elementsB->data : nullptr, rowOffsetsB->data,
+                       columnIndecesB->data, rows, products, work, offsets, nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
+    if (ok && longest > kMultiplyLdsMax) {
+        const long long fit = (1LL << 27) / longest;                                    // 2^27 keys = 1 GiB
+        longGrid = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(kMultiplyLongGrid, listed), fit));
+        const size_t room = (size_t)longGrid * (size_t)longest;
+        ok = MGCG_HIP(hipMalloc((void**)&keys, sizeof(unsigned long long) * room)) && (countOnly || !elementsA || MGCG_HIP(hipMalloc((void**)&scratchProducts, sizeof(double) * room)));
+        a.scratchKeys = keys; a.scratchProducts = scratchProducts; a.scratchStride = longest;
+    }
+    // count: the stored entries of every row of C and, in 64 bits, of C
+    ok = ok && launch_multiply_pass(s, a, false, listed, longest, longGrid);
+    if (ok) launch_multiply_total(s, offsets, rows, dTotal);
+    ok = ok && MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(&total, dTotal, sizeof(total), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+    if (ok && total > 0x7fffffffULL) { set_error("%s: the product has %llu entries, more than %d", who, total, 0x7fffffff); ok = false; }
+    if (ok && !countOnly && (long long)total > outCapacity) {
+        set_error("%s: outCapacity %d is below the %llu entries of the product", who, outCapacity, total);
+        ok = false;
+    }
+    if (ok && !countOnly) {                               // every refusal is behind: the outputs are written from here on
+        ok = exclusive_scan(s, offsets, (long long)rows + 1);
+        analysis_note_write(outRowOffsets->data, sizeof(int) * (n + 1));
+        analysis_note_write(outColumnIndeces->data, sizeof(int) * (size_t)total);
+        if (outElements) analysis_note_write(outElements->data, sizeof(double) * (size_t)total);
+        a.lengths = nullptr; a.offsetsC = offsets; a.outColumnIndeces = outColumnIndeces->data; a.outElements = outElements ? outElements->data : nullptr;
+        ok = ok && MGCG_HIP(hipMemcpyAsync(outRowOffsets->data, offsets, sizeof(int) * (n + 1), hipMemcpyDeviceToDevice, s)) &&
+             launch_multiply_pass(s, a, true, listed, longest, longGrid);
+    }
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    for (void* p : { (void*)products, (void*)work, (void*)stat, (void*)offsets, (void*)dTotal, (void*)keys, (void*)scratchProducts })
+        if (p) (void)hipFree(p);
+    return ok ? (long long)total : -1;
+}
+
 MgcgMg* MgSetupAggregates(MgcgBlas* cublas, MgcgSparse* cusparse, Vector* elementsVector, VectorInt* rowOffsetsVector, VectorInt* columnIndecesVector,
                           int elementsCount, int count, int levels, const int levelRows[], const int aggregateOf[],
                           double omega, int nu, int nuCoarse, double sigma)

@@ -503,6 +503,42 @@ long long MgcgCsrTranspose(MgcgBlas* cublas, MgcgSparse* cusparse,
                            Vector* outElements /* NULL iff elementsVector is NULL */, VectorInt* outRowOffsets, VectorInt* outColumnIndeces,
                            VectorInt* outSource /* may be NULL */);
 void      MgcgTransposeClassLimits(int* shortMax, int* ldsMax);           /* the longest column of the register class and of the LDS class (either may be NULL) */
+/* C = A B of two CSR matrices, A rows x inner and B inner x columns, formed on the device into the caller's vectors (device vectors of the
+ * library, as the inputs).  elementsA NULL asks for the pattern alone (elementsB and outElements are then NULL too).  Returns the stored
+ * entries of C.  With all three output vectors NULL it returns that count and writes nothing: the symbolic phase alone.
+ * CONTRACT (one fixed sequence of IEEE operations, the same in every mode and in every call; no atomics on values):
+ *   products: row i of A, walked in stored order, gives stored entries p with column k_p.  Each p contributes the stored entries q of row
+ *             k_p of B, in stored order.  This numbers the products of row i as t = 0, 1, 2, ...
+ *   pattern:  row i of C stores column j exactly when some product of row i lands on j.  Columns ascend and each appears once.  A sum
+ *             that comes out zero is KEPT as a stored 0.0.
+ *   value:    acc = +0.0; for the products that land on j, in ascending t: acc = acc + (a_p * b_q) -- the product is rounded, then the
+ *             sum is rounded (no fused multiply-add) -- c_ij = acc.
+ * Inputs allowed: either matrix may be rectangular.  Rows may be unsorted, empty and hold duplicates, in A and in B alike; duplicates are
+ * separate products, in stored order.  A row of B that no entry of A points to takes no part: its values and, in the product, its columns
+ * are never read (the column check below covers every stored entry of B).  Entries beyond rowOffsets[last] are ignored.  Output entries
+ * beyond the result are left alone.  Non-finite values follow IEEE (inf * 0 is NaN); a NaN's payload is not promised.  Hence a lone
+ * product -0.0 gives +0.0 (0.0 + -0.0), and an integer-valued product whose partial sums stay below 2^53 is exact.
+ * How: one integer pass gives u_i, the products of row i of C; a count pass gives the stored entries of every row, the library's scan the
+ * offsets, and a fill pass writes columns and values -- the count of C is known before anything is written, and no array of all products
+ * exists.  Rows of C fall into three classes: u_i <= *shortMax = 32, one lane with columns and products in registers; u_i <= *ldsMax =
+ * 2048, one workgroup that expands the keys (j << 32) | t into LDS, sorts them and lets the lane at a run's first key sum the run in
+ * ascending t; longer rows, one workgroup doing the same in global scratch of the library's own (slow, correct, no limit but INT_MAX
+ * products a row and the memory: 16 bytes a product of the longest row for each of up to 64 workgroups, 1 GiB of keys at the most).
+ * MgcgMultiplyClassLimits reports the two boundaries.  While it runs the call also holds 3 x rows ints.  The call is synchronous.
+ * Returns -1 with MgcgGetLastError() on a refusal.  Refused before a device is asked for: a null handle; value vectors and outElements
+ * not given together; the three outputs not all given or all NULL; rows, inner or columns < 1; a negative element count or capacity;
+ * input vectors smaller than their counts / rows + 1 / inner + 1; output vectors smaller than outCapacity / rows + 1.  Refused once the
+ * arrays have been read, with the outputs untouched: offsets of A or B that do not start at 0, descend or end beyond the count (the
+ * transposition's messages after "MgcgCsrMultiply: A: " or "... B: "); a column of A outside [0, inner) or of B outside [0, columns)
+ * ("MgcgCsrMultiply: A: row %lld stores column %d, the matrix has %lld columns": the smallest such row, its first such entry); a row of
+ * C with more than INT_MAX products, or a C of more than INT_MAX entries; an outCapacity below the count of C (the message states the
+ * count). */
+long long MgcgCsrMultiply(MgcgBlas* cublas, MgcgSparse* cusparse,
+                          Vector* elementsA /* NULL: pattern only */, VectorInt* rowOffsetsA, VectorInt* columnIndecesA, int elementsCountA,
+                          Vector* elementsB /* NULL iff elementsA is NULL */, VectorInt* rowOffsetsB, VectorInt* columnIndecesB, int elementsCountB,
+                          int rows, int inner, int columns,          /* A: rows x inner, B: inner x columns */
+                          Vector* outElements, VectorInt* outRowOffsets, VectorInt* outColumnIndeces, int outCapacity);
+void      MgcgMultiplyClassLimits(int* shortMax, int* ldsMax);            /* the most products of a row of the register class and of the LDS class (either may be NULL; needs no device) */
 /* MgSetupAggregation with a choice of what the matching reads.  strength = 0: the level's own matrix -- MgSetupAggregation, which is this
  * call with 0, bit for bit.  strength = 1: the matching of every level l runs on S_l, the symmetric part (MgcgSymmetricPart's contract) of
  * the level's OWN matrix A_l: pass 1 on S_l, pass p > 1 on the unscaled Galerkin matrix of pass p - 1 built from S_l; S_l is then freed
