@@ -117,6 +117,9 @@ SIGNATURES = {
     "MgSetInterpolation": (_i, [_vp, _i]),
     "MgSetSmoother": (_i, [_vp, _i]),
     "MgSmoother": (_i, [_vp]),
+    "MgSetCycle": (_i, [_vp, _i, _i]),
+    "MgCycle": (_i, [_vp]),
+    "MgCycleInner": (_i, [_vp]),
     "MgLevelColours": (_i, [_vp, _i]),
     "MgLevelCopyColours": (_i, [_vp, _i, _vp]),
     "MgSetupIlu0": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _d]),

@@ -22,6 +22,8 @@ from .solver import ConjugateGradientGpu, VectorDouble, VectorInt, _ptr
 
 SMOOTHERS = {"jacobi": 0, "gs": 1}          # MgSetSmoother's modes
 STRENGTHS = {"own": 0, "symmetric": 1}      # MgSetupAggregationEx's: what the matching reads
+CYCLES = {"V": 0, "K": 1}                   # MgSetCycle's modes ...
+INNERS = {"conjugate": 0, "minimal": 1}     # ... and the inner steps of the K-cycle
 
 
 def symmetric_part_gpu(system: LinearSystem) -> LinearSystem:
@@ -201,17 +203,27 @@ class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
 
     ``strength``: what the library's matching reads -- "own" (the level's own matrix, the default: MgSetupAggregation) or "symmetric" (the
     symmetric part of every level's own matrix, formed on the device: MgSetupAggregationEx with strength = 1; the level matrices stay
-    sigma * P^T A P of A itself).  For A != A^T, where "own" may not coarsen at all.  Ignored with ``aggregates``."""
+    sigma * P^T A P of A itself).  For A != A^T, where "own" may not coarsen at all.  Ignored with ``aggregates``.
+
+    ``cycle``: "V" (the default) or "K" (MgSetCycle(mg, 1, inner): on every level whose coarse level has a map of its own, two Krylov steps
+    preconditioned by the cycle stand where the V-cycle runs one coarse cycle), with ``inner`` "conjugate" or "minimal" (residual) steps.
+    It is applied in ``Setup()`` after the smoother; a refusal raises MgcgError with the library's message and leaves ``self.mg`` a usable
+    V hierarchy.  The K-cycle is no fixed linear map: ``Apply``, ``Solve`` and ``SolveGmres`` take it, ``SolveMinres``, ``SolveBicgstab`` and
+    ``SolveLobpcg`` raise the library's refusal."""
 
     def __init__(self, count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual,
                  levels: int = 8, passes: int = 3, theta: float = 0.25, minCoarse: int = 64, omega: float = 0.8, nu: int = 1, nuCoarse: int = 4,
                  sigma: float = 0.5, aggregates=None, rule=_lib.RULE_CSHARP, smoother: str = "jacobi",
-                 strength: str = "own"):
+                 strength: str = "own", cycle: str = "V", inner: str = "conjugate"):
         if smoother not in SMOOTHERS:
             raise MgcgError(f"smoother {smoother!r}, must be one of {sorted(SMOOTHERS)}")
         if strength not in STRENGTHS:
             raise MgcgError(f"strength {strength!r}, must be one of {sorted(STRENGTHS)}")
-        self.smoother, self.strength = smoother, strength
+        if cycle not in CYCLES:
+            raise MgcgError(f"cycle {cycle!r}, must be one of {sorted(CYCLES)}")
+        if inner not in INNERS:
+            raise MgcgError(f"inner {inner!r}, must be one of {sorted(INNERS)}")
+        self.smoother, self.strength, self.cycle, self.inner = smoother, strength, cycle, inner
         super().__init__(count, maxNonZeroCount, _minIteration, _maxIteration, allowableResidual, (count, 1, 1),
                          levels=levels, omega=omega, nu=nu, nuCoarse=nuCoarse, sigma=sigma, rule=rule)
         self.passes, self.theta, self.minCoarse = int(passes), float(theta), int(minCoarse)
@@ -258,6 +270,9 @@ class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
         if SMOOTHERS[self.smoother] and L.MgSetSmoother(self.mg, SMOOTHERS[self.smoother]) != 0:
             check("MgSetSmoother")
             raise MgcgError("MgSetSmoother failed")
+        if CYCLES[self.cycle] and L.MgSetCycle(self.mg, CYCLES[self.cycle], INNERS[self.inner]) != 0:
+            check("MgSetCycle")
+            raise MgcgError("MgSetCycle failed")
 
     def level_colours(self, l: int) -> np.ndarray:
         """The colour of every row of level ``l`` under ``smoother="gs"`` (MgcgError under "jacobi")."""

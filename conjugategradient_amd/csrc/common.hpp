@@ -987,6 +987,18 @@ void launch_amg_galerkin_fill(hipStream_t s, long long nc, const int* aggOffsets
 // out[k] = elements[source[k]], k < m: the values of the merged matrix [A | A^T] of MgcgSymmetricPart through its source list
 void launch_amg_gather_values(hipStream_t s, long long m, const int* source, const double* elements, double* out);
 
+// ---------------------------------------------------------------- the K-cycle's vector passes (kernels_kcycle.hip; MgSetCycle)
+// Vectors of n rows of one coarse level; `partials`: that level's kKcycleSums regions of kMaxGrid doubles (0 rho1, 1 beta1, 2 gamma, 3 beta,
+// 4 a2).  inner 0: u = c, 1: u = v.  The sums passes return the partial sums per region (1 under dot_order = 1), which the next pass takes.
+constexpr int kKcycleSums = 5;
+int  launch_kcycle_sums1(hipStream_t s, int inner, const double* c1, const double* v1, const double* b, long long n, double* partials, const int* done);
+int  launch_kcycle_sums2(hipStream_t s, int inner, const double* c2, const double* v2, const double* v1, const double* rr, long long n, double* partials, const int* done);
+// rr = b - a1 v1 with a1 = beta1 / rho1, or b when rho1 broke down
+void launch_kcycle_residual(hipStream_t s, const double* b, const double* v1, double* rr, long long n, const double* partials, int nPartials, const int* done);
+// e = k1 c1 + k2 c2 (c1 / a1 c1 on a breakdown); e may be c2
+void launch_kcycle_combine(hipStream_t s, const double* c1, const double* c2, double* e, long long n, const double* partials, int nPartials, const int* done);
+void preload_kernels_kcycle();
+
 // ---------------------------------------------------------------- CSR transposition (kernels_transpose.hip; MgcgCsrTranspose, MgcgSymmetricPart)
 constexpr int kTransposeShortMax = 32;     // a column stored this often or less is sorted by one lane in registers
 constexpr int kTransposeLdsMax = 4096;     // ... this often or less by one workgroup in LDS; a longer one by one workgroup in global memory

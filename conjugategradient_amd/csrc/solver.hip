@@ -56,6 +56,11 @@ struct MgLevel {
     int* gsRows = nullptr;                 // n (device)
     std::vector<int> gsOffsets;            // colours + 1 (host: a sweep is one launch per colour)
     std::vector<int> gsColourOf;           // n (host): what MgLevelCopyColours hands out
+    // K-cycle (MgSetCycle(mg, 1, inner)), every level that has a finer level and a map of its own -- the C of a K step: four vectors of n rows
+    // and the partial sums of the step's five sums.  All null in V mode.
+    double *kSpare = nullptr;              // the second cycle's other iterate buffer: c1 stays where the first cycle left it, in xa or xb
+    double *kv1 = nullptr, *kv2 = nullptr, *krr = nullptr;   // A c1, A c2, b - a1 v1
+    double* kPartials = nullptr;           // kKcycleSums regions of kMaxGrid doubles
 };
 
 // Multicolour ILU(0) (MgSetupIlu0): the factor of B = P (A + shift diag(A)) P^T in the colour order, rows sorted by new column.  The rows
@@ -79,6 +84,7 @@ struct MgcgMg {
     double omega = 0; int nu = 1, nuCoarse = 4; double sigma = 0.5;
     int interp = 0;                        // 0: piecewise-constant P (slab-local), 1: cell-centred linear P (MgSetInterpolation)
     int smoother = 0;                      // 0: weighted Jacobi, 1: multicolour Gauss-Seidel (MgSetSmoother; aggregation hierarchies only)
+    int cycle = 0, cycleInner = 0;         // MgSetCycle: 0 the V-cycle, 1 the K-cycle with conjugate (0) or minimal-residual (1) inner steps; aggregation hierarchies only
     std::vector<mgcg::MgLevel> lv;
     mgcg::SpmvConfig cfg;
     hipStream_t stream = nullptr;
@@ -113,6 +119,15 @@ static SpmvConfig cfg_of(const MgcgSparse* h)
 {
     SpmvConfig c; c.kernel = h->kernel; c.rowsPerBlock = h->rowsPerBlock; c.flags = h->flags; c.gridBlocks = h->gridBlocks; c.periodRows = h->periodRows; c.tileRows = h->tileRows; c.tilePlanes = h->tilePlanes;
     return c;
+}
+
+// the K step's vectors of one level (MgSetCycle): freed on the way back to V mode and by MgDestroy
+static void kcycle_free(MgLevel& L)
+{
+    for (double** p : { &L.kSpare, &L.kv1, &L.kv2, &L.krr, &L.kPartials }) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
 }
 
 // The interior rows of a row slice -- rows [*i0, *i1) reference local columns only -- and whether its halo exchange should hide behind them
@@ -387,6 +402,33 @@ static void mg_deep_prolong_halo(MgcgMg* mg, MgLevel& L, MgLevel& C, double* cur
     if (L.z1 < L.nz) launch_prolong_add(mg->stream, L.nx, L.ny, 1, cur + (long long)L.z1 * plane, e + (long long)(L.z1 / 2) * cplane, done);
 }
 
+static bool mg_vcycle(MgcgMg* mg, int l, const double* b, double* x0, double* x1, const int* done, double** result);
+
+// The K step on level c of an aggregation hierarchy in K mode (MgSetCycle; the contract is written out in include/MgcgGpu.h), in place of
+// one cycle for the level's right-hand side C.b: two Krylov steps preconditioned by the cycle.  c1 stays in the iterate buffer the first
+// cycle leaves it in; the second cycle ping-pongs between the other one and kSpare.  *result receives e, formed in c2's buffer.  The
+// launch sequence does not depend on the data: a breakdown is decided inside the passes (kernels_kcycle.hip).
+static bool mg_kstep(MgcgMg* mg, int c, const int* done, double** result)
+{
+    MgLevel& C = mg->lv[c];
+    hipStream_t s = mg->stream;
+    auto product = [&](double* x, double* y) {               // y = A_C x: the level's own product, rows summed as every pass of the level sums them
+        SpmvArgs a{};
+        a.elements = C.elements; a.rowOffsets = C.rowOffsets; a.columnIndeces = C.columnIndeces; a.x = x; a.y = y;
+        a.elementsCount = (int)C.nnz; a.rowCount = (int)C.n; a.columnCount = (int)C.nGlobal; a.alpha = 1.0; a.beta = 0.0; a.doneFlag = done;
+        return mg_spmv(mg, C, EPI_AXPBY, a, x);
+    };
+    double *c1 = nullptr, *c2 = nullptr;
+    if (!mg_vcycle(mg, c, C.b, C.xa, C.xb, done, &c1) || !product(c1, C.kv1)) return false;
+    int nSums = launch_kcycle_sums1(s, mg->cycleInner, c1, C.kv1, C.b, C.n, C.kPartials, done);
+    launch_kcycle_residual(s, C.b, C.kv1, C.krr, C.n, C.kPartials, nSums, done);
+    if (!mg_vcycle(mg, c, C.krr, c1 == C.xa ? C.xb : C.xa, C.kSpare, done, &c2) || !product(c2, C.kv2)) return false;
+    nSums = launch_kcycle_sums2(s, mg->cycleInner, c2, C.kv2, C.kv1, C.krr, C.n, C.kPartials, done);
+    launch_kcycle_combine(s, c1, c2, c2, C.n, C.kPartials, nSums, done);
+    *result = c2;
+    return true;
+}
+
 // One V(nu,nu) cycle on level l for right-hand side b (local); x0/x1 are that level's two full-length iterate
 // buffers.  *result receives the buffer that holds the answer.  Mirrors vcycle() of oracle/mg_oracle.c.
 static bool mg_vcycle(MgcgMg* mg, int l, const double* b, double* x0, double* x1, const int* done, double** result)
@@ -406,7 +448,7 @@ static bool mg_vcycle(MgcgMg* mg, int l, const double* b, double* x0, double* x1
         if (!mg_spmv(mg, L, EPI_RESIDUAL, ar, cur)) return false;                              // r = b - A x
         launch_amg_restrict(mg->stream, C.n, L.aggOffsets, L.aggMembers, L.r, C.b, done);      // b_c = P^T r
         double* ec = nullptr;
-        if (!mg_vcycle(mg, l + 1, C.b, C.xa, C.xb, done, &ec)) return false;
+        if (C.kSpare != nullptr ? !mg_kstep(mg, l + 1, done, &ec) : !mg_vcycle(mg, l + 1, C.b, C.xa, C.xb, done, &ec)) return false;   // (K mode, and C has a map of its own)
         launch_amg_prolong_add(mg->stream, L.n, L.agg, cur, ec, done);                         // x += P e
         return mg_smooth(mg, L, b, cur, spare, mg->nu, false, done, result, l == 0);
     }
@@ -2120,6 +2162,15 @@ static bool cg_hierarchy_refused(const char* who, const MgcgMg* mg, int count)
     return true;
 }
 
+// The loops whose recurrence takes M for one fixed linear map (SolveMgParallel, SolveMinresMg, SolveBicgstabMg, MgcgSolveLobpcgMg): the K-cycle
+// is not one (its scalars depend on the vector it is applied to).  True: refused.
+static bool cg_kcycle_refused(const char* who, const MgcgMg* mg)
+{
+    if (mg->cycle == 0) return false;
+    set_error("%s: the hierarchy runs the K-cycle (MgSetCycle), which is not a fixed linear map; this loop needs one -- MgSetCycle(mg, 0, 0) restores the V-cycle, SolveMg and SolveGmresMg take the K-cycle", who);
+    return true;
+}
+
 // Their entry (refusals: cg_variant_call).  params(): the export's refusals of its own sizes, in front of the rule's; slices: how many
 // vectors the work vector holds, cg_work_stride(count) apart; noun, value: the size that the short work vector's message names; loop(R): the solve.
 template <typename Params, typename Loop>
@@ -2212,7 +2263,7 @@ static int lob_entry(const char* who, bool vcycle, MgcgMg* mg, MgcgBlas* cublas,
     // (need > 0 behind the checks of k and count above; were it not, no size would pass for nothing)
     if (need <= 0 || workVector->size < need) { set_error("%s: the work vector holds %lld entries, MgcgLobpcgWorkSize(%d, %d) = %lld", who, workVector->size, count, k, need); return MGCG_ERROR; }
     if (dinvVector && cg_vector_short(who, "dinv", dinvVector, count, "rows")) return MGCG_ERROR;
-    if (vcycle && cg_hierarchy_refused(who, mg, count)) return MGCG_ERROR;
+    if (vcycle && (cg_hierarchy_refused(who, mg, count) || cg_kcycle_refused(who, mg))) return MGCG_ERROR;
     if (!device_state()) return MGCG_ERROR;
     CgRun R;
     R.ws = &cublas->ws; R.cusparse = cusparse; R.nLocal = count; R.count = count;
@@ -3444,6 +3495,7 @@ void MgDestroy(MgcgMg* mg)
         if (L.aggOffsets) (void)hipFree(L.aggOffsets);
         if (L.aggMembers) (void)hipFree(L.aggMembers);
         if (L.gsRows) (void)hipFree(L.gsRows);
+        kcycle_free(L);
         if (L.dinv) (void)hipFree(L.dinv);
         if (L.xa) (void)hipFree(L.xa);
         if (L.xb) (void)hipFree(L.xb);
@@ -3518,6 +3570,42 @@ int MgSetSmoother(MgcgMg* mg, int mode)
 }
 
 int MgSmoother(const MgcgMg* mg) { return mg ? mg->smoother : 0; }
+
+// The K-cycle (the contract is written out in include/MgcgGpu.h; kernels_kcycle.hip).  Mode 1 allocates the K step's vectors on every level
+// that has a finer level and a map of its own; mode 0 frees them.  Nothing else of the hierarchy changes.
+int MgSetCycle(MgcgMg* mg, int cycle, int inner)
+{
+    if (!mg) { set_error("MgSetCycle: null handle"); return -1; }
+    if (cycle != 0 && cycle != 1) { set_error("MgSetCycle: cycle %d, must be 0 (V-cycle) or 1 (K-cycle)", cycle); return -1; }
+    if (inner != 0 && inner != 1) { set_error("MgSetCycle: inner %d, must be 0 (conjugate steps) or 1 (minimal-residual steps)", inner); return -1; }
+    if (mg->ilu) { set_error("MgSetCycle: the handle is an ILU(0) factor (MgSetupIlu0): it has no cycle"); return -1; }
+    if (!mg->algebraic) {
+        set_error("MgSetCycle: the K-cycle needs every level stored; this hierarchy was built from a grid (MgSetupAggregates with 2x2x2 box maps builds the same hierarchy)");
+        return -1;
+    }
+    if (mg->nranks != 1 || mg->multi) { set_error("MgSetCycle: the hierarchy was built for %d rank(s)%s; the K-cycle runs on one rank", mg->nranks, mg->multi ? " on the several-ranks path" : ""); return -1; }
+    if (!device_state()) return -1;
+    if (mg->stream) (void)hipStreamSynchronize(mg->stream);          // no cycle in flight reads the vectors that go
+    if (cycle == 1 && mg->cycle == 0) {
+        bool ok = true;
+        for (int l = 1; ok && l + 1 < mg->levels; ++l) {
+            MgLevel& L = mg->lv[(size_t)l];
+            const size_t bytes = sizeof(double) * (size_t)(L.n > 0 ? L.n : 1);
+            for (double** p : { &L.kSpare, &L.kv1, &L.kv2, &L.krr }) ok = ok && MGCG_HIP(hipMalloc((void**)p, bytes));
+            ok = ok && MGCG_HIP(hipMalloc((void**)&L.kPartials, sizeof(double) * (size_t)kKcycleSums * kMaxGrid));
+        }
+        if (!ok) {                                                   // refused: the hierarchy stays in V mode
+            for (MgLevel& L : mg->lv) kcycle_free(L);
+            return -1;
+        }
+    }
+    if (cycle == 0) for (MgLevel& L : mg->lv) kcycle_free(L);
+    mg->cycle = cycle; mg->cycleInner = cycle == 1 ? inner : 0;
+    return 0;
+}
+
+int MgCycle(const MgcgMg* mg) { return mg ? mg->cycle : 0; }
+int MgCycleInner(const MgcgMg* mg) { return mg ? mg->cycleInner : 0; }
 
 int MgLevelColours(const MgcgMg* mg, int level)
 {
@@ -3729,6 +3817,7 @@ int SolveMgParallel(MgcgComm* comm, MgcgBlas* cublas, MgcgSparse* cusparse, Mgcg
         }
         if (mg->nranks != MgcgCommSize(comm) || mg->multi != comm_multi(comm)) { set_error("SolveMg: the hierarchy was built for %d rank(s)%s", mg->nranks, mg->multi ? " on the several-ranks path" : ""); return false; }
         if (rule == MGCG_RULE_HANDMADECL || rule == MGCG_RULE_VIENNACL) { set_error("SolveMg supports the 2-norm absolute rules only"); return false; }
+        if (comm != nullptr && cg_kcycle_refused("SolveMgParallel", mg)) return false;     // (SolveMg, one rank without a communicator, takes the K-cycle)
         return true;
     };
     int st = MGCG_ERROR;
@@ -4020,7 +4109,7 @@ static int bicgstab_entry(const char* who, bool jacobi, bool vcycle, MgcgMg* mg,
         return !cg_rule_refused(who, rule, "the loop carries no max|r|") && !cg_vector_short(who, "v", vVector, countForDevice, "local rows") &&
                !cg_vector_short(who, "t", tVector, countForDevice, "local rows") && !cg_vector_short(who, "rhat", rhatVector, countForDevice, "local rows") &&
                !cg_vector_short(who, "s", sVector, count, "columns (p and s are full length)") &&
-               !(jacobi && cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows")) && !(vcycle && cg_hierarchy_refused(who, mg, count));
+               !(jacobi && cg_vector_short(who, "dinv", dinvVector, countForDevice, "local rows")) && !(vcycle && (cg_hierarchy_refused(who, mg, count) || cg_kcycle_refused(who, mg)));
     };
     return cg_variant_call(c, cublas && cusparse && vVector && sVector && tVector && rhatVector && (!jacobi || dinvVector) && (!vcycle || mg), checks, [&](CgRun& R) {
         if (vcycle && R.multi) { set_error("%s: the V-cycle form runs on one rank", who); return (int)MGCG_ERROR; }
@@ -4226,7 +4315,7 @@ int SolveMinresMg(MgcgBlas* cublas, MgcgSparse* cusparse, MgcgMatDescr* matDescr
     const CgCall c = cg_call_one_rank(who, cublas, cusparse, elementsVector, rowOffsetsVector, columnIndecesVector, xVector, bVector, ApVector, pVector, rVector, elementsCount, count);
     auto checks = [&] {
         if (!pminres_common_checks(who, shift, rule, r1Vector, w1Vector, w2Vector, count) || cg_vector_short(who, "z", zVector, count, "rows")) return false;
-        return !cg_hierarchy_refused(who, mg, count);
+        return !cg_hierarchy_refused(who, mg, count) && !cg_kcycle_refused(who, mg);
     };
     // one rank always: cg_variant_call refuses in front of the device, and cg_call's second look at checks() finds nothing new
     return cg_variant_call(c, cublas && cusparse && mg && r1Vector && w1Vector && w2Vector && zVector, checks, [&](CgRun& R) {

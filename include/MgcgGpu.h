@@ -606,6 +606,50 @@ int     MgSmoother(const MgcgMg* mg);                                     /* the
 int     MgLevelColours(const MgcgMg* mg, int level);                      /* the colours of the level; 0 under mode 0; -1 on a bad level */
 /* colourOf[0 .. MgLevelRows(level)-1] = the colour of every row.  Returns 0; -1 with MgcgGetLastError() under mode 0 or on a bad level. */
 int     MgLevelCopyColours(const MgcgMg* mg, int level, int colourOf[]);
+/* The cycle of an aggregation hierarchy: 0 (default) the V-cycle, 1 Notay's K-cycle with inner = 0 conjugate or inner = 1 minimal-residual
+ * steps.  With the unsmoothed piecewise-constant transfer of pairwise aggregates the V-cycle's iteration count grows with the matrix; the
+ * K-cycle solves the coarse problem of every level by TWO Krylov steps preconditioned by the cycle, where the V-cycle runs one cycle, and
+ * its count stays flat.  The level matrices, maps, smoother and transfers are the V-cycle's; with L + 1 levels the cycle of level l runs 2^l times per
+ * application for 1 <= l < L and 2^(L-1) times on the last level.
+ *
+ * ACCEPTED: aggregation hierarchies (MgSetupAggregation, MgSetupAggregationEx, MgSetupAggregates), one rank, either smoother.
+ * REFUSED before a device is asked for (-1, MgcgGetLastError(), the handle unchanged and usable): a null handle; cycle outside {0, 1};
+ * inner outside {0, 1}; an ILU(0) handle; a geometric hierarchy (MgSetup / MgSetupParallel); a hierarchy of several ranks.
+ *
+ * The K STEP runs on level l whenever level l + 1 = C is not the last level (C has a map of its own), where the V-cycle calls
+ * cycle(C, b_c) once between the restriction b_c = P^T r and x += P e.  On a hierarchy of one or two levels no level qualifies and the
+ * cycle is the V-cycle bit for bit.  Every vector has C's rows.  Every sum is a dot product of the library: in the default mode per-lane
+ * and per-workgroup partial sums added in a fixed order (reproducible from run to run), under dot_order = 1 one serial sum left to right
+ * from +0.0 of the rounded products.  u(c, v) = c for inner = 0 and v for inner = 1:
+ *     c1 = cycle(C, b_c);   v1 = A_C c1   (the level's own product: rows summed as the level's residual pass sums them)
+ *     rho1 = sum u1_i * v1_i;   beta1 = sum u1_i * b_c,i                                      (u1 = u(c1, v1))
+ *     a1 = beta1 / rho1;   rr_i = b_c,i - p_i with p_i = a1 * v1_i
+ *     c2 = cycle(C, rr);   v2 = A_C c2
+ *     gamma = sum u2_i * v1_i;   beta = sum u2_i * v2_i;   a2 = sum u2_i * rr_i               (u2 = u(c2, v2))
+ *     t = gamma * gamma;   q = t / rho1;   rho2 = beta - q
+ *     g = gamma * a2;   d = rho1 * rho2;   h = g / d;   k1 = a1 - h;   k2 = a2 / rho2
+ *     e_i = p1_i + p2_i with p1_i = k1 * c1_i and p2_i = k2 * c2_i
+ * Every named quantity is one rounded operation on doubles; no product is fused with the sum or difference that takes it.  e takes the
+ * place of the V-cycle's coarse result.  (inner = 0 is two steps of CG on A_C e = b_c preconditioned by the cycle, inner = 1 the two-step
+ * minimal-residual form: c1^T (b_c - A_C e) = c2^T (b_c - A_C e) = 0, respectively the same with v1 and v2.)
+ * BREAKDOWN is decided on the device, with no host read; "finite and > 0" is the library's test 0 < v <= 1.79e308:
+ *     rho1 not finite or not > 0:             rr = b_c and e = c1, the V-cycle's answer (b_c = 0 gives e = +0.0, never NaN);
+ *     otherwise rho2 not finite or not > 0:   e_i = a1 * c1_i.
+ * The second cycle and its product are enqueued in every case: the launch sequence does not depend on the data.  Notay's early exit
+ * (no second step when ||rr|| <= 0.25 ||b_c||) would need a data-dependent launch and is not built.
+ *
+ * WHICH SOLVES: under mode 1 M is no longer one fixed linear map (a1, k1, k2 depend on the vector).  MgApply and SolveGmresMg (flexible by
+ * construction) take it.  SolveMg takes it and KEEPS its standard beta = r_new . z_new / r . z: a CPU trial of both on 32^3 .. 64^3 Poisson matrices
+ *  saw the same iteration counts with the standard and with the flexible (Polak-Ribiere) beta.  SolveMgParallel, SolveMinresMg, SolveBicgstabMg and MgcgSolveLobpcgMg refuse a handle in mode 1 at
+ * entry, before anything is enqueued, with a message that names MgSetCycle; the handle and the caller's vectors stay untouched.
+ * STORAGE: every level that is the C of a K step gets four vectors of its rows (the second cycle's spare iterate buffer, so that c1 stays
+ * where the first cycle left it, v1, v2 and rr) and 5 x 2048 doubles of partial sums, allocated by mode 1 and freed by mode 0 and MgDestroy.
+ * An allocation failure is a refusal that leaves the hierarchy in V mode.
+ * Returns 0; -1 on a refusal.  Mode 0 after mode 1 restores the V-cycle bit for bit; mode 1 twice gives the same bits (the second call may
+ * change inner).  Not to be called while a solve on the hierarchy is running. */
+int     MgSetCycle(MgcgMg* mg, int cycle, int inner);
+int     MgCycle(const MgcgMg* mg);                                        /* the mode in force (0 for NULL) */
+int     MgCycleInner(const MgcgMg* mg);                                   /* the inner steps in force (0 for NULL and under mode 0) */
 /* Multicolour ILU(0): M = L U, the incomplete factorisation without fill of A + shift * diag(A) in the COLOUR ORDER, as one more kind of
  * MgcgMg handle.  MgApply, SolveMg, SolveMinresMg, SolveBicgstabMg and SolveGmresMg take it wherever they take a hierarchy: z = M^-1 r is
  * U^-1 L^-1 r.  One rank; any CSR matrix with a stored diagonal in every row, rows in any stored order, no column twice in a row, a
