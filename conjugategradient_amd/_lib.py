@@ -113,6 +113,9 @@ SIGNATURES = {
     "MgcgMultiplyClassLimits": (None, [_pi, _pi]),
     "MgSetupAggregates": (_vp, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _d, _i, _i, _d]),
     "MgLevelCopyAggregates": (_i, [_vp, _i, _vp]),
+    "MgUpdateValues": (_i, [_vp, _vp, _i]),
+    "MgUpdateBytes": (_ll, [_vp]),
+    "MgLevelCopyGalerkinSources": (_ll, [_vp, _i, _vp, _vp]),
     "MgDestroy": (None, [_vp]),
     "MgSetInterpolation": (_i, [_vp, _i]),
     "MgSetSmoother": (_i, [_vp, _i]),

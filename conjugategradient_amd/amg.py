@@ -274,6 +274,43 @@ class ConjugateGradientAmgGpu(ConjugateGradientMgGpu):
             check("MgSetCycle")
             raise MgcgError("MgSetCycle failed")
 
+    def UpdateValues(self, elements=None):
+        """New values for the pattern the hierarchy was built from (``MgUpdateValues``): the maps, the colours and the modes stay, every
+        coarse matrix and every D^-1 is formed again -- bit for bit what ``aggregates=[level_aggregates(l) ...]`` builds from the new
+        values, not necessarily what the matching would choose for them.  ``elements``: a host array of the nnz values in stored order,
+        which overwrites ``self.A.Elements`` and ``vectorA``; or None, for a caller who wrote ``vectorA`` on the device.  A refusal (a bad
+        diagonal on some level among them) raises MgcgError with the library's message and leaves the coarse levels and D^-1 as they were."""
+        nnz = int(self.A.RowOffsets[self.Count]) if self.A is not None else self._nnz
+        if elements is not None:
+            e = np.ascontiguousarray(elements, dtype=np.float64)
+            if e.shape != (nnz,):
+                raise MgcgError(f"UpdateValues: {e.size} values, the matrix has {nnz} entries")
+            if self.A is not None:                          # (a new array: ``load`` may have taken the system's own, which stays the caller's)
+                held = np.array(self.A.Elements, dtype=np.float64)
+                held[:nnz] = e
+                self.A.Elements = held
+            self.vectorA.CopyFrom(e, nnz)
+        status = lib().MgUpdateValues(self.mg, self.vectorA.Ptr, nnz)
+        check("MgUpdateValues")
+        if status != 0:
+            raise MgcgError("MgUpdateValues failed")
+
+    def update_bytes(self) -> int:
+        """Device bytes of the source lists and shadow buffers of ``UpdateValues`` (0 before its first call)."""
+        return int(lib().MgUpdateBytes(self.mg))
+
+    def level_galerkin_sources(self, l: int):
+        """``(sources, segment_offsets)`` of level ``l``: entry q of level ``l + 1`` is sigma times the serial sum of level l's stored entries
+        ``sources[segment_offsets[q]:segment_offsets[q + 1]]`` in that order (MgcgError before the first ``UpdateValues`` and on the last level)."""
+        L = lib()
+        offsets = np.empty(max(int(L.MgLevelNnz(self.mg, l + 1)), 0) + 1, dtype=np.int32)
+        sources = np.empty(max(int(L.MgLevelNnz(self.mg, l)), 1), dtype=np.int32)
+        count = L.MgLevelCopyGalerkinSources(self.mg, l, _ptr(offsets), _ptr(sources))
+        check("MgLevelCopyGalerkinSources")
+        if count < 0:
+            raise MgcgError("MgLevelCopyGalerkinSources failed")
+        return sources[:count], offsets
+
     def level_colours(self, l: int) -> np.ndarray:
         """The colour of every row of level ``l`` under ``smoother="gs"`` (MgcgError under "jacobi")."""
         c = np.empty(lib().MgLevelRows(self.mg, l), dtype=np.int32)

@@ -987,6 +987,20 @@ void launch_amg_galerkin_fill(hipStream_t s, long long nc, const int* aggOffsets
 // out[k] = elements[source[k]], k < m: the values of the merged matrix [A | A^T] of MgcgSymmetricPart through its source list
 void launch_amg_gather_values(hipStream_t s, long long m, const int* source, const double* elements, double* out);
 
+// ---------------------------------------------------------------- the numeric refresh of an aggregation hierarchy (kernels_refresh.hip; MgUpdateValues)
+constexpr int kRefreshTile = 2048;         // entries of the source list a workgroup stages in LDS at a time (16 KiB of values)
+// The source list of sigma * P^T A P, built once per level from the pattern and the map (C's offsets and columns as the set-up left them).
+// Count pass: counts[q] (zeroed, nnz(C) + 1 ints) = the entries of A behind coarse entry q; the caller scans them into segment offsets.
+// Fill pass: sources[segment of q] = the stored positions of those entries in the contract's order; cursor = a copy of the offsets (consumed).
+void launch_refresh_sources_count(hipStream_t s, long long nc, const int* aggOffsets, const int* members, const int* rowOffsets, const int* columnIndeces,
+                                  const int* agg, const int* rowOffsetsC, const int* columnIndecesC, int* counts);
+void launch_refresh_sources_fill(hipStream_t s, long long nc, const int* aggOffsets, const int* members, const int* rowOffsets, const int* columnIndeces,
+                                 const int* agg, const int* rowOffsetsC, const int* columnIndecesC, int* cursor, long long held, int* sources);
+// elementsC[q] = sigma * (((+0.0 + a[src[o]]) + a[src[o + 1]]) + ...), o in [segmentOffsets[q], segmentOffsets[q + 1]), q < segments
+void launch_refresh_numeric(hipStream_t s, long long segments, long long sourceCount, const int* segmentOffsets, const int* sources, const double* elements,
+                            double sigma, double* elementsC);
+void preload_kernels_refresh();
+
 // ---------------------------------------------------------------- the K-cycle's vector passes (kernels_kcycle.hip; MgSetCycle)
 // Vectors of n rows of one coarse level; `partials`: that level's kKcycleSums regions of kMaxGrid doubles (0 rho1, 1 beta1, 2 gamma, 3 beta,
 // 4 a2).  inner 0: u = c, 1: u = v.  The sums passes return the partial sums per region (1 under dot_order = 1), which the next pass takes.

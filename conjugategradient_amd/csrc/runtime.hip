@@ -107,7 +107,7 @@ DeviceState* device_state()
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, pd) == hipSuccess) d->numCu = prop.multiProcessorCount;
         preload_kernels_spmv(); preload_kernels_rowtile(); preload_kernels_blas1(); preload_solver(); preload_ops();
-        preload_kernels_rows(); preload_kernels_mg(); preload_kernels_amg(); preload_kernels_kcycle(); preload_kernels_transpose(); preload_kernels_multiply(); preload_kernels_gs(); preload_kernels_ilu(); preload_kernels_dcsr(); preload_kernels_tiled(); preload_kernels_pb(); preload_kernels_block(); preload_kernels_shift(); preload_kernels_bkrylov(); preload_kernels_mixed(); preload_kernels_sreduce(); preload_kernels_cheb(); preload_kernels_minres(); preload_kernels_pminres(); preload_kernels_bicgstab(); preload_kernels_bicgstabl(); preload_kernels_gmres(); preload_kernels_lsqr(); preload_kernels_lobpcg(); preload_comm(); preload_spectrum();
+        preload_kernels_rows(); preload_kernels_mg(); preload_kernels_amg(); preload_kernels_kcycle(); preload_kernels_refresh(); preload_kernels_transpose(); preload_kernels_multiply(); preload_kernels_gs(); preload_kernels_ilu(); preload_kernels_dcsr(); preload_kernels_tiled(); preload_kernels_pb(); preload_kernels_block(); preload_kernels_shift(); preload_kernels_bkrylov(); preload_kernels_mixed(); preload_kernels_sreduce(); preload_kernels_cheb(); preload_kernels_minres(); preload_kernels_pminres(); preload_kernels_bicgstab(); preload_kernels_bicgstabl(); preload_kernels_gmres(); preload_kernels_lsqr(); preload_kernels_lobpcg(); preload_comm(); preload_spectrum();
     }
     return d;
 }

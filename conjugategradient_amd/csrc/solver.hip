@@ -61,6 +61,14 @@ struct MgLevel {
     double *kSpare = nullptr;              // the second cycle's other iterate buffer: c1 stays where the first cycle left it, in xa or xb
     double *kv1 = nullptr, *kv2 = nullptr, *krr = nullptr;   // A c1, A c2, b - a1 v1
     double* kPartials = nullptr;           // kKcycleSums regions of kMaxGrid doubles
+    // MgUpdateValues, all null before its first call.  A level that has a map: the source list of the product that forms the next level
+    // (kernels_refresh.hip).  Every level: the buffers the next refresh writes -- D^-1 and, below the first level, the values -- which change
+    // places with dinv and elements when a refresh succeeds.
+    int* refreshSegments = nullptr;        // nnz of the next level + 1
+    int* refreshSources = nullptr;         // refreshCount stored positions of this level
+    long long refreshCount = 0;
+    double* shadowElements = nullptr;      // nnz (levels >= 1)
+    double* shadowDinv = nullptr;          // n
 };
 
 // Multicolour ILU(0) (MgSetupIlu0): the factor of B = P (A + shift diag(A)) P^T in the colour order, rows sorted by new column.  The rows
@@ -111,6 +119,12 @@ struct MgcgMg {
     bool algebraic = false;                // built from aggregates of the matrix graph, not from a grid (also when it has a single level)
     int strength = 0;                      // what the matching read (MgSetupAggregationEx): 0 the level's own matrix, 1 its symmetric part
     mgcg::MgIlu* ilu = nullptr;            // MgSetupIlu0: the handle is an ILU(0) factor (one level, one rank), M^-1 = U^-1 L^-1; owned
+    // MgUpdateValues (aggregation hierarchies): the handle whose analysis cache serves the levels (not owned); after the first call the
+    // device flags (two ints a level: the bad row, D^-1 differs) and first D^-1 of every level that one copy brings to the host, and the
+    // device bytes of the lists and shadow buffers
+    MgcgSparse* sparse = nullptr;
+    int* refreshFlags = nullptr; double* refreshScalars = nullptr;
+    long long refreshBytes = 0;
 };
 
 namespace mgcg {
@@ -3050,6 +3064,7 @@ static MgcgMg* amg_setup(const char* who, MgcgBlas* cublas, MgcgSparse* cusparse
     mg->omega = omega; mg->nu = nu; mg->nuCoarse = nuCoarse; mg->sigma = sigma; mg->stream = s; mg->cfg = cfg_of(cusparse);
     mg->cfg.kernel = 0;   // every level picks its kernel from its own nnz/row
     mg->algebraic = true;
+    mg->sparse = cusparse;
     int* dflag = nullptr;
     bool ok = MGCG_HIP(hipMalloc((void**)&dflag, sizeof(int)));
     AmgMatrix A; A.elements = elementsVector->data; A.rowOffsets = rowOffsetsVector->data; A.columnIndeces = columnIndecesVector->data; A.n = count; A.nnz = elementsCount;
@@ -3475,11 +3490,153 @@ int MgLevelCopyAggregates(const MgcgMg* mg, int level, int aggregateOf[])
     return MGCG_HIP(hipMemcpy(aggregateOf, L.agg, sizeof(int) * (size_t)L.n, hipMemcpyDeviceToHost)) ? 0 : -1;
 }
 
+// The first MgUpdateValues of a hierarchy: the source list of every level that has a map (count, scan, fill: kernels_refresh.hip), the
+// shadow buffers and the flags.  One int per level comes to the host: where the offsets end, which must be within the level's entries.
+// Whatever a failure leaves allocated stays on the level and is freed by MgDestroy; refreshFlags is set last and says "built".
+static bool refresh_build(const char* who, MgcgMg* mg)
+{
+    hipStream_t s = mg->stream;
+    long long bytes = 0;
+    bool ok = true;
+    for (int l = 0; ok && l < mg->levels; ++l) {
+        MgLevel& L = mg->lv[(size_t)l];
+        const size_t nAlloc = (size_t)(L.n > 0 ? L.n : 1), nzAlloc = (size_t)(L.nnz > 0 ? L.nnz : 1);
+        if (!L.shadowDinv) { ok = MGCG_HIP(hipMalloc((void**)&L.shadowDinv, sizeof(double) * nAlloc)); bytes += (long long)(sizeof(double) * nAlloc); }
+        if (ok && l > 0 && !L.shadowElements) { ok = MGCG_HIP(hipMalloc((void**)&L.shadowElements, sizeof(double) * nzAlloc)); bytes += (long long)(sizeof(double) * nzAlloc); }
+        if (!ok || l + 1 >= mg->levels || L.agg == nullptr || L.refreshSegments != nullptr) continue;
+        const MgLevel& C = mg->lv[(size_t)l + 1];
+        const size_t segments = (size_t)C.nnz;
+        int* cursor = nullptr;
+        int total = 0;
+        ok = MGCG_HIP(hipMalloc((void**)&L.refreshSegments, sizeof(int) * (segments + 1))) && MGCG_HIP(hipMalloc((void**)&L.refreshSources, sizeof(int) * nzAlloc)) &&
+             MGCG_HIP(hipMalloc((void**)&cursor, sizeof(int) * (segments + 1))) && MGCG_HIP(hipMemsetAsync(L.refreshSegments, 0, sizeof(int) * (segments + 1), s));
+        bytes += (long long)(sizeof(int) * (segments + 1) + sizeof(int) * nzAlloc);
+        if (ok) launch_refresh_sources_count(s, C.n, L.aggOffsets, L.aggMembers, L.rowOffsets, L.columnIndeces, L.agg, C.rowOffsets, C.columnIndeces, L.refreshSegments);
+        ok = ok && MGCG_HIP(hipGetLastError()) && exclusive_scan(s, L.refreshSegments, (long long)segments + 1) &&
+             MGCG_HIP(hipMemcpyAsync(cursor, L.refreshSegments, sizeof(int) * (segments + 1), hipMemcpyDeviceToDevice, s)) &&
+             MGCG_HIP(hipMemcpyAsync(&total, L.refreshSegments + segments, sizeof(int), hipMemcpyDeviceToHost, s)) && MGCG_HIP(hipStreamSynchronize(s));
+        if (ok && (total < 0 || total > L.nnz)) {
+            set_error("%s: level %d: the row offsets reach %d entries, the level holds %lld: they are not those of the set-up", who, l, total, L.nnz);
+            ok = false;
+        }
+        if (ok) {
+            launch_refresh_sources_fill(s, C.n, L.aggOffsets, L.aggMembers, L.rowOffsets, L.columnIndeces, L.agg, C.rowOffsets, C.columnIndeces, cursor, total, L.refreshSources);
+            ok = MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipStreamSynchronize(s));
+        }
+        if (cursor) (void)hipFree(cursor);
+        if (ok) L.refreshCount = total;
+        else {                                             // (a list that is not whole must not pass for one at the next call)
+            if (L.refreshSegments) (void)hipFree(L.refreshSegments);
+            if (L.refreshSources) (void)hipFree(L.refreshSources);
+            L.refreshSegments = nullptr; L.refreshSources = nullptr;
+        }
+    }
+    ok = ok && MGCG_HIP(hipMalloc((void**)&mg->refreshScalars, sizeof(double) * (size_t)mg->levels));
+    mg->refreshBytes += bytes;
+    if (ok) ok = MGCG_HIP(hipMalloc((void**)&mg->refreshFlags, 2 * sizeof(int) * (size_t)mg->levels));
+    if (ok) mg->refreshBytes += (long long)((2 * sizeof(int) + sizeof(double)) * (size_t)mg->levels);
+    else if (mg->refreshScalars) { (void)hipFree(mg->refreshScalars); mg->refreshScalars = nullptr; }
+    return ok;
+}
+
+int MgUpdateValues(MgcgMg* mg, Vector* elementsVector, int elementsCount)
+{
+    const char* who = "MgUpdateValues";
+    if (!mg || !elementsVector) { set_error("%s: null argument", who); return -1; }
+    if (mg->ilu) { set_error("%s: the handle is an ILU(0) factor: it has no numeric refresh, call MgSetupIlu0 again for the new values", who); return -1; }
+    if (!mg->algebraic) {
+        set_error("%s: a geometric hierarchy has no numeric refresh, call MgSetup again for the new values (MgSetupAggregates with 2x2x2 box maps builds the same "
+                  "hierarchy, which can be refreshed)", who);
+        return -1;
+    }
+    if (mg->nranks != 1 || mg->multi) { set_error("%s: the hierarchy was built for %d rank(s)%s; the refresh runs on one rank", who, mg->nranks, mg->multi ? " on the several-ranks path" : ""); return -1; }
+    if (mg->levels < 1 || mg->lv.empty()) { set_error("%s: the hierarchy has no level", who); return -1; }
+    if (elementsCount != mg->lv[0].nnz) { set_error("%s: elementsCount %d, the hierarchy was built from %lld entries (MgLevelNnz(mg, 0))", who, elementsCount, mg->lv[0].nnz); return -1; }
+    if (elementsVector->size < elementsCount) { set_error("%s: the vector holds %lld values, fewer than the %d entries", who, (long long)elementsVector->size, elementsCount); return -1; }
+    if (!device_state()) return -1;
+    hipStream_t s = mg->stream;
+    const int levels = mg->levels;
+    if (mg->refreshFlags == nullptr && !refresh_build(who, mg)) return -1;
+
+    // every level: check, D^-1 and its uniformity on the new values, then the next level's values -- all into the shadow buffers
+    std::vector<int> flags(2 * (size_t)levels);
+    std::vector<double> scalars((size_t)levels, 0.0);
+    for (int l = 0; l < levels; ++l) { flags[2 * (size_t)l] = 0x7fffffff; flags[2 * (size_t)l + 1] = 0; }
+    bool ok = MGCG_HIP(hipMemcpyAsync(mg->refreshFlags, flags.data(), sizeof(int) * flags.size(), hipMemcpyHostToDevice, s));
+    const double* values = elementsVector->data;
+    for (int l = 0; ok && l < levels; ++l) {
+        MgLevel& L = mg->lv[(size_t)l];
+        launch_amg_check_diagonal(s, values, L.rowOffsets, L.columnIndeces, L.n, mg->refreshFlags + 2 * l);
+        launch_extract_dinv(s, values, L.rowOffsets, L.columnIndeces, L.n, 0, L.shadowDinv);
+        launch_uniform_check(s, L.shadowDinv, L.n, mg->refreshFlags + 2 * l + 1);
+        ok = MGCG_HIP(hipGetLastError()) && MGCG_HIP(hipMemcpyAsync(mg->refreshScalars + l, L.shadowDinv, sizeof(double), hipMemcpyDeviceToDevice, s));
+        if (!ok || l + 1 >= levels) break;
+        MgLevel& C = mg->lv[(size_t)l + 1];
+        analysis_note_write(C.shadowElements, sizeof(double) * (size_t)C.nnz);
+        launch_refresh_numeric(s, C.nnz, L.refreshCount, L.refreshSegments, L.refreshSources, values, mg->sigma, C.shadowElements);
+        ok = MGCG_HIP(hipGetLastError());
+        values = C.shadowElements;
+    }
+    ok = ok && MGCG_HIP(hipMemcpyAsync(flags.data(), mg->refreshFlags, sizeof(int) * flags.size(), hipMemcpyDeviceToHost, s)) &&
+         MGCG_HIP(hipMemcpyAsync(scalars.data(), mg->refreshScalars, sizeof(double) * scalars.size(), hipMemcpyDeviceToHost, s));
+    ok = MGCG_HIP(hipStreamSynchronize(s)) && ok;
+    MgLevel& L0 = mg->lv[0];
+    const bool inPlace = elementsVector->data == L0.elements;
+    for (int l = 0; ok && l < levels; ++l)
+        if (flags[2 * (size_t)l] != 0x7fffffff) { set_error("%s: level %d, row %d: the diagonal must be stored, finite and > 0", who, l, flags[2 * (size_t)l]); ok = false; }
+    if (!ok) {
+        // nothing changes hands.  In place, level 0 IS what the caller wrote: its matrix form must not stay that of the values before
+        if (inPlace) {
+            analysis_note_write(L0.elements, sizeof(double) * (size_t)L0.nnz);
+            L0.dcsr = dcsr_lookup(mg->sparse, L0.elements, L0.rowOffsets, L0.columnIndeces, L0.n, L0.nnz, 0);
+        }
+        return -1;
+    }
+    analysis_note_write(L0.elements, sizeof(double) * (size_t)L0.nnz);                        // leaves the hierarchy, or was rewritten
+    analysis_note_write(elementsVector->data, sizeof(double) * (size_t)L0.nnz);
+    L0.elements = elementsVector->data;
+    for (int l = 0; l < levels; ++l) {
+        MgLevel& L = mg->lv[(size_t)l];
+        if (l > 0) {
+            analysis_note_write(L.elements, sizeof(double) * (size_t)L.nnz);
+            std::swap(L.elements, L.shadowElements);
+        }
+        std::swap(L.dinv, L.shadowDinv);
+        L.dinvUniform = flags[2 * (size_t)l + 1] == 0;
+        L.dinvScalar = scalars[(size_t)l];
+        L.dcsr = dcsr_lookup(mg->sparse, L.elements, L.rowOffsets, L.columnIndeces, L.n, L.nnz, 0);
+    }
+    return 0;
+}
+
+long long MgUpdateBytes(const MgcgMg* mg) { return mg ? mg->refreshBytes : 0; }
+
+long long MgLevelCopyGalerkinSources(const MgcgMg* mg, int level, int segmentOffsets[], int sources[])
+{
+    const char* who = "MgLevelCopyGalerkinSources";
+    if (!mg) { set_error("%s: null handle", who); return -1; }
+    if (mg->ilu || !mg->algebraic) { set_error("%s: the handle is no aggregation hierarchy: it has no Galerkin source lists", who); return -1; }
+    if (mg->refreshFlags == nullptr) { set_error("%s: the lists are built by the first MgUpdateValues, which this hierarchy has not seen", who); return -1; }
+    if (level < 0 || level >= mg->levels - 1 || mg->lv[(size_t)level].refreshSegments == nullptr) {
+        set_error("%s: level %d forms no next level (the hierarchy has %d levels)", who, level, mg->levels);
+        return -1;
+    }
+    const MgLevel& L = mg->lv[(size_t)level];
+    const size_t segments = (size_t)mg->lv[(size_t)level + 1].nnz;
+    (void)hipStreamSynchronize(mg->stream);
+    bool ok = true;
+    if (segmentOffsets) ok = ok && MGCG_HIP(hipMemcpy(segmentOffsets, L.refreshSegments, sizeof(int) * (segments + 1), hipMemcpyDeviceToHost));
+    if (sources && L.refreshCount > 0) ok = ok && MGCG_HIP(hipMemcpy(sources, L.refreshSources, sizeof(int) * (size_t)L.refreshCount, hipMemcpyDeviceToHost));
+    return ok ? L.refreshCount : -1;
+}
+
 void MgDestroy(MgcgMg* mg)
 {
     if (!mg) return;
     if (mg->stream) (void)hipStreamSynchronize(mg->stream);
     if (mg->rExt) (void)hipFree(mg->rExt);
+    if (mg->refreshFlags) (void)hipFree(mg->refreshFlags);
+    if (mg->refreshScalars) (void)hipFree(mg->refreshScalars);
     if (mg->ilu) {
         for (void* p : { (void*)mg->ilu->values, (void*)mg->ilu->columns, (void*)mg->ilu->offsets, (void*)mg->ilu->diag, (void*)mg->ilu->pinv, (void*)mg->ilu->rowOf })
             if (p) (void)hipFree(p);
@@ -3496,6 +3653,10 @@ void MgDestroy(MgcgMg* mg)
         if (L.aggMembers) (void)hipFree(L.aggMembers);
         if (L.gsRows) (void)hipFree(L.gsRows);
         kcycle_free(L);
+        if (L.refreshSegments) (void)hipFree(L.refreshSegments);
+        if (L.refreshSources) (void)hipFree(L.refreshSources);
+        if (L.shadowElements) { analysis_note_write(L.shadowElements, sizeof(double) * (size_t)(L.nnz > 0 ? L.nnz : 1)); (void)hipFree(L.shadowElements); }
+        if (L.shadowDinv) (void)hipFree(L.shadowDinv);
         if (L.dinv) (void)hipFree(L.dinv);
         if (L.xa) (void)hipFree(L.xa);
         if (L.xb) (void)hipFree(L.xb);

@@ -650,6 +650,52 @@ int     MgLevelCopyColours(const MgcgMg* mg, int level, int colourOf[]);
 int     MgSetCycle(MgcgMg* mg, int cycle, int inner);
 int     MgCycle(const MgcgMg* mg);                                        /* the mode in force (0 for NULL) */
 int     MgCycleInner(const MgcgMg* mg);                                   /* the inner steps in force (0 for NULL and under mode 0) */
+/* New VALUES for the pattern an aggregation hierarchy was built from: the numeric half of the set-up alone, for time steppers, Newton and
+ * Picard loops and parameter sweeps, which solve a sequence of matrices of one sparsity pattern.  The maps, the pattern of every level,
+ * the colours of MgSetSmoother(mg, 1), the vectors of MgSetCycle, the modes, omega, nu, nuCoarse and sigma stay; the values of every
+ * level below the first, every D^-1 and dinvUniform / dinvScalar are formed again.
+ *
+ * THE RESULT is, bit for bit, the hierarchy MgSetupAggregates builds from the new values and the maps of MgLevelCopyAggregates: the same
+ * level matrices, the same D^-1, hence the same cycle.  THE MAPS ARE KEPT: it is NOT necessarily the hierarchy the matching of
+ * MgSetupAggregation(Ex) would choose for the new values; whether the kept maps still suit them is the caller's judgement (the iteration
+ * counts show it).
+ *
+ * ARGUMENTS: elementsVector holds elementsCount values in the stored order of set-up; elementsCount must equal MgLevelNnz(mg, 0).  It may
+ * be the vector the hierarchy was built from, rewritten in place, or another vector: level 0 then points at it from now on and the caller
+ * keeps it alive, as at set-up (the solvers still multiply by the vectors THEY are given).  THE CALLER'S PROMISE, not checked: the row
+ * offsets and column indices of level 0 are those of set-up, unchanged, in the vectors given then.
+ *
+ * ACCEPTED: one-rank aggregation hierarchies (MgSetupAggregation, MgSetupAggregationEx, MgSetupAggregates), either strength, either
+ * smoother, V or K cycle, one level (only D^-1 changes) or many.  REFUSED before a device is asked for (-1, MgcgGetLastError(), the handle
+ * untouched): a null handle or vector; an ILU(0) handle (the message says: MgSetupIlu0 again); a geometric hierarchy (MgSetup again);
+ * several ranks; elementsCount != MgLevelNnz(mg, 0); a vector of fewer than elementsCount values.
+ *
+ * THE SOURCE LISTS.  By the Galerkin contract above every entry q of level l + 1 is sigma times the serial sum, from +0.0, of a fixed
+ * list of entries of level l in a fixed order: the entries (i, j) with aggregate(i) = row(q) and aggregate(j) = column(q), members i
+ * ascending, each member's entries in stored order.  The first call builds that list for every level that has a map, on the device, from
+ * the pattern and the maps alone (no value is read): sources[segmentOffsets[q] .. segmentOffsets[q + 1]) = the stored positions in level l
+ * of q's entries in that order -- a stable counting sort of the contract-order entry stream by coarse entry.  The lists
+ * (MgLevelNnz(l + 1) + 1 + MgLevelNnz(l) ints per such level) and the shadow buffers below are kept until MgDestroy; MgUpdateBytes tells
+ * what they hold.  A handle that never sees this call allocates none of it.
+ *
+ * THE NUMERIC PASS, one launch per level: C[q] = sigma * (((+0.0 + a[src[o]]) + a[src[o + 1]]) + ...), o from segmentOffsets[q].  One
+ * lane sums a segment, serially; no atomic, no reordering, sums that come to zero are kept: the bits do not depend on the grid or on
+ * where a tile of the list ends.  Then set-up's diagonal check, D^-1 and its uniformity test on the new values of every level.
+ *
+ * ALL OR NOTHING.  The new coarse values and the new D^-1 go to shadow buffers (allocated by the first call, then used in turns with the
+ * buffers in force) and the pointers change hands only when EVERY level has passed the diagonal check.  A diagonal that is not stored, not
+ * finite or not > 0 returns -1 with set-up's words, "level l, row i: the diagonal must be stored, finite and > 0" (the first such level,
+ * its smallest such row), and nothing of the handle has changed: with another vector the handle is the old hierarchy, bit for bit; with
+ * an in-place rewrite level 0 is whatever the caller wrote, over the OLD coarse levels and the OLD D^-1 -- a usable handle, no longer a
+ * Galerkin hierarchy, until a later call succeeds.  After the first call the host reads the levels' flags in one copy and nothing else.
+ * Matrix forms of MgcgSetMatrixCompression are those of the new values: every buffer written or given up is reported to the analysis cache
+ * and every level is looked up afresh.  Returns 0, -1 on a refusal.  Not to be called while a solve on the hierarchy is running. */
+int       MgUpdateValues(MgcgMg* mg, Vector* elementsVector, int elementsCount);
+long long MgUpdateBytes(const MgcgMg* mg);                                /* device bytes the source lists and shadow buffers hold; 0 before the first MgUpdateValues, for NULL and for other handles */
+/* Level `level`'s list for the product that forms level + 1: segmentOffsets[0 .. MgLevelNnz(level + 1)] and sources[0 .. MgLevelNnz(level) - 1]
+ * (host arrays; either may be NULL).  Returns the number of sources; -1 with MgcgGetLastError() before the first MgUpdateValues, on the
+ * last level and on a bad level or handle. */
+long long MgLevelCopyGalerkinSources(const MgcgMg* mg, int level, int segmentOffsets[], int sources[]);
 /* Multicolour ILU(0): M = L U, the incomplete factorisation without fill of A + shift * diag(A) in the COLOUR ORDER, as one more kind of
  * MgcgMg handle.  MgApply, SolveMg, SolveMinresMg, SolveBicgstabMg and SolveGmresMg take it wherever they take a hierarchy: z = M^-1 r is
  * U^-1 L^-1 r.  One rank; any CSR matrix with a stored diagonal in every row, rows in any stored order, no column twice in a row, a
